@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Blend.fit() hot path: proximal-gradient iterations/s on synthetic scenes.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--strong]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--strong] [--dump-outputs DIR]
 
 A "step" is one PGM iteration (Blend.fit inner loop: render [+ PSF convolution], loss gradient,
 Lipschitz step, constraint pipeline, convergence flags) over the whole resident batch of scenes.
@@ -24,6 +24,8 @@ scatters them over RCCL (timed separately), every rank fits its shard, results a
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
 "roofline" (dominant kernel class, HIP-event timed on the launch stream) and "cpu_baseline" (the
 CPU oracle timed on this host's cores -- one core and all cores -- rank 0 at N=1 only).
+`--dump-outputs DIR` writes, after the timed steps, what they computed (dump_outputs) so that two builds can be
+compared output for output: the inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -278,6 +280,39 @@ def run_other_configs(args):
     return out
 
 
+# ----------------------------------------------------------------------------- output dump
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240617
+
+
+def dump_outputs(batch, out_dir):
+    """What the timed fit() leaves for its caller, written as out_dir/<name>.npy in float32 / float64: current SEDs
+    and morphologies, centres, shifts, the loss of the last step, iteration counts and convergence flags.  A batch
+    whose arrays exceed DUMP_LIMIT_BYTES is represented by a fixed, seeded sample of its scenes (the same for the same
+    scene count), sorted; scenes.npy holds their indices.  Returns a summary for the result line."""
+    import torch
+    S = batch.S
+    last = (batch.it.long() - 1).clamp(min=0)[:, None]
+    arrays = [("sed", batch.sed_current, np.float32), ("morph", batch.morph_current, np.float32),
+              ("centers", batch.centers, np.float64), ("shifts", batch.shifts, np.float64),
+              ("loss", batch.mse_buf.gather(1, last)[:, 0], np.float64),
+              ("iterations", batch.it, np.float64), ("flags", batch.flags, np.float64)]
+    per_scene = 8 + sum(int(np.prod(t.shape[1:])) * np.dtype(dt).itemsize for _, t, dt in arrays)
+    n = min(S, (DUMP_LIMIT_BYTES - 4096) // per_scene)         # 4096: the .npy headers
+    if n < S:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(S, n, replace=False))
+    else:
+        idx = np.arange(S)
+    sel = torch.as_tensor(idx, device=batch.device)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t, dt in [("scenes", None, np.float64)] + arrays:
+        a = idx.astype(dt) if t is None else t.index_select(0, sel).cpu().numpy().astype(dt)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": os.path.abspath(out_dir), "scenes": int(n), "of_scenes": int(S), "bytes": int(total)}
+
+
 # ----------------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -299,7 +334,12 @@ def main():
     ap.add_argument("--no-monotonic", action="store_true", help="ablation: drop the monotonicity constraint")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch of the dominant kernel from rocprofv3 PMC passes (profiles/)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (rank 0's batch; a seeded sample of its "
+                         "scenes when larger than 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -465,6 +505,7 @@ def main():
     t_gather = distributed.max_over_ranks(time.perf_counter() - t0)
     if rank != 0:
         return
+    dumped = dump_outputs(batch, args.dump_outputs) if args.dump_outputs else None
     total_scene_iters = float(S_total) * args.steps
     value = total_scene_iters / elapsed
     bytes_unit = algorithmic_bytes_per_scene_iteration(B, K, H, W)
@@ -572,6 +613,8 @@ def main():
         rf["traffic_source"] = None
         rf["algorithmic_bytes_per_launch"] = bytes_unit * S0
         rf["avg_launch_ms"] = it_ms
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if other is not None:
         out["other_configs"] = other
     if cpu is not None:
