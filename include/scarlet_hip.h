@@ -45,9 +45,12 @@ extern "C" {
 
 #define SCARLET_OK            0
 #define SCARLET_E_ARG        -1   /* bad shape / null pointer / unsupported option  */
-#define SCARLET_E_TOO_LARGE  -2   /* frame larger than 256 x 256                    */
+#define SCARLET_E_TOO_LARGE  -2   /* frame side larger than SCARLET_MAX_SIDE        */
 #define SCARLET_E_HIP        -3   /* a HIP runtime call failed (see scarlet_last_error) */
 #define SCARLET_E_NOTIMPL    -4   /* reference raises NotImplementedError here      */
+
+/* largest frame side (H and W, square or not) of the engine, init_extended and the operators */
+#define SCARLET_MAX_SIDE     1024
 
 /* BlendFlag bits -- scarlet/component.py:13-36 */
 #define SCARLET_FLAG_SED_NOT_CONVERGED   1
@@ -204,7 +207,8 @@ int scarlet_match_psfs(const float *psf1, int n, int P1y, int P1x, const float *
 /* ------------------------------------------------------------------------------
  * 3. Batched Blend.fit() engine (blend.py:65-223, source.py:402-440)
  *
- * Supported shapes: K <= 32 components per scene, B <= 8 bands, frames up to 256 x 256,
+ * Supported shapes: K <= 32 components per scene, B <= 8 bands, frames up to
+ * SCARLET_MAX_SIDE (1024) pixels on either side,
  * with or without a PSF difference kernel.  Which kernels run is an internal choice:
  * one fused launch per iteration when the K morphology tiles fit LDS (H, W <= 64), the
  * four-kernel general path otherwise, chunked gradient passes for K > 8, operators in

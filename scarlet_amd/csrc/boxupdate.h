@@ -1,5 +1,5 @@
 // boxupdate.h -- k_source_update_box: the constraint pipeline of PointSource/ExtendedSource.update
-// (source.py:402-440) for frames beyond the wave-level tile (H or W > 64, up to 256 x 256), computed ONLY
+// (source.py:402-440) for frames beyond the wave-level tile (H or W > 64, up to SCARLET_MAX_SIDE), computed ONLY
 // WHERE ITS RESULT CAN BE NON-ZERO.
 //
 // With the default pipeline (symmetry -> radial monotonicity -> positivity) the weighted sweep ends as soon
@@ -44,7 +44,21 @@ __host__ __device__ inline size_t ub_lds_floats(int H, int W, int R)
     return (stage > (size_t)ub_floats(R) ? stage : (size_t)ub_floats(R)) + 2 * hp + 4 * wp + wp + ub_n(R);
 }
 
-// NB: bands of 16 window rows the kernel is built for (8: frames up to 128 rows, 16: up to 256); R: box half-size.
+// The streamed instance (NB = 0, frames with a side over 256 up to SCARLET_MAX_SIDE): T never exists as a whole.  Each
+// band of 16 window rows is multiplied by B[:, box] in chunks of SC_UB_CH columns (one per thread) staged in LDS, and
+// its 16 x 64 (or x 128) slab of T goes straight into the second product, Y += A[box rows, band] T[band, :], whose
+// accumulators stay in registers for the whole window.  Every accumulator sees its k steps in the order of the
+// banded instances (T: k ascending in two interleaved chains; Y: band, then r), so the results are the same.
+#define SC_UB_CH 256
+__host__ __device__ inline size_t ub_lds_floats_streamed(int H, int W, int R)
+{
+    const int hp = round16(H), wp = round16(W);
+    const size_t stage = (size_t)SC_UB_BR * tile_stride(SC_UB_CH);
+    return (stage > (size_t)ub_floats(R) ? stage : (size_t)ub_floats(R)) + 2 * hp + 4 * wp + wp + ub_n(R);
+}
+
+// NB: bands of 16 window rows the kernel is built for (8: frames up to 128 rows, 16: up to 256; 0: any number, the
+// streamed form above, frames up to SCARLET_MAX_SIDE); R: box half-size.
 // ub_component: the pipeline for component `c` by the calling workgroup (every return is uniform over it).
 // `list` / `count` != NULL (the small box): a component whose sweep leaves the box is appended to the list for the
 // large-box kernel; without them it is only flagged in `fallback` (the full-frame kernel runs for those).
@@ -63,7 +77,7 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
     UB_STAMP(0);
     const int H = XS ? XS : a.H, W = XS ? XS : a.W, HW = H * W, B = a.B;
     const int hpF = round16(H), wpF = round16(W);
-    const int BR = SC_UB_BR, SW = tile_stride(wpF);
+    const int BR = SC_UB_BR, SW = NB ? tile_stride(wpF) : tile_stride(SC_UB_CH);
     float *stage = lds;                                   // [BR][SW]   band of X rows (GEMM 1) ...
     float *box = lds;                                     // [63][65]   ... then the box around the peak
     const size_t stage_floats_ = (size_t)BR * SW;
@@ -154,7 +168,7 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
             for (int q = 0; q < NPF; ++q) if (q == slot) xr[q][j] = v;
         }
     };
-    if (mode == 1) {
+    if (NB > 0 && mode == 1) {
         load_band(0, 0);
         if (NPF > 1) load_band(SC_UB_BR, 1);
     }
@@ -182,8 +196,119 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
         kspace_vectors(av, bv, cv, hp, wp, ry, rx, h, w, Fy, Fx, dy, dx);
         const float sy = (Fy & 1) ? 0.f : (float)(sinpi(2.0 * dy) / Fy);
         const bool need_rank1 = (sy != 0.f);
-        float vloc = 0.f;
+        // after GEMM 1 (v in zv, the last band / chunk consumed): the box takes the stage's place, and the rank-1 term's
+        // z[j] = sum_j2 C[j][j2] v[j2] for the box columns goes to vsum
+        auto box_z = [&]() {
+            store_box();
+            UB_STAMP(3);
+            if (need_rank1 && (int)threadIdx.x < SC_UB_N) {
+                const int j = ja + threadIdx.x;
+                float zloc = 0.f;
+                if (j < w)
+                    for (int j2 = 0; j2 < w; ++j2) zloc += cv[j + j2] * zv[j2];
+                vsum[threadIdx.x] = zloc;
+            }
+            __syncthreads();
+            UB_STAMP(4);
+        };
+        // GEMM 2's epilogue: the 16 x 16 tile (row tile rt, column tile ct2) of Y combined with X in the box
+        auto box_epilogue = [&](int rt, int ct2, const f32x4 &acc) {
+            if (rt * 16 >= nbh || ct2 * 16 >= nbw) return;
+            const int jl = ct2 * 16 + lr, j = ja + jl;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int il = rt * 16 + lq * 4 + r, i = ia + il;
+                if (il < nbh && jl < nbw) {
+                    float *p = &box[(sw.y0 + i - by0) * SC_UB_LW + (sw.x0 + j - bx0)];
+                    const float x = *p;
+                    float y2 = acc[r];
+                    if (need_rank1) y2 += (((i - ry) & 1) ? -sy : sy) * vsum[jl];
+                    *p = (x <= 0.f) ? 0.f : 0.5f * x + 0.5f * y2;
+                }
+            }
+        };
         UB_STAMP(2);
+        if constexpr (NB == 0) {
+        // streamed: per band of window rows, GEMM 1 over column chunks, then the band's share of GEMM 2
+        constexpr int NCH = SC_RANK1_COLS;                         // column chunks of a window SCARLET_MAX_SIDE wide
+        static_assert(SC_UB_CH == SC_BLOCK, "one column of a chunk per thread");
+        float vl[NCH];
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) vl[q] = 0.f;
+        f32x4 Y[SC_UB_NT][CTW];
+#pragma unroll
+        for (int rt = 0; rt < SC_UB_NT; ++rt)
+#pragma unroll
+            for (int q = 0; q < CTW; ++q) Y[rt][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int i0 = 0; i0 < hp; i0 += BR) {
+            f32x4 acc[CTW], acc2[CTW];
+#pragma unroll
+            for (int q = 0; q < CTW; ++q) { acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc2[q] = acc[q]; }
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                const int k00 = ch * SC_UB_CH;
+                if (k00 < wp) {                                    // (uniform)
+                    const int cc = k00 + threadIdx.x;
+                    float xv[SC_UB_BR];
+#pragma unroll
+                    for (int r = 0; r < SC_UB_BR; ++r)
+                        xv[r] = (i0 + r < h && cc < w) ? gm[(sw.y0 + i0 + r) * W + sw.x0 + cc] : 0.f;
+                    __syncthreads();                               // vectors ready / previous chunk consumed
+#pragma unroll
+                    for (int r = 0; r < SC_UB_BR; ++r) stage[r * SW + threadIdx.x] = xv[r];
+                    __syncthreads();
+                    if (need_rank1 && cc < w) {                    // v[j] = sum_i (-1)^(i - ry) X[i][j], i ascending
+#pragma unroll
+                        for (int r = 0; r < SC_UB_BR; ++r)
+                            if (i0 + r < h) vl[ch] += ((i0 + r - ry) & 1) ? -xv[r] : xv[r];
+                    }
+                    const float *arow = stage + lr * SW;
+                    const int kn = min(SC_UB_CH, wp - k00);
+#pragma unroll 2
+                    for (int k0 = 0; k0 < kn; k0 += 8) {
+                        const int k = k00 + k0 + lq;
+                        const float xa = arow[k0 + lq], xb = arow[k0 + lq + 4];
+#pragma unroll
+                        for (int q = 0; q < CTW; ++q) {
+                            const int jc = ja + (wid + SC_NWAVES * q) * 16 + lr;
+                            acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa, bv[min(k + jc, 2 * wp - 1)], acc[q], 0, 0, 0);
+                            acc2[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb, bv[min(k + 4 + jc, 2 * wp - 1)], acc2[q], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            f32x4 T[CTW];
+#pragma unroll
+            for (int q = 0; q < CTW; ++q) T[q] = acc[q] + acc2[q];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = i0 + 4 * lq + r;
+#pragma unroll
+                for (int rt = 0; rt < SC_UB_NT; ++rt) {
+                    const float aa = av[min(ia + rt * 16 + lr + k, 2 * hp - 1)];
+#pragma unroll
+                    for (int q = 0; q < CTW; ++q) Y[rt][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa, T[q][r], Y[rt][q], 0, 0, 0);
+                }
+            }
+        }
+        if (need_rank1) {
+#pragma unroll
+            for (int q = 0; q < NCH; ++q) {
+                const int j = q * SC_UB_CH + threadIdx.x;
+                if (j < wp) zv[j] = j < w ? vl[q] : 0.f;
+            }
+        }
+        __syncthreads();                                           // v complete; the last chunk is consumed
+        box_z();
+#pragma unroll
+        for (int rt = 0; rt < SC_UB_NT; ++rt)
+#pragma unroll
+            for (int q = 0; q < CTW; ++q) {
+                box_epilogue(rt, wid + SC_NWAVES * q, Y[rt][q]);
+            }
+        } else {
+        float vloc = 0.f;
         // GEMM 1: T[:, box columns] = X (h x w, zero outside the window) . Hankel(bv); X streams through `stage`,
         // wave `wid` accumulates the box columns 16 wid .. 16 wid + 15 for every band (registers)
         f32x4 Tacc[NB][CTW];
@@ -231,17 +356,7 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
         }
         if (need_rank1 && threadIdx.x < wp) zv[threadIdx.x] = threadIdx.x < w ? vloc : 0.f;
         __syncthreads();                                           // T and v complete; the last band is consumed
-        store_box();                                               // (the box takes the band's place; read from GEMM 2's epilogue on)
-        UB_STAMP(3);
-        if (need_rank1 && (int)threadIdx.x < SC_UB_N) {            // z[j] = sum_j2 C[j][j2] v[j2] for the box columns
-            const int j = ja + threadIdx.x;
-            float zloc = 0.f;
-            if (j < w)
-                for (int j2 = 0; j2 < w; ++j2) zloc += cv[j + j2] * zv[j2];
-            vsum[threadIdx.x] = zloc;
-        }
-        __syncthreads();
-        UB_STAMP(4);
+        box_z();
         // GEMM 2: Y[box rows, box columns] = Hankel(av)[box rows, :] . T ; epilogue combines with X in the box.
         // Wave `wid`: its column tile of T from the accumulators, the four row tiles of the box.
         // (row tiles in groups of four: the accumulators of a group, 4 x CTW, stay in registers)
@@ -273,22 +388,9 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
             for (int rt2 = 0; rt2 < 4; ++rt2)
 #pragma unroll
                 for (int q = 0; q < CTW; ++q) {
-                    const int ct2 = wid + SC_NWAVES * q, rt = rg + rt2;
-                    if (rt * 16 >= nbh || ct2 * 16 >= nbw) continue;
-                    const f32x4 acc = Y[rt2][q];
-                    const int jl = ct2 * 16 + lr, j = ja + jl;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int il = rt * 16 + lq * 4 + r, i = ia + il;
-                        if (il < nbh && jl < nbw) {
-                            float *p = &box[(sw.y0 + i - by0) * SC_UB_LW + (sw.x0 + j - bx0)];
-                            const float x = *p;
-                            float y2 = acc[r];
-                            if (need_rank1) y2 += (((i - ry) & 1) ? -sy : sy) * vsum[jl];
-                            *p = (x <= 0.f) ? 0.f : 0.5f * x + 0.5f * y2;
-                        }
-                    }
+                    box_epilogue(rg + rt2, wid + SC_NWAVES * q, Y[rt2][q]);
                 }
+        }
         }
         __syncthreads();
     } else if (mode == 2) {
@@ -479,8 +581,8 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
 #undef UB_STAMP
 }
 
-// NB: bands of 16 window rows the kernel is built for (8: frames up to 128 rows, 16: up to 256).
-// The small box: one workgroup per component, four per CU.
+// NB: bands of 16 window rows the kernel is built for (8: frames up to 128 rows, 16: up to 256, 0: streamed, up to
+// SCARLET_MAX_SIDE).  The small box: one workgroup per component, four per CU.
 #ifndef SC_UB_WAVES
 #define SC_UB_WAVES 4            // workgroups of the small-box kernel per CU (tools/ab_box.sh builds variants with -DSC_UB_WAVES=n)
 #endif

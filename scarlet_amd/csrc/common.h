@@ -162,6 +162,8 @@ __device__ __forceinline__ float4 lds_load4(const float *p)
 // ---------------------------------------------------------------- fast FFT lengths
 // next_fast_len(n) for n < SC_NFL_MAX, filled on the host at first use (scarlet_hip.hip)
 #define SC_NFL_MAX 2304
+// columns per thread of a window SCARLET_MAX_SIDE wide when every thread of the workgroup owns whole columns
+#define SC_RANK1_COLS ((SCARLET_MAX_SIDE + SC_BLOCK - 1) / SC_BLOCK)
 extern __constant__ unsigned short sc_nfl_table[SC_NFL_MAX];
 
 __device__ __forceinline__ int dev_next_fast_len(int n) { return sc_nfl_table[n]; }

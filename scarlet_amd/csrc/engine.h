@@ -484,7 +484,7 @@ struct UpdateArgs {
 };
 
 // MODE 0/1: the morphology tile lives in LDS (tiles up to ~128 x 128).
-// MODE 2   : frames whose tile does not fit (up to 256 x 256, BASELINE config 5): the same
+// MODE 2   : frames whose tile does not fit (up to SCARLET_MAX_SIDE; BASELINE config 5): the same
 //             operators run IN PLACE on the morphology plane in HBM / L2 with the scratch in a
 //             global workspace; only the Hankel vectors are in LDS.  Threads of the workgroup
 //             exchange pixels through global memory across __syncthreads(), exactly as they do

@@ -322,16 +322,21 @@ __device__ inline void kspace_symmetry_tile(const Tile &t, const SymWindow &s, d
     kspace_vectors(av, bv, cv, hp, wp, ry, rx, h, w, Fy, Fx, dy, dx);
     const float sy = (Fy & 1) ? 0.f : (float)(sinpi(2.0 * dy) / Fy);
 
-    // rank-1 term, part 1: v[j] = sum_i (-1)^(i-ry) X[i][j]   (stored in zv, then z = C v)
+    // rank-1 term, part 1: v[j] = sum_i (-1)^(i-ry) X[i][j]   (stored in zv, then z = C v).  Column j is summed by
+    // thread j % SC_BLOCK, rows ascending (a window up to SCARLET_MAX_SIDE wide: SC_RANK1_COLS columns per thread)
     const bool need_rank1 = (sy != 0.f);
-    float vloc = 0.f;
-    if (need_rank1 && threadIdx.x < w) {
-        for (int i = 0; i < h; ++i) {
-            const float x = m[(s.y0 + i) * LW + s.x0 + threadIdx.x];
-            vloc += ((i - ry) & 1) ? -x : x;
+    if (need_rank1) {
+        for (int j = threadIdx.x; j < wp; j += SC_BLOCK) {
+            float vloc = 0.f;
+            if (j < w)
+                for (int i = 0; i < h; ++i) {
+                    const float x = m[(s.y0 + i) * LW + s.x0 + j];
+                    vloc += ((i - ry) & 1) ? -x : x;
+                }
+            zv[j] = vloc;
         }
     }
-    __syncthreads();                       // vectors ready
+    __syncthreads();                       // vectors and v ready
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
     const int tiles_x = wp >> 4, tiles = (hp >> 4) * tiles_x;
@@ -373,16 +378,21 @@ __device__ inline void kspace_symmetry_tile(const Tile &t, const SymWindow &s, d
 #pragma unroll
         for (int r = 0; r < 4; ++r) scr[(i0 + lq * 4 + r) * LS + j0 + lr] = acc[r];
     }
-    if (need_rank1) {
-        if (threadIdx.x < wp) zv[threadIdx.x] = threadIdx.x < w ? vloc : 0.f;
-    }
-    __syncthreads();                       // T and v complete
-    float zloc = 0.f;
-    if (need_rank1 && threadIdx.x < w) {
-        for (int j2 = 0; j2 < w; ++j2) zloc += cv[threadIdx.x + j2] * zv[j2];
+    __syncthreads();                       // T complete
+    float zloc[SC_RANK1_COLS];
+#pragma unroll
+    for (int q = 0; q < SC_RANK1_COLS; ++q) {
+        const int j = threadIdx.x + q * SC_BLOCK;
+        zloc[q] = 0.f;
+        if (need_rank1 && j < w)
+            for (int j2 = 0; j2 < w; ++j2) zloc[q] += cv[j + j2] * zv[j2];
     }
     __syncthreads();
-    if (need_rank1 && threadIdx.x < w) zv[threadIdx.x] = zloc;
+#pragma unroll
+    for (int q = 0; q < SC_RANK1_COLS; ++q) {
+        const int j = threadIdx.x + q * SC_BLOCK;
+        if (need_rank1 && j < w) zv[j] = zloc[q];
+    }
     __syncthreads();
 
     // GEMM 2: Y = Hankel(av) . T ; epilogue combines with X in place

@@ -203,7 +203,7 @@ struct OpArgs {
     const double *psf; int P;
 };
 
-// GT: arrays whose tile does not fit LDS (up to 256 x 256) are processed in place in HBM, the GEMM
+// GT: arrays whose tile does not fit LDS (up to SCARLET_MAX_SIDE a side) are processed in place in HBM, the GEMM
 // scratch of the k-space symmetry in `gscratch` (see k_source_update<2> in engine.h)
 template <bool GT>
 __global__ __launch_bounds__(SC_BLOCK) void k_operator(OpArgs a, float *gscratch)
@@ -314,8 +314,10 @@ __global__ __launch_bounds__(SC_BLOCK) void k_operator_w(OpArgs a)
 
 static int launch_operator(OpArgs a, void *stream)
 {
-    if (!a.x || a.n < 0 || a.H <= 0 || a.W <= 0 || a.W > 256 || !a.centers)
+    if (!a.x || a.n < 0 || a.H <= 0 || a.W <= 0 || !a.centers)
         return set_err(SCARLET_E_ARG, "bad operator arguments");
+    if (a.H > SCARLET_MAX_SIDE || a.W > SCARLET_MAX_SIDE)
+        return set_err(SCARLET_E_TOO_LARGE, "arrays larger than 1024 x 1024 (SCARLET_MAX_SIDE) are not supported");
     if (a.n == 0) return SCARLET_OK;
     int rc = ensure_tables();
     if (rc) return rc;
@@ -331,11 +333,12 @@ static int launch_operator(OpArgs a, void *stream)
         if (rc) return rc;
         hipLaunchKernelGGL(k_operator<false>, dim3(a.n), dim3(SC_BLOCK), lds, (hipStream_t)stream, a, (float *)nullptr);
     } else {
-        if (a.H > 256) return set_err(SCARLET_E_TOO_LARGE, "arrays larger than 256 x 256 are not supported");
         DevBuf gscratch;                      // released on every path, after the kernel has finished
         if (a.op == OP_SYMMETRY)
             DEV_ALLOC(gscratch, sizeof(float) * (size_t)a.n * round16(a.H) * scratch_stride(round16(a.W)));
         const size_t lds = sizeof(float) * (2 * round16(a.H) + 5 * round16(a.W) + stage_floats(round16(a.H), round16(a.W)));
+        rc = allow_lds(k_operator<true>, lds);          // (past 48 KB from ~512 columns on)
+        if (rc) return rc;
         hipLaunchKernelGGL(k_operator<true>, dim3(a.n), dim3(SC_BLOCK), lds, (hipStream_t)stream, a, gscratch.as<float>());
         HIP_TRY(hipGetLastError());
         if (gscratch.p) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -753,7 +756,8 @@ static int check_batch(const scarlet_batch *b)
     if (b->S <= 0 || b->K <= 0 || b->B <= 0 || b->H <= 0 || b->W <= 0) return set_err(SCARLET_E_ARG, "bad batch shape");
     if (b->K > SC_KBIG || b->B > SC_BMAX)
         return set_err(SCARLET_E_NOTIMPL, "K > 32 or B > 8 not supported by this build of the gradient kernels");
-    if (b->W > 256) return set_err(SCARLET_E_TOO_LARGE, "W > 256 unsupported");
+    if (b->H > SCARLET_MAX_SIDE || b->W > SCARLET_MAX_SIDE)
+        return set_err(SCARLET_E_TOO_LARGE, "frames larger than 1024 x 1024 (SCARLET_MAX_SIDE) are not supported");
     if (!b->images || !b->sed[0] || !b->sed[1] || !b->morph[0] || !b->morph[1] || !b->cur || !b->centers ||
         !b->shifts || !b->flags || !b->lipschitz || !b->mse || !b->it || !b->active || !b->status || !b->workspace)
         return set_err(SCARLET_E_ARG, "null pointer in batch");
@@ -1562,12 +1566,15 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
         hipLaunchKernelGGL(k_group_centers, dim3(b->S), dim3(SC_WAVE), ldsg, (hipStream_t)stream, u);
     }
     u.hybrid_sweep = opt(OPT_NO_HYBRID_SWEEP) ? 0 : 1;
-    if ((b->H > 64 || b->W > 64) && b->H <= 256 && b->W <= 256 && b->monotonic && !opt(OPT_NO_BOX) &&
-        sizeof(float) * ub_lds_floats(b->H, b->W, 63) <= LDS_LIMIT) {
+    // (frames with a side over 256 take the streamed instance, NB = 0)
+    const bool streamed = b->H > 256 || b->W > 256;
+    if ((b->H > 64 || b->W > 64) && b->monotonic && !opt(OPT_NO_BOX) &&
+        sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 63) : ub_lds_floats(b->H, b->W, 63)) <= LDS_LIMIT) {
         // frames beyond the wave-level tile: the pipeline on the box around each peak (boxupdate.h) -- 63 x 63 for
         // every component, 127 x 127 for those whose footprint left it; the kernels below then run only for the
         // components that left the second box too
-        const size_t lds1 = sizeof(float) * ub_lds_floats(b->H, b->W, 31), lds2 = sizeof(float) * ub_lds_floats(b->H, b->W, 63);
+        const size_t lds1 = sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 31) : ub_lds_floats(b->H, b->W, 31)),
+                     lds2 = sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 63) : ub_lds_floats(b->H, b->W, 63));
         long long *dbg = debug_stamps((size_t)b->S * b->K * 16);
         int *fb = ws_box_fallback(b);
         int *list = ws_box_list(b), *count = list + (size_t)b->S * b->K;
@@ -1576,7 +1583,7 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
         if (second) hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, count);   // (a 4-byte hipMemsetAsync costs 16 us)
         // the large box: workgroup i takes list[i]
         const int listed_grid = b->S * b->K;
-        // instances: bands of X per frame height (8: up to 128 rows, 16: up to 256), and the two BASELINE frame shapes
+        // instances: bands of X per frame height (8: up to 128 rows, 16: up to 256, 0: streamed), and the two BASELINE frame shapes
         // (128 x 128, 256 x 256) as compile-time constants
         auto run = [&](auto small_k, auto listed_k) -> int {
             int r2;
@@ -1587,7 +1594,8 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
             return SCARLET_OK;
         };
         const bool exact = !opt(OPT_NO_EXACT);
-        if (exact && b->H == 128 && b->W == 128) rc = run(k_source_update_box<8, 128>, k_source_update_box_listed<8, 128>);
+        if (streamed) rc = run(k_source_update_box<0, 0>, k_source_update_box_listed<0, 0>);
+        else if (exact && b->H == 128 && b->W == 128) rc = run(k_source_update_box<8, 128>, k_source_update_box_listed<8, 128>);
         else if (exact && b->H == 256 && b->W == 256) rc = run(k_source_update_box<16, 256>, k_source_update_box_listed<16, 256>);
         else if (b->H <= 128 && b->W <= 128) rc = run(k_source_update_box<8, 0>, k_source_update_box_listed<8, 0>);
         else rc = run(k_source_update_box<16, 0>, k_source_update_box_listed<16, 0>);
@@ -1618,11 +1626,11 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
             hipLaunchKernelGGL(k_source_update<0>, dim3(b->S * b->K), dim3(SC_BLOCK), lds, (hipStream_t)stream, u);
         }
     } else {
-        // frames beyond the LDS tile (up to 256 x 256): operators in place on the plane in HBM / L2
-        if (b->H > 256 || b->W > 256) return set_err(SCARLET_E_TOO_LARGE, "frames larger than 256 x 256 are not supported");
+        // frames beyond the LDS tile (up to SCARLET_MAX_SIDE): operators in place on the plane in HBM / L2
         u.gscratch = ws_gscratch(b);
         const size_t lds = sizeof(float) * (2 * round16(b->H) + 5 * round16(b->W) +       // av, bv, cv, zv, stage
                                             stage_floats(round16(b->H), round16(b->W)));
+        if ((rc = allow_lds(k_source_update<2>, lds))) return rc;                         // (94 KB at 1024 x 1024)
         hipLaunchKernelGGL(k_source_update<2>, dim3(b->S * b->K), dim3(SC_BLOCK), lds, (hipStream_t)stream, u);
     }
     HIP_TRY(hipGetLastError());
@@ -2059,7 +2067,6 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
         hipLaunchKernelGGL(k_init_extended<false>, dim3(b->S * b->K), dim3(SC_BLOCK), lds, (hipStream_t)stream, a,
                            (double *)nullptr);
     } else {
-        if (b->H > 256 || b->W > 256) return set_err(SCARLET_E_TOO_LARGE, "frames larger than 256 x 256 are not supported");
         DevBuf gtile;                                  // one-time setup: a temporary float64 tile per component
         DEV_ALLOC(gtile, lds * (size_t)b->S * b->K);
         hipLaunchKernelGGL(k_init_extended<true>, dim3(b->S * b->K), dim3(SC_BLOCK), 0, (hipStream_t)stream, a, gtile.as<double>());
