@@ -51,6 +51,8 @@ extern "C" {
 
 /* largest frame side (H and W, square or not) of the engine, init_extended and the operators */
 #define SCARLET_MAX_SIDE     1024
+/* most components per scene (K) of the engine and init_extended; more: SCARLET_E_NOTIMPL */
+#define SCARLET_MAX_COMPONENTS 256
 
 /* BlendFlag bits -- scarlet/component.py:13-36 */
 #define SCARLET_FLAG_SED_NOT_CONVERGED   1
@@ -207,8 +209,8 @@ int scarlet_match_psfs(const float *psf1, int n, int P1y, int P1x, const float *
 /* ------------------------------------------------------------------------------
  * 3. Batched Blend.fit() engine (blend.py:65-223, source.py:402-440)
  *
- * Supported shapes: K <= 32 components per scene, B <= 8 bands, frames up to
- * SCARLET_MAX_SIDE (1024) pixels on either side,
+ * Supported shapes: K <= SCARLET_MAX_COMPONENTS (256) components per scene, B <= 8
+ * bands, frames up to SCARLET_MAX_SIDE (1024) pixels on either side,
  * with or without a PSF difference kernel.  Which kernels run is an internal choice:
  * one fused launch per iteration when the K morphology tiles fit LDS (H, W <= 64), the
  * four-kernel general path otherwise, chunked gradient passes for K > 8, operators in

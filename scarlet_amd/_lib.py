@@ -41,6 +41,7 @@ STATUS_CENTER_AT_EDGE, STATUS_NONFINITE = 1, 2
 SYM_KSPACE, SYM_SOFT, SYM_SDSS = 0, 1, 2
 SYM_FULL_WINDOW = 16
 NORM_SED, NORM_MORPH, NORM_MORPH_MAX = 0, 1, 2
+MAX_SIDE, MAX_COMPONENTS = 1024, 256       # SCARLET_MAX_SIDE, SCARLET_MAX_COMPONENTS
 
 
 class ScarletBatch(Structure):

@@ -1,4 +1,4 @@
-// bigk.h -- the gradient step of Blend.fit for MANY components per scene (8 < K <= 32).
+// bigk.h -- the gradient step of Blend.fit for MANY components per scene (8 < K <= 32; above 32: hugek.h).
 //
 // The register-tiled kernels of engine.h keep sed[K][B], d loss/d sed[K][B] and the K (K+1)/2
 // Gram accumulators per thread, which stops at K = 8.  Crowded scenes (BASELINE config 5: 30
@@ -31,13 +31,14 @@
 
 #define SC_CHUNK 8
 
-// ---- pass 1: model, residual, loss
+// ---- pass 1: model, residual, loss.  KC: the most components the instance takes (SC_KBIG, or SC_KHUGE: hugek.h)
+template <int KC>
 __global__ __launch_bounds__(SC_BLOCK) void k_bigk_resid(GradArgs a, float *resid)
 {
     const int s = blockIdx.y, tile = blockIdx.x;
     if (!a.active[s]) return;
     const int K = a.K, B = a.B, HW = a.HW;
-    __shared__ float sed_s[SC_KBIG * SC_BMAX];
+    __shared__ float sed_s[KC * SC_BMAX];
     __shared__ double red[SC_NWAVES];
     const int c0 = a.cur[s];
     for (int i = threadIdx.x; i < K * B; i += SC_BLOCK)
@@ -500,13 +501,15 @@ __global__ __launch_bounds__(SC_BLOCK) void k_bigk_lipschitz(GradArgs a, int sed
 
 // lambda_max(A^T A) alone (blend.py:205-218), one wave per scene: all the morphology step needs.  Power iteration
 // by repeated squaring on the wave (wave_lambda_max8) instead of the single-lane Jacobi above: ~10 k cycles.
+// KC as for k_bigk_resid.
+template <int KC>
 __global__ __launch_bounds__(SC_WAVE) void k_bigk_lmorph(GradArgs a)
 {
     const int s = blockIdx.x;
     if (!a.active[s]) return;
     const int K = a.K, B = a.B, P = n_partials(K, B), lane = threadIdx.x;
     __shared__ double ata[SC_BMAX * SC_BMAX];
-    __shared__ float sed_s[SC_KBIG * SC_BMAX];
+    __shared__ float sed_s[KC * SC_BMAX];
     __shared__ double buf[2][64];
     const int c0 = a.cur[s];
     for (int i = lane; i < K * B; i += SC_WAVE)

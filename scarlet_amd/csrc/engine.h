@@ -21,7 +21,9 @@
 #define SC_KBIG 32              // chunked gradient kernels (bigk.h)
 #define SC_BMAX 8
 
-__host__ __device__ inline int n_partials(int K, int B) { return 1 + K * B + K * (K + 1) / 2; }
+// per (scene, tile): loss, d loss / d sed [K][B] and, up to SC_KBIG components, the packed upper triangle of the
+// morphology Gram matrix (above SC_KBIG it has an area of its own, hugek.h)
+__host__ __device__ inline int n_partials(int K, int B) { return 1 + K * B + (K <= SC_KBIG ? K * (K + 1) / 2 : 0); }
 
 struct GradArgs {
     int S, K, B, HW, T;

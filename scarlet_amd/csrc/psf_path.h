@@ -58,14 +58,15 @@ struct PsfArgs {
 
 // model_b = sum_k sed[k][b] morph[k] written into the padded FFT input planes (a1, a2 + pad).
 // One thread per padded pixel and scene: the K morphology values are read once and all B band
-// planes are written from them.  grid (ceil(Fy Fx / 256), S).
+// planes are written from them.  grid (ceil(Fy Fx / 256), S).  KC: the most components the instance takes.
+template <int KC>
 __global__ __launch_bounds__(SC_BLOCK) void k_psf_model(PsfArgs a)
 {
     const int s = blockIdx.y;
     if (!a.active[s]) return;
     const PsfGeom g = a.g;
     const int c0 = a.cur[s], HW = g.H * g.W, K = a.K, B = a.B;
-    __shared__ float sed_s[SC_KBIG * SC_BMAX];
+    __shared__ float sed_s[KC * SC_BMAX];
     for (int i = threadIdx.x; i < K * B; i += SC_BLOCK)
         sed_s[(i / B) * SC_BMAX + (i % B)] = a.sed[c0][(size_t)s * K * B + i];
     __syncthreads();
@@ -508,12 +509,13 @@ __global__ __launch_bounds__(SC_BLOCK) void k_step_psf4(PsfArgs a)
 }
 
 // model planes, compact [S][B][H*W], 16 B per lane (k_psf_model with the geometry of an unpadded plane)
+template <int KC>
 __global__ __launch_bounds__(SC_BLOCK) void k_psf_model4(PsfArgs a)
 {
     const int s = blockIdx.y;
     if (!a.active[s]) return;
     const int c0 = a.cur[s], HW4 = (a.g.H * a.g.W) >> 2, K = a.K, B = a.B;
-    __shared__ float sed_s[SC_KBIG * SC_BMAX];
+    __shared__ float sed_s[KC * SC_BMAX];
     for (int i = threadIdx.x; i < K * B; i += SC_BLOCK)
         sed_s[(i / B) * SC_BMAX + (i % B)] = a.sed[c0][(size_t)s * K * B + i];
     __syncthreads();

@@ -20,6 +20,7 @@
 #include "fused.h"
 #include "fused2.h"
 #include "bigk.h"
+#include "hugek.h"
 #include "boxupdate.h"
 #include "psf_path.h"
 #include "fftconv.h"
@@ -49,10 +50,10 @@ extern "C" const char *scarlet_version(void) { return "scarlet_amd-hip 0.2 (gfx9
 // environment (SCARLET_<NAME>) at first use and changed afterwards only through scarlet_set_option.
 // None of them changes results beyond float32 rounding.
 enum { OPT_NO_EXACT = 0, OPT_NO_KSCACHE, OPT_FUSED_V1, OPT_NO_FUSED, OPT_FORCE_BLOCK_UPDATE, OPT_NO_HYBRID_SWEEP,
-       OPT_PAD_LDS, OPT_STAMPS, OPT_PSF_HIPFFT, OPT_NO_BOX, OPT_NO_BOX2, OPT_NO_PSF3PASS, OPT_NO_SIDE_STREAM, OPT_NO_GRAM_MFMA, OPT_NO_BIGK_FUSED, OPT_NO_PIPELINE, OPT_NO_PERSIST, OPT_PERSIST_DBG, OPT_COUNT };
+       OPT_PAD_LDS, OPT_STAMPS, OPT_PSF_HIPFFT, OPT_NO_BOX, OPT_NO_BOX2, OPT_NO_PSF3PASS, OPT_NO_SIDE_STREAM, OPT_NO_GRAM_MFMA, OPT_NO_BIGK_FUSED, OPT_NO_PIPELINE, OPT_NO_PERSIST, OPT_PERSIST_DBG, OPT_FORCE_HUGEK, OPT_COUNT };
 static const char *const g_opt_names[OPT_COUNT] = {"NO_EXACT", "NO_KSCACHE", "FUSED_V1", "NO_FUSED", "FORCE_BLOCK_UPDATE",
                                                    "NO_HYBRID_SWEEP", "PAD_LDS", "STAMPS", "PSF_HIPFFT", "NO_BOX", "NO_BOX2",
-                                                   "NO_PSF3PASS", "NO_SIDE_STREAM", "NO_GRAM_MFMA", "NO_BIGK_FUSED", "NO_PIPELINE", "NO_PERSIST", "PERSIST_DBG"};
+                                                   "NO_PSF3PASS", "NO_SIDE_STREAM", "NO_GRAM_MFMA", "NO_BIGK_FUSED", "NO_PIPELINE", "NO_PERSIST", "PERSIST_DBG", "FORCE_HUGEK"};
 static std::atomic<int> g_opt[OPT_COUNT];
 static std::once_flag g_opt_once;
 static void options_init(void)
@@ -75,12 +76,18 @@ static inline int opt(int which) { options_init(); return g_opt[which].load(std:
 // (K-hat and tables read from the wrong offsets, writes past the allocation).  The first layout computed in the
 // process therefore FREEZES the two switches: scarlet_set_option then refuses a different value (SCARLET_E_ARG).
 static std::atomic<bool> g_layout_frozen{false};
+// FORCE_HUGEK (diagnostics: the K > 32 gradient path of hugek.h for 8 < K <= 32 as well) adds the Gram area of that
+// path to the workspace of such batches: it freezes, likewise, once a workspace with 8 < K <= 32 has been sized.
+static std::atomic<bool> g_hugek_frozen{false};
 extern "C" int scarlet_set_option(const char *name, int value)
 {
     options_init();
     if (!name) return set_err(SCARLET_E_ARG, "null option name");
     for (int i = 0; i < OPT_COUNT; ++i)
         if (!strcmp(name, g_opt_names[i])) {
+            if (i == OPT_FORCE_HUGEK && g_hugek_frozen.load() && (g_opt[i].load() != 0) != (value != 0))
+                return set_err(SCARLET_E_ARG, "FORCE_HUGEK fixes the workspace layout of batches with 8 < K <= 32: it cannot "
+                                              "change after the first such workspace of the process was sized");
             if ((i == OPT_PSF_HIPFFT || i == OPT_STAMPS) && g_layout_frozen.load() && (g_opt[i].load() != 0) != (value != 0))
                 return set_err(SCARLET_E_ARG, "PSF_HIPFFT / STAMPS fix the workspace layout of PSF batches: they cannot change "
                                               "after the first PSF workspace of the process was sized");
@@ -754,8 +761,10 @@ static int check_batch(const scarlet_batch *b)
     (void)hipGetLastError();
     if (!b) return set_err(SCARLET_E_ARG, "null batch");
     if (b->S <= 0 || b->K <= 0 || b->B <= 0 || b->H <= 0 || b->W <= 0) return set_err(SCARLET_E_ARG, "bad batch shape");
-    if (b->K > SC_KBIG || b->B > SC_BMAX)
-        return set_err(SCARLET_E_NOTIMPL, "K > 32 or B > 8 not supported by this build of the gradient kernels");
+    if (b->K > SCARLET_MAX_COMPONENTS)
+        return set_err(SCARLET_E_NOTIMPL, "K > 256 components per scene (SCARLET_MAX_COMPONENTS) is not supported");
+    if (b->B > SC_BMAX)
+        return set_err(SCARLET_E_NOTIMPL, "B > 8 bands is not supported by this build of the gradient kernels");
     if (b->H > SCARLET_MAX_SIDE || b->W > SCARLET_MAX_SIDE)
         return set_err(SCARLET_E_TOO_LARGE, "frames larger than 1024 x 1024 (SCARLET_MAX_SIDE) are not supported");
     if (!b->images || !b->sed[0] || !b->sed[1] || !b->morph[0] || !b->morph[1] || !b->cur || !b->centers ||
@@ -813,13 +822,29 @@ static int64_t kscache_bytes(const scarlet_batch *b)
     if (b->K > 4 || b->B > 5 || b->H > 64 || b->W > 64) return 0;
     return align256(sizeof(float) * (int64_t)b->S * b->K * 2 * SC_KSC_FLOATS);
 }
+// the gradient path of hugek.h: every K > SC_KBIG, and 8 < K <= SC_KBIG under FORCE_HUGEK
+static bool use_hugek(const scarlet_batch *b)
+{
+    if (b->K > SC_KBIG) return true;
+    if (b->K <= SC_KMAX) return false;
+    g_hugek_frozen.store(true);                       // (see scarlet_set_option)
+    return opt(OPT_FORCE_HUGEK) != 0;
+}
+// its Gram area: per-chunk blocks [S][pairs][C][32][32], then G and the two squaring buffers [S][Kp][Kp] (float64)
+static int64_t hugek_bytes(const scarlet_batch *b)
+{
+    if (!use_hugek(b)) return 0;
+    const int64_t Kp = (int64_t)huge_nblk(b->K) * SC_GBLK;
+    return align256(sizeof(double) * (int64_t)b->S * huge_npairs(b->K) * huge_nchunks(b->H * b->W) * SC_GBLK * SC_GBLK) +
+           3 * align256(sizeof(double) * (int64_t)b->S * Kp * Kp);
+}
 static int64_t base_workspace_bytes(const scarlet_batch *b)
 {
     const int64_t P = n_partials(b->K, b->B);
     // K > 8 (bigk.h): one scratch plane set [S][B][HW] for G = w^2 (model - image)
     const int64_t resid = b->K > SC_KMAX ? align256(sizeof(float) * (int64_t)b->S * b->B * b->H * b->W) : 0;
     return align256(sizeof(double) * ((int64_t)b->S * n_tiles(b) * P + (int64_t)b->S * b->K * 4) + sizeof(int) * (2 * (int64_t)b->S * b->K + 64)) +
-           resid + gscratch_bytes(b) + kscache_bytes(b) + 256;
+           resid + gscratch_bytes(b) + kscache_bytes(b) + hugek_bytes(b) + 256;
 }
 // ---- LDS-resident convolution (fftconv.h): plan = lengths, radices, kernel placement
 // smallest circular length that reproduces the cropped linear convolution: image at 0..N-1, kernel at
@@ -1063,6 +1088,21 @@ static float *ws_kscache(const scarlet_batch *b)
     return kscache_bytes(b) ? (float *)((char *)ws_gscratch(b) + gscratch_bytes(b)) : nullptr;
 }
 
+static HugeArgs huge_args(const scarlet_batch *b)
+{
+    const int64_t Kp = (int64_t)huge_nblk(b->K) * SC_GBLK;
+    char *p = (char *)ws_gscratch(b) + gscratch_bytes(b) + kscache_bytes(b);
+    HugeArgs h;
+    h.C = huge_nchunks(b->H * b->W);
+    h.gpart = (double *)p;
+    p += align256(sizeof(double) * (int64_t)b->S * huge_npairs(b->K) * h.C * SC_GBLK * SC_GBLK);
+    h.gram = (double *)p;
+    p += align256(sizeof(double) * (int64_t)b->S * Kp * Kp);
+    h.msq[0] = (double *)p;
+    h.msq[1] = (double *)(p + align256(sizeof(double) * (int64_t)b->S * Kp * Kp));
+    return h;
+}
+
 static GradArgs grad_args(const scarlet_batch *b, int approximate_L, int raw_gradient = 0)
 {
     GradArgs a;
@@ -1212,6 +1252,41 @@ static void launch_bigk_step(const GradArgs &a, int nch, const float *resid, hip
     else hipLaunchKernelGGL((k_bigk_step<SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a, resid);
 }
 
+// The gradient step for K > SC_KBIG (hugek.h).  Without a PSF it starts from the morphologies (k_bigk_resid); with one,
+// `psf_resid` holds the compact gradient planes G [S][B][H][W] and `psf_loss` the per-plane loss sums.
+static int backward_hugek(scarlet_batch *b, int approximate_L, int raw_gradient, const float *psf_resid,
+                          const double *psf_loss, hipStream_t st)
+{
+    const GradArgs a = grad_args(b, approximate_L, raw_gradient);
+    const HugeArgs h = huge_args(b);
+    const int nb = huge_nblk(b->K), npairs = huge_npairs(b->K), nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
+    const float *resid = psf_resid;
+    prof_start(0, st);
+    if (psf_resid)
+        hipLaunchKernelGGL(k_bigk_loss_from_planes, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a, psf_loss);
+    else {
+        resid = ws_resid(b);
+        hipLaunchKernelGGL((k_bigk_resid<SC_KHUGE>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a, ws_resid(b));
+    }
+    if ((a.HW & 3) == 0) hipLaunchKernelGGL((k_huge_gram<true>), dim3(h.C, npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
+    else hipLaunchKernelGGL((k_huge_gram<false>), dim3(h.C, npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
+    hipLaunchKernelGGL(k_huge_gram_reduce, dim3(npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
+    const double *last = h.gram;
+    if (!approximate_L)
+        for (int q = 0; q < SC_HUGE_SQUARINGS; ++q) {
+            hipLaunchKernelGGL(k_huge_square, dim3(nb, nb, a.S), dim3(SC_BLOCK), 0, st, a, last, h.msq[q & 1]);
+            last = h.msq[q & 1];
+        }
+    hipLaunchKernelGGL(k_huge_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, st, a, h, last);
+    hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
+    prof_stop(st); prof_start(1, st);
+    launch_bigk_step(a, nch, resid, st);
+    hipLaunchKernelGGL(k_bigk_sed, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 0);
+    prof_stop(st);
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
 static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradient, void *stream)
 {
     const PsfGeom g = psf_geom(b->H, b->W, b->psf_h, b->psf_w);
@@ -1248,14 +1323,19 @@ static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradie
         prof_start(5, st);
         // model planes, compact [S][B][H][W], into `real` (k_psf_model with the geometry of an unpadded plane)
         a.g.Fy = b->H; a.g.Fx = b->W; a.g.Fxh = b->W / 2 + 1; a.g.oy = 0; a.g.ox = 0;
-        if (three_pass) {
+        if (b->K > SC_KBIG) {
+            if ((b->H * b->W) % 4 == 0)
+                hipLaunchKernelGGL(k_psf_model4<SC_KHUGE>, dim3(((b->H * b->W) / 4 + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+            else
+                hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, dim3((b->H * b->W + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+        } else if (three_pass) {
             // model planes + Gram partials in one pass (psf_path.h, "three-pass form")
             if (b->K <= 4) hipLaunchKernelGGL((k_psf_model4g<4>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a);
             else hipLaunchKernelGGL((k_psf_model4g<SC_KMAX>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a);
         } else if ((b->H * b->W) % 4 == 0)
-            hipLaunchKernelGGL(k_psf_model4, dim3(((b->H * b->W) / 4 + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+            hipLaunchKernelGGL(k_psf_model4<SC_KBIG>, dim3(((b->H * b->W) / 4 + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
         else
-            hipLaunchKernelGGL(k_psf_model, dim3((b->H * b->W + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+            hipLaunchKernelGGL(k_psf_model<SC_KBIG>, dim3((b->H * b->W + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
         long long *stamps = opt(OPT_STAMPS) ? (long long *)((char *)b->workspace + l.stamps) : nullptr;
         fp.stagger_wgs = 0;
         if (x128) {
@@ -1272,7 +1352,8 @@ static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradie
     rc = get_plans(g.Fy, g.Fx, planes, &p);
     if (rc) return rc;
     prof_start(5, st);
-    hipLaunchKernelGGL(k_psf_model, dim3((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+    if (b->K > SC_KBIG) hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, dim3((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL(k_psf_model<SC_KBIG>, dim3((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
     if ((rc = fft_r2c(p, a.real, a.spec, st))) return rc;
     hipLaunchKernelGGL(k_spec_mul, dim3(grid_for((int64_t)planes * plane_elems)), dim3(SC_BLOCK), 0, st,
                        a.spec, a.khat, nkh, plane_elems, (int64_t)planes * plane_elems, 0, scale);
@@ -1285,6 +1366,13 @@ static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradie
     prof_stop(st);
     }
     dim3 grid(a.T, a.S);
+    if (use_hugek(b)) {
+        float *resid = lds_path ? a.real : ws_resid(b);
+        if (!lds_path)
+            hipLaunchKernelGGL(k_plane_crop, dim3(grid_for((int64_t)planes * b->H * b->W)), dim3(SC_BLOCK), 0, st,
+                               (const float *)a.real, planes, b->H, b->W, g.Fy, g.Fx, g.oy, g.ox, resid);
+        return backward_hugek(b, approximate_L, raw_gradient, resid, (const double *)a.loss_part, st);
+    }
     if (b->K > SC_KMAX) {
         // many components: G is cropped out of the FFT buffers once (the LDS path's planes are compact already),
         // then the chunked passes of bigk.h
@@ -1448,6 +1536,7 @@ static int backward_impl(scarlet_batch *b, int approximate_L, int raw_gradient, 
     GradArgs a = grad_args(b, approximate_L, raw_gradient);
     dim3 grid(a.T, a.S);
     hipStream_t st = (hipStream_t)stream;
+    if (use_hugek(b)) return backward_hugek(b, approximate_L, raw_gradient, nullptr, nullptr, st);
     if (b->K > SC_KMAX) {
         // many components per scene: passes over chunks of eight (bigk.h)
         const int nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
@@ -1467,7 +1556,7 @@ static int backward_impl(scarlet_batch *b, int approximate_L, int raw_gradient, 
                 HIP_TRY(hipEventRecord(side->ev[2], side->st));
             }
             prof_start(0, st);
-            hipLaunchKernelGGL(k_bigk_lmorph, dim3(a.S), dim3(SC_WAVE), 0, st, a);
+            hipLaunchKernelGGL(k_bigk_lmorph<SC_KBIG>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
             prof_stop(st); prof_start(1, st);
             hipLaunchKernelGGL(k_bigk_fused, grid, dim3(SC_BLOCK), 0, st, a);
             if (side) HIP_TRY(hipStreamWaitEvent(st, side->ev[2], 0));
@@ -1489,12 +1578,12 @@ static int backward_impl(scarlet_batch *b, int approximate_L, int raw_gradient, 
             HIP_TRY(hipStreamWaitEvent(side->st, side->ev[0], 0));
             launch_bigk_gram(a, nch, side->st);
             prof_start(0, st);
-            hipLaunchKernelGGL(k_bigk_resid, grid, dim3(SC_BLOCK), 0, st, a, resid);
+            hipLaunchKernelGGL(k_bigk_resid<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a, resid);
             HIP_TRY(hipEventRecord(side->ev[1], st));
             HIP_TRY(hipStreamWaitEvent(side->st, side->ev[1], 0));
             hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, side->st, a, 1);
             HIP_TRY(hipEventRecord(side->ev[2], side->st));
-            hipLaunchKernelGGL(k_bigk_lmorph, dim3(a.S), dim3(SC_WAVE), 0, st, a);
+            hipLaunchKernelGGL(k_bigk_lmorph<SC_KBIG>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
             prof_stop(st); prof_start(1, st);
             launch_bigk_step(a, nch, resid, st);
             HIP_TRY(hipStreamWaitEvent(st, side->ev[2], 0));
@@ -1504,7 +1593,7 @@ static int backward_impl(scarlet_batch *b, int approximate_L, int raw_gradient, 
             return SCARLET_OK;
         }
         prof_start(0, st);
-        hipLaunchKernelGGL(k_bigk_resid, grid, dim3(SC_BLOCK), 0, st, a, resid);
+        hipLaunchKernelGGL(k_bigk_resid<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a, resid);
         launch_bigk_gram(a, nch, st);
         hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 0);
         prof_stop(st); prof_start(1, st);
