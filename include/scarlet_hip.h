@@ -270,7 +270,9 @@ typedef struct scarlet_batch {
     const int32_t *group;
 } scarlet_batch;
 
-/* bytes of device workspace needed for `b` (depends on S, K, B, H, W only) */
+/* bytes of device workspace needed for `b`.  Depends on S, K, B, H, W; on diff_kernel (NULL or not), psf_h, psf_w and
+   diff_kernel_per_scene; on group (NULL or not: it rules out two pipelines); and on the switches FORCE_HUGEK
+   (8 < K <= 32), PSF_HIPFFT and STAMPS (batches with a PSF), which this call fixes for the rest of the process */
 int64_t scarlet_batch_workspace_bytes(const scarlet_batch *b);
 /* Number of pipelines scarlet_fit() runs `b` as: 2 for a large batch with a PSF (>= 1024 scenes, K <= 8, the
  * LDS-resident transform) -- the two halves of the batch as views with their own workspace regions, the second on the

@@ -71,10 +71,10 @@ static void options_init(void)
     });
 }
 static inline int opt(int which) { options_init(); return g_opt[which].load(std::memory_order_relaxed); }
-// PSF_HIPFFT and STAMPS decide the LAYOUT of a PSF batch's workspace (psf_layout): they are read when a workspace is
+// PSF_HIPFFT and STAMPS decide the LAYOUT of a PSF batch's workspace (ws_layout): they are read when a workspace is
 // sized and again by every later call on that batch, so a change in between would move regions under a live batch
-// (K-hat and tables read from the wrong offsets, writes past the allocation).  The first layout computed in the
-// process therefore FREEZES the two switches: scarlet_set_option then refuses a different value (SCARLET_E_ARG).
+// (K-hat and tables read from the wrong offsets, writes past the allocation).  The first PSF layout computed for a live
+// batch (ws_layout, WS_FIX) therefore FREEZES the two switches: scarlet_set_option then refuses a different value.
 static std::atomic<bool> g_layout_frozen{false};
 // FORCE_HUGEK (diagnostics: the K > 32 gradient path of hugek.h for 8 < K <= 32 as well) adds the Gram area of that
 // path to the workspace of such batches: it freezes, likewise, once a workspace with 8 < K <= 32 has been sized.
@@ -809,43 +809,6 @@ static PsfGeom psf_geom(int H, int W, int Py, int Px)
     return g;
 }
 static int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-// frames whose tile does not fit LDS: per-component GEMM scratch of the k-space symmetry in HBM
-static int64_t gscratch_bytes(const scarlet_batch *b)
-{
-    if (b->H <= 64 && b->W <= 64) return 0;
-    if (update_lds_bytes(b->H, b->W) <= 80 * 1024) return 0;      // two workgroups per CU already
-    return align256(sizeof(float) * (int64_t)b->S * b->K * round16(b->H) * scratch_stride(round16(b->W)));
-}
-// cache of the k-space symmetry's Hankel vectors (k_iterate2, fused2.h); zero = empty (no magic word)
-static int64_t kscache_bytes(const scarlet_batch *b)
-{
-    if (b->K > 4 || b->B > 5 || b->H > 64 || b->W > 64) return 0;
-    return align256(sizeof(float) * (int64_t)b->S * b->K * 2 * SC_KSC_FLOATS);
-}
-// the gradient path of hugek.h: every K > SC_KBIG, and 8 < K <= SC_KBIG under FORCE_HUGEK
-static bool use_hugek(const scarlet_batch *b)
-{
-    if (b->K > SC_KBIG) return true;
-    if (b->K <= SC_KMAX) return false;
-    g_hugek_frozen.store(true);                       // (see scarlet_set_option)
-    return opt(OPT_FORCE_HUGEK) != 0;
-}
-// its Gram area: per-chunk blocks [S][pairs][C][32][32], then G and the two squaring buffers [S][Kp][Kp] (float64)
-static int64_t hugek_bytes(const scarlet_batch *b)
-{
-    if (!use_hugek(b)) return 0;
-    const int64_t Kp = (int64_t)huge_nblk(b->K) * SC_GBLK;
-    return align256(sizeof(double) * (int64_t)b->S * huge_npairs(b->K) * huge_nchunks(b->H * b->W) * SC_GBLK * SC_GBLK) +
-           3 * align256(sizeof(double) * (int64_t)b->S * Kp * Kp);
-}
-static int64_t base_workspace_bytes(const scarlet_batch *b)
-{
-    const int64_t P = n_partials(b->K, b->B);
-    // K > 8 (bigk.h): one scratch plane set [S][B][HW] for G = w^2 (model - image)
-    const int64_t resid = b->K > SC_KMAX ? align256(sizeof(float) * (int64_t)b->S * b->B * b->H * b->W) : 0;
-    return align256(sizeof(double) * ((int64_t)b->S * n_tiles(b) * P + (int64_t)b->S * b->K * 4) + sizeof(int) * (2 * (int64_t)b->S * b->K + 64)) +
-           resid + gscratch_bytes(b) + kscache_bytes(b) + hugek_bytes(b) + 256;
-}
 // ---- LDS-resident convolution (fftconv.h): plan = lengths, radices, kernel placement
 // smallest circular length that reproduces the cropped linear convolution: image at 0..N-1, kernel at
 // (q + o) mod F, output read at 0..N-1 (o <= 0 is the kernel's offset in the reference's padded array)
@@ -929,8 +892,6 @@ static void fft_fill_tables(const FftPlan &p, std::vector<float2> &t)
 }
 static bool psf_lds_possible(const scarlet_batch *b, FftPlan *p)
 {
-    FftPlan tmp;
-    if (!p) p = &tmp;
     if (b->W & 1) return false;                       // k_psf_conv reads pixel pairs (float2)
     return fft_make_plan(b->H, b->W, b->psf_h, b->psf_w, p);
 }
@@ -947,33 +908,112 @@ static bool psf_conv_finish_plan(const scarlet_batch *b, FftPlan *fp)
            fp->R2y == 15 && fp->R1x == 5 && fp->R2x == 15 && fp->dma_image == 1 && !opt(OPT_NO_EXACT);
 }
 
-// Workspace of a batch with a PSF.  Which convolution runs is a function of the shapes alone -- the
-// LDS-resident transform whenever the half-spectrum plane fits LDS, batched hipFFT otherwise (frames
-// beyond ~150 + P pixels) -- except for the diagnostic switch PSF_HIPFFT, which forces the library path
-// and must not change during the life of a batch (it is read when the workspace is sized).
-static bool psf_use_lds(const scarlet_batch *b, FftPlan *p) { return psf_lds_possible(b, p) && !opt(OPT_PSF_HIPFFT); }
-struct PsfLayout { int64_t loss, real, spec, khat, lds_khat, lds_tables, stamps, total; };
-static PsfLayout psf_layout(const scarlet_batch *b)
+// ---- the workspace: one device buffer, allocated by the caller (scarlet_batch_workspace_bytes) and zeroed once, holds
+// every kernel's scratch.  ws_layout() is the one place that decides which regions a batch has and where they lie;
+// every size and pointer comes from its result, computed once per entry-point call and passed down.
+// Which PSF convolution runs is a function of the shapes alone -- the LDS-resident transform whenever the half-spectrum
+// plane fits LDS, batched hipFFT otherwise (frames beyond ~150 + P pixels) -- except for the diagnostic switch
+// PSF_HIPFFT, which forces the library path.
+enum { GRAD_SMALL, GRAD_BIGK, GRAD_HUGEK };    // gradient step: K <= 8 (engine.h), chunks of eight (bigk.h), hugek.h
+struct WsLayout {
+    // the decisions that size regions
+    int grad;                           // GRAD_HUGEK: K > 32, and 8 < K <= 32 under FORCE_HUGEK
+    bool psf;                           // a diff_kernel of psf_h x psf_w (has_psf)
+    bool psf_lds;                       // its convolution runs in LDS (`plan`); false: batched hipFFT (`geom`)
+    bool has_gscratch, has_kscache;
+    bool split;                         // two half-batch pipelines are possible (split_views)
+    PsfGeom geom;
+    FftPlan plan;
+    int n0;                             // (split) scenes of the first half
+    // byte offsets of the base area
+    int64_t partials;                   // per-tile partials [S][T][P] (float64); at 0 for tools/stamps.py, tools/occupancy.py
+    int64_t conv;                       // convergence sums [S][K][4] (float64); scarlet_fit_multi's Lipschitz sums
+    int64_t box_fallback;               // per component: 1 = k_source_update_box left it to the full-frame kernel (int)
+    int64_t box_list, box_count;        // the components the small box left to the large one [S * K], their number (int)
+    int64_t gplanes;                    // K > 8: G = w^2 (model - image) [S][B][H][W] (float32)
+    int64_t gscratch;                   // frames whose tile does not fit LDS: the k-space symmetry's GEMM scratch per component
+    int64_t kscache;                    // k_iterate2's cache of the k-space symmetry's Hankel vectors (fused2.h); zero = empty
+    int64_t gpart, gram, msq[2];        // hugek.h (float64): Gram blocks [S][pairs][C][32][32]; G and the two squaring
+                                        // buffers [S][Kp][Kp]
+    int64_t fit2x_queue;                // k_fit2x's scene queue (int)
+    int64_t active_count;               // active scenes, counted for the host (int)
+    int64_t base_end;
+    // byte offsets of the PSF area
+    int64_t loss;                       // per-plane loss sums [S][B] (float64)
+    int64_t real;                       // hipFFT: padded planes [S][B][Fy][Fx]; LDS: compact gradient planes G [S][B][H][W]
+    int64_t spec, khat;                 // hipFFT: spectra of the planes and of the kernels (float2)
+    int64_t lds_khat, lds_tables;       // LDS: spectra of the kernels, twiddle / permutation tables (float2)
+    int64_t stamps;                     // LDS under STAMPS: k_psf_conv's phase stamps [S][B][32] (int64)
+    int64_t half[2];                    // (split) the workspace of each half-batch
+    int64_t total;
+};
+static bool has_psf(const scarlet_batch *b) { return b->diff_kernel && b->psf_h > 0 && b->psf_w > 0; }
+// How a call uses the layout.  WS_FIX: on a live batch -- the switches that placed its regions (FORCE_HUGEK for
+// 8 < K <= 32, PSF_HIPFFT and STAMPS for a PSF batch) stay fixed from then on (see scarlet_set_option).  WS_PEEK: the
+// call only reports, or reads regions no switch moves.  WS_HALF: one half of a split batch (no halves of its own).
+enum LayoutUse { WS_PEEK, WS_FIX, WS_HALF };
+static WsLayout ws_layout(const scarlet_batch *b, LayoutUse use)
 {
-    g_layout_frozen.store(true);                      // (see scarlet_set_option)
-    const PsfGeom g = psf_geom(b->H, b->W, b->psf_h, b->psf_w);
-    const int64_t planes = (int64_t)b->S * b->B;
-    const int64_t nk = b->diff_kernel_per_scene ? planes : (int64_t)b->B;
-    FftPlan p;
-    const bool lds = psf_use_lds(b, &p), want_hipfft = !lds;
-    PsfLayout l;
-    l.loss = base_workspace_bytes(b);
-    l.real = l.loss + align256(planes * (int64_t)sizeof(double));
-    // `real`: padded FFT planes (hipFFT path) or the compact gradient planes G [S][B][H][W] (LDS path)
-    l.spec = l.real + align256(planes * (want_hipfft ? (int64_t)g.Fy * g.Fx : (int64_t)b->H * b->W) * (int64_t)sizeof(float));
-    l.khat = l.spec + (want_hipfft ? align256(planes * g.Fy * g.Fxh * (int64_t)sizeof(float2)) : 0);
-    l.lds_khat = l.khat + (want_hipfft ? align256(nk * g.Fy * g.Fxh * (int64_t)sizeof(float2)) : 0);
-    l.lds_tables = l.lds_khat + (lds ? align256(nk * p.Fy * (p.M + 1) * (int64_t)sizeof(float2)) : 0);
-    l.stamps = l.lds_tables + (lds ? align256(fft_table_float2s(p.Fy, p.M) * (int64_t)sizeof(float2)) : 0);
-    // diagnostics (STAMPS switch, read when the workspace is sized): 32 shader-clock stamps per plane
-    l.total = l.stamps + ((lds && opt(OPT_STAMPS)) ? align256(planes * 32 * (int64_t)sizeof(long long)) : 0) + 256;
+    WsLayout l = {};
+    const int64_t S = b->S, K = b->K, B = b->B, HW = (int64_t)b->H * b->W;
+    int64_t at = 0;
+    auto place = [&at](int64_t bytes) { const int64_t o = at; at += bytes; return o; };
+    if (use == WS_FIX && K > SC_KMAX && K <= SC_KBIG) g_hugek_frozen.store(true);
+    l.grad = K <= SC_KMAX ? GRAD_SMALL : (K > SC_KBIG || opt(OPT_FORCE_HUGEK)) ? GRAD_HUGEK : GRAD_BIGK;
+    // (frames up to 80 KB of LDS run two workgroups per CU without the scratch)
+    l.has_gscratch = (b->H > 64 || b->W > 64) && update_lds_bytes(b->H, b->W) > 80 * 1024;
+    l.has_kscache = K <= 4 && B <= 5 && b->H <= 64 && b->W <= 64;
+    l.partials = place(sizeof(double) * S * n_tiles(b) * n_partials(b->K, b->B));
+    l.conv = place(sizeof(double) * S * K * 4);
+    l.box_fallback = place(sizeof(int) * S * K);
+    l.box_list = place(sizeof(int) * S * K);
+    l.box_count = place(sizeof(int) * 64);             // (the count, then 63 spare ints)
+    at = align256(at);
+    l.gplanes = place(l.grad != GRAD_SMALL ? align256(sizeof(float) * S * B * HW) : 0);
+    l.gscratch = place(l.has_gscratch ? align256(sizeof(float) * S * K * round16(b->H) * scratch_stride(round16(b->W))) : 0);
+    l.kscache = place(l.has_kscache ? align256(sizeof(float) * S * K * 2 * SC_KSC_FLOATS) : 0);
+    const bool huge = l.grad == GRAD_HUGEK;
+    const int64_t Kp = (int64_t)huge_nblk(b->K) * SC_GBLK, gram = huge ? align256(sizeof(double) * S * Kp * Kp) : 0;
+    l.gpart = place(huge ? align256(sizeof(double) * S * huge_npairs(b->K) * huge_nchunks(b->H * b->W) * SC_GBLK * SC_GBLK) : 0);
+    l.gram = place(gram);
+    l.msq[0] = place(gram);
+    l.msq[1] = place(gram);
+    const int64_t words = place(256);                  // the base area ends in 256 bytes that hold two words
+    l.fit2x_queue = words + 128;
+    l.active_count = words + 192;
+    l.base_end = l.total = at;
+    l.psf = has_psf(b);
+    if (!l.psf) return l;
+
+    if (use == WS_FIX) g_layout_frozen.store(true);
+    const int64_t planes = S * B, nk = b->diff_kernel_per_scene ? planes : B;
+    l.geom = psf_geom(b->H, b->W, b->psf_h, b->psf_w);
+    const PsfGeom &g = l.geom;
+    const FftPlan &p = l.plan;
+    const bool lds_possible = psf_lds_possible(b, &l.plan);
+    l.psf_lds = lds_possible && !opt(OPT_PSF_HIPFFT);
+    const bool fft = !l.psf_lds;
+    l.loss = place(align256(planes * (int64_t)sizeof(double)));
+    l.real = place(align256(planes * (fft ? (int64_t)g.Fy * g.Fx : HW) * (int64_t)sizeof(float)));
+    l.spec = place(fft ? align256(planes * g.Fy * g.Fxh * (int64_t)sizeof(float2)) : 0);
+    l.khat = place(fft ? align256(nk * g.Fy * g.Fxh * (int64_t)sizeof(float2)) : 0);
+    l.lds_khat = place(l.psf_lds ? align256(nk * p.Fy * (p.M + 1) * (int64_t)sizeof(float2)) : 0);
+    l.lds_tables = place(l.psf_lds ? align256(fft_table_float2s(p.Fy, p.M) * (int64_t)sizeof(float2)) : 0);
+    l.stamps = place((l.psf_lds && opt(OPT_STAMPS)) ? align256(planes * 32 * (int64_t)sizeof(long long)) : 0);
+    place(256);
+    // the regions of the halves follow (there under PSF_HIPFFT too, which runs one pipeline)
+    l.split = use != WS_HALF && K <= SC_KMAX && S >= 1024 && !b->group && HW % 4 == 0 && lds_possible;
+    if (l.split) {
+        scarlet_batch h = *b;
+        h.S = l.n0 = ((b->S / 2 + 7) / 8) * 8;        // (the convolution maps groups of eight scenes to the XCDs)
+        l.half[0] = place(align256(ws_layout(&h, WS_HALF).total));
+        h.S = b->S - l.n0;
+        l.half[1] = place(ws_layout(&h, WS_HALF).total);
+    }
+    l.total = at;
     return l;
 }
+template <typename T> static T *ws_at(const scarlet_batch *b, int64_t offset) { return (T *)((char *)b->workspace + offset); }
 
 // ---- two half-batches on two streams (scarlet_fit with a PSF, LDS-resident transform, K <= 8).
 // The convolution kernel is bound by the latency of its passes at one workgroup per CU and moves under 1 TB/s;
@@ -982,10 +1022,9 @@ static PsfLayout psf_layout(const scarlet_batch *b)
 // calling thread's second stream: one half's convolution overlaps the other half's streaming passes.  Each half
 // is a VIEW of the batch (every per-scene array advanced to its first scene) with its own workspace region behind
 // the batch's (its own K-hat and tables, prepared with the batch's): the kernels do not know.
-static bool split_possible(const scarlet_batch *b)
+static bool two_pipelines(const WsLayout &l)
 {
-    return b->diff_kernel && b->psf_h > 0 && b->psf_w > 0 && b->K <= SC_KMAX && b->S >= 1024 && !b->group &&
-           (b->H * b->W) % 4 == 0 && psf_lds_possible(b, nullptr);
+    return l.split && l.psf_lds && !opt(OPT_NO_PIPELINE) && !opt(OPT_NO_SIDE_STREAM);
 }
 static scarlet_batch batch_view(const scarlet_batch *b, int s0, int n, void *ws)
 {
@@ -1004,23 +1043,21 @@ static scarlet_batch batch_view(const scarlet_batch *b, int s0, int n, void *ws)
     v.workspace = ws;
     return v;
 }
-static void split_views(const scarlet_batch *b, scarlet_batch v[2])
+static void split_views(const scarlet_batch *b, const WsLayout &l, scarlet_batch v[2], WsLayout lv[2])
 {
-    const int n0 = ((b->S / 2 + 7) / 8) * 8;            // (the convolution maps groups of eight scenes to the XCDs)
-    char *ws = (char *)b->workspace + psf_layout(b).total;
-    v[0] = batch_view(b, 0, n0, ws);
-    v[1] = batch_view(b, n0, b->S - n0, ws + align256(psf_layout(&v[0]).total));
+    v[0] = batch_view(b, 0, l.n0, ws_at<char>(b, l.half[0]));
+    v[1] = batch_view(b, l.n0, b->S - l.n0, ws_at<char>(b, l.half[1]));
+    for (int h = 0; h < 2; ++h) lv[h] = ws_layout(&v[h], WS_HALF);
 }
 
-// diagnostics (STAMPS switch): byte offset, inside the batch's workspace, of k_psf_conv's phase stamps
-// ([S][B][32] int64 shader-clock values), or -1 when the batch has none
 // diagnostics: the plan of the LDS-resident convolution for this batch, 16 ints {H, W, Fy, Fx, M, RS, R1y, R2y, R1x, R2x,
 // oky, okx, dma_image, exact-shape instance, LDS bytes, 0}; returns 0, or -1 when the batch takes another path
 extern "C" int scarlet_debug_psf_plan(const scarlet_batch *b, int32_t *out16)
 {
-    if (!b || !out16 || !b->diff_kernel || b->psf_h <= 0 || b->psf_w <= 0) return -1;
-    FftPlan p;
-    if (!psf_use_lds(b, &p)) return -1;
+    if (!b || !out16) return -1;
+    const WsLayout l = ws_layout(b, WS_PEEK);
+    if (!l.psf_lds) return -1;
+    FftPlan p = l.plan;
     const bool x = psf_conv_finish_plan(b, &p);
     const int v[16] = {p.H, p.W, p.Fy, p.Fx, p.M, p.RS, p.R1y, p.R2y, p.R1x, p.R2x, p.oky, p.okx, p.dma_image, x ? 1 : 0,
                        (int)fft_lds_bytes(p.Fy, p.M, p.RS, b->H, b->W, p.dma_image != 0), 0};
@@ -1028,89 +1065,33 @@ extern "C" int scarlet_debug_psf_plan(const scarlet_batch *b, int32_t *out16)
     return 0;
 }
 
+// diagnostics (STAMPS switch): byte offset, inside the batch's workspace, of k_psf_conv's phase stamps
+// ([S][B][32] int64 shader-clock values), or -1 when the batch has none
 extern "C" int64_t scarlet_debug_psf_stamps_offset(const scarlet_batch *b)
 {
-    if (!b || !b->diff_kernel || b->psf_h <= 0 || b->psf_w <= 0 || !opt(OPT_STAMPS)) return -1;
-    FftPlan p;
-    if (!psf_use_lds(b, &p)) return -1;
-    return psf_layout(b).stamps;
+    if (!b || !opt(OPT_STAMPS) || !ws_layout(b, WS_PEEK).psf_lds) return -1;
+    return ws_layout(b, WS_FIX).stamps;               // (only a batch that has stamps fixes the switches)
 }
 
 extern "C" int scarlet_batch_pipelines(const scarlet_batch *b)
 {
     if (!b) return 0;
-    return (split_possible(b) && !opt(OPT_PSF_HIPFFT) && !opt(OPT_NO_PIPELINE) && !opt(OPT_NO_SIDE_STREAM)) ? 2 : 1;
+    return two_pipelines(ws_layout(b, WS_PEEK)) ? 2 : 1;
 }
 
 extern "C" int64_t scarlet_batch_workspace_bytes(const scarlet_batch *b)
 {
-    if (!b) return 0;
-    if (b->diff_kernel && b->psf_h > 0 && b->psf_w > 0) {
-        int64_t total = psf_layout(b).total;
-        if (split_possible(b)) {
-            scarlet_batch v[2];
-            scarlet_batch tmp = *b;
-            tmp.workspace = nullptr;
-            const int n0 = ((b->S / 2 + 7) / 8) * 8;
-            v[0] = tmp; v[0].S = n0; v[1] = tmp; v[1].S = b->S - n0;
-            total += align256(psf_layout(&v[0]).total) + psf_layout(&v[1]).total;
-        }
-        return total;
-    }
-    return base_workspace_bytes(b);
+    return b ? ws_layout(b, WS_FIX).total : 0;
 }
 
-static double *ws_partials(const scarlet_batch *b) { return (double *)b->workspace; }
-static double *ws_conv(const scarlet_batch *b)
-{
-    return (double *)b->workspace + (size_t)b->S * n_tiles(b) * n_partials(b->K, b->B);
-}
-
-static float *ws_resid(const scarlet_batch *b)
-{
-    const int64_t P = n_partials(b->K, b->B);
-    return (float *)((char *)b->workspace +
-                     align256(sizeof(double) * ((int64_t)b->S * n_tiles(b) * P + (int64_t)b->S * b->K * 4) + sizeof(int) * (2 * (int64_t)b->S * b->K + 64)));
-}
-// per component: 1 = k_source_update_box left it to the full-frame kernel (behind the convergence sums)
-static int *ws_box_fallback(const scarlet_batch *b) { return (int *)(ws_conv(b) + (size_t)b->S * b->K * 4); }
-// the components the small box left to the large one: list [S * K] + its length (behind the fallback flags)
-static int *ws_box_list(const scarlet_batch *b) { return ws_box_fallback(b) + (size_t)b->S * b->K; }
-
-static float *ws_gscratch(const scarlet_batch *b)
-{
-    const int64_t resid = b->K > SC_KMAX ? align256(sizeof(float) * (int64_t)b->S * b->B * b->H * b->W) : 0;
-    return (float *)((char *)ws_resid(b) + resid);
-}
-
-static float *ws_kscache(const scarlet_batch *b)
-{
-    return kscache_bytes(b) ? (float *)((char *)ws_gscratch(b) + gscratch_bytes(b)) : nullptr;
-}
-
-static HugeArgs huge_args(const scarlet_batch *b)
-{
-    const int64_t Kp = (int64_t)huge_nblk(b->K) * SC_GBLK;
-    char *p = (char *)ws_gscratch(b) + gscratch_bytes(b) + kscache_bytes(b);
-    HugeArgs h;
-    h.C = huge_nchunks(b->H * b->W);
-    h.gpart = (double *)p;
-    p += align256(sizeof(double) * (int64_t)b->S * huge_npairs(b->K) * h.C * SC_GBLK * SC_GBLK);
-    h.gram = (double *)p;
-    p += align256(sizeof(double) * (int64_t)b->S * Kp * Kp);
-    h.msq[0] = (double *)p;
-    h.msq[1] = (double *)(p + align256(sizeof(double) * (int64_t)b->S * Kp * Kp));
-    return h;
-}
-
-static GradArgs grad_args(const scarlet_batch *b, int approximate_L, int raw_gradient = 0)
+static GradArgs grad_args(const scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient)
 {
     GradArgs a;
     a.S = b->S; a.K = b->K; a.B = b->B; a.HW = b->H * b->W; a.T = n_tiles(b);
     a.images = b->images; a.weights = b->weights; a.weight_scalar = b->weight_scalar;
     a.sed[0] = b->sed[0]; a.sed[1] = b->sed[1]; a.morph[0] = b->morph[0]; a.morph[1] = b->morph[1];
     a.cur = b->cur; a.fix_sed = b->fix_sed; a.fix_morph = b->fix_morph;
-    a.partials = ws_partials(b); a.lipschitz = b->lipschitz; a.mse = b->mse; a.mse_capacity = b->mse_capacity;
+    a.partials = ws_at<double>(b, l.partials); a.lipschitz = b->lipschitz; a.mse = b->mse; a.mse_capacity = b->mse_capacity;
     a.it = b->it; a.active = b->active; a.approximate_L = approximate_L; a.raw_gradient = raw_gradient;
     return a;
 }
@@ -1154,44 +1135,29 @@ static int fft_c2r(const FftPlans &p, float2 *in, float *out, hipStream_t st)
 }
 static unsigned grid_for(int64_t n) { int64_t g = (n + SC_BLOCK - 1) / SC_BLOCK; return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); }
 
-static int prepare_psf_impl(scarlet_batch *b, void *stream);
-extern "C" int scarlet_batch_prepare_psf(scarlet_batch *b, void *stream)
+static int prepare_psf_impl(scarlet_batch *b, const WsLayout &l, void *stream)
 {
-    int rc = prepare_psf_impl(b, stream);
-    if (rc == SCARLET_OK && split_possible(b) && !opt(OPT_PSF_HIPFFT)) {
-        scarlet_batch v[2];
-        split_views(b, v);
-        for (int h = 0; h < 2 && rc == SCARLET_OK; ++h) rc = prepare_psf_impl(&v[h], stream);
-    }
-    return rc;
-}
-static int prepare_psf_impl(scarlet_batch *b, void *stream)
-{
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!b->diff_kernel || b->psf_h <= 0 || b->psf_w <= 0) return set_err(SCARLET_E_ARG, "no diff_kernel in batch");
-    const PsfGeom g = psf_geom(b->H, b->W, b->psf_h, b->psf_w);
-    const PsfLayout l = psf_layout(b);
+    const PsfGeom &g = l.geom;
     hipStream_t st = (hipStream_t)stream;
     const int nk = b->diff_kernel_per_scene ? b->S * b->B : b->B;
-    FftPlan fp;
-    if (psf_use_lds(b, &fp)) {
+    int rc;
+    if (l.psf_lds) {
         // LDS-resident transform (fftconv.h): tables, then K-hat by the same forward code as the iteration
+        FftPlan fp = l.plan;
         std::vector<float2> tab;
         fft_fill_tables(fp, tab);
-        float2 *dtab = (float2 *)((char *)b->workspace + l.lds_tables);
+        float2 *dtab = ws_at<float2>(b, l.lds_tables);
         HIP_TRY(hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));            // `tab` is host memory of this call
         fp.tables = dtab;
         const size_t lds = fft_lds_bytes(fp.Fy, fp.M, fp.RS);
         if ((rc = allow_lds(k_fft_khat, lds))) return rc;
-        hipLaunchKernelGGL(k_fft_khat, dim3(nk), dim3(SC_FFT_NT), lds, st, b->diff_kernel, fp,
-                           (float2 *)((char *)b->workspace + l.lds_khat));
+        hipLaunchKernelGGL(k_fft_khat, dim3(nk), dim3(SC_FFT_NT), lds, st, b->diff_kernel, fp, ws_at<float2>(b, l.lds_khat));
         HIP_TRY(hipGetLastError());
         return SCARLET_OK;
     }
-    float *real = (float *)((char *)b->workspace + l.real);
-    float2 *khat = (float2 *)((char *)b->workspace + l.khat);
+    float *real = ws_at<float>(b, l.real);
+    float2 *khat = ws_at<float2>(b, l.khat);
     const int oky = (g.Fry - b->psf_h + 1) / 2 - g.Fry / 2, okx = (g.Frx - b->psf_w + 1) / 2 - g.Frx / 2;
     hipLaunchKernelGGL(k_psf_pad_kernel, dim3(grid_for((int64_t)nk * g.Fy * g.Fx)), dim3(SC_BLOCK), 0, st,
                        b->diff_kernel, nk, b->psf_h, b->psf_w, g.Fy, g.Fx, oky, okx, real);
@@ -1202,6 +1168,21 @@ static int prepare_psf_impl(scarlet_batch *b, void *stream)
     if ((rc = get_plans(g.Fy, g.Fx, b->S * b->B, &pb))) return rc;     // create the big plans now
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
+}
+extern "C" int scarlet_batch_prepare_psf(scarlet_batch *b, void *stream)
+{
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if (!has_psf(b)) return set_err(SCARLET_E_ARG, "no diff_kernel in batch");
+    const WsLayout l = ws_layout(b, WS_FIX);
+    rc = prepare_psf_impl(b, l, stream);
+    if (rc == SCARLET_OK && l.split && l.psf_lds) {
+        scarlet_batch v[2];
+        WsLayout lv[2];
+        split_views(b, l, v, lv);
+        for (int h = 0; h < 2 && rc == SCARLET_OK; ++h) rc = prepare_psf_impl(&v[h], lv[h], stream);
+    }
+    return rc;
 }
 
 // A second stream per calling thread for work that is off an iteration's critical path (fork / join by events, so a
@@ -1254,19 +1235,22 @@ static void launch_bigk_step(const GradArgs &a, int nch, const float *resid, hip
 
 // The gradient step for K > SC_KBIG (hugek.h).  Without a PSF it starts from the morphologies (k_bigk_resid); with one,
 // `psf_resid` holds the compact gradient planes G [S][B][H][W] and `psf_loss` the per-plane loss sums.
-static int backward_hugek(scarlet_batch *b, int approximate_L, int raw_gradient, const float *psf_resid,
+static int backward_hugek(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, const float *psf_resid,
                           const double *psf_loss, hipStream_t st)
 {
-    const GradArgs a = grad_args(b, approximate_L, raw_gradient);
-    const HugeArgs h = huge_args(b);
+    const GradArgs a = grad_args(b, l, approximate_L, raw_gradient);
+    HugeArgs h;
+    h.C = huge_nchunks(b->H * b->W);
+    h.gpart = ws_at<double>(b, l.gpart); h.gram = ws_at<double>(b, l.gram);
+    h.msq[0] = ws_at<double>(b, l.msq[0]); h.msq[1] = ws_at<double>(b, l.msq[1]);
     const int nb = huge_nblk(b->K), npairs = huge_npairs(b->K), nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
     const float *resid = psf_resid;
     prof_start(0, st);
     if (psf_resid)
         hipLaunchKernelGGL(k_bigk_loss_from_planes, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a, psf_loss);
     else {
-        resid = ws_resid(b);
-        hipLaunchKernelGGL((k_bigk_resid<SC_KHUGE>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a, ws_resid(b));
+        resid = ws_at<float>(b, l.gplanes);
+        hipLaunchKernelGGL((k_bigk_resid<SC_KHUGE>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a, ws_at<float>(b, l.gplanes));
     }
     if ((a.HW & 3) == 0) hipLaunchKernelGGL((k_huge_gram<true>), dim3(h.C, npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
     else hipLaunchKernelGGL((k_huge_gram<false>), dim3(h.C, npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
@@ -1287,20 +1271,19 @@ static int backward_hugek(scarlet_batch *b, int approximate_L, int raw_gradient,
     return SCARLET_OK;
 }
 
-static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradient, void *stream)
+static int backward_step_psf(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, void *stream)
 {
-    const PsfGeom g = psf_geom(b->H, b->W, b->psf_h, b->psf_w);
-    const PsfLayout l = psf_layout(b);
+    const PsfGeom &g = l.geom;
     hipStream_t st = (hipStream_t)stream;
     PsfArgs a;
     a.S = b->S; a.K = b->K; a.B = b->B; a.T = n_tiles(b); a.g = g;
     a.images = b->images; a.weights = b->weights; a.weight_scalar = b->weight_scalar;
     a.sed[0] = b->sed[0]; a.sed[1] = b->sed[1]; a.morph[0] = b->morph[0]; a.morph[1] = b->morph[1];
     a.cur = b->cur; a.fix_sed = b->fix_sed; a.fix_morph = b->fix_morph;
-    a.real = (float *)((char *)b->workspace + l.real);
-    a.spec = (float2 *)((char *)b->workspace + l.spec);
-    a.khat = (const float2 *)((char *)b->workspace + l.khat);
-    a.partials = ws_partials(b); a.loss_part = (double *)((char *)b->workspace + l.loss);
+    a.real = ws_at<float>(b, l.real);
+    a.spec = ws_at<float2>(b, l.spec);
+    a.khat = ws_at<const float2>(b, l.khat);
+    a.partials = ws_at<double>(b, l.partials); a.loss_part = ws_at<double>(b, l.loss);
     a.lipschitz = b->lipschitz; a.mse = b->mse; a.mse_capacity = b->mse_capacity;
     a.it = b->it; a.active = b->active; a.approximate_L = approximate_L; a.raw_gradient = raw_gradient;
     const int planes = b->S * b->B;
@@ -1309,13 +1292,13 @@ static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradie
     const int nkh = b->diff_kernel_per_scene ? planes : b->B;
     a.khat_per_scene = b->diff_kernel_per_scene;
     int rc;
-    FftPlan fp;
-    const bool lds_path = psf_use_lds(b, &fp);
-    const bool three_pass = lds_path && (b->H * b->W) % 4 == 0 && b->K <= SC_KMAX && !opt(OPT_NO_PSF3PASS);
+    FftPlan fp = l.plan;
+    const bool lds_path = l.psf_lds;
+    const bool three_pass = lds_path && (b->H * b->W) % 4 == 0 && l.grad == GRAD_SMALL && !opt(OPT_NO_PSF3PASS);
     if (lds_path) {
         // one kernel: model, render, residual + loss, adjoint -> compact gradient planes G [S][B][H][W] in `real`
-        fp.tables = (const float2 *)((char *)b->workspace + l.lds_tables);
-        a.khat = (const float2 *)((char *)b->workspace + l.lds_khat);
+        fp.tables = ws_at<const float2>(b, l.lds_tables);
+        a.khat = ws_at<const float2>(b, l.lds_khat);
         const bool x128 = psf_conv_finish_plan(b, &fp);
         const size_t lds = fft_lds_bytes(fp.Fy, fp.M, fp.RS, b->H, b->W, fp.dma_image != 0);
         if ((rc = allow_lds(k_psf_conv, lds))) return rc;
@@ -1336,7 +1319,7 @@ static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradie
             hipLaunchKernelGGL(k_psf_model4<SC_KBIG>, dim3(((b->H * b->W) / 4 + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
         else
             hipLaunchKernelGGL(k_psf_model<SC_KBIG>, dim3((b->H * b->W + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
-        long long *stamps = opt(OPT_STAMPS) ? (long long *)((char *)b->workspace + l.stamps) : nullptr;
+        long long *stamps = opt(OPT_STAMPS) ? ws_at<long long>(b, l.stamps) : nullptr;
         fp.stagger_wgs = 0;
         if (x128) {
             // (the instance keeps the image in registers unless built with SC_X128_DMA: plane + tables only)
@@ -1366,18 +1349,18 @@ static int backward_step_psf(scarlet_batch *b, int approximate_L, int raw_gradie
     prof_stop(st);
     }
     dim3 grid(a.T, a.S);
-    if (use_hugek(b)) {
-        float *resid = lds_path ? a.real : ws_resid(b);
+    if (l.grad == GRAD_HUGEK) {
+        float *resid = lds_path ? a.real : ws_at<float>(b, l.gplanes);
         if (!lds_path)
             hipLaunchKernelGGL(k_plane_crop, dim3(grid_for((int64_t)planes * b->H * b->W)), dim3(SC_BLOCK), 0, st,
                                (const float *)a.real, planes, b->H, b->W, g.Fy, g.Fx, g.oy, g.ox, resid);
-        return backward_hugek(b, approximate_L, raw_gradient, resid, (const double *)a.loss_part, st);
+        return backward_hugek(b, l, approximate_L, raw_gradient, resid, (const double *)a.loss_part, st);
     }
-    if (b->K > SC_KMAX) {
+    if (l.grad == GRAD_BIGK) {
         // many components: G is cropped out of the FFT buffers once (the LDS path's planes are compact already),
         // then the chunked passes of bigk.h
-        GradArgs ga = grad_args(b, approximate_L, raw_gradient);
-        float *resid = lds_path ? a.real : ws_resid(b);
+        GradArgs ga = grad_args(b, l, approximate_L, raw_gradient);
+        float *resid = lds_path ? a.real : ws_at<float>(b, l.gplanes);
         const int nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
         prof_start(0, st);
         if (!lds_path)
@@ -1528,19 +1511,20 @@ extern "C" int scarlet_convolve_same(const float *model, int n, int H, int W, co
 }
 
 // raw_gradient = 0: buffer 1-cur receives the stepped factors; 1: the gradients themselves
-static int backward_impl(scarlet_batch *b, int approximate_L, int raw_gradient, void *stream)
+static int backward_impl(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, void *stream)
 {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (b->diff_kernel) return backward_step_psf(b, approximate_L, raw_gradient, stream);
-    GradArgs a = grad_args(b, approximate_L, raw_gradient);
+    int rc;
+    if (b->diff_kernel)            // (a kernel without a size has no PSF area in the workspace)
+        return l.psf ? backward_step_psf(b, l, approximate_L, raw_gradient, stream)
+                     : set_err(SCARLET_E_ARG, "diff_kernel without psf_h, psf_w");
+    GradArgs a = grad_args(b, l, approximate_L, raw_gradient);
     dim3 grid(a.T, a.S);
     hipStream_t st = (hipStream_t)stream;
-    if (use_hugek(b)) return backward_hugek(b, approximate_L, raw_gradient, nullptr, nullptr, st);
-    if (b->K > SC_KMAX) {
+    if (l.grad == GRAD_HUGEK) return backward_hugek(b, l, approximate_L, raw_gradient, nullptr, nullptr, st);
+    if (l.grad == GRAD_BIGK) {
         // many components per scene: passes over chunks of eight (bigk.h)
         const int nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
-        float *resid = ws_resid(b);
+        float *resid = ws_at<float>(b, l.gplanes);
         SideStream *side = nullptr;
         if (!opt(OPT_NO_SIDE_STREAM) && (rc = side_stream(&side))) return rc;
         if (!approximate_L && (a.HW & 63) == 0 && !opt(OPT_NO_BIGK_FUSED)) {
@@ -1622,17 +1606,19 @@ static int backward_impl(scarlet_batch *b, int approximate_L, int raw_gradient, 
 
 extern "C" int scarlet_backward_step(scarlet_batch *b, int approximate_L, void *stream)
 {
-    return backward_impl(b, approximate_L, 0, stream);
+    const int rc = check_batch(b);
+    return rc ? rc : backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 0, stream);
 }
 
 extern "C" int scarlet_backward_gradients(scarlet_batch *b, int approximate_L, void *stream)
 {
-    return backward_impl(b, approximate_L, 1, stream);
+    const int rc = check_batch(b);
+    return rc ? rc : backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 1, stream);
 }
 
 __global__ void k_zero_int(int *p) { *p = 0; }
 
-static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void *stream)
+static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, int force_it0, void *stream)
 {
     int rc = ensure_tables();
     if (rc) return rc;
@@ -1643,7 +1629,7 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
     u.centers = b->centers; u.shifts = b->shifts; u.lipschitz = b->lipschitz; u.it = b->it; u.active = b->active;
     u.status = b->status; u.symmetric = b->symmetric; u.monotonic = b->monotonic;
     u.l0_thresh = b->l0_thresh; u.l1_thresh = b->l1_thresh;
-    u.centroid_psf = b->centroid_psf; u.centroid_P = b->centroid_P; u.conv = ws_conv(b); u.force_it0 = force_it0;
+    u.centroid_psf = b->centroid_psf; u.centroid_P = b->centroid_P; u.conv = ws_at<double>(b, l.conv); u.force_it0 = force_it0;
     u.gscratch = nullptr;
     u.only_flagged = nullptr;
     u.group = b->group;
@@ -1665,8 +1651,7 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
         const size_t lds1 = sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 31) : ub_lds_floats(b->H, b->W, 31)),
                      lds2 = sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 63) : ub_lds_floats(b->H, b->W, 63));
         long long *dbg = debug_stamps((size_t)b->S * b->K * 16);
-        int *fb = ws_box_fallback(b);
-        int *list = ws_box_list(b), *count = list + (size_t)b->S * b->K;
+        int *fb = ws_at<int>(b, l.box_fallback), *list = ws_at<int>(b, l.box_list), *count = ws_at<int>(b, l.box_count);
         hipStream_t st = (hipStream_t)stream;
         const bool second = !opt(OPT_NO_BOX2);
         if (second) hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, count);   // (a 4-byte hipMemsetAsync costs 16 us)
@@ -1703,9 +1688,9 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
         const size_t lds = update_lds_bytes(b->H, b->W);
         const size_t lds1 = sizeof(float) * ((size_t)b->H * tile_stride(b->W) + 2 * round16(b->H) + 5 * round16(b->W) +
                                              stage_floats(round16(b->H), round16(b->W)));
-        if (lds > 80 * 1024 && lds1 <= 78 * 1024 && gscratch_bytes(b) > 0) {
+        if (lds > 80 * 1024 && lds1 <= 78 * 1024 && l.has_gscratch) {
             // scratch in HBM: two workgroups per CU instead of one
-            u.gscratch = ws_gscratch(b);
+            u.gscratch = ws_at<float>(b, l.gscratch);
             rc = allow_lds(k_source_update<1>, lds1);
             if (rc) return rc;
             hipLaunchKernelGGL(k_source_update<1>, dim3(b->S * b->K), dim3(SC_BLOCK), lds1, (hipStream_t)stream, u);
@@ -1716,7 +1701,7 @@ static int launch_update(scarlet_batch *b, int in_iteration, int force_it0, void
         }
     } else {
         // frames beyond the LDS tile (up to SCARLET_MAX_SIDE): operators in place on the plane in HBM / L2
-        u.gscratch = ws_gscratch(b);
+        u.gscratch = ws_at<float>(b, l.gscratch);
         const size_t lds = sizeof(float) * (2 * round16(b->H) + 5 * round16(b->W) +       // av, bv, cv, zv, stage
                                             stage_floats(round16(b->H), round16(b->W)));
         if ((rc = allow_lds(k_source_update<2>, lds))) return rc;                         // (94 KB at 1024 x 1024)
@@ -1730,17 +1715,20 @@ extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *s
 {
     int rc = check_batch(b);
     if (rc) return rc;
-    return launch_update(b, in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream);
+    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream);
 }
 
-extern "C" int scarlet_check_convergence(scarlet_batch *b, double e_rel, void *stream)
+static int launch_converge(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream)
 {
-    int rc = check_batch(b);
-    if (rc) return rc;
     hipLaunchKernelGGL(k_converge, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
-                       b->S, b->K, ws_conv(b), b->flags, b->active, b->it, b->cur, e_rel * e_rel);
+                       b->S, b->K, ws_at<double>(b, l.conv), b->flags, b->active, b->it, b->cur, e_rel * e_rel);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
+}
+extern "C" int scarlet_check_convergence(scarlet_batch *b, double e_rel, void *stream)
+{
+    const int rc = check_batch(b);
+    return rc ? rc : launch_converge(b, ws_layout(b, WS_PEEK), e_rel, stream);
 }
 
 // workgroups of k_fit2x the current device keeps resident at once (occupancy query x compute units), per device
@@ -1779,7 +1767,7 @@ static bool fused_ok(const scarlet_batch *b, int approximate_L)
 }
 // n_iter > 1: that many iterations in ONE launch where the persistent form exists (k_fit2: the headline shape's
 // exact instance); *done receives the number of iterations the launch covers
-static int launch_fused(scarlet_batch *b, double e_rel, void *stream, int n_iter = 1, int *done = nullptr)
+static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream, int n_iter, int *done)
 {
     if (done) *done = 1;
     int rc = ensure_tables();
@@ -1795,8 +1783,8 @@ static int launch_fused(scarlet_batch *b, double e_rel, void *stream, int n_iter
     f.symmetric = b->symmetric; f.monotonic = b->monotonic; f.l0_thresh = b->l0_thresh; f.l1_thresh = b->l1_thresh;
     f.centroid_psf = b->centroid_psf; f.centroid_P = b->centroid_P; f.e_rel2 = e_rel * e_rel;
     // diagnostics: SCARLET_STAMPS=1 writes phase stamps into the (otherwise unused) partials area
-    f.kscache = (b->diff_kernel || opt(OPT_NO_KSCACHE)) ? nullptr : ws_kscache(b);
-    f.stamps = (opt(OPT_STAMPS) && n_partials(b->K, b->B) >= 16) ? (long long *)ws_partials(b) : nullptr;
+    f.kscache = (!l.has_kscache || b->diff_kernel || opt(OPT_NO_KSCACHE)) ? nullptr : ws_at<float>(b, l.kscache);
+    f.stamps = (opt(OPT_STAMPS) && n_partials(b->K, b->B) >= 16) ? ws_at<long long>(b, l.partials) : nullptr;
     // experiment knob: SCARLET_PAD_LDS=<bytes> lowers the number of co-resident workgroups
     const size_t lds = fused_lds_bytes(b) + (size_t)opt(OPT_PAD_LDS);
     hipStream_t st = (hipStream_t)stream;
@@ -1836,7 +1824,7 @@ static int launch_fused(scarlet_batch *b, double e_rel, void *stream, int n_iter
             int n_wg = 0;
             if ((rc = fit2x_resident_workgroups(lds2x, &n_wg))) return rc;
             if (n_wg > b->S || (opt(OPT_PERSIST_DBG) & 4)) n_wg = b->S;            // (4: diagnostic, one workgroup per scene)
-            int *queue = (int *)((char *)b->workspace + base_workspace_bytes(b) - 128);
+            int *queue = ws_at<int>(b, l.fit2x_queue);
             HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), st));
             prof_start(4, st, n_iter);
             hipLaunchKernelGGL(k_fit2x, dim3(n_wg), dim3(SC_FB2), lds2x, st, f, n_iter | ((opt(OPT_PERSIST_DBG) & 1) << 30), queue, n_wg);
@@ -1881,15 +1869,17 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
     if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
     hipStream_t st = (hipStream_t)stream;
     int launched = 0;
-    int *d_count = (int *)((char *)b->workspace + base_workspace_bytes(b) - 64);
+    const WsLayout l = ws_layout(b, WS_FIX);
+    int *d_count = ws_at<int>(b, l.active_count);
     const bool fused = fused_ok(b, approximate_L);
-    if (!fused && scarlet_batch_pipelines(b) == 2) {
-        // two half-batches, two streams (see split_possible)
+    if (!fused && two_pipelines(l)) {
+        // two half-batches, two streams (see split_views)
         SideStream *side = nullptr;
         if ((rc = side_stream(&side))) return rc;
         if (side) {
             scarlet_batch v[2];
-            split_views(b, v);
+            WsLayout lv[2];
+            split_views(b, l, v, lv);
             hipStream_t sv[2] = {st, side->st};
             bool forked = false;
             // (an error between fork and join: the caller's stream still gets the second stream's work ordered before
@@ -1906,11 +1896,11 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
                     forked = true;
                 }
                 for (int h = 0; h < 2; ++h) {
-                    if ((rc = scarlet_backward_step(&v[h], approximate_L, sv[h]))) return bail(rc);
+                    if ((rc = backward_impl(&v[h], lv[h], approximate_L, 0, sv[h]))) return bail(rc);
                     prof_start(2, sv[h]);
-                    if ((rc = launch_update(&v[h], 1, 0, sv[h]))) return bail(rc);
+                    if ((rc = launch_update(&v[h], lv[h], 1, 0, sv[h]))) return bail(rc);
                     prof_stop(sv[h]); prof_start(3, sv[h]);
-                    if ((rc = scarlet_check_convergence(&v[h], e_rel, sv[h]))) return bail(rc);
+                    if ((rc = launch_converge(&v[h], lv[h], e_rel, sv[h]))) return bail(rc);
                     prof_stop(sv[h]);
                 }
                 ++launched;
@@ -1937,14 +1927,14 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
             // up to the next host check (or the end) in one launch where the persistent kernel applies
             int want = max_iter - i, did = 1;
             if (check_every > 0) { const int to_check = check_every - i % check_every; if (to_check < want) want = to_check; }
-            if ((rc = launch_fused(b, e_rel, stream, want, &did))) return rc;
+            if ((rc = launch_fused(b, l, e_rel, stream, want, &did))) return rc;
             i += did - 1; launched += did - 1;
         } else {
-            if ((rc = scarlet_backward_step(b, approximate_L, stream))) return rc;
+            if ((rc = backward_impl(b, l, approximate_L, 0, stream))) return rc;
             prof_start(2, st);
-            if ((rc = launch_update(b, 1, 0, stream))) return rc;
+            if ((rc = launch_update(b, l, 1, 0, stream))) return rc;
             prof_stop(st); prof_start(3, st);
-            if ((rc = scarlet_check_convergence(b, e_rel, stream))) return rc;
+            if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
             prof_stop(st);
         }
         ++launched;
@@ -1984,23 +1974,26 @@ extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs
         m.obs[o].mse = ob->mse; m.obs[o].mse_capacity = ob->mse_capacity; m.obs[o].B = ob->B; m.obs[o].band0 = band0[o];
     }
     hipStream_t st = (hipStream_t)stream;
+    const WsLayout l = ws_layout(state, WS_FIX);
+    WsLayout lo[SC_MULTI_MAX];
+    for (int o = 0; o < n_obs; ++o) lo[o] = ws_layout(obs[o], WS_FIX);
     // scratch for the approximate Lipschitz sums: the state's convergence-sum area is free until the update runs
-    double *approx = ws_conv(state);
-    int *d_count = (int *)((char *)state->workspace + base_workspace_bytes(state) - 64);
+    double *approx = ws_at<double>(state, l.conv);
+    int *d_count = ws_at<int>(state, l.active_count);
     const dim3 gridc((m.HW + 4 * SC_BLOCK - 1) / (4 * SC_BLOCK), m.S * m.K);
     int launched = 0;
     for (int i = 0; i < max_iter; ++i) {
         hipLaunchKernelGGL(k_multi_scatter, gridc, dim3(SC_BLOCK), 0, st, m);
         for (int o = 0; o < n_obs; ++o)
-            if ((rc = scarlet_backward_gradients(obs[o], 0, stream))) return rc;
+            if ((rc = backward_impl(obs[o], lo[o], 0, 1, stream))) return rc;
         // exact L of the FULL factors (blend.py:205-218): the state's own gradient pass (its loss and gradients
         // are overwritten below); approximate L: the two sums of squares
         if (approximate_L) hipLaunchKernelGGL(k_multi_approx, dim3(m.S), dim3(SC_BLOCK), 0, st, m, approx);
-        else if ((rc = scarlet_backward_gradients(state, 0, stream))) return rc;
+        else if ((rc = backward_impl(state, l, 0, 1, stream))) return rc;
         hipLaunchKernelGGL(k_multi_loss, dim3((m.S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, m, (const double *)approx);
         hipLaunchKernelGGL(k_multi_step, gridc, dim3(SC_BLOCK), 0, st, m);
-        if ((rc = launch_update(state, 1, 0, stream))) return rc;
-        if ((rc = scarlet_check_convergence(state, e_rel, stream))) return rc;
+        if ((rc = launch_update(state, l, 1, 0, stream))) return rc;
+        if ((rc = launch_converge(state, l, e_rel, stream))) return rc;
         ++launched;
         if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter) {
             int h_count = 0;
@@ -2163,7 +2156,7 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     }
     HIP_TRY(hipGetLastError());
-    return run_update ? launch_update(b, 0, 1, stream) : SCARLET_OK;   // constructor's self.update()
+    return run_update ? launch_update(b, ws_layout(b, WS_PEEK), 0, 1, stream) : SCARLET_OK;   // constructor's self.update()
 }
 
 // ---- convergence sums for the Python-override path (the built-in pipeline computes them itself)
@@ -2195,7 +2188,8 @@ extern "C" int scarlet_convergence_sums(scarlet_batch *b, void *stream)
     int rc = check_batch(b);
     if (rc) return rc;
     hipLaunchKernelGGL(k_conv_sums, dim3(b->S * b->K), dim3(SC_BLOCK), 0, (hipStream_t)stream, b->K, b->B,
-                       b->H * b->W, b->sed[0], b->sed[1], b->morph[0], b->morph[1], b->cur, b->active, ws_conv(b));
+                       b->H * b->W, b->sed[0], b->sed[1], b->morph[0], b->morph[1], b->cur, b->active,
+                       ws_at<double>(b, ws_layout(b, WS_PEEK).conv));
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
