@@ -64,6 +64,8 @@ extern "C" {
 #define SCARLET_STATUS_CENTER_AT_EDGE    1  /* max_pixel window start < 0: the reference
                                                would raise (measurement.py:24-29)          */
 #define SCARLET_STATUS_NONFINITE         2  /* NaN/Inf met in centroid or normalisation   */
+#define SCARLET_STATUS_BAD_COUNT         4  /* n_components[s] outside 1..K: the scene is
+                                               left untouched and inactive                 */
 
 /* symmetry algorithms -- scarlet/operator.py:291-350 */
 #define SCARLET_SYM_KSPACE 0
@@ -219,7 +221,7 @@ int scarlet_match_psfs(const float *psf1, int n, int P1y, int P1x, const float *
  * ---------------------------------------------------------------------------- */
 
 typedef struct scarlet_batch {
-    /* shapes: S scenes, K components per scene, B bands, H x W pixels */
+    /* shapes: S scenes, K components per scene (at most: see n_components), B bands, H x W pixels */
     int32_t S, K, B, H, W;
     /* data (read only) */
     const float *images;      /* [S][B][H][W]                                          */
@@ -268,6 +270,19 @@ typedef struct scarlet_batch {
        and are symmetrised about it with shift = None (update.symmetric falls back to soft symmetry,
        operator.py:337-339).  The members of a source must be adjacent components.             */
     const int32_t *group;
+    /* Ragged batches: [S] device int32, or NULL = every scene has K components.  Scene s uses components
+       0 .. n_components[s] - 1; components n_components[s] .. K - 1 are ABSENT:
+         - their factors must be zero in both buffers (sed[0/1], morph[0/1]) when a call starts; the library
+           never reads them and never writes anything non-zero to them, so they stay exactly zero and add
+           nothing to the model, the loss, the gradients or the Lipschitz constants;
+         - their centers / shifts are not read, and their flags are left at 0 (set them to 0);
+         - group[s][k] must be -1 for an absent component;
+         - they never enter the constraint pipeline, the initialisation or the convergence test.
+       Every entry point that iterates or initialises checks the counts on the device first: a scene whose
+       count lies outside 1..K gets SCARLET_STATUS_BAD_COUNT and active = 0 and is not touched again; the
+       other scenes go on.  The workspace does not depend on the counts.  scarlet_fit_multi does not take
+       them (SCARLET_E_NOTIMPL).                                                                       */
+    const int32_t *n_components;
 } scarlet_batch;
 
 /* bytes of device workspace needed for `b`.  Depends on S, K, B, H, W; on diff_kernel (NULL or not), psf_h, psf_w and

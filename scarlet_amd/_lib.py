@@ -37,7 +37,7 @@ lib = ctypes.CDLL(LIB_PATH)
 # error codes / enums (mirror include/scarlet_hip.h)
 OK, E_ARG, E_TOO_LARGE, E_HIP, E_NOTIMPL = 0, -1, -2, -3, -4
 FLAG_SED_NOT_CONVERGED, FLAG_MORPH_NOT_CONVERGED, FLAG_EDGE_PIXELS, FLAG_NO_VALID_PIXELS = 1, 2, 4, 8
-STATUS_CENTER_AT_EDGE, STATUS_NONFINITE = 1, 2
+STATUS_CENTER_AT_EDGE, STATUS_NONFINITE, STATUS_BAD_COUNT = 1, 2, 4
 SYM_KSPACE, SYM_SOFT, SYM_SDSS = 0, 1, 2
 SYM_FULL_WINDOW = 16
 NORM_SED, NORM_MORPH, NORM_MORPH_MAX = 0, 1, 2
@@ -61,6 +61,7 @@ class ScarletBatch(Structure):
         ("diff_kernel_per_scene", c_int32),
         ("workspace", c_void_p),
         ("group", c_void_p),
+        ("n_components", c_void_p),
     ]
 
 

@@ -20,13 +20,38 @@ def default_centroid_weight():
     return psf / psf.max()
 
 
+def pad_centers(centers, K=None):
+    """Ragged centre lists -> one padded array and the counts (no device needed).
+
+    centers : list of S arrays of shape (n_s, 2), the integer pixel centres (y, x) of scene s's sources
+    K : components per scene of the padded array; default max(n_s)
+    Returns ((S, K, 2) int32 with zeros in the absent rows, (S,) int32 counts n_s)."""
+    rows = [np.asarray(c, dtype=np.int64).reshape(-1, 2) if np.size(c) else np.zeros((0, 2), np.int64) for c in centers]
+    if not rows:
+        raise ValueError("pad_centers: no scenes")
+    counts = np.array([len(r) for r in rows], dtype=np.int32)
+    if (counts < 1).any():
+        raise ValueError("pad_centers: scene %d has no sources" % int(np.argmin(counts)))
+    K = int(counts.max()) if K is None else int(K)
+    if K > _lib.MAX_COMPONENTS:
+        raise ValueError("pad_centers: %d components per scene, at most %d are supported" % (K, _lib.MAX_COMPONENTS))
+    if (counts > K).any():
+        s = int(np.argmax(counts > K))
+        raise ValueError("pad_centers: scene %d has %d sources, more than K = %d" % (s, counts[s], K))
+    out = np.zeros((len(rows), K, 2), dtype=np.int32)
+    for s, r in enumerate(rows):
+        out[s, :len(r)] = r
+    return out, counts
+
+
 class BlendBatch(object):
     """S scenes x K components x B bands x H x W pixels, all float32 on one device.
 
     Parameters
     ----------
     images : (S, B, H, W) array or tensor
-    centers : (S, K, 2) integer pixel centres (y, x) of the sources
+    centers : (S, K, 2) integer pixel centres (y, x) of the sources, or a list of S arrays (n_s, 2): the scenes then
+        have different numbers of sources, padded to K = max n_s (`pad_centers`), and n_components is derived
     weights : None (scalar 1, reference observation.py:148-151), a Python scalar, or (S, B, H, W)
     symmetric, monotonic : constraint switches of PointSource/ExtendedSource.update
     l0_thresh, l1_thresh : None or sparsity thresholds (update.sparse_l0 / sparse_l1)
@@ -34,11 +59,13 @@ class BlendBatch(object):
     group : None, or (S, K) integers: -1 = the component is a source of its own, g >= 0 = it is a layer of
         multi-component source g of its scene (reference MultiComponentSource, source.py:538-641): the layers
         of a source (adjacent components) share one centre measured on their flux-weighted sum
+    n_components : None (every scene has K components), or (S,) counts: scene s uses components 0 .. n[s] - 1, the
+        others are absent -- zero in both buffers, flags 0, outside the model, the constraints and the convergence test
     """
 
     def __init__(self, images, centers, weights=None, symmetric=True, monotonic=True,
                  l0_thresh=None, l1_thresh=None, centroid_weight=None, mse_capacity=256,
-                 device=None, group=None):
+                 device=None, group=None, n_components=None):
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -48,10 +75,26 @@ class BlendBatch(object):
         self.images = torch.as_tensor(images).to(**f32).contiguous()
         assert self.images.ndim == 4, "images must be (S, B, H, W)"
         S, B, H, W = self.images.shape
+        if isinstance(centers, (list, tuple)) and len(centers) and np.ndim(centers[0]) == 2 and \
+                len(set(np.shape(c)[0] for c in centers)) > 1:
+            centers, counts = pad_centers(centers)
+            if n_components is not None and not np.array_equal(np.asarray(n_components).reshape(-1), counts):
+                raise ValueError("n_components does not match the lengths of the centre lists")
+            n_components = counts
         self.centers = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers).to(**i32).contiguous()
         assert self.centers.ndim == 3 and self.centers.shape[0] == S and self.centers.shape[2] == 2
         K = self.centers.shape[1]
         self.S, self.K, self.B, self.H, self.W = S, K, B, H, W
+        self.n_components = None
+        if n_components is not None:
+            n = np.asarray(n_components.cpu() if torch.is_tensor(n_components) else n_components).reshape(-1)
+            if n.shape != (S,) or not np.issubdtype(n.dtype, np.integer):
+                raise ValueError("n_components must be S = %d integers" % S)
+            bad = (n < 1) | (n > K)
+            if bad.any():
+                s = int(np.argmax(bad))
+                raise ValueError("n_components[%d] = %d lies outside 1..K = 1..%d" % (s, int(n[s]), K))
+            self.n_components = torch.as_tensor(n.astype(np.int32)).to(**i32).contiguous()
         self._check_centers(self.centers)
         self.weight_scalar = 1.0
         if weights is not None and np.ndim(weights) == 0 and not torch.is_tensor(weights):
@@ -62,6 +105,8 @@ class BlendBatch(object):
         self.cur = torch.zeros((S,), **i32)
         self.shifts = torch.full((S, K, 2), float("nan"), **f64)      # NaN == reference's "no shift yet"
         self.flags = torch.full((S, K), _lib.FLAG_SED_NOT_CONVERGED | _lib.FLAG_MORPH_NOT_CONVERGED, **i32)
+        if self.n_components is not None:
+            self.flags.masked_fill_(~self._present(), 0)          # absent components keep flags 0
         self.lipschitz = torch.ones((S, 2), **f64)
         self.mse_capacity = int(mse_capacity)
         self.mse_buf = torch.zeros((S, self.mse_capacity), **f64)
@@ -79,6 +124,11 @@ class BlendBatch(object):
                     if v >= 0 and v in seen and row[k - 1] != v:
                         raise ValueError("the components of a multi-component source must be adjacent")
                     seen.add(int(v))
+            if self.n_components is not None:
+                absent = ~self._present().cpu().numpy()
+                if (g[absent] >= 0).any():
+                    s, k = [int(v[0]) for v in np.nonzero(absent & (g >= 0))]
+                    raise ValueError("group[%d][%d] = %d: an absent component must have group -1" % (s, k, g[s, k]))
             self.group = torch.as_tensor(g).to(**i32).contiguous()
         self.symmetric, self.monotonic = bool(symmetric), bool(monotonic)
         self.l0_thresh, self.l1_thresh = l0_thresh, l1_thresh
@@ -92,11 +142,21 @@ class BlendBatch(object):
         self._c.workspace = self.workspace.data_ptr()
 
     # ------------------------------------------------------------------ plumbing
+    def _present(self):
+        """(S, K) bool device mask of the components each scene uses (all of them without n_components)."""
+        k = self.torch.arange(self.K, device=self.device)
+        if self.n_components is None:
+            return self.torch.ones((self.S, self.K), dtype=self.torch.bool, device=self.device)
+        return k.view(1, -1) < self.n_components.view(-1, 1)
+
     def _check_centers(self, centers):
         """Source centres index the frame directly (init, max_pixel window, sweeps): the reference raises
-        IndexError for a source outside the image; here it is a ValueError before anything is launched."""
+        IndexError for a source outside the image; here it is a ValueError before anything is launched.
+        The centres of absent components are not read and not checked."""
         c = centers
         bad = (c[..., 0] < 0) | (c[..., 0] >= self.H) | (c[..., 1] < 0) | (c[..., 1] >= self.W)
+        if self.n_components is not None:
+            bad &= self._present()
         if bool(bad.any().item()):
             s, k = [int(v[0]) for v in self.torch.nonzero(bad, as_tuple=True)]
             raise ValueError("centre %s of scene %d, source %d lies outside the %d x %d frame"
@@ -118,6 +178,7 @@ class BlendBatch(object):
         c.l1_thresh = -1.0 if self.l1_thresh is None else float(self.l1_thresh)
         c.centroid_psf, c.centroid_P = p(self.centroid_weight), int(self.centroid_weight.shape[0])
         c.group = p(self.group)
+        c.n_components = p(self.n_components)
         if getattr(self, "workspace", None) is not None:
             c.workspace = self.workspace.data_ptr()
 
@@ -138,11 +199,17 @@ class BlendBatch(object):
 
     # ------------------------------------------------------------------ state access
     def set_state(self, sed, morph, centers=None, shifts=None):
-        """Load factors into the current buffers (e.g. a state produced elsewhere)."""
+        """Load factors into the current buffers (e.g. a state produced elsewhere).  The rows of absent components
+        are stored as zeros whatever they hold."""
         t = self.torch
         as_t = lambda a: a if t.is_tensor(a) else t.as_tensor(np.asarray(a))
         sed = as_t(sed).to(self.sed[0])
         morph = as_t(morph).to(self.morph[0])
+        if self.n_components is not None:
+            present = self._present()
+            sed = t.where(present.view(self.S, self.K, 1), sed.expand_as(self.sed[0]), t.zeros((), dtype=sed.dtype, device=self.device))
+            morph = t.where(present.view(self.S, self.K, 1, 1), morph.expand_as(self.morph[0]),
+                            t.zeros((), dtype=morph.dtype, device=self.device))
         for b in range(2):
             self.sed[b].copy_(sed)
             self.morph[b].copy_(morph)
@@ -180,6 +247,12 @@ class BlendBatch(object):
     @property
     def morph_current(self):
         return self._pick(self.morph)
+
+    def scene(self, s):
+        """Current (sed, morph) of scene s: (n, B) and (n, H, W) tensors of its n = n_components[s] components."""
+        n = self.K if self.n_components is None else int(self.n_components[s].item())
+        c = int(self.cur[s].item())
+        return self.sed[c][s, :n], self.morph[c][s, :n]
 
     def mse(self, s=0):
         """List of losses of scene `s`, one per iteration (reference Blend.mse)."""

@@ -134,6 +134,8 @@ __global__ __launch_bounds__(SC_BLOCK) void k_bigk_gram(GradArgs a)
     int c1 = 0, rem = blockIdx.y;
     while (rem >= nch - c1) { rem -= nch - c1; ++c1; }
     const int c2 = c1 + rem;
+    // ragged batch: a pair with an absent chunk (c2 >= c1) writes nothing; k_bigk_lipschitz reads only the present block
+    if (c2 * SC_CHUNK >= scene_ncomp(a.ncomp, s, K)) return;
     __shared__ float red[SC_NWAVES][64];
     const float *mor = a.morph[a.cur[s]] + (size_t)s * K * HW;
     float acc[64];
@@ -409,10 +411,11 @@ __global__ __launch_bounds__(SC_BLOCK) void k_bigk_lipschitz(GradArgs a, int sed
     const int c0 = a.cur[s];
     for (int i = tid; i < K * B; i += SC_BLOCK)
         sed_s[(i / B) * SC_BMAX + (i % B)] = a.sed[c0][(size_t)s * K * B + i];
+    const int n = scene_ncomp(a.ncomp, s, K);            // (absent components: zero rows and columns, not summed)
     for (int i = tid; i < SC_KBIG * SC_KBIG; i += SC_BLOCK) {
         const int k = i / SC_KBIG, k2 = i - k * SC_KBIG;
         double r = 0;
-        if (k < K && k2 < K) {
+        if (k < n && k2 < n) {
             const int lo = k < k2 ? k : k2, hi = k < k2 ? k2 : k;
             const int go = lo * K - (lo * (lo - 1)) / 2 + (hi - lo);
             for (int t = 0; t < a.T; ++t) r += a.partials[((size_t)s * a.T + t) * P + 1 + K * B + go];
@@ -549,6 +552,9 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_bigk_step(GradArgs a, const flo
     const int s = blockIdx.z, tile = blockIdx.x, ch = blockIdx.y;
     if (!a.active[s]) return;
     const int K = a.K, B = a.B, HW = a.HW;
+    // ragged batch: a chunk of absent components has nothing to step (its planes stay zero) and writes no partials;
+    // k_bigk_sed reads only the present components'
+    if (ch * SC_CHUNK >= scene_ncomp(a.ncomp, s, K)) return;
     __shared__ float sed_s[SC_CHUNK * SC_BMAX];
     __shared__ float red[SC_NWAVES][64];
     const int c0 = a.cur[s];
@@ -649,7 +655,8 @@ __global__ __launch_bounds__(SC_BLOCK) void k_bigk_sed(GradArgs a, int write_mse
         if (it_new <= a.mse_capacity) a.mse[(size_t)s * a.mse_capacity + it_new - 1] = loss;
     }
     const float step_sed = 1.0f / (float)a.lipschitz[2 * s];
-    for (int i = threadIdx.x; i < K * B; i += SC_BLOCK) {
+    const int n = scene_ncomp(a.ncomp, s, K);            // absent components' SEDs stay zero
+    for (int i = threadIdx.x; i < n * B; i += SC_BLOCK) {
         double g = 0;
         for (int t = 0; t < a.T; ++t) g += a.partials[((size_t)s * a.T + t) * P + 1 + i];
         const float cur = a.sed[c0][(size_t)s * K * B + i];

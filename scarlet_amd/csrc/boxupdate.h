@@ -72,6 +72,7 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
     extern __shared__ __align__(16) float lds[];
     const int s = c / a.K;
     if (!a.force_it0 && !a.active[s]) return;
+    if (c - s * a.K >= scene_ncomp(a.ncomp, s, a.K)) return;        // absent component: never listed either
     long long *stamps = stamps_all ? stamps_all + (size_t)c * 16 : nullptr;
 #define UB_STAMP(i) do { if (stamps && threadIdx.x == 0) stamps[(i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
     UB_STAMP(0);

@@ -40,6 +40,15 @@ __device__ __forceinline__ double uniform(double v) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
                             __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
+// Ragged batches (scarlet_batch::n_components): the number of components scene s uses.  NULL: all K.  A count
+// outside 1..K (SCARLET_STATUS_BAD_COUNT, set by k_check_counts) leaves no component present, so that even the
+// kernels that ignore `active` (constructor updates, init_extended) do not touch the scene.
+__device__ __forceinline__ int scene_ncomp(const int *ncomp, int s, int K)
+{
+    if (!ncomp) return K;
+    const int n = ncomp[s];
+    return (n >= 1 && n <= K) ? n : 0;
+}
 #define SC_DPP_XOR1 0xB1        // quad_perm [1,0,3,2]
 #define SC_DPP_XOR2 0x4E        // quad_perm [2,3,0,1]
 #define SC_DPP_HALF_MIRROR 0x141

@@ -39,6 +39,7 @@ struct GradArgs {
     const int *active;
     int approximate_L;
     int raw_gradient;             // 1: write d loss/d sed and d loss/d morph instead of the stepped factors
+    const int *ncomp;             // [S] or NULL: components per scene (scene_ncomp); absent ones are zero
 };
 
 // ------------------------------------------------------------------------------------
@@ -483,6 +484,7 @@ struct UpdateArgs {
     const int *only_flagged;          // [S*K] or NULL: run only for the components k_source_update_box left to the full path
     const int *group;                 // [S*K] or NULL: >= 0 = layer of a multi-component source: centre given (k_group_centers),
                                       // shift = None (soft symmetry); -1 = a source of its own
+    const int *ncomp;                 // [S] or NULL: components per scene (scene_ncomp); absent ones are skipped
 };
 
 // MODE 0/1: the morphology tile lives in LDS (tiles up to ~128 x 128).
@@ -503,6 +505,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     extern __shared__ __align__(16) float lds[];
     const int c = blockIdx.x, s = c / a.K;
     if (!a.force_it0 && !a.active[s]) return;
+    if (c - s * a.K >= scene_ncomp(a.ncomp, s, a.K)) return;        // absent component
     if (a.only_flagged && !a.only_flagged[c]) return;
     const int H = a.H, W = a.W, HW = H * W, B = a.B;
     const int hp = round16(H), wp = round16(W);
@@ -734,11 +737,12 @@ __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
     const int c0 = a.cur[s], wbuf = a.in_iteration ? 1 - c0 : c0;
     const int it = a.force_it0 ? 0 : a.it[s] + (a.in_iteration ? 1 : 0);
     const int R = a.centroid_P / 2 + 2, PW = 2 * R + 1 + 1;                      // patch radius, LDS row stride
-    for (int k0 = 0; k0 < K; ++k0) {
+    const int n = scene_ncomp(a.ncomp, s, K);                                     // (absent components are not members)
+    for (int k0 = 0; k0 < n; ++k0) {
         const int g = a.group[s * K + k0];
         if (g < 0 || (k0 > 0 && a.group[s * K + k0 - 1] == g)) continue;          // not a layer / not the first layer of its source
         int k1 = k0 + 1;
-        while (k1 < K && a.group[s * K + k1] == g) ++k1;
+        while (k1 < n && a.group[s * K + k1] == g) ++k1;
         int cy = a.centers[2 * (s * K + k0)], cx = a.centers[2 * (s * K + k0) + 1];
         const int py0 = max(0, cy - R), px0 = max(0, cx - R);
         const int ph = min(H, cy + R + 1) - py0, pw = min(W, cx + R + 1) - px0;
@@ -779,7 +783,7 @@ __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
 // k_converge: Blend._check_convergence (blend.py:141-184), one thread per scene.
 // Also closes the iteration for the scene: it += 1 (len(mse)), cur flips.
 __global__ void k_converge(int S, int K, const double *conv, int *flags, int *active,
-                           int *it, int *cur, double e_rel2)
+                           int *it, int *cur, double e_rel2, const int *ncomp)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S || !active[s]) return;
@@ -788,7 +792,8 @@ __global__ void k_converge(int S, int K, const double *conv, int *flags, int *ac
     cur[s] = 1 - cur[s];
     if (it_new > 1) {
         bool done = true;
-        for (int k = 0; k < K; ++k) {
+        const int n = scene_ncomp(ncomp, s, K);       // absent components: no test, flags stay 0
+        for (int k = 0; k < n; ++k) {
             const double *c = conv + 4 * ((size_t)s * K + k);
             int f = flags[s * K + k];
             if (c[0] <= e_rel2 * c[1]) f &= ~SCARLET_FLAG_SED_NOT_CONVERGED;
@@ -943,6 +948,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w(UpdateArgs a)
     const int c = blockIdx.x * SC_NWAVES + wid;
     if (c >= a.S * a.K) return;
     if (!a.force_it0 && !a.active[c / a.K]) return;
+    if (c % a.K >= scene_ncomp(a.ncomp, c / a.K, a.K)) return;      // absent component
     const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;
     wave_pipeline(a, c, lds + (size_t)wid * per_wave);
 }

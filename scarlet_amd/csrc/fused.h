@@ -44,6 +44,7 @@ struct FusedArgs {
     double e_rel2;
     long long *stamps;               // NULL, or [S][16] shader-clock stamps (diagnostics only)
     float *kscache;                  // NULL, or [S][K][2][SC_KSC_FLOATS]: Hankel vectors of the last k-space symmetry (k_iterate2)
+    const int *ncomp;                // [S] or NULL: components per scene (scene_ncomp); absent ones skip the constraints
 };
 // Per component and wave of its pair: 64 entries of av, bv, cv (this wave's half), then the header
 // {H W cy cx, magic, dy (2 words), dx (2 words), s} the vectors were made for
@@ -272,8 +273,9 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(FusedArgs a)
     __syncthreads();
     STAMP(4);
 
-    // ---------------- phase 2: constraints, one wave per component
-    for (int k = wid; k < K; k += SC_NWAVES) {
+    // ---------------- phase 2: constraints, one wave per component (absent components: none, and no convergence test)
+    const int n_present = scene_ncomp(a.ncomp, s, K);
+    for (int k = wid; k < n_present; k += SC_NWAVES) {
         const int c = s * K + k;
         Tile t; t.H = H; t.W = W; t.LW = LW; t.m = tiles + k * tile_floats;
         float *vec = vecs + wid * SC_WAVE_VEC_FLOATS;
@@ -435,7 +437,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(FusedArgs a)
         a.cur[s] = 1 - c0;
         if (it_new > 1) {
             bool done = true;
-            for (int k = 0; k < K; ++k) {
+            for (int k = 0; k < n_present; ++k) {
                 int f = a.flags[s * K + k];
                 if (conv_s[k][0] <= a.e_rel2 * conv_s[k][1]) f &= ~SCARLET_FLAG_SED_NOT_CONVERGED;
                 else { f |= SCARLET_FLAG_SED_NOT_CONVERGED; done = false; }

@@ -230,6 +230,8 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         float v = 0.f;
         if (!(P && reentered)) v = sed_in[i];
         if (P) { const float lv = carry_sed[(i / B) * BM + (i % B)]; if (reentered) v = lv; }
+        // (a new scene: the carry starts from its SEDs -- an absent component's stays zero, nothing else writes it)
+        if (P && !reentered) carry_sed[(i / B) * BM + (i % B)] = v;
         sed_s[(i / B) * BM + (i % B)] = v;
     }
     ks_fill_lengths(fl_s, tid, fl_req);
@@ -464,7 +466,8 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
-    const bool mine = k < K;
+    const int n_present = a.ncomp ? scene_ncomp(a.ncomp, s, K) : K;   // absent components: the pair skips the constraints
+    const bool mine = k < n_present;
     const int c = s * K + (mine ? k : 0);
     Tile t; t.H = H; t.W = W; t.LW = LW; t.m = tiles + (mine ? k : 0) * tile_floats;
     float *vec = vecs + (mine ? k : 0) * SC_PAIR_VEC_FLOATS;
@@ -752,7 +755,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     // component k (one lane for all of them was ~2.6k cycles at the end of every scene's chain)
     if (wid == 0) {
         bool pending = false;
-        if (lane < K && it_new > 1) {
+        if (lane < n_present && it_new > 1) {
             // the two convergence bits are rewritten whatever they were, the other bits stay: posted
             // atomics instead of load - modify - store (a load here would put an HBM round trip at the
             // very end of the workgroup, with its LDS and registers still held)

@@ -71,6 +71,8 @@ __global__ __launch_bounds__(SC_BLOCK) void k_huge_gram(GradArgs a, HugeArgs h)
     const int K = a.K, HW = a.HW, nb = huge_nblk(K);
     int bi, bj;
     huge_pair(pair, nb, bi, bj);
+    // ragged batch: a pair with an absent block (bj >= bi) is not formed; its readers stop at the present blocks
+    if (bj * SC_GBLK >= scene_ncomp(a.ncomp, s, K)) return;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const float *mor = a.morph[a.cur[s]] + (size_t)s * K * HW;
     const int k0 = bi * SC_GBLK + r, k1 = k0 + 16, k2 = bj * SC_GBLK + r, k3 = k2 + 16;
@@ -141,6 +143,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_huge_gram_reduce(GradArgs a, HugeA
     const int nb = huge_nblk(a.K), Kp = nb * SC_GBLK;
     int bi, bj;
     huge_pair(pair, nb, bi, bj);
+    if (bj * SC_GBLK >= scene_ncomp(a.ncomp, s, a.K)) return;           // (not formed by k_huge_gram: not read)
     const double *in = h.gpart + ((size_t)s * huge_npairs(a.K) + pair) * h.C * (SC_GBLK * SC_GBLK);
     double *G = h.gram + (size_t)s * Kp * Kp;
     for (int e = threadIdx.x; e < SC_GBLK * SC_GBLK; e += SC_BLOCK) {
@@ -162,18 +165,22 @@ __global__ __launch_bounds__(SC_BLOCK) void k_huge_square(GradArgs a, const doub
     const int s = blockIdx.z, bi = blockIdx.y, bj = blockIdx.x;
     if (!a.active[s]) return;
     const int Kp = huge_nblk(a.K) * SC_GBLK;
+    // ragged batch: only the blocks of present components (Kn = 32 ceil(n / 32)) are squared and read; the rest of G and
+    // of the squares is neither written nor read in this call (absent components add zero rows and columns only)
+    const int n = scene_ncomp(a.ncomp, s, a.K), Kn = huge_nblk(n) * SC_GBLK;
+    if (bi * SC_GBLK >= n || bj * SC_GBLK >= n) return;
     const double *src = src_all + (size_t)s * Kp * Kp;
     double *dst = dst_all + (size_t)s * Kp * Kp;
     __shared__ double As[SC_GBLK][SC_GBLK + 1], Bs[SC_GBLK][SC_GBLK + 1];
     __shared__ double red[SC_NWAVES];
     const int tid = threadIdx.x;
     double tr = 0;
-    for (int i = tid; i < Kp; i += SC_BLOCK) tr += src[(size_t)i * Kp + i];
+    for (int i = tid; i < Kn; i += SC_BLOCK) tr += src[(size_t)i * Kp + i];
     tr = block_sum(tr, red);
     const double sc = 1.0 / (tr * tr);
     const int ti = (tid >> 4) * 2, tj = (tid & 15) * 2;
     double c00 = 0, c01 = 0, c10 = 0, c11 = 0;
-    for (int k0 = 0; k0 < Kp; k0 += SC_GBLK) {
+    for (int k0 = 0; k0 < Kn; k0 += SC_GBLK) {
         for (int e = tid; e < SC_GBLK * SC_GBLK; e += SC_BLOCK) {
             const int x = e / SC_GBLK, y = e % SC_GBLK;
             As[x][y] = src[(size_t)(bi * SC_GBLK + x) * Kp + k0 + y];            // A[row][k]
@@ -198,7 +205,8 @@ __global__ __launch_bounds__(SC_BLOCK) void k_huge_lipschitz(GradArgs a, HugeArg
 {
     const int s = blockIdx.x;
     if (!a.active[s]) return;
-    const int K = a.K, B = a.B, P = n_partials(K, B), Kp = huge_nblk(K) * SC_GBLK, tid = threadIdx.x;
+    const int B = a.B, P = n_partials(a.K, B), Kp = huge_nblk(a.K) * SC_GBLK, tid = threadIdx.x;
+    const int K = scene_ncomp(a.ncomp, s, a.K);        // ragged batch: the present components' rows of G and M only
     const double *G = h.gram + (size_t)s * Kp * Kp;
     __shared__ double red[SC_NWAVES];
     __shared__ double vcol[SC_KHUGE];

@@ -754,7 +754,7 @@ extern "C" int scarlet_profile_end(double total_ms[SC_NCLASS], int64_t launches[
     return scarlet_profile_end_ex(total_ms, launches, nullptr);
 }
 
-static int check_batch(const scarlet_batch *b)
+static int check_batch(const scarlet_batch *b, bool multi = false)
 {
     // Every entry point ends with a look at hipGetLastError(); that value is per thread and keeps whatever an EARLIER HIP
     // call of the thread left there.  Start from a clean slate: what is reported is ours.
@@ -767,11 +767,31 @@ static int check_batch(const scarlet_batch *b)
         return set_err(SCARLET_E_NOTIMPL, "B > 8 bands is not supported by this build of the gradient kernels");
     if (b->H > SCARLET_MAX_SIDE || b->W > SCARLET_MAX_SIDE)
         return set_err(SCARLET_E_TOO_LARGE, "frames larger than 1024 x 1024 (SCARLET_MAX_SIDE) are not supported");
+    if (multi && b->n_components)
+        return set_err(SCARLET_E_NOTIMPL, "scarlet_fit_multi does not take n_components (ragged batches): pass NULL");
     if (!b->images || !b->sed[0] || !b->sed[1] || !b->morph[0] || !b->morph[1] || !b->cur || !b->centers ||
         !b->shifts || !b->flags || !b->lipschitz || !b->mse || !b->it || !b->active || !b->status || !b->workspace)
         return set_err(SCARLET_E_ARG, "null pointer in batch");
     if (b->symmetric && (!b->centroid_psf || b->centroid_P <= 0 || !(b->centroid_P & 1)))
         return set_err(SCARLET_E_ARG, "symmetric pipeline needs an odd-sized centroid psf");
+    return SCARLET_OK;
+}
+
+// Ragged batches: one small kernel per call of an entry point that iterates or initialises.  A scene whose count lies
+// outside 1..K gets SCARLET_STATUS_BAD_COUNT and active = 0; the kernels then see no component of it (scene_ncomp).
+__global__ void k_check_counts(const int *ncomp, int S, int K, int *status, int *active)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const int n = ncomp[s];
+    if (n < 1 || n > K) { status[s] |= SCARLET_STATUS_BAD_COUNT; active[s] = 0; }
+}
+static int check_counts(const scarlet_batch *b, void *stream)
+{
+    if (!b->n_components) return SCARLET_OK;
+    hipLaunchKernelGGL(k_check_counts, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
+                       b->n_components, b->S, b->K, b->status, b->active);
+    HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
 
@@ -1040,6 +1060,7 @@ static scarlet_batch batch_view(const scarlet_batch *b, int s0, int n, void *ws)
     v.lipschitz += 2 * (size_t)s0; v.mse += (size_t)s0 * b->mse_capacity; v.it += s0; v.active += s0; v.status += s0;
     if (v.diff_kernel_per_scene) v.diff_kernel += s0 * B * (size_t)b->psf_h * b->psf_w;
     if (v.group) v.group += s0 * K;
+    if (v.n_components) v.n_components += s0;
     v.workspace = ws;
     return v;
 }
@@ -1093,6 +1114,7 @@ static GradArgs grad_args(const scarlet_batch *b, const WsLayout &l, int approxi
     a.cur = b->cur; a.fix_sed = b->fix_sed; a.fix_morph = b->fix_morph;
     a.partials = ws_at<double>(b, l.partials); a.lipschitz = b->lipschitz; a.mse = b->mse; a.mse_capacity = b->mse_capacity;
     a.it = b->it; a.active = b->active; a.approximate_L = approximate_L; a.raw_gradient = raw_gradient;
+    a.ncomp = b->n_components;
     return a;
 }
 
@@ -1606,13 +1628,15 @@ static int backward_impl(scarlet_batch *b, const WsLayout &l, int approximate_L,
 
 extern "C" int scarlet_backward_step(scarlet_batch *b, int approximate_L, void *stream)
 {
-    const int rc = check_batch(b);
+    int rc = check_batch(b);
+    if (!rc) rc = check_counts(b, stream);
     return rc ? rc : backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 0, stream);
 }
 
 extern "C" int scarlet_backward_gradients(scarlet_batch *b, int approximate_L, void *stream)
 {
-    const int rc = check_batch(b);
+    int rc = check_batch(b);
+    if (!rc) rc = check_counts(b, stream);
     return rc ? rc : backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 1, stream);
 }
 
@@ -1633,6 +1657,7 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.gscratch = nullptr;
     u.only_flagged = nullptr;
     u.group = b->group;
+    u.ncomp = b->n_components;
     if (b->group) {
         // MultiComponentSource: the shared centre of every source first (one wave per scene)
         const int R = b->centroid_P / 2 + 2;
@@ -1714,6 +1739,7 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
 extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *stream)
 {
     int rc = check_batch(b);
+    if (!rc) rc = check_counts(b, stream);
     if (rc) return rc;
     return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream);
 }
@@ -1721,13 +1747,15 @@ extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *s
 static int launch_converge(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream)
 {
     hipLaunchKernelGGL(k_converge, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
-                       b->S, b->K, ws_at<double>(b, l.conv), b->flags, b->active, b->it, b->cur, e_rel * e_rel);
+                       b->S, b->K, ws_at<double>(b, l.conv), b->flags, b->active, b->it, b->cur, e_rel * e_rel,
+                       (const int *)b->n_components);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
 extern "C" int scarlet_check_convergence(scarlet_batch *b, double e_rel, void *stream)
 {
-    const int rc = check_batch(b);
+    int rc = check_batch(b);
+    if (!rc) rc = check_counts(b, stream);
     return rc ? rc : launch_converge(b, ws_layout(b, WS_PEEK), e_rel, stream);
 }
 
@@ -1782,6 +1810,7 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
     f.it = b->it; f.active = b->active; f.status = b->status;
     f.symmetric = b->symmetric; f.monotonic = b->monotonic; f.l0_thresh = b->l0_thresh; f.l1_thresh = b->l1_thresh;
     f.centroid_psf = b->centroid_psf; f.centroid_P = b->centroid_P; f.e_rel2 = e_rel * e_rel;
+    f.ncomp = b->n_components;
     // diagnostics: SCARLET_STAMPS=1 writes phase stamps into the (otherwise unused) partials area
     f.kscache = (!l.has_kscache || b->diff_kernel || opt(OPT_NO_KSCACHE)) ? nullptr : ws_at<float>(b, l.kscache);
     f.stamps = (opt(OPT_STAMPS) && n_partials(b->K, b->B) >= 16) ? ws_at<long long>(b, l.partials) : nullptr;
@@ -1867,6 +1896,7 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
     int rc = check_batch(b);
     if (rc) return rc;
     if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
+    if ((rc = check_counts(b, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
     int launched = 0;
     const WsLayout l = ws_layout(b, WS_FIX);
@@ -1953,7 +1983,7 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
 extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
                                  int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
 {
-    int rc = check_batch(state);
+    int rc = check_batch(state, true);
     if (rc) return rc;
     if (!obs || !band0 || n_obs < 1 || n_obs > SC_MULTI_MAX) return set_err(SCARLET_E_ARG, "1 to 8 observations");
     if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
@@ -1964,7 +1994,7 @@ extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs
     m.lipschitz = state->lipschitz; m.mse = state->mse; m.mse_capacity = state->mse_capacity;
     m.fix_sed = state->fix_sed; m.fix_morph = state->fix_morph; m.approximate_L = approximate_L;
     for (int o = 0; o < n_obs; ++o) {
-        if ((rc = check_batch(obs[o]))) return rc;
+        if ((rc = check_batch(obs[o], true))) return rc;
         const scarlet_batch *ob = obs[o];
         if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || band0[o] < 0 ||
             band0[o] + ob->B > state->B || ob->mse_capacity < 1)
@@ -2018,6 +2048,7 @@ struct InitArgs {
     const int *centers;
     int *flags;
     int *status;
+    const int *ncomp;                 // [S] or NULL: absent components are left as they are (zero)
     double bg_rms[SC_BMAX];
     double sed_scale[SC_BMAX];
     int has_scale;
@@ -2036,6 +2067,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_extended(InitArgs a, double *
     t.m = GT ? gtile + (size_t)c * H * (W + 1) : ldsd;
     __shared__ double red[SC_NWAVES];
     __shared__ float sed_s[SC_BMAX];
+    if (c - s * a.K >= scene_ncomp(a.ncomp, s, a.K)) return;        // absent component
     const int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
     if (cy < 0 || cy >= H || cx < 0 || cx >= W) {
         // a source outside the frame (IndexError in the reference, ValueError in BlendBatch): empty component
@@ -2132,7 +2164,7 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
     a.S = b->S; a.K = b->K; a.B = b->B; a.H = b->H; a.W = b->W;
     a.images = b->images; a.sed[0] = b->sed[0]; a.sed[1] = b->sed[1];
     a.morph[0] = b->morph[0]; a.morph[1] = b->morph[1]; a.cur = b->cur; a.centers = b->centers; a.flags = b->flags;
-    a.status = b->status;
+    a.status = b->status; a.ncomp = b->n_components;
     a.has_scale = sed_scale_host != nullptr; a.thresh = thresh;
     a.do_symmetric = init_symmetric; a.do_monotonic = init_monotonic;
     a.no_hybrid = opt(OPT_NO_HYBRID_SWEEP) ? 1 : 0;
@@ -2142,6 +2174,7 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
         if (i < b->B && !(a.bg_rms[i] > 0))
             return set_err(SCARLET_E_ARG, "bg_rms must be greater than zero in all channels");
     }
+    if ((rc = check_counts(b, stream))) return rc;
     const size_t lds = sizeof(double) * (size_t)b->H * (b->W + 1);
     if (lds <= LDS_LIMIT) {
         rc = allow_lds(k_init_extended<false>, lds);
@@ -2162,11 +2195,15 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
 // ---- convergence sums for the Python-override path (the built-in pipeline computes them itself)
 __global__ __launch_bounds__(SC_BLOCK) void k_conv_sums(int K, int B, int HW, float *const sed0, float *const sed1,
                                                         float *const morph0, float *const morph1, const int *cur,
-                                                        const int *active, double *conv)
+                                                        const int *active, const int *ncomp, double *conv)
 {
     __shared__ double red[SC_NWAVES];
     const int c = blockIdx.x, s = c / K;
     if (!active[s]) return;
+    if (c - s * K >= scene_ncomp(ncomp, s, K)) {                     // absent component: zero sums
+        if (threadIdx.x == 0) { conv[4 * c] = 0; conv[4 * c + 1] = 0; conv[4 * c + 2] = 0; conv[4 * c + 3] = 0; }
+        return;
+    }
     const int c0 = cur[s];
     const float *mn = (c0 ? morph0 : morph1) + (size_t)c * HW, *ml = (c0 ? morph1 : morph0) + (size_t)c * HW;
     const float *sn = (c0 ? sed0 : sed1) + (size_t)c * B, *sl = (c0 ? sed1 : sed0) + (size_t)c * B;
@@ -2186,10 +2223,11 @@ __global__ __launch_bounds__(SC_BLOCK) void k_conv_sums(int K, int B, int HW, fl
 extern "C" int scarlet_convergence_sums(scarlet_batch *b, void *stream)
 {
     int rc = check_batch(b);
+    if (!rc) rc = check_counts(b, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_conv_sums, dim3(b->S * b->K), dim3(SC_BLOCK), 0, (hipStream_t)stream, b->K, b->B,
                        b->H * b->W, b->sed[0], b->sed[1], b->morph[0], b->morph[1], b->cur, b->active,
-                       ws_at<double>(b, ws_layout(b, WS_PEEK).conv));
+                       (const int *)b->n_components, ws_at<double>(b, ws_layout(b, WS_PEEK).conv));
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
