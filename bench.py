@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Blend.fit() hot path: proximal-gradient iterations/s on synthetic scenes.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--strong] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--strong] [--dump-outputs DIR] [--full]
 
 A "step" is one PGM iteration (Blend.fit inner loop: render [+ PSF convolution], loss gradient,
 Lipschitz step, constraint pipeline, convergence flags) over the whole resident batch of scenes.
@@ -21,9 +21,13 @@ Default = weak scaling: every rank owns its own `scenes` scenes, no collective i
 region.  `--strong` = BASELINE configs[3] literally: rank 0 generates `scenes` scenes in total,
 scatters them over RCCL (timed separately), every rank fits its shard, results are gathered.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-"roofline" (dominant kernel class, HIP-event timed on the launch stream) and "cpu_baseline" (the
-CPU oracle timed on this host's cores -- one core and all cores -- rank 0 at N=1 only).
+Prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, ...) with an extra "roofline" object
+(dominant kernel class, HIP-event timed on the launch stream during the timed steps themselves).
+A plain run does only what that line needs: generate the scenes, warm up, time the K steps, dump.
+`--full` adds the legs that take runs of their own, rank 0 at N=1 only: "cpu_baseline" (the CPU
+oracle timed on this host's cores -- one core and all cores; `--no-cpu` drops it) and, for the
+default c2 workload, "other_configs" (c3 and c5, each timed by a child run of this script with
+`--full`; `--no-other` drops them).
 `--dump-outputs DIR` writes, after the timed steps, what they computed (dump_outputs) so that two builds can be
 compared output for output: the inputs depend only on the arguments.
 """
@@ -257,12 +261,13 @@ def self_launch(n, argv, limit_s=None):
 
 # ----------------------------------------------------------------------------- the other BASELINE configs
 def run_other_configs(args):
-    """The default single-GPU run also times BASELINE configs[2] (c3) and configs[4] (c5), each in a fresh child
-    process started BEFORE this process touches the GPU (same script, `--config c3|c5`, a few seconds each), and
+    """A `--full` single-GPU c2 run also times BASELINE configs[2] (c3) and configs[4] (c5), each in a fresh child
+    process started BEFORE this process touches the GPU (same script, `--config c3|c5 --full`, a few seconds each), and
     embeds their JSON lines under "other_configs".  A failure is recorded, it does not fail the headline."""
     out = {}
     for cfg, steps, warm in (("c3", min(args.steps, 10), min(args.warmup, 3)), ("c5", min(args.steps, 10), min(args.warmup, 3))):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", str(steps), "--warmup", str(warm)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", str(steps), "--warmup", str(warm),
+               "--full"]
         if args.no_cpu:
             cmd.append("--no-cpu")
         t0 = time.perf_counter()
@@ -314,7 +319,7 @@ def dump_outputs(batch, out_dir):
 
 
 # ----------------------------------------------------------------------------- main
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -323,11 +328,13 @@ def main():
     ap.add_argument("--scenes", type=int, default=None, help="scenes per GPU (total scenes with --strong)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: `scenes` in total, generated on rank 0 and scattered over RCCL")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (single GPU): cpu_baseline and, for c2, other_configs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--clock-warmup-ms", type=float, default=60.0,
                     help="untimed device clock warm-up on a scratch copy of the batch before the W warmup steps (0: none)")
     ap.add_argument("--no-other", action="store_true",
-                    help="headline workload only (the default single-GPU c2 run also times c3 and c5 in child processes)")
+                    help="with --full: skip other_configs (c3 and c5 timed in child processes)")
     ap.add_argument("--cpu-scenes", type=int, default=None, help="oracle scenes per host process")
     ap.add_argument("--cpu-iters", type=int, default=None)
     ap.add_argument("--no-symmetric", action="store_true", help="ablation: drop the symmetry constraint")
@@ -337,10 +344,23 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what they computed (rank 0's batch; a seeded sample of its "
                          "scenes when larger than 64 MB) as DIR/<name>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
+
+def extra_legs(args, world, rank):
+    """(other_configs, cpu_baseline): which legs beyond the headline this rank runs.  Only a `--full` run on one GPU
+    has any; other_configs only for the unmodified c2 workload."""
+    full = args.full and world == 1 and rank == 0
+    other = (full and args.config == "c2" and not args.no_other and not args.strong and args.scenes is None
+             and not args.no_symmetric and not args.no_monotonic)
+    return other, full and not args.no_cpu
+
+
+def main():
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -354,10 +374,8 @@ def main():
     if world != args.gpus:
         print("error: WORLD_SIZE=%d but --gpus %d" % (world, args.gpus), file=sys.stderr)
         sys.exit(2)
-    other = None
-    if (args.config == "c2" and world == 1 and not args.no_other and not args.strong and args.scenes is None
-            and not args.no_symmetric and not args.no_monotonic):
-        other = run_other_configs(args)
+    want_other, want_cpu = extra_legs(args, world, rank)
+    other = run_other_configs(args) if want_other else None
     cfg = CONFIGS[args.config]
     B, H, W, K = cfg["B"], cfg["H"], cfg["W"], cfg["K"]
     S_arg = args.scenes if args.scenes is not None else cfg["S"]
@@ -378,7 +396,7 @@ def main():
     try:
         if cfg["psf"]:
             obs_psfs, model_psf = pool.apply(psf_setup, (B,))
-        if rank == 0 and world == 1 and not args.no_cpu:
+        if want_cpu:
             cpu = cpu_baseline(pool, workers, args.cpu_scenes or cfg["cpu_scenes"], args.cpu_iters or cfg["cpu_iters"],
                                kw, cfg["psf"], cfg["l0"], cfg["first"])
         t0 = time.perf_counter()

@@ -7,9 +7,10 @@ cd $R
 rm -f gpurun_out/${TAG}_rel_err_log.txt
 SCARLET_LOG_REL_ERR=$R/gpurun_out/${TAG}_rel_err_log.txt python -m pytest tests -m gpu -q > gpurun_out/${TAG}_gputest.log 2>&1
 sort -g -r gpurun_out/${TAG}_rel_err_log.txt > gpurun_out/${TAG}_rel_err_all_gpu_tests.txt
+B=${BENCH_OUT:-bench_out}; mkdir -p $B      # the three configs' bench lines, CPU legs included (--full)
 for c in c2 c3 c5; do
-  python bench.py --steps 20 --warmup 5 --config $c > gpurun_out/${TAG}_bench_$c.log 2>&1
-  grep '^{"metric"' gpurun_out/${TAG}_bench_$c.log > gpurun_out/${TAG}_bench_$c.json
+  python bench.py --steps 20 --warmup 5 --config $c --full > $B/${TAG}_bench_$c.log 2>&1
+  grep '^{"metric"' $B/${TAG}_bench_$c.log > $B/${TAG}_bench_$c.json
 done
 SCARLET_BENCH_REHEARSE=1 python bench.py --gpus 2 --steps 20 --warmup 5 --scenes 5000 --no-cpu 2>/dev/null | grep '^{"metric"' > gpurun_out/${TAG}_bench_c2_2ranks_one_gpu_rehearsal_weak.json
 SCARLET_BENCH_REHEARSE=1 python bench.py --gpus 2 --steps 20 --warmup 5 --scenes 10000 --strong --no-cpu 2>/dev/null | grep '^{"metric"' > gpurun_out/${TAG}_bench_c2_2ranks_one_gpu_rehearsal_strong.json

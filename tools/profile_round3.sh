@@ -15,7 +15,7 @@ tail -3 $O/${TAG}_gputest.log
 
 # 2. the driver's invocation (headline + c3 + c5 + CPU legs), then the headline alone at 50 steps and the
 #    single-GPU proxies of the strong-scaling shards (10 000 scenes over 2 / 4 / 8 GPUs)
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver.log 2>&1; line $O/${TAG}_bench_driver.log $O/${TAG}_bench_driver_invocation.json
+timeout -k 10 900 python bench.py --steps 20 --warmup 5 --full > $O/${TAG}_bench_driver.log 2>&1; line $O/${TAG}_bench_driver.log $O/${TAG}_bench_driver_invocation.json
 for S in 10000 5000 2500 1250; do
   timeout -k 10 300 python bench.py --steps 50 --warmup 5 --no-cpu --no-other --scenes $S > $O/${TAG}_b.log 2>&1; line $O/${TAG}_b.log $O/${TAG}_bench_c2_S${S}_50steps.json
 done
