@@ -66,6 +66,14 @@ extern "C" {
 #define SCARLET_STATUS_NONFINITE         2  /* NaN/Inf met in centroid or normalisation   */
 #define SCARLET_STATUS_BAD_COUNT         4  /* n_components[s] outside 1..K: the scene is
                                                left untouched and inactive                 */
+#define SCARLET_STATUS_BAD_INIT          8  /* bad input of scarlet_init_sources in this scene:
+                                               it is left untouched and inactive           */
+
+/* source types of scarlet_init_sources (scarlet_init_spec::kind) */
+#define SCARLET_INIT_EXTENDED 0   /* ExtendedSource (source.py:139-180, 443-492)                */
+#define SCARLET_INIT_POINT    1   /* PointSource (source.py:340-400)                            */
+/* most members of one multi-component source that scarlet_init_sources layers */
+#define SCARLET_MAX_LAYERS    8
 
 /* symmetry algorithms -- scarlet/operator.py:291-350 */
 #define SCARLET_SYM_KSPACE 0
@@ -367,6 +375,43 @@ int scarlet_profile_end_ex(double total_ms[8], int64_t iterations[8], int64_t la
 int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host, float thresh,
                           const float *sed_scale_host, int init_symmetric, int init_monotonic,
                           int run_update, void *stream);
+
+/* Initialisation of a batch of mixed sources, all inputs on the device (initsrc.h).  Per component:
+ *   - group[s][k] >= 0: a layer of MultiComponentSource g (init_multicomponent_source, source.py:242-295).  The n
+ *     members of a group (1 <= n <= SCARLET_MAX_LAYERS) start from the extended initialisation at the centre of the
+ *     first member (symmetric = b->symmetric); member j >= 1 starts at flux_percentiles[s][k + j] * max / 100
+ *     (ascending, inside (0, 100); NULL: 25), each layer is divided by its own max, and the SEDs are the
+ *     least-squares fit (M M^T)^-1 M D^T to the scene's images (float64 sums and solve, source.py:74-98);
+ *   - kind[s][k] == SCARLET_INIT_POINT: PointSource -- the model PSF pasted with its centre on the pixel and clipped
+ *     to the frame (a single 1 without model_psf); SED = pixel / obs PSF peak;
+ *   - otherwise ExtendedSource, what scarlet_init_extended does with the scene's own bg_rms row and
+ *     sed = pixel / obs PSF peak x max(model PSF) (get_psf_sed, source.py:41-71).
+ * Absent components (n_components) are not touched; a centre outside the frame gives an empty component and
+ * SCARLET_STATUS_CENTER_AT_EDGE; nothing above the cut gives FLAG_NO_VALID_PIXELS (every member of a group).
+ * run_update != 0: the constructors' update() once with it = 0 (the group pipeline for groups).
+ * A scene with bad input -- bg_rms <= 0 in a band, a group of more than SCARLET_MAX_LAYERS members, percentiles
+ * not ascending or outside (0, 100), an unknown kind -- gets SCARLET_STATUS_BAD_INIT and active = 0 and is left
+ * untouched; the bit is cleared on the other scenes.  A layer whose max is <= 0 (the reference divides by zero)
+ * or a singular normal matrix is found only while the group is layered: that scene gets BAD_INIT and active = 0
+ * too, its other components keep their new start and the update does not run on it.
+ * Needs no workspace; allocates a temporary [S] int buffer (and the float64 tiles of frames beyond LDS) and
+ * returns after the stream has finished the work. */
+typedef struct scarlet_init_spec {
+    const float   *bg_rms;               /* device [B], or [S][B] when bg_rms_per_scene                     */
+    int32_t        bg_rms_per_scene;
+    const float   *obs_psf_peak;         /* device [B] / [S][B]: max of each observed PSF band, or NULL      */
+    int32_t        obs_psf_peak_per_scene;
+    const float   *model_psf;            /* device [P][P], P odd: the model frame's PSF, or NULL             */
+    int32_t        model_psf_P;
+    const int32_t *kind;                 /* device [S][K] SCARLET_INIT_*, or NULL = all EXTENDED;
+                                            ignored where group[s][k] >= 0                                   */
+    const float   *flux_percentiles;     /* device [S][K]: at member j >= 1 of a group, the percentile of
+                                            boundary j, ascending; NULL = 25 (groups of 2)                   */
+    float          thresh;
+    int32_t        init_symmetric, init_monotonic, run_update;
+} scarlet_init_spec;
+
+int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *spec, void *stream);
 
 /* Row a3b set-up: FFT the difference kernel into the workspace (K-hat at the reference's FFT
  * shape next_fast_len(N + P + 3), fft.py:68-106) and create the batched hipFFT plans (cached

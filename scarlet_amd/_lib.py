@@ -37,7 +37,9 @@ lib = ctypes.CDLL(LIB_PATH)
 # error codes / enums (mirror include/scarlet_hip.h)
 OK, E_ARG, E_TOO_LARGE, E_HIP, E_NOTIMPL = 0, -1, -2, -3, -4
 FLAG_SED_NOT_CONVERGED, FLAG_MORPH_NOT_CONVERGED, FLAG_EDGE_PIXELS, FLAG_NO_VALID_PIXELS = 1, 2, 4, 8
-STATUS_CENTER_AT_EDGE, STATUS_NONFINITE, STATUS_BAD_COUNT = 1, 2, 4
+STATUS_CENTER_AT_EDGE, STATUS_NONFINITE, STATUS_BAD_COUNT, STATUS_BAD_INIT = 1, 2, 4, 8
+INIT_EXTENDED, INIT_POINT = 0, 1           # SCARLET_INIT_*
+MAX_LAYERS = 8                             # SCARLET_MAX_LAYERS
 SYM_KSPACE, SYM_SOFT, SYM_SDSS = 0, 1, 2
 SYM_FULL_WINDOW = 16
 NORM_SED, NORM_MORPH, NORM_MORPH_MAX = 0, 1, 2
@@ -62,6 +64,19 @@ class ScarletBatch(Structure):
         ("workspace", c_void_p),
         ("group", c_void_p),
         ("n_components", c_void_p),
+    ]
+
+
+class ScarletInitSpec(Structure):
+    """struct scarlet_init_spec of include/scarlet_hip.h (field order must match)."""
+    _fields_ = [
+        ("bg_rms", c_void_p), ("bg_rms_per_scene", c_int32),
+        ("obs_psf_peak", c_void_p), ("obs_psf_peak_per_scene", c_int32),
+        ("model_psf", c_void_p), ("model_psf_P", c_int32),
+        ("kind", c_void_p),
+        ("flux_percentiles", c_void_p),
+        ("thresh", c_float),
+        ("init_symmetric", c_int32), ("init_monotonic", c_int32), ("run_update", c_int32),
     ]
 
 
@@ -107,6 +122,7 @@ _SIGNATURES = {
     "scarlet_profile_end": (c_int, [_P, _P]),
     "scarlet_profile_end_ex": (c_int, [_P, _P, _P]),
     "scarlet_init_extended": (c_int, [POINTER(ScarletBatch), _P, c_float, _P, c_int, c_int, c_int, _P]),
+    "scarlet_init_sources": (c_int, [POINTER(ScarletBatch), POINTER(ScarletInitSpec), _P]),
     "scarlet_convergence_sums": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_batch_prepare_psf": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_convolve_same": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P]),

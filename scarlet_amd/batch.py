@@ -115,6 +115,7 @@ class BlendBatch(object):
         self.status = torch.zeros((S,), **i32)
         self.fix_sed = None
         self.fix_morph = None
+        self._init_checked = False    # init_sources ran: scenes may carry STATUS_BAD_INIT
         self.group = None
         if group is not None:
             g = np.asarray(group, dtype=np.int32).reshape(S, K)
@@ -265,6 +266,11 @@ class BlendBatch(object):
             bad = np.nonzero(st & _lib.STATUS_CENTER_AT_EDGE)[0][:5]
             raise ValueError("max_pixel window left the image in scenes {} (the reference fails "
                              "there too: measurement.py:24-29)".format(bad.tolist()))
+        if (st & _lib.STATUS_BAD_INIT).any():
+            bad = np.nonzero(st & _lib.STATUS_BAD_INIT)[0]
+            raise ValueError("init_sources: bad input in scenes {} (bg_rms <= 0 in a band, a group of more than {} "
+                             "components, percentiles not ascending inside (0, 100), or an empty layer); they were "
+                             "left inactive".format(bad.tolist(), _lib.MAX_LAYERS))
 
     # ------------------------------------------------------------------ operations
     def init_extended(self, bg_rms, thresh=1.0, sed_scale=None, init_symmetric=True, init_monotonic=None,
@@ -282,6 +288,102 @@ class BlendBatch(object):
         _lib.check(rc)
         return self
 
+    def init_sources(self, bg_rms, kind=None, flux_percentiles=None, obs_psfs=None, model_psf=None, thresh=1.0,
+                     init_symmetric=True, init_monotonic=None, run_update=True):
+        """Initialise every component as the source type the reference's constructors would make of it, on the
+        device for the whole batch (scarlet_init_sources), then run their update() once.
+
+        bg_rms : (B,) shared by all scenes, or (S, B) per scene
+        kind : None (every component is an ExtendedSource), or (S, K) of "extended" / "point" or INIT_* integers;
+            ignored for the layers of a multi-component source (`group` >= 0)
+        flux_percentiles : the boundaries between the layers of a MultiComponentSource: None (the reference's
+            default [25]), one list for every group (sorted, as the reference does: groups then have len + 1
+            members), or an (S, K) array holding at member j >= 1 of each group the percentile of boundary j
+        obs_psfs : None, (B, P, P) or (S, B, P, P): the observed PSFs; their peaks divide the pixel SEDs
+        model_psf : None or (P, P), P odd: the model frame's PSF (frame.psfs[0]); point sources paste it, extended
+            SEDs are multiplied by its max (get_psf_sed)
+        init_symmetric, init_monotonic : the arguments of init_extended_source for the extended sources (the layers
+            use the batch's `symmetric`, as MultiComponentSource does)
+
+        Bad input of the whole call raises ValueError; bad input of single scenes (a bg_rms row with a value <= 0, a
+        group of more than MAX_LAYERS members, percentiles not ascending inside (0, 100)) gives those scenes
+        STATUS_BAD_INIT and leaves them untouched and inactive (`raise_on_status` names them)."""
+        t = self.torch
+        S, K, B = self.S, self.K, self.B
+        keep = []
+
+        def dev(a, dtype):
+            x = (a if t.is_tensor(a) else t.as_tensor(np.asarray(a))).to(device=self.device, dtype=dtype).contiguous()
+            keep.append(x)
+            return x
+
+        bg = dev(bg_rms, t.float32)
+        if tuple(bg.shape) not in ((B,), (S, B)):
+            raise ValueError("bg_rms must have shape (B,) = (%d,) or (S, B) = (%d, %d), not %s" % (B, S, B, tuple(bg.shape)))
+        if bg.ndim == 1 and not bool((bg > 0).all().item()):
+            raise ValueError("bg_rms must be greater than zero in all channels")
+        spec = _lib.ScarletInitSpec()
+        spec.bg_rms, spec.bg_rms_per_scene = bg.data_ptr(), int(bg.ndim == 2)
+        if kind is not None:
+            kk = np.asarray(kind.cpu() if t.is_tensor(kind) else kind)
+            if kk.shape != (S, K):
+                raise ValueError("kind must have shape (S, K) = (%d, %d), not %s" % (S, K, kk.shape))
+            if kk.dtype.kind in "US":
+                names = {"extended": _lib.INIT_EXTENDED, "point": _lib.INIT_POINT}
+                unknown = set(kk.ravel().tolist()) - set(names)
+                if unknown:
+                    raise ValueError("unknown source kind %r (extended or point)" % sorted(unknown)[0])
+                kk = np.vectorize(names.get, otypes=[np.int32])(kk)
+            elif not np.issubdtype(kk.dtype, np.integer) or not np.isin(kk, (_lib.INIT_EXTENDED, _lib.INIT_POINT)).all():
+                raise ValueError("kind must hold INIT_EXTENDED or INIT_POINT")
+            spec.kind = dev(kk.astype(np.int32), t.int32).data_ptr()
+        if flux_percentiles is not None and np.ndim(flux_percentiles) == 2:
+            perc = np.asarray(flux_percentiles.cpu() if t.is_tensor(flux_percentiles) else flux_percentiles)
+            if perc.shape != (S, K):
+                raise ValueError("flux_percentiles must be one list or (S, K) = (%d, %d), not %s" % (S, K, perc.shape))
+            spec.flux_percentiles = dev(perc.astype(np.float32), t.float32).data_ptr()
+        elif self.group is not None:
+            # one list for every group (the reference sorts it): every group needs len + 1 members
+            lst = np.sort(np.asarray([25] if flux_percentiles is None else flux_percentiles, dtype=np.float64).ravel())
+            if ((lst <= 0) | (lst >= 100)).any():
+                raise ValueError("flux_percentiles must lie inside (0, 100): %s" % lst.tolist())
+            g = self.group.cpu().numpy()
+            perc = np.zeros((S, K), np.float32)
+            for s in range(S):
+                k = 0
+                while k < K:
+                    if g[s, k] < 0:
+                        k += 1
+                        continue
+                    n = 1
+                    while k + n < K and g[s, k + n] == g[s, k]:
+                        n += 1
+                    if n != len(lst) + 1:
+                        raise ValueError("scene %d, component %d: a group of %d components needs %d flux_percentiles, "
+                                         "%d given" % (s, k, n, n - 1, len(lst)))
+                    perc[s, k + 1:k + n] = lst
+                    k += n
+            spec.flux_percentiles = dev(perc, t.float32).data_ptr()
+        if obs_psfs is not None:
+            op = dev(obs_psfs, t.float32)
+            if op.ndim not in (3, 4) or tuple(op.shape[:-2]) not in ((B,), (S, B)):
+                raise ValueError("obs_psfs must be (B, P, P) or (S, B, P, P), not %s" % (tuple(op.shape),))
+            peak = op.amax(dim=(-2, -1)).contiguous()
+            keep.append(peak)
+            spec.obs_psf_peak, spec.obs_psf_peak_per_scene = peak.data_ptr(), int(op.ndim == 4)
+        if model_psf is not None:
+            mp = dev(model_psf, t.float32)
+            if mp.ndim != 2 or mp.shape[0] != mp.shape[1] or mp.shape[0] % 2 != 1:
+                raise ValueError("model_psf must be (P, P) with P odd, not %s" % (tuple(mp.shape),))
+            spec.model_psf, spec.model_psf_P = mp.data_ptr(), int(mp.shape[0])
+        spec.thresh = float(thresh)
+        spec.init_symmetric = int(bool(init_symmetric))
+        spec.init_monotonic = int(self.monotonic if init_monotonic is None else bool(init_monotonic))
+        spec.run_update = int(bool(run_update))
+        _lib.check(_lib.lib.scarlet_init_sources(ctypes.byref(self._c), ctypes.byref(spec), _lib.stream_ptr()))
+        self._init_checked = True
+        return self
+
     def update_sources(self):
         """Run the constraint pipeline once with it=0 (what the source constructors do)."""
         _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 0, _lib.stream_ptr()))
@@ -292,6 +394,8 @@ class BlendBatch(object):
         stop iterating individually.  Returns the number of iterations launched."""
         self._ensure_mse_capacity(max_iter)
         self.active.fill_(1)          # a new fit() call iterates again, like the reference
+        if self._init_checked:        # ... except the scenes whose init_sources input was bad
+            self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
         rc = _lib.lib.scarlet_fit(ctypes.byref(self._c), int(max_iter), float(e_rel),
                                   int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
         return _lib.check(rc)

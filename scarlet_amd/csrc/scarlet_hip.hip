@@ -25,6 +25,7 @@
 #include "psf_path.h"
 #include "fftconv.h"
 #include "extras.h"
+#include "initsrc.h"
 
 __constant__ unsigned short sc_nfl_table[SC_NFL_MAX];
 
@@ -2089,50 +2090,10 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_extended(InitArgs a, double *
         sed_s[threadIdx.x] = v;
     }
     __syncthreads();
-    // build_detection_coadd (source.py:101-136): bands with positive SED only
-    double wb[SC_BMAX], jac = 0, var = 0;
-#pragma unroll
-    for (int b = 0; b < SC_BMAX; ++b) {
-        wb[b] = 0;
-        if (b < B && sed_s[b] > 0.f) {
-            const double sd = (double)sed_s[b], bg = a.bg_rms[b];
-            wb[b] = sd / (bg * bg);
-            jac += sd * sd / (bg * bg);
-            var += wb[b] * wb[b] * bg * bg;
-        }
-    }
-    const double cutoff = a.thresh * sqrt(var) / jac;
-    for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
-        double acc = 0;
-#pragma unroll
-        for (int b = 0; b < SC_BMAX; ++b)
-            if (b < B && wb[b] != 0) acc += wb[b] * (double)img[(size_t)b * HW + i];
-        t.m[(i / W) * t.LW + (i % W)] = acc / jac;
-    }
-    __syncthreads();
-    const SymWindow sw = sym_window(H, W, cy, cx);
-    if (a.do_symmetric) flip_symmetry_tile<double>(t, sw, true, 1.0);      // sdss (source.py:162)
-    // thresh=.1 (source.py:165-167).  Everything <= cutoff is zeroed below (source.py:170-175), so the sweep
-    // may stop once three levels hold nothing above the cutoff: the levels beyond cannot exceed it either
-    __shared__ int lastpos_s;
-    int lstop = 1 << 30;
-    if (a.do_monotonic) {
-        if (!GT && cutoff >= 0 && !a.no_hybrid) {
-            // levels 1 .. 46 on one wave without barriers (wave_ops.h), the rest on the workgroup if needed
-            __shared__ int hyb[2];
-            if (threadIdx.x < SC_WAVE) {
-                int done, quiet;
-                wave_monotonic<double>(t, cy, cx, 0.1, &done, &quiet, cutoff);
-                if (threadIdx.x == 0) { hyb[0] = done; hyb[1] = quiet; }
-            }
-            __syncthreads();
-            lstop = hyb[0];
-            if (lstop == (1 << 30))
-                lstop = monotonic_tile<false, double>(t, cy, cx, 0.1, &lastpos_s, cutoff, SC_COMPACT_LAST + 1,
-                                                      SC_COMPACT_LAST - hyb[1]);
-        } else
-            lstop = monotonic_tile<false, double>(t, cy, cx, 0.1, cutoff >= 0 ? &lastpos_s : nullptr, cutoff);
-    }
+    // detection coadd, sdss symmetry, thresh=.1 monotone sweep (initsrc.h)
+    double cutoff;
+    const int lstop = init_detect_tile<GT>(t, img, B, cy, cx, sed_s, a.bg_rms, a.thresh, a.do_symmetric,
+                                           a.do_monotonic, a.no_hybrid, cutoff);
     double cnt = 0;
     for (int i = threadIdx.x; i < HW; i += SC_BLOCK)
         if (t.m[(i / W) * t.LW + (i % W)] > cutoff && sweep_level(i / W, i % W, cy, cx) <= lstop) cnt += 1;
@@ -2190,6 +2151,61 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
     }
     HIP_TRY(hipGetLastError());
     return run_update ? launch_update(b, ws_layout(b, WS_PEEK), 0, 1, stream) : SCARLET_OK;   // constructor's self.update()
+}
+
+// ---- scarlet_init_sources (initsrc.h): every stock source type, per-scene noise and PSF peaks
+extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *spec, void *stream)
+{
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if (!spec) return set_err(SCARLET_E_ARG, "null init spec");
+    if (!spec->bg_rms) return set_err(SCARLET_E_ARG, "bg_rms is required");
+    if (spec->model_psf && (spec->model_psf_P <= 0 || !(spec->model_psf_P & 1) || spec->model_psf_P > 2 * SCARLET_MAX_SIDE + 1))
+        return set_err(SCARLET_E_ARG, "model_psf must be P x P with P odd");
+    InitSrcArgs a;
+    a.S = b->S; a.K = b->K; a.B = b->B; a.H = b->H; a.W = b->W;
+    a.images = b->images; a.sed[0] = b->sed[0]; a.sed[1] = b->sed[1];
+    a.morph[0] = b->morph[0]; a.morph[1] = b->morph[1]; a.cur = b->cur; a.centers = b->centers;
+    a.flags = b->flags; a.status = b->status; a.active = b->active;
+    a.ncomp_in = b->n_components; a.group = b->group; a.kind = spec->kind;
+    a.bg_rms = spec->bg_rms; a.bg_stride = spec->bg_rms_per_scene ? b->B : 0;
+    a.obs_peak = spec->obs_psf_peak; a.peak_stride = spec->obs_psf_peak_per_scene ? b->B : 0;
+    a.model_psf = spec->model_psf; a.P = spec->model_psf ? spec->model_psf_P : 0;
+    a.perc = spec->flux_percentiles; a.thresh = spec->thresh;
+    a.do_symmetric = spec->init_symmetric; a.do_monotonic = spec->init_monotonic; a.group_symmetric = b->symmetric;
+    a.no_hybrid = opt(OPT_NO_HYBRID_SWEEP) ? 1 : 0;
+    const size_t lds = sizeof(double) * (size_t)b->H * (b->W + 1);
+    if (lds <= LDS_LIMIT &&
+        ((rc = allow_lds(k_init_extended_rows<false>, lds)) || (rc = allow_lds(k_init_layers<false>, lds))))
+        return rc;
+    if ((rc = check_counts(b, stream))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // the counts this call works with: a scene with bad input keeps none (one-time set-up: a temporary buffer)
+    DevBuf ncomp, gtile;
+    DEV_ALLOC(ncomp, sizeof(int) * (size_t)b->S);
+    a.ncomp = ncomp.as<int>();
+    hipLaunchKernelGGL(k_init_check, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a);
+    const dim3 grid(b->S * b->K);
+    if (lds <= LDS_LIMIT) {
+        hipLaunchKernelGGL(k_init_extended_rows<false>, grid, dim3(SC_BLOCK), lds, st, a, (double *)nullptr);
+        if (b->group) hipLaunchKernelGGL(k_init_layers<false>, grid, dim3(SC_BLOCK), lds, st, a, (double *)nullptr);
+    } else {
+        DEV_ALLOC(gtile, lds * (size_t)b->S * b->K);
+        hipLaunchKernelGGL(k_init_extended_rows<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
+        if (b->group) hipLaunchKernelGGL(k_init_layers<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
+    }
+    hipLaunchKernelGGL(k_init_point, grid, dim3(SC_BLOCK), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (spec->run_update) {                          // the constructors' self.update(), on the scenes initialised here
+        scarlet_batch c = *b;
+        c.n_components = a.ncomp;
+        if ((rc = launch_update(&c, ws_layout(b, WS_PEEK), 0, 1, stream))) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));               // before the temporary buffers go
+    return SCARLET_OK;
 }
 
 // ---- convergence sums for the Python-override path (the built-in pipeline computes them itself)
