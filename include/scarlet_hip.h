@@ -53,6 +53,8 @@ extern "C" {
 #define SCARLET_MAX_SIDE     1024
 /* most components per scene (K) of the engine and init_extended; more: SCARLET_E_NOTIMPL */
 #define SCARLET_MAX_COMPONENTS 256
+/* most observations of scarlet_fit_observations / scarlet_fit_multi */
+#define SCARLET_MAX_OBSERVATIONS 8
 
 /* BlendFlag bits -- scarlet/component.py:13-36 */
 #define SCARLET_FLAG_SED_NOT_CONVERGED   1
@@ -289,7 +291,7 @@ typedef struct scarlet_batch {
        Every entry point that iterates or initialises checks the counts on the device first: a scene whose
        count lies outside 1..K gets SCARLET_STATUS_BAD_COUNT and active = 0 and is not touched again; the
        other scenes go on.  The workspace does not depend on the counts.  scarlet_fit_multi does not take
-       them (SCARLET_E_NOTIMPL).                                                                       */
+       them (SCARLET_E_NOTIMPL); scarlet_fit_observations does.                                         */
     const int32_t *n_components;
 } scarlet_batch;
 
@@ -316,15 +318,30 @@ int scarlet_batch_pipelines(const scarlet_batch *b);
 int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int approximate_L,
                 int check_every, void *stream);
 
-/* Blend.fit with SEVERAL observations (blend.py:24-43, 120-139, 219-220), no host synchronisation per
- * iteration.  `state` holds the factors over the model frame's C = state->B channels (its `images` are not
- * read: pass any buffer of the right size); obs[i] (n_obs <= 8) is a batch over the channels band0[i] ..
- * band0[i] + obs[i]->B - 1 with its own images / weights / PSF kernel / workspace and the same S, K, H, W --
- * its factor buffers are scratch of this call.  Per iteration: every observation's loss gradient
- * (scarlet_backward_gradients), their sum, L * n_obs (exact or approximate), the step, the constraint
- * pipeline and the convergence test on `state`.  Returns the number of iterations launched. */
+/* Blend.fit with SEVERAL observations (blend.py:24-43, 120-139, 219-220) for a whole batch, no host synchronisation per
+ * iteration.  `state` holds the factors over the model frame's C = state->B channels (its `images` and `weights` are
+ * not read: pass any buffer of the right size) and governs everything but the data: counts (n_components), fix_sed /
+ * fix_morph, centres, the constraint pipeline and the convergence test.  obs[i] (1 <= n_obs <= SCARLET_MAX_OBSERVATIONS)
+ * is a batch over the channels band0[i] .. band0[i] + obs[i]->B - 1 of the model (observations may overlap in
+ * channels, e.g. two epochs of the same bands) with its own images / weights / PSF kernel (prepared by
+ * scarlet_batch_prepare_psf) / workspace and the same S, K, H, W; its n_components must be NULL (SCARLET_E_ARG), its
+ * factor buffers are scratch of this call (sed[0] holds the band slice its PSF chain reads).  Per iteration: the loss
+ * summed over the observations, ONE pass over the state's morphologies for all of them (no morphology copies), L_sed =
+ * n_obs lambda_max(S S^T), L_morph = n_obs lambda_max(A^T A) over the C channels (or the approximate form of
+ * blend.py:189-201 on the summed loss), the step, the constraint pipeline and the convergence test on `state`.
+ * Returns the number of iterations launched. */
+int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                             int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+/* The same without ragged batches (state->n_components or an observation's: SCARLET_E_NOTIMPL). */
 int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
                       int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+/* CombinedExtendedSource's SED (source.py:183-240 through get_psf_sed, source.py:41-71) from one observation: for every
+ * present component of a scene without SCARLET_STATUS_BAD_INIT, channels band0 .. band0 + B - 1 of buffer cur get the
+ * observation's pixel values at the centre (images: device [S][B][H][W]), divided by obs_psf_peak (device [B], or
+ * [S][B] when peak_per_scene; NULL: no division) and multiplied by *model_psf_max (device float; NULL: no factor).
+ * The morphology is scarlet_init_sources on the batch of observation obs_idx (symmetric, no update). */
+int scarlet_init_combined_sed(scarlet_batch *state, const float *images, int B, int band0, const float *obs_psf_peak,
+                              int peak_per_scene, const float *model_psf_max, void *stream);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

@@ -22,7 +22,7 @@ from .source import (SourceInitError, get_pixel_sed, get_psf_sed, get_best_fit_s
                      ExtendedSource, MultiComponentSource, RandomSource)
 from .observation import Frame, Observation
 from .blend import Blend
-from .batch import BlendBatch
+from .batch import BlendBatch, ObservationBatch
 from . import bbox, cache, component, source, observation, blend, batch, synth, distributed, io
 
 update = _update_module

@@ -44,6 +44,7 @@ SYM_KSPACE, SYM_SOFT, SYM_SDSS = 0, 1, 2
 SYM_FULL_WINDOW = 16
 NORM_SED, NORM_MORPH, NORM_MORPH_MAX = 0, 1, 2
 MAX_SIDE, MAX_COMPONENTS = 1024, 256       # SCARLET_MAX_SIDE, SCARLET_MAX_COMPONENTS
+MAX_OBSERVATIONS = 8                       # SCARLET_MAX_OBSERVATIONS
 
 
 class ScarletBatch(Structure):
@@ -111,6 +112,8 @@ _SIGNATURES = {
     "scarlet_batch_workspace_bytes": (c_int64, [POINTER(ScarletBatch)]),
     "scarlet_batch_pipelines": (c_int, [POINTER(ScarletBatch)]),
     "scarlet_fit": (c_int, [POINTER(ScarletBatch), c_int, c_double, c_int, c_int, _P]),
+    "scarlet_fit_observations": (c_int, [POINTER(ScarletBatch), POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
+    "scarlet_init_combined_sed": (c_int, [POINTER(ScarletBatch), _P, c_int, c_int, _P, c_int, _P, _P]),
     "scarlet_fit_multi": (c_int, [POINTER(ScarletBatch), POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
     "scarlet_backward_step": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),

@@ -44,6 +44,44 @@ def pad_centers(centers, K=None):
     return out, counts
 
 
+class ObservationBatch(object):
+    """One observation of S scenes for `BlendBatch.from_observations` (reference Observation, observation.py:101-224,
+    as one element of Blend(sources, [obs_a, obs_b])): the images cover the model channels band0 .. band0 + B - 1.
+
+    images : (S, B, H, W) array or tensor
+    band0 : first model channel of the observation; observations may overlap in channels (several epochs of the same
+        bands)
+    weights : None (scalar 1), a Python scalar, or (S, B, H, W)
+    """
+
+    def __init__(self, images, band0=0, weights=None):
+        if np.ndim(images) != 4:
+            raise ValueError("ObservationBatch: images must be (S, B, H, W), not %s" % (tuple(np.shape(images)),))
+        self.images = images
+        self.shape = tuple(int(v) for v in np.shape(images))
+        self.band0 = int(band0)
+        if self.band0 < 0:
+            raise ValueError("ObservationBatch: band0 must be >= 0, not %d" % self.band0)
+        if weights is not None and np.ndim(weights) != 0 and tuple(np.shape(weights)) != self.shape:
+            raise ValueError("ObservationBatch: weights must be a scalar or %s, not %s" % (self.shape, tuple(np.shape(weights))))
+        self.weights = weights
+        self.diff_kernel = None
+
+    @property
+    def B(self):
+        return self.shape[1]
+
+    def set_diff_kernel(self, kernel):
+        """PSF difference kernel of this observation (Observation.match): (B, P, P) shared by all scenes or
+        (S, B, P, P) one set per scene, as BlendBatch.set_diff_kernel."""
+        S, B = self.shape[:2]
+        if tuple(np.shape(kernel)[:-2]) not in ((B,), (S, B)) or np.ndim(kernel) not in (3, 4):
+            raise ValueError("ObservationBatch: the kernel must be (B, P, P) or (S, B, P, P), not %s"
+                             % (tuple(np.shape(kernel)),))
+        self.diff_kernel = kernel
+        return self
+
+
 class BlendBatch(object):
     """S scenes x K components x B bands x H x W pixels, all float32 on one device.
 
@@ -65,16 +103,22 @@ class BlendBatch(object):
 
     def __init__(self, images, centers, weights=None, symmetric=True, monotonic=True,
                  l0_thresh=None, l1_thresh=None, centroid_weight=None, mse_capacity=256,
-                 device=None, group=None, n_components=None):
+                 device=None, group=None, n_components=None, _frame=None):
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         f32 = dict(dtype=torch.float32, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         f64 = dict(dtype=torch.float64, device=self.device)
-        self.images = torch.as_tensor(images).to(**f32).contiguous()
-        assert self.images.ndim == 4, "images must be (S, B, H, W)"
-        S, B, H, W = self.images.shape
+        if images is None:
+            # the model-frame state of several observations (from_observations): no data of its own, the library
+            # does not read it
+            S, B, H, W = _frame
+            self.images = torch.zeros((1,), **f32)
+        else:
+            self.images = torch.as_tensor(images).to(**f32).contiguous()
+            assert self.images.ndim == 4, "images must be (S, B, H, W)"
+            S, B, H, W = self.images.shape
         if isinstance(centers, (list, tuple)) and len(centers) and np.ndim(centers[0]) == 2 and \
                 len(set(np.shape(c)[0] for c in centers)) > 1:
             centers, counts = pad_centers(centers)
@@ -136,6 +180,7 @@ class BlendBatch(object):
         cw = default_centroid_weight() if centroid_weight is None else np.asarray(centroid_weight, dtype=np.float64)
         assert cw.ndim == 2 and cw.shape[0] == cw.shape[1] and cw.shape[0] % 2 == 1
         self.centroid_weight = torch.as_tensor(cw).to(**f64).contiguous()
+        self._observations = None     # from_observations: [(ObservationBatch, its gradient batch)]
         self._c = _lib.ScarletBatch()
         self._fill_struct()
         nbytes = _lib.lib.scarlet_batch_workspace_bytes(ctypes.byref(self._c))
@@ -277,6 +322,7 @@ class BlendBatch(object):
                       run_update=True):
         """ExtendedSource initialisation for every component (reference source.py:139-180,
         444-492) followed by the constructor's update() call."""
+        self._refuse_single_init()
         bg = np.ascontiguousarray(bg_rms, dtype=np.float32)
         assert bg.shape == (self.B,)
         sc = None if sed_scale is None else np.ascontiguousarray(sed_scale, dtype=np.float32)
@@ -308,6 +354,7 @@ class BlendBatch(object):
         Bad input of the whole call raises ValueError; bad input of single scenes (a bg_rms row with a value <= 0, a
         group of more than MAX_LAYERS members, percentiles not ascending inside (0, 100)) gives those scenes
         STATUS_BAD_INIT and leaves them untouched and inactive (`raise_on_status` names them)."""
+        self._refuse_single_init()
         t = self.torch
         S, K, B = self.S, self.K, self.B
         keep = []
@@ -391,20 +438,162 @@ class BlendBatch(object):
 
     def fit(self, max_iter=200, e_rel=1e-2, approximate_L=False, check_every=10):
         """Blend.fit for every scene (reference blend.py:65-102).  Scenes that reach e_rel
-        stop iterating individually.  Returns the number of iterations launched."""
+        stop iterating individually.  Returns the number of iterations launched.  A batch made by
+        `from_observations` fits all its observations jointly (scarlet_fit_observations)."""
         self._ensure_mse_capacity(max_iter)
         self.active.fill_(1)          # a new fit() call iterates again, like the reference
         if self._init_checked:        # ... except the scenes whose init_sources input was bad
             self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
+        if self._observations is not None:
+            return self._fit_observations(max_iter, e_rel, approximate_L, check_every)
         rc = _lib.lib.scarlet_fit(ctypes.byref(self._c), int(max_iter), float(e_rel),
                                   int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
         return _lib.check(rc)
 
     def step(self, e_rel=1e-2, approximate_L=False):
         """One iteration in three separately callable phases (used by tests and by the
-        Python-level update() override path)."""
+        Python-level update() override path).  A batch made by `from_observations` runs one iteration
+        of scarlet_fit_observations."""
         self._ensure_mse_capacity(1)
+        if self._observations is not None:
+            if self._init_checked:
+                self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
+            self._fit_observations(1, e_rel, approximate_L, 0)
+            return
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step(ctypes.byref(self._c), int(bool(approximate_L)), s))
         _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 1, s))
         _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), float(e_rel), s))
+
+    # ------------------------------------------------------------------ several observations
+    @classmethod
+    def from_observations(cls, observations, centers, **kwargs):
+        """A batch fitted jointly against several observations of every scene (reference Blend(sources, [obs_a,
+        obs_b]), blend.py:24-43, 120-139, 219-220).  The factors span the model frame's C = max(band0 + B) channels
+        (C <= 8); `centers` and the other keyword arguments are those of BlendBatch (ragged centre lists give
+        n_components).  Start the sources with `init_combined` (or `set_state`), then `fit` / `step`."""
+        obs = list(observations)
+        if not 1 <= len(obs) <= _lib.MAX_OBSERVATIONS:
+            raise ValueError("from_observations: 1 to %d observations, not %d" % (_lib.MAX_OBSERVATIONS, len(obs)))
+        if not all(isinstance(o, ObservationBatch) for o in obs):
+            raise ValueError("from_observations: every observation must be an ObservationBatch")
+        S, _, H, W = obs[0].shape
+        for i, o in enumerate(obs):
+            if (o.shape[0], o.shape[2], o.shape[3]) != (S, H, W):
+                raise ValueError("from_observations: observation %d has %d scenes of %d x %d, observation 0 %d of %d x %d"
+                                 % (i, o.shape[0], o.shape[2], o.shape[3], S, H, W))
+        C = max(o.band0 + o.B for o in obs)
+        if C > 8:
+            raise ValueError("from_observations: the observations span %d model channels, at most 8 are supported" % C)
+        for k in ("weights", "images"):
+            if k in kwargs:
+                raise ValueError("from_observations: %s belong to the observations" % k)
+        state = cls(None, centers, _frame=(S, C, H, W), **kwargs)
+        torch, f32 = state.torch, dict(dtype=state.torch.float32, device=state.device)
+        batches = []
+        for o in obs:
+            ob = cls(o.images, state.centers, weights=o.weights, symmetric=False, monotonic=False, mse_capacity=1,
+                     centroid_weight=state.centroid_weight.cpu().numpy(), device=state.device)
+            # the fit reads the state's morphologies: the observation's own planes are not used
+            ob.morph = [torch.zeros((1,), **f32) for _ in range(2)]
+            ob._fill_struct()
+            if o.diff_kernel is not None:
+                ob.set_diff_kernel(o.diff_kernel)
+            batches.append((o, ob))
+        state._observations = batches
+        return state
+
+    def _refuse_single_init(self):
+        if self._observations is not None:
+            raise ValueError("a batch of several observations starts its sources with init_combined "
+                             "(CombinedExtendedSource), not init_extended / init_sources")
+
+    def _fit_observations(self, max_iter, e_rel, approximate_L, check_every):
+        n = len(self._observations)
+        ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
+        band0 = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
+        self._keep = (ptrs, band0)
+        rc = _lib.lib.scarlet_fit_observations(ctypes.byref(self._c), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n,
+                                               int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every),
+                                               _lib.stream_ptr())
+        return _lib.check(rc)
+
+    def init_combined(self, bg_rms, obs_idx=0, obs_psfs=None, model_psf=None, thresh=1.0, init_monotonic=None):
+        """CombinedExtendedSource for every component (reference source.py:183-240, 495-536): the SED is the
+        concatenation of every observation's pixel SED (divided by the observation's PSF peak and multiplied by the
+        model PSF's max when PSFs are given, get_psf_sed), the morphology the extended start from observation
+        `obs_idx` alone with its noise, always symmetric; no update() runs, as in the reference.
+
+        bg_rms : one entry per observation, each (B_o,) or (S, B_o)
+        obs_psfs : None, or one entry per observation: None, (B_o, P, P) or (S, B_o, P, P)
+        model_psf : None or (P, P), P odd
+        The observations' channel slices must tile 0 .. C - 1 in order (the reference's concatenation).  A scene
+        whose bg_rms row of observation obs_idx has a value <= 0 gets STATUS_BAD_INIT and stays inactive."""
+        if self._observations is None:
+            raise ValueError("init_combined needs a batch made by BlendBatch.from_observations")
+        t, obs = self.torch, self._observations
+        n = len(obs)
+        end = 0
+        for o, _ in obs:
+            if o.band0 != end:
+                raise ValueError("init_combined: the observations' channels must tile 0 .. %d in order (observation "
+                                 "at band0 = %d, expected %d)" % (self.B - 1, o.band0, end))
+            end += o.B
+        if end != self.B:
+            raise ValueError("init_combined: the observations cover %d of the %d model channels" % (end, self.B))
+        if not 0 <= int(obs_idx) < n:
+            raise ValueError("init_combined: obs_idx = %d, there are %d observations" % (obs_idx, n))
+        obs_idx = int(obs_idx)
+        if len(bg_rms) != n:
+            raise ValueError("init_combined: one bg_rms per observation (%d), not %d" % (n, len(bg_rms)))
+        if obs_psfs is not None and len(obs_psfs) != n:
+            raise ValueError("init_combined: one obs_psfs entry per observation (%d), not %d" % (n, len(obs_psfs)))
+        keep = []
+
+        def dev(a):
+            x = (a if t.is_tensor(a) else t.as_tensor(np.asarray(a))).to(device=self.device, dtype=t.float32).contiguous()
+            keep.append(x)
+            return x
+
+        peaks = []
+        for i, (o, _) in enumerate(obs):
+            bg = np.shape(bg_rms[i])
+            if tuple(bg) not in ((o.B,), (self.S, o.B)):
+                raise ValueError("init_combined: bg_rms[%d] must be (%d,) or (%d, %d), not %s" % (i, o.B, self.S, o.B, tuple(bg)))
+            p = None if obs_psfs is None else obs_psfs[i]
+            if p is not None:
+                if np.ndim(p) not in (3, 4) or tuple(np.shape(p)[:-2]) not in ((o.B,), (self.S, o.B)):
+                    raise ValueError("init_combined: obs_psfs[%d] must be (%d, P, P) or (%d, %d, P, P), not %s"
+                                     % (i, o.B, self.S, o.B, tuple(np.shape(p))))
+                p = dev(p).amax(dim=(-2, -1)).contiguous()
+                keep.append(p)
+            peaks.append(p)
+        mmax = None
+        if model_psf is not None:
+            mp = np.asarray(model_psf.cpu() if t.is_tensor(model_psf) else model_psf)
+            if mp.ndim != 2 or mp.shape[0] != mp.shape[1] or mp.shape[0] % 2 != 1:
+                raise ValueError("init_combined: model_psf must be (P, P) with P odd, not %s" % (mp.shape,))
+            mmax = dev(mp).amax().reshape(1).contiguous()
+            keep.append(mmax)
+        # the morphology: the extended start on observation obs_idx, written straight into the state's current buffers
+        # (the observation batch's SEDs receive its own band slice, which the SED kernel below replaces)
+        o, ob = obs[obs_idx]
+        c = ob._c
+        c.morph[0], c.morph[1] = self.morph[0].data_ptr(), self.morph[1].data_ptr()
+        c.cur, c.flags, c.status, c.active = self.cur.data_ptr(), self.flags.data_ptr(), self.status.data_ptr(), self.active.data_ptr()
+        c.n_components = None if self.n_components is None else self.n_components.data_ptr()
+        c.centers = self.centers.data_ptr()
+        try:
+            ob.init_sources( bg_rms[obs_idx], obs_psfs=None if obs_psfs is None else obs_psfs[obs_idx],
+                                    model_psf=model_psf, thresh=thresh, init_symmetric=True,
+                                    init_monotonic=self.monotonic if init_monotonic is None else init_monotonic,
+                                    run_update=False)
+        finally:
+            ob._fill_struct()
+        for i, (o, ob) in enumerate(obs):
+            p = peaks[i]
+            _lib.check(_lib.lib.scarlet_init_combined_sed(
+                ctypes.byref(self._c), ob.images.data_ptr(), int(o.B), int(o.band0), None if p is None else p.data_ptr(),
+                int(p is not None and p.ndim == 2), None if mmax is None else mmax.data_ptr(), _lib.stream_ptr()))
+        self._init_checked = True
+        return self

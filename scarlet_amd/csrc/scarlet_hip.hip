@@ -26,6 +26,7 @@
 #include "fftconv.h"
 #include "extras.h"
 #include "initsrc.h"
+#include "multiobs.h"
 
 __constant__ unsigned short sc_nfl_table[SC_NFL_MAX];
 
@@ -1980,51 +1981,171 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
     return launched;
 }
 
-// ---- several observations per blend (extras.h: MultiArgs)
-extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+// ---- several observations per blend (multiobs.h)
+// G planes of an observation with a PSF: model planes from the STATE's morphologies and the observation's band slice
+// of the SEDs (its own buffer sed[0], filled by k_obs_slice), then the convolution chain of backward_step_psf up to the
+// adjoint.  `v` receives where the planes and the per-plane losses lie.
+static int obs_psf_planes(scarlet_batch *ob, const WsLayout &l, const scarlet_batch *state, hipStream_t st, ObsView *v)
+{
+    const PsfGeom &g = l.geom;
+    PsfArgs a = {};
+    a.S = ob->S; a.K = ob->K; a.B = ob->B; a.T = n_tiles(ob); a.g = g;
+    a.images = ob->images; a.weights = ob->weights; a.weight_scalar = ob->weight_scalar;
+    a.sed[0] = a.sed[1] = ob->sed[0];
+    a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
+    a.cur = state->cur; a.active = state->active; a.it = state->it;
+    a.real = ws_at<float>(ob, l.real); a.spec = ws_at<float2>(ob, l.spec); a.khat = ws_at<const float2>(ob, l.khat);
+    a.partials = ws_at<double>(ob, l.partials); a.loss_part = ws_at<double>(ob, l.loss);
+    a.lipschitz = ob->lipschitz; a.mse = ob->mse; a.mse_capacity = ob->mse_capacity;
+    a.khat_per_scene = ob->diff_kernel_per_scene;
+    const int HW = ob->H * ob->W, planes = ob->S * ob->B;
+    const bool huge = ob->K > SC_KBIG;
+    int rc;
+    v->G = a.real; v->loss_part = a.loss_part;
+    if (l.psf_lds) {
+        FftPlan fp = l.plan;
+        fp.tables = ws_at<const float2>(ob, l.lds_tables);
+        a.khat = ws_at<const float2>(ob, l.lds_khat);
+        const bool x128 = psf_conv_finish_plan(ob, &fp);
+        const size_t lds = fft_lds_bytes(fp.Fy, fp.M, fp.RS, ob->H, ob->W, fp.dma_image != 0);
+        if ((rc = allow_lds(k_psf_conv, lds))) return rc;
+        a.g.Fy = ob->H; a.g.Fx = ob->W; a.g.Fxh = ob->W / 2 + 1; a.g.oy = 0; a.g.ox = 0;
+        if (HW % 4 == 0) {
+            const dim3 grid((HW / 4 + SC_BLOCK - 1) / SC_BLOCK, ob->S);
+            if (huge) hipLaunchKernelGGL(k_psf_model4<SC_KHUGE>, grid, dim3(SC_BLOCK), 0, st, a);
+            else hipLaunchKernelGGL(k_psf_model4<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a);
+        } else {
+            const dim3 grid((HW + SC_BLOCK - 1) / SC_BLOCK, ob->S);
+            if (huge) hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, grid, dim3(SC_BLOCK), 0, st, a);
+            else hipLaunchKernelGGL(k_psf_model<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a);
+        }
+        long long *stamps = opt(OPT_STAMPS) ? ws_at<long long>(ob, l.stamps) : nullptr;
+        fp.stagger_wgs = 0;
+        const int groups = (ob->S + 7) / 8;
+        if (x128) {
+            const size_t lds_x = fft_lds_bytes(fp.Fy, fp.M, fp.RS, ob->H, ob->W, SC_X128_DMA != 0);
+            if ((rc = allow_lds(k_psf_conv_x128, lds_x))) return rc;
+            hipLaunchKernelGGL(k_psf_conv_x128, dim3(groups * 8 * ob->B), dim3(SC_FFT_NT_X), lds_x, st, a, fp, a.real, stamps);
+        } else
+            hipLaunchKernelGGL(k_psf_conv, dim3(groups * 8 * ob->B), dim3(SC_FFT_NT), lds, st, a, fp, a.real, stamps);
+        v->Fy = ob->H; v->Fx = ob->W; v->oy = 0; v->ox = 0;
+    } else {
+        FftPlans p;
+        if ((rc = get_plans(g.Fy, g.Fx, planes, &p))) return rc;
+        const int plane_elems = g.Fy * g.Fxh;
+        const float scale = 1.0f / ((float)g.Fy * (float)g.Fx);
+        const int nkh = ob->diff_kernel_per_scene ? planes : ob->B;
+        const dim3 grid((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, ob->S);
+        if (huge) hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, grid, dim3(SC_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL(k_psf_model<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a);
+        if ((rc = fft_r2c(p, a.real, a.spec, st))) return rc;
+        hipLaunchKernelGGL(k_spec_mul, dim3(grid_for((int64_t)planes * plane_elems)), dim3(SC_BLOCK), 0, st,
+                           a.spec, a.khat, nkh, plane_elems, (int64_t)planes * plane_elems, 0, scale);
+        if ((rc = fft_c2r(p, a.spec, a.real, st))) return rc;
+        hipLaunchKernelGGL(k_psf_resid, dim3(planes), dim3(SC_BLOCK), 0, st, a);
+        if ((rc = fft_r2c(p, a.real, a.spec, st))) return rc;
+        hipLaunchKernelGGL(k_spec_mul, dim3(grid_for((int64_t)planes * plane_elems)), dim3(SC_BLOCK), 0, st,
+                           a.spec, a.khat, nkh, plane_elems, (int64_t)planes * plane_elems, 1, scale);
+        if ((rc = fft_c2r(p, a.spec, a.real, st))) return rc;
+        v->Fy = g.Fy; v->Fx = g.Fx; v->oy = g.oy; v->ox = g.ox;
+    }
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
+// L_sed of the state's current morphologies (blend.py:186-218, before the factor n_obs): the Gram matrix and its largest
+// eigenvalue by the existing code of the K range, or its trace with approximate constants
+static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const GradArgs &ga, int approximate_L, hipStream_t st)
+{
+    if (l.grad == GRAD_HUGEK) {
+        HugeArgs h;
+        h.C = huge_nchunks(state->H * state->W);
+        h.gpart = ws_at<double>(state, l.gpart); h.gram = ws_at<double>(state, l.gram);
+        h.msq[0] = ws_at<double>(state, l.msq[0]); h.msq[1] = ws_at<double>(state, l.msq[1]);
+        const int nb = huge_nblk(state->K), npairs = huge_npairs(state->K);
+        if ((ga.HW & 3) == 0) hipLaunchKernelGGL((k_huge_gram<true>), dim3(h.C, npairs, ga.S), dim3(SC_BLOCK), 0, st, ga, h);
+        else hipLaunchKernelGGL((k_huge_gram<false>), dim3(h.C, npairs, ga.S), dim3(SC_BLOCK), 0, st, ga, h);
+        hipLaunchKernelGGL(k_huge_gram_reduce, dim3(npairs, ga.S), dim3(SC_BLOCK), 0, st, ga, h);
+        const double *last = h.gram;
+        if (!approximate_L)
+            for (int q = 0; q < SC_HUGE_SQUARINGS; ++q) {
+                hipLaunchKernelGGL(k_huge_square, dim3(nb, nb, ga.S), dim3(SC_BLOCK), 0, st, ga, last, h.msq[q & 1]);
+                last = h.msq[q & 1];
+            }
+        hipLaunchKernelGGL(k_huge_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, h, last);
+    } else {
+        launch_bigk_gram(ga, (state->K + SC_CHUNK - 1) / SC_CHUNK, st);
+        hipLaunchKernelGGL(k_bigk_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, approximate_L ? 1 : 2);
+    }
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
+static int fit_observations_impl(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
                                  int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
 {
-    int rc = check_batch(state, true);
-    if (rc) return rc;
-    if (!obs || !band0 || n_obs < 1 || n_obs > SC_MULTI_MAX) return set_err(SCARLET_E_ARG, "1 to 8 observations");
-    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
-    MultiArgs m;
-    m.S = state->S; m.K = state->K; m.C = state->B; m.HW = state->H * state->W; m.n_obs = n_obs;
-    m.sed[0] = state->sed[0]; m.sed[1] = state->sed[1]; m.morph[0] = state->morph[0]; m.morph[1] = state->morph[1];
-    m.cur = state->cur; m.active = state->active; m.it = state->it;
-    m.lipschitz = state->lipschitz; m.mse = state->mse; m.mse_capacity = state->mse_capacity;
-    m.fix_sed = state->fix_sed; m.fix_morph = state->fix_morph; m.approximate_L = approximate_L;
-    for (int o = 0; o < n_obs; ++o) {
-        if ((rc = check_batch(obs[o], true))) return rc;
-        const scarlet_batch *ob = obs[o];
-        if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || band0[o] < 0 ||
-            band0[o] + ob->B > state->B || ob->mse_capacity < 1)
-            return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
-        m.obs[o].sed[0] = ob->sed[0]; m.obs[o].sed[1] = ob->sed[1]; m.obs[o].morph[0] = ob->morph[0]; m.obs[o].morph[1] = ob->morph[1];
-        m.obs[o].cur = ob->cur; m.obs[o].it = ob->it; m.obs[o].active = ob->active;
-        m.obs[o].mse = ob->mse; m.obs[o].mse_capacity = ob->mse_capacity; m.obs[o].B = ob->B; m.obs[o].band0 = band0[o];
-    }
+    int rc;
     hipStream_t st = (hipStream_t)stream;
+    if ((rc = check_counts(state, stream))) return rc;
     const WsLayout l = ws_layout(state, WS_FIX);
-    WsLayout lo[SC_MULTI_MAX];
-    for (int o = 0; o < n_obs; ++o) lo[o] = ws_layout(obs[o], WS_FIX);
-    // scratch for the approximate Lipschitz sums: the state's convergence-sum area is free until the update runs
-    double *approx = ws_at<double>(state, l.conv);
+    WsLayout lo[SC_MAX_OBS];
+    ObsArgs m = {};
+    m.S = state->S; m.K = state->K; m.C = state->B; m.H = state->H; m.W = state->W; m.HW = state->H * state->W;
+    m.T = n_tiles(state); m.n_obs = n_obs;
+    m.sed[0] = state->sed[0]; m.sed[1] = state->sed[1]; m.morph[0] = state->morph[0]; m.morph[1] = state->morph[1];
+    m.cur = state->cur; m.active = state->active; m.ncomp = state->n_components;
+    m.fix_sed = state->fix_sed; m.fix_morph = state->fix_morph;
+    m.partials = ws_at<double>(state, l.partials);
+    m.lipschitz = state->lipschitz; m.mse = state->mse; m.mse_capacity = state->mse_capacity; m.it = state->it;
+    for (int o = 0; o < n_obs; ++o) {
+        const scarlet_batch *ob = obs[o];
+        lo[o] = ws_layout(ob, WS_FIX);
+        ObsView &v = m.obs[o];
+        v.images = ob->images; v.weights = ob->weights; v.weight_scalar = ob->weight_scalar;
+        v.G = nullptr; v.loss_part = nullptr; v.Fy = ob->H; v.Fx = ob->W; v.oy = v.ox = 0;
+        v.B = ob->B; v.band0 = band0[o];
+        if (ob->diff_kernel && !lo[o].psf) return set_err(SCARLET_E_ARG, "diff_kernel without psf_h, psf_w");
+    }
+    // the state's gradient arguments: its partials (engine.h layout over the C channels) feed the Gram / lambda_max code
+    const GradArgs ga = grad_args(state, l, approximate_L, 0);
+    // K <= 8: the contraction also sums the Gram matrix (no Gram pass); its lambda_max is found in k_obs_head
+    const bool small = state->K <= SC_KMAX && l.grad == GRAD_SMALL;
+    auto contract = small ? k_obs_contract<SC_KMAX> : k_obs_contract<0>;
+    m.head_lsed = small && !approximate_L;
+    const size_t lds = obs_contract_lds(state->K);
+    if ((rc = allow_lds(contract, lds))) return rc;
+    const dim3 grid(m.T, m.S);
     int *d_count = ws_at<int>(state, l.active_count);
-    const dim3 gridc((m.HW + 4 * SC_BLOCK - 1) / (4 * SC_BLOCK), m.S * m.K);
     int launched = 0;
     for (int i = 0; i < max_iter; ++i) {
-        hipLaunchKernelGGL(k_multi_scatter, gridc, dim3(SC_BLOCK), 0, st, m);
-        for (int o = 0; o < n_obs; ++o)
-            if ((rc = backward_impl(obs[o], lo[o], 0, 1, stream))) return rc;
-        // exact L of the FULL factors (blend.py:205-218): the state's own gradient pass (its loss and gradients
-        // are overwritten below); approximate L: the two sums of squares
-        if (approximate_L) hipLaunchKernelGGL(k_multi_approx, dim3(m.S), dim3(SC_BLOCK), 0, st, m, approx);
-        else if ((rc = backward_impl(state, l, 0, 1, stream))) return rc;
-        hipLaunchKernelGGL(k_multi_loss, dim3((m.S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, m, (const double *)approx);
-        hipLaunchKernelGGL(k_multi_step, gridc, dim3(SC_BLOCK), 0, st, m);
+        prof_start(0, st);
+        for (int o = 0; o < n_obs; ++o) {
+            if (!lo[o].psf) continue;
+            hipLaunchKernelGGL(k_obs_slice, dim3(m.S), dim3(SC_BLOCK), 0, st, m, band0[o], obs[o]->B, obs[o]->sed[0]);
+            if ((rc = obs_psf_planes(obs[o], lo[o], state, st, &m.obs[o]))) return rc;
+        }
+        prof_stop(st); prof_start(1, st);
+        if (!approximate_L) {
+            hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
+            m.mode = OBS_FULL;
+            hipLaunchKernelGGL(contract, grid, dim3(SC_BLOCK), lds, st, m);
+            if (!small && (rc = obs_lipschitz_sed(state, l, ga, 0, st))) return rc;
+        } else {
+            m.mode = OBS_PARTIALS;
+            hipLaunchKernelGGL(contract, grid, dim3(SC_BLOCK), lds, st, m);
+            hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
+            if (small) hipLaunchKernelGGL(k_bigk_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, 1);   // (trace of the pass's Gram)
+            else if ((rc = obs_lipschitz_sed(state, l, ga, 1, st))) return rc;
+            m.mode = OBS_STEP;
+            hipLaunchKernelGGL(contract, grid, dim3(SC_BLOCK), lds, st, m);
+        }
+        hipLaunchKernelGGL(k_obs_head, dim3(m.S), dim3(SC_BLOCK), 0, st, m);
+        HIP_TRY(hipGetLastError());
+        prof_stop(st); prof_start(2, st);
         if ((rc = launch_update(state, l, 1, 0, stream))) return rc;
+        prof_stop(st); prof_start(3, st);
         if ((rc = launch_converge(state, l, e_rel, stream))) return rc;
+        prof_stop(st);
         ++launched;
         if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter) {
             int h_count = 0;
@@ -2036,6 +2157,63 @@ extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs
     }
     HIP_TRY(hipGetLastError());
     return launched;
+}
+
+extern "C" int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                        int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    (void)hipGetLastError();
+    if (!state) return set_err(SCARLET_E_ARG, "null batch");
+    if (n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
+    if (!obs || !band0) return set_err(SCARLET_E_ARG, "null observation list");
+    int rc = check_batch(state);
+    if (rc) return rc;
+    for (int o = 0; o < n_obs; ++o) {
+        const scarlet_batch *ob = obs[o];
+        if (!ob) return set_err(SCARLET_E_ARG, "null observation batch");
+        if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || ob->B < 1 ||
+            band0[o] < 0 || band0[o] + ob->B > state->B)
+            return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
+        if (ob->n_components)
+            return set_err(SCARLET_E_ARG, "an observation batch takes no n_components: the state's counts govern every observation");
+        if ((rc = check_batch(ob))) return rc;
+    }
+    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
+    return fit_observations_impl(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                 int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    int rc = check_batch(state, true);
+    if (rc) return rc;
+    if (!obs || !band0 || n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
+    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
+    for (int o = 0; o < n_obs; ++o) {
+        if ((rc = check_batch(obs[o], true))) return rc;
+        const scarlet_batch *ob = obs[o];
+        if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || band0[o] < 0 ||
+            band0[o] + ob->B > state->B || ob->mse_capacity < 1)
+            return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
+    }
+    return fit_observations_impl(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+extern "C" int scarlet_init_combined_sed(scarlet_batch *state, const float *images, int B, int band0,
+                                         const float *obs_psf_peak, int peak_per_scene, const float *model_psf_max,
+                                         void *stream)
+{
+    int rc = check_batch(state);
+    if (rc) return rc;
+    if (!images || B < 1 || band0 < 0 || band0 + B > state->B)
+        return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
+    const int n = state->S * state->K;
+    hipLaunchKernelGGL(k_combined_sed, dim3((n + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
+                       state->S, state->K, state->B, state->H, state->W, (const int *)state->n_components,
+                       (const int *)state->status, (const int *)state->cur, (const int *)state->centers, state->sed[0],
+                       state->sed[1], images, B, band0, obs_psf_peak, peak_per_scene ? B : 0, model_psf_max);
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
 }
 
 // ------------------------------------------------------------------------------------
