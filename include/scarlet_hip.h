@@ -343,6 +343,45 @@ int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int
 int scarlet_init_combined_sed(scarlet_batch *state, const float *images, int B, int band0, const float *obs_psf_peak,
                               int peak_per_scene, const float *model_psf_max, void *stream);
 
+/* Components with a Prior (component.py:39-67, 177-187; blend.py:86-96): a gradient and a Lipschitz constant that
+ * are added to ONE component's step.  scarlet_batch does not change; the prior travels in a struct of its own.  Every
+ * pointer is device memory owned by the caller, float32 unless stated, indexed like the batch ([S][K] per component);
+ * any of the inputs may be NULL.  Per active scene and present component k, on the factors x of buffer cur:
+ *     g_prior = given gradient + w (x - target)          L_k = L + given L + w     (float32, as the frame's dtype)
+ *     x' = x - (1 / L_k) (g + g_prior)                   unless fix_sed / fix_morph: x' = x and L_k = L
+ * with g, L the likelihood's gradient and the scene's constant as scarlet_backward_gradients computes them
+ * (`lipschitz` and `mse` keep their meaning: no prior in them).  The constraint pipeline that follows scales the
+ * sparse_l0 / sparse_l1 cut with the component's own step 1 / L_morph,k (update.py:71-82).  Absent components,
+ * inactive scenes and the rows of L_comp that belong to them are not read and not written. */
+typedef struct scarlet_prior {
+    /* given values, e.g. what the caller's own code computed from buffer cur for this iteration */
+    const float *grad_sed;          /* [S][K][B]     added to d loss / d sed   */
+    const float *grad_morph;        /* [S][K][H][W]  added to d loss / d morph */
+    const float *L_sed;             /* [S][K]        added to the component's L_sed   */
+    const float *L_morph;           /* [S][K]        added to the component's L_morph */
+    /* built-in quadratic prior  w/2 |x - target|^2, evaluated by the library on buffer cur:
+       gradient w (x - target), Lipschitz constant w; target NULL = 0; a target needs its weight */
+    const float *quad_sed_weight;   /* [S][K]        */
+    const float *quad_sed_target;   /* [S][K][B]     */
+    const float *quad_morph_weight; /* [S][K]        */
+    const float *quad_morph_target; /* [S][K][H][W]  */
+    /* out, required: the constants each component stepped with, {L_sed, L_morph} */
+    double *L_comp;                 /* [S][K][2]     */
+} scarlet_prior;
+
+/* scarlet_backward_step with priors: the gradient pass, then one streaming kernel (k_prior_step) that steps the
+ * gradients in buffer 1-cur in place and writes L_comp; cur / it are not advanced.  For callers that recompute the
+ * given arrays every iteration. */
+int scarlet_backward_step_prior(scarlet_batch *b, const scarlet_prior *p, int approximate_L, void *stream);
+/* scarlet_source_update for a batch that stepped with priors: the sparsity cut reads p->L_comp (the only field it uses) */
+int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior *p, int in_iteration, void *stream);
+/* scarlet_fit with priors whose inputs do not change between iterations (the quadratic form, constant given
+ * gradients): gradients, prior step, constraint pipeline, convergence test per iteration, on the general
+ * (unfused, one-pipeline) path; no host synchronisation other than the check_every one, no allocation.  Returns the
+ * number of iterations launched.  The several-observation entry points do not take priors. */
+int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
+                      int check_every, void *stream);
+
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes
  * the stepped factors into buffer 1-cur; cur/it are NOT advanced yet                   */
@@ -365,7 +404,7 @@ int scarlet_check_convergence(scarlet_batch *b, double e_rel, void *stream);
 /* Per-kernel timing of scarlet_fit with hipEvents recorded on the launch stream (used by
  * bench.py for the roofline line).  begin: allocate events for up to max_iterations
  * iterations and start recording; end: synchronise, return per kernel class
- * {0 k_grad, 1 k_step, 2 k_source_update, 3 k_converge, 4 k_iterate (fused), 5-7 unused}
+ * {0 k_grad, 1 k_step, 2 k_source_update, 3 k_converge, 4 k_iterate (fused), 5 the PSF convolution chain, 6 k_prior_step, 7 unused}
  * the summed milliseconds and launch counts, and stop recording. */
 /* diagnostics (STAMPS switch on): byte offset inside b->workspace of the convolution kernel's phase stamps
  * ([S][B][32] int64 shader-clock values, written by every k_psf_conv launch), or -1 */

@@ -81,6 +81,16 @@ class ScarletInitSpec(Structure):
     ]
 
 
+class ScarletPrior(Structure):
+    """struct scarlet_prior of include/scarlet_hip.h (field order must match)."""
+    _fields_ = [
+        ("grad_sed", c_void_p), ("grad_morph", c_void_p), ("L_sed", c_void_p), ("L_morph", c_void_p),
+        ("quad_sed_weight", c_void_p), ("quad_sed_target", c_void_p),
+        ("quad_morph_weight", c_void_p), ("quad_morph_target", c_void_p),
+        ("L_comp", c_void_p),
+    ]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "scarlet_version": (c_char_p, []),
@@ -116,6 +126,9 @@ _SIGNATURES = {
     "scarlet_init_combined_sed": (c_int, [POINTER(ScarletBatch), _P, c_int, c_int, _P, c_int, _P, _P]),
     "scarlet_fit_multi": (c_int, [POINTER(ScarletBatch), POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
     "scarlet_backward_step": (c_int, [POINTER(ScarletBatch), c_int, _P]),
+    "scarlet_backward_step_prior": (c_int, [POINTER(ScarletBatch), POINTER(ScarletPrior), c_int, _P]),
+    "scarlet_source_update_prior": (c_int, [POINTER(ScarletBatch), POINTER(ScarletPrior), c_int, _P]),
+    "scarlet_fit_prior": (c_int, [POINTER(ScarletBatch), POINTER(ScarletPrior), c_int, c_double, c_int, c_int, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from . import prior as _prior
 
 
 def default_centroid_weight():
@@ -181,6 +182,7 @@ class BlendBatch(object):
         assert cw.ndim == 2 and cw.shape[0] == cw.shape[1] and cw.shape[0] % 2 == 1
         self.centroid_weight = torch.as_tensor(cw).to(**f64).contiguous()
         self._observations = None     # from_observations: [(ObservationBatch, its gradient batch)]
+        self.L_components = None      # (S, K, 2) float64 after a fit with a prior: the constants each component stepped with
         self._c = _lib.ScarletBatch()
         self._fill_struct()
         nbytes = _lib.lib.scarlet_batch_workspace_bytes(ctypes.byref(self._c))
@@ -436,34 +438,113 @@ class BlendBatch(object):
         _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 0, _lib.stream_ptr()))
         return self
 
-    def fit(self, max_iter=200, e_rel=1e-2, approximate_L=False, check_every=10):
+    def fit(self, max_iter=200, e_rel=1e-2, approximate_L=False, check_every=10, prior=None):
         """Blend.fit for every scene (reference blend.py:65-102).  Scenes that reach e_rel
         stop iterating individually.  Returns the number of iterations launched.  A batch made by
-        `from_observations` fits all its observations jointly (scarlet_fit_observations)."""
+        `from_observations` fits all its observations jointly (scarlet_fit_observations).
+
+        prior : None, or what scarlet_amd.prior describes -- a QuadraticPrior and / or constant given tensors (one
+            call of scarlet_fit_prior), a callable evaluated once per iteration on the current stream (the host looks
+            at `active` only every `check_every` iterations), or a list of these.  `L_components` then holds the
+            constants each component stepped with.  Not available for a batch made by `from_observations`."""
+        if prior is not None and self._observations is not None:
+            raise NotImplementedError("a batch of several observations does not take priors")
         self._ensure_mse_capacity(max_iter)
         self.active.fill_(1)          # a new fit() call iterates again, like the reference
         if self._init_checked:        # ... except the scenes whose init_sources input was bad
             self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
         if self._observations is not None:
             return self._fit_observations(max_iter, e_rel, approximate_L, check_every)
+        if prior is not None:
+            return self._fit_prior(prior, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every))
         rc = _lib.lib.scarlet_fit(ctypes.byref(self._c), int(max_iter), float(e_rel),
                                   int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
         return _lib.check(rc)
 
-    def step(self, e_rel=1e-2, approximate_L=False):
+    def step(self, e_rel=1e-2, approximate_L=False, prior=None):
         """One iteration in three separately callable phases (used by tests and by the
         Python-level update() override path).  A batch made by `from_observations` runs one iteration
-        of scarlet_fit_observations."""
+        of scarlet_fit_observations.  `prior`: as in `fit`."""
+        if prior is not None and self._observations is not None:
+            raise NotImplementedError("a batch of several observations does not take priors")
         self._ensure_mse_capacity(1)
         if self._observations is not None:
             if self._init_checked:
                 self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
             self._fit_observations(1, e_rel, approximate_L, 0)
             return
+        if prior is not None:
+            quad, given, fns = _prior.split_priors(prior)
+            self._prior_iteration(self._prior_struct(quad), given, fns, float(e_rel), int(bool(approximate_L)))
+            return
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step(ctypes.byref(self._c), int(bool(approximate_L)), s))
         _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 1, s))
         _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), float(e_rel), s))
+
+    # ------------------------------------------------------------------ priors
+    def _prior_struct(self, quad):
+        """scarlet_prior with the quadratic part bound to this batch and L_comp = L_components."""
+        t = self.torch
+        if self.L_components is None:
+            self.L_components = t.zeros((self.S, self.K, 2), dtype=t.float64, device=self.device)
+        ps = _lib.ScarletPrior()
+        self._prior_keep = bound = {} if quad is None else quad.bind(self)
+        for name, x in bound.items():
+            setattr(ps, name, None if x is None else x.data_ptr())
+        ps.L_comp = self.L_components.data_ptr()
+        return ps
+
+    def _set_given(self, ps, dicts):
+        """Sum the given values of `dicts` into full-shape float32 tensors and point the struct at them."""
+        t = self.torch
+        f32 = dict(dtype=t.float32, device=self.device)
+        shapes = dict(grad_sed=(self.S, self.K, self.B), grad_morph=(self.S, self.K, self.H, self.W),
+                      L_sed=(self.S, self.K), L_morph=(self.S, self.K))
+        keep = {}
+        for d in dicts:
+            _prior.check_given_keys(d)
+            for key, v in d.items():
+                if v is None:
+                    continue
+                if not t.is_tensor(v):
+                    v = t.full((), float(v), **f32) if np.ndim(v) == 0 else t.as_tensor(np.asarray(v, dtype=np.float32))
+                v = v.to(**f32)
+                _prior.check_target(v.shape, shapes[key], key)
+                keep[key] = v.expand(shapes[key]) if key not in keep else keep[key] + v
+        for key in _prior.GIVEN_KEYS:
+            x = keep.get(key)
+            if x is not None:
+                keep[key] = x = x.contiguous()
+            setattr(ps, key, None if x is None else x.data_ptr())
+        self._given_keep = keep          # alive until the next iteration replaces them (same stream)
+
+    def _prior_iteration(self, ps, given, fns, e_rel, approximate_L):
+        dicts = list(given)
+        if fns:
+            sed, morph = self.sed_current, self.morph_current          # gathered copies: the callables cannot touch the state
+            dicts += [fn(sed, morph) for fn in fns]
+        self._set_given(ps, dicts)
+        s = _lib.stream_ptr()
+        _lib.check(_lib.lib.scarlet_backward_step_prior(ctypes.byref(self._c), ctypes.byref(ps), approximate_L, s))
+        _lib.check(_lib.lib.scarlet_source_update_prior(ctypes.byref(self._c), ctypes.byref(ps), 1, s))
+        _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), e_rel, s))
+
+    def _fit_prior(self, prior, max_iter, e_rel, approximate_L, check_every):
+        quad, given, fns = _prior.split_priors(prior)
+        ps = self._prior_struct(quad)
+        if not fns:
+            # nothing changes between iterations: the library's own loop
+            self._set_given(ps, given)
+            return _lib.check(_lib.lib.scarlet_fit_prior(ctypes.byref(self._c), ctypes.byref(ps), max_iter, e_rel,
+                                                         approximate_L, check_every, _lib.stream_ptr()))
+        launched = 0
+        for i in range(max_iter):
+            self._prior_iteration(ps, given, fns, e_rel, approximate_L)
+            launched += 1
+            if check_every > 0 and (i + 1) % check_every == 0 and i + 1 < max_iter and not bool(self.active.any().item()):
+                break
+        return launched
 
     # ------------------------------------------------------------------ several observations
     @classmethod

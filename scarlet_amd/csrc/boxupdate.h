@@ -462,7 +462,7 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
         if (new_shift) { a.shifts[2 * c] = dy; a.shifts[2 * c + 1] = dx; }
     }
     // sparse_l0 / sparse_l1, positive, normalized('morph_max') (update.py:71-82, 27-32, 62-65): as k_source_update
-    const float step_morph = 1.0f / (float)a.lipschitz[2 * s + 1];
+    const float step_morph = update_step_morph(a, s, c);
     const float l0 = a.l0_thresh >= 0.f ? a.l0_thresh * step_morph : -1.f;
     const float l1 = a.l1_thresh >= 0.f ? a.l1_thresh * step_morph : -1.f;
     auto sparse_plus = [&](float v, int y, int x) {

@@ -485,7 +485,15 @@ struct UpdateArgs {
     const int *group;                 // [S*K] or NULL: >= 0 = layer of a multi-component source: centre given (k_group_centers),
                                       // shift = None (soft symmetry); -1 = a source of its own
     const int *ncomp;                 // [S] or NULL: components per scene (scene_ncomp); absent ones are skipped
+    const double *L_comp;             // [S*K][2] or NULL: the constants each component stepped with (prior.h); NULL: the scene's
 };
+
+// the step that scales the sparse_l0 / sparse_l1 cut (update.py:71-82): 1 / L_morph of the scene, or of the component
+// itself when it stepped with a prior's constant added (component.py:177-187)
+__device__ __forceinline__ float update_step_morph(const UpdateArgs &a, int s, int c)
+{
+    return 1.0f / (float)(a.L_comp ? a.L_comp[2 * (size_t)c + 1] : a.lipschitz[2 * s + 1]);
+}
 
 // MODE 0/1: the morphology tile lives in LDS (tiles up to ~128 x 128).
 // MODE 2   : frames whose tile does not fit (up to SCARLET_MAX_SIDE; BASELINE config 5): the same
@@ -627,7 +635,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
 
     // sparse_l0 / sparse_l1 (update.py:71-82; config 5), positive (update.py:27-32),
     // normalized('morph_max') (update.py:62-65)
-    const float step_morph = 1.0f / (float)a.lipschitz[2 * s + 1];
+    const float step_morph = update_step_morph(a, s, c);
     const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * HW : nullptr;
     const float l0 = a.l0_thresh >= 0.f ? a.l0_thresh * step_morph : -1.f;
     const float l1 = a.l1_thresh >= 0.f ? a.l1_thresh * step_morph : -1.f;
@@ -850,7 +858,7 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
     int lstop = 1 << 30;                // last sweep level computed; pixels beyond are <= 0 -> 0
     if (a.monotonic) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
     if (lane == 0) { a.centers[2 * c] = cy; a.centers[2 * c + 1] = cx; }
-    const float step_morph = 1.0f / (float)a.lipschitz[2 * s + 1];
+    const float step_morph = update_step_morph(a, s, c);
     const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * HW : nullptr;
     const float l0 = a.l0_thresh >= 0.f ? a.l0_thresh * step_morph : -1.f;
     const float l1 = a.l1_thresh >= 0.f ? a.l1_thresh * step_morph : -1.f;

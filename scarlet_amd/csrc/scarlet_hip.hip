@@ -27,6 +27,7 @@
 #include "extras.h"
 #include "initsrc.h"
 #include "multiobs.h"
+#include "prior.h"
 
 __constant__ unsigned short sc_nfl_table[SC_NFL_MAX];
 
@@ -1644,7 +1645,9 @@ extern "C" int scarlet_backward_gradients(scarlet_batch *b, int approximate_L, v
 
 __global__ void k_zero_int(int *p) { *p = 0; }
 
-static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, int force_it0, void *stream)
+// L_comp: the constants each component stepped with (scarlet_prior::L_comp), or NULL: the scene's
+static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, int force_it0, void *stream,
+                         const double *L_comp = nullptr)
 {
     int rc = ensure_tables();
     if (rc) return rc;
@@ -1660,6 +1663,7 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.only_flagged = nullptr;
     u.group = b->group;
     u.ncomp = b->n_components;
+    u.L_comp = L_comp;
     if (b->group) {
         // MultiComponentSource: the shared centre of every source first (one wave per scene)
         const int R = b->centroid_P / 2 + 2;
@@ -1969,6 +1973,88 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
             if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
             prof_stop(st);
         }
+        ++launched;
+        if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter) {
+            int h_count = 0;
+            hipLaunchKernelGGL(k_count_active, dim3(1), dim3(SC_BLOCK), 0, st, b->active, b->S, d_count);
+            HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (h_count == 0) break;
+        }
+    }
+    return launched;
+}
+
+// ---- components with a Prior (prior.h)
+static int check_prior(const scarlet_prior *p)
+{
+    if (!p) return set_err(SCARLET_E_ARG, "null prior");
+    if (!p->L_comp) return set_err(SCARLET_E_ARG, "prior: L_comp is NULL (required output)");
+    if (p->quad_sed_target && !p->quad_sed_weight) return set_err(SCARLET_E_ARG, "prior: quad_sed_target without quad_sed_weight");
+    if (p->quad_morph_target && !p->quad_morph_weight)
+        return set_err(SCARLET_E_ARG, "prior: quad_morph_target without quad_morph_weight");
+    return SCARLET_OK;
+}
+// buffer 1-cur holds the raw gradients (backward_impl with raw_gradient = 1): step them in place
+static int launch_prior_step(const scarlet_batch *b, const scarlet_prior *p, void *stream)
+{
+    PriorArgs a;
+    a.S = b->S; a.K = b->K; a.B = b->B; a.HW = b->H * b->W;
+    a.sed[0] = b->sed[0]; a.sed[1] = b->sed[1]; a.morph[0] = b->morph[0]; a.morph[1] = b->morph[1];
+    a.cur = b->cur; a.active = b->active; a.ncomp = b->n_components;
+    a.fix_sed = b->fix_sed; a.fix_morph = b->fix_morph; a.lipschitz = b->lipschitz;
+    a.p = *p;
+    const uintptr_t bits = (uintptr_t)b->morph[0] | (uintptr_t)b->morph[1] | (uintptr_t)p->grad_morph | (uintptr_t)p->quad_morph_target;
+    const bool vec = (a.HW & 3) == 0 && (bits & 15) == 0;
+    const dim3 grid((unsigned)(b->S * b->K), (unsigned)((a.HW + SC_PRIOR_PIX - 1) / SC_PRIOR_PIX));
+    hipStream_t st = (hipStream_t)stream;
+    prof_start(6, st);
+    if (vec) hipLaunchKernelGGL(k_prior_step<true>, grid, dim3(SC_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL(k_prior_step<false>, grid, dim3(SC_BLOCK), 0, st, a);
+    prof_stop(st);
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
+extern "C" int scarlet_backward_step_prior(scarlet_batch *b, const scarlet_prior *p, int approximate_L, void *stream)
+{
+    int rc = check_batch(b);
+    if (!rc) rc = check_prior(p);
+    if (!rc) rc = check_counts(b, stream);
+    if (!rc) rc = backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 1, stream);
+    return rc ? rc : launch_prior_step(b, p, stream);
+}
+
+extern "C" int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior *p, int in_iteration, void *stream)
+{
+    int rc = check_batch(b);
+    if (!rc) rc = check_prior(p);
+    if (!rc) rc = check_counts(b, stream);
+    if (rc) return rc;
+    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream, p->L_comp);
+}
+
+// scarlet_fit's loop on the unfused path, one pipeline: gradients, prior step, constraints, convergence test
+extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
+                                 int check_every, void *stream)
+{
+    int rc = check_batch(b);
+    if (!rc) rc = check_prior(p);
+    if (rc) return rc;
+    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
+    if ((rc = check_counts(b, stream))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const WsLayout l = ws_layout(b, WS_FIX);
+    int *d_count = ws_at<int>(b, l.active_count);
+    int launched = 0;
+    for (int i = 0; i < max_iter; ++i) {
+        if ((rc = backward_impl(b, l, approximate_L, 1, stream))) return rc;
+        if ((rc = launch_prior_step(b, p, stream))) return rc;
+        prof_start(2, st);
+        if ((rc = launch_update(b, l, 1, 0, stream, p->L_comp))) return rc;
+        prof_stop(st); prof_start(3, st);
+        if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
+        prof_stop(st);
         ++launched;
         if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter) {
             int h_count = 0;
