@@ -61,6 +61,16 @@ __device__ __forceinline__ T wave_sum(T v) {
     v += dpp_mov<SC_DPP_MIRROR>(v);
     return (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
 }
+// Sums over the 16-lane rows of the wave: every lane gets its row's sum.  The same four steps, i.e. the same pairing
+// of the lanes, as wave_sum takes inside a row.
+template <typename T>
+__device__ __forceinline__ T row_sum(T v) {
+    v += dpp_mov<SC_DPP_XOR1>(v);
+    v += dpp_mov<SC_DPP_XOR2>(v);
+    v += dpp_mov<SC_DPP_HALF_MIRROR>(v);
+    v += dpp_mov<SC_DPP_MIRROR>(v);
+    return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_mov<SC_DPP_XOR1>(v));
     v = fmaxf(v, dpp_mov<SC_DPP_XOR2>(v));

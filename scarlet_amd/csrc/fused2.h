@@ -81,13 +81,31 @@ __device__ __forceinline__ KsGeom ks_geom(const SymWindow &s, const unsigned sho
 // the previous iteration left them there), so phase 0 reads LDS instead of HBM.  Returns bit 0 = scene still
 // active, bit 1 = tiles resident for the next iteration.
 //
-// What one iteration hands to the next inside a launch travels through LDS (tiles, SEDs, centres, shifts), never
-// through a global store followed by a cached global load: the CU's vector L1 can still hold the line from the
-// PREVIOUS iteration's load of the same address (centres, shifts: re-read every iteration; measured: ~1 % of the
-// scenes of a 10 000-scene launch then started an iteration from a stale centre or SED), and nothing short of an
-// L1 invalidate per iteration (buffer_inv, ~2 us) repairs that.  The two streams that must come back from memory
-// -- the previous morphology for the convergence sums, the cached Hankel vectors -- are loaded past the L1
-// (non-temporal loads, L2-served).
+// What one iteration hands to the next inside a launch travels through LDS (tiles, SEDs, centres, shifts, the
+// morphology step size): it takes the global loads off the start of every iteration.  The invariant is about LDS
+// words, not about caches: a word that one wave hands to another is written before a synchronisation the reader
+// waits on (a pair_sync, a workgroup barrier) and is not rewritten until the reader is past its read.  (The
+// differences that ~1 % of the scenes of a 10 000-scene launch once showed were a breach of exactly that -- the
+// lead's final pass overwrote the peak pixel its partner had yet to read -- and not stale lines of the vector L1,
+// as this comment used to say; profiles/r03_notes.md.)  The two streams that do come back from memory -- the
+// previous morphology for the convergence sums, the cached Hankel vectors -- are loaded past the L1 (non-temporal
+// loads, L2-served).
+//
+// Step sizes (monotonic pipelines; the exact instance always is one).  The SED step needs 1 / lambda_max of the
+// morphology Gram, but its result is read only after the sweep; the morphology step needs 1 / lambda_max(S S^T) of
+// the SEDs the iteration starts from, which the PREVIOUS iteration has already produced.  Neither solve has to
+// stall the workgroup between the two pixel passes:
+//   * the gradient pass's combine stage leaves the raw SED gradients in sed_new;
+//   * after B3 the partner (non-lead) wave of every present pair publishes its component's normalisation value (the
+//     processed peak, final by then) in nmax_s[k][1] and adds one to arrive_s; the wave whose add completes the count
+//     is this iteration's WORKER -- nobody waits for anybody.  While its own lead sweeps, the worker solves L_sed
+//     from mat[0], takes the SED step, finalises the SEDs of every component (sed_out, carry_sed, conv_s) and, in the
+//     persistent form, solves the next iteration's L_morph from those SEDs: 1 / L in step_s[1], L in mat[1][0].  All
+//     of it is complete before the worker reaches B5.
+//   * a re-entered iteration whose tiles are resident takes step_morph from step_s[1] and stores lipschitz[2 s + 1]
+//     from mat[1][0] when it USES the value (an iteration that never runs leaves no trace).  The hand-over is valid
+//     exactly when the tiles are: the NaN fix-up after B5, the only code that rewrites SEDs after the worker, clears
+//     the `tiles resident` word, and such an iteration -- like a scene's first -- solves L_morph between the passes.
 template <int KM, int BM, int XS, bool P>
 __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, const int c0, const int it_old, const bool resident,
                                              const bool reentered = false)
@@ -126,6 +144,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     __shared__ int lstop_s[KM];
     __shared__ float nmax_s[KM][2];
     __shared__ int pair_flag[KM][2];           // phase counters of the pair-local synchronisation
+    __shared__ int arrive_s;                   // partner waves past B3 (the last one is the iteration's worker)
     __shared__ double cent_s[KM][2][3];        // centroid moments of the two row halves
     __shared__ unsigned short fl_s[2][32];
     __shared__ int ctl_s[2][2];                // persistent form, by iteration parity: {scene still active, tiles resident}
@@ -146,6 +165,13 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     const float *img = a.images + (size_t)s * B * HW;
     const float *wgt = (!X && a.weights) ? a.weights + (size_t)s * B * HW : nullptr;
 #define STAMP(i) do { if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+    // (diagnostic build -DSC_STAMP_WORKER: slots 12 / 13 hold the start and the end of the worker's step-size work,
+    // stamped by the worker wave, instead of wave 0's B1 / B2)
+#ifdef SC_STAMP_WORKER
+#define WSTAMP(i) do { if (a.stamps && lane == 0) a.stamps[(size_t)s * 16 + 12 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define WSTAMP(i) do { } while (0)
+#endif
     STAMP(0);
     // (diagnostics: the constant 100 MHz counter beside the shader clock of stamps 0 / 6 gives the clock the chip holds)
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 7] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -236,6 +262,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     }
     ks_fill_lengths(fl_s, tid, fl_req);
     if (tid < 2 * KM) (&pair_flag[0][0])[tid] = 0;
+    if (tid == 2 * KM) arrive_s = 0;
     if (P && tid == 0) { ctl_s[it_old & 1][0] = 1; ctl_s[it_old & 1][1] = 1; }
     if (P && !reentered && tid < KM * 4) (&rowrange_s[0][0][0])[tid] = (short)((tid & 1) ? H - 1 : 0);
     if (P && resident) {
@@ -250,6 +277,24 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         }
     }
     const bool small_side = (K <= B);          // nonzero spectrum of A^T A == that of A A^T
+    const int n_present = a.ncomp ? scene_ncomp(a.ncomp, s, K) : K;   // absent components: the pair skips the constraints
+    // step_morph and its L_morph were left in step_s[1] / mat[1][0] by the previous iteration's worker (there is a
+    // worker whenever a component is present)
+    const bool carried = P && reentered && resident && monotonic && n_present > 0;
+    // one element of the SED Gram per lane (lane < K * K, or B * B where B < K): here from sed_s, by the worker from
+    // the SEDs it has finalised (carry_sed) -- the same expression on the same values
+    auto sed_gram = [&](const float *sed, double *m) {
+        double r = 0;
+        if (small_side) {
+            const int k = lane / K, k2 = lane - k * K;
+            for (int b = 0; b < B; ++b) r += (double)sed[k * BM + b] * sed[k2 * BM + b];
+            m[k * KM + k2] = r;
+        } else {
+            const int b = lane / B, b2 = lane - b * B;
+            for (int k = 0; k < K; ++k) r += (double)sed[k * BM + b] * sed[k * BM + b2];
+            m[b * BM + b2] = r;
+        }
+    };
     __syncthreads();                           // sed_s visible
     {
         // packed-f32 products (v_pk_fma_f32): the .x lanes of gram2 sum pixels 0 and 2 of the groups,
@@ -294,8 +339,11 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     for (int j = 1; j < GPT; ++j) load_images(j);       // the tile registers are free now
     __syncthreads();
     STAMP(1);
-    // Lipschitz constants (blend.py:205-218): L_sed = lambda_max(S S^T) on lane 0,
-    // L_morph = lambda_max(A^T A) on lane 1 of wave 0 -- one instruction stream for both
+    // Lipschitz constants (blend.py:205-218): that of the SED step, lambda_max of the morphology Gram (mat[0]), and
+    // that of the morphology step, lambda_max of the SED Gram (mat[1]).  Monotonic pipelines: the first is solved by
+    // the iteration's worker under the sweep, the second here on lane 1 of wave 0 -- unless the previous iteration's
+    // worker has left it (`carried`), and then only the float64 combine of the Gram stands between the two passes.
+    // Otherwise: lanes 0 and 1 of wave 0, one instruction stream for both.
     if (wid == 0) {
         {   // the 4 x 8 row partials of every Gram entry: lane = 4 entry + q adds eight of them, the four
             // lanes of a quad combine (K * K <= 16 entries on the 64 lanes)
@@ -312,24 +360,17 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
             r += dpp_mov<SC_DPP_XOR2>(r);
             if (e < K * K && q == 0) mat[0][k * KM + k2] = r;
         }
-        if (lane < (small_side ? K * K : B * B)) {
-            double r = 0;
-            if (small_side) {
-                const int k = lane / K, k2 = lane - k * K;
-                for (int b = 0; b < B; ++b) r += (double)sed_s[k * BM + b] * sed_s[k2 * BM + b];
-                mat[1][k * KM + k2] = r;
-            } else {
-                const int b = lane / B, b2 = lane - b * B;
-                for (int k = 0; k < K; ++k) r += (double)sed_s[k * BM + b] * sed_s[k * BM + b2];
-                mat[1][b * BM + b2] = r;
+        if (carried) {
+            if (lane == 1) a.lipschitz[2 * s + 1] = mat[1][0];
+        } else {
+            if (lane < (small_side ? K * K : B * B)) sed_gram(sed_s, mat[1]);
+            wave_sync();
+            if (lane < 2 && !(monotonic && lane == 0)) {
+                const int n = (lane == 0 || small_side) ? K : B, ld = (lane == 0 || small_side) ? KM : BM;
+                const double L = n <= 4 ? lambda_max_charpoly4(mat[lane], n, ld) : jacobi_lambda_max(mat[lane], n, ld);
+                step_s[lane] = 1.0f / (float)L;
+                a.lipschitz[2 * s + lane] = L;
             }
-        }
-        wave_sync();
-        if (lane < 2) {
-            const int n = (lane == 0 || small_side) ? K : B, ld = (lane == 0 || small_side) ? KM : BM;
-            const double L = n <= 4 ? lambda_max_charpoly4(mat[lane], n, ld) : jacobi_lambda_max(mat[lane], n, ld);
-            step_s[lane] = 1.0f / (float)L;
-            a.lipschitz[2 * s + lane] = L;
         }
     }
     __syncthreads();
@@ -430,15 +471,20 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         r += dpp_mov<SC_DPP_XOR2>(r);
         r += dpp_mov<SC_DPP_HALF_MIRROR>(r);
         r += dpp_mov<SC_DPP_MIRROR>(r);
-        // the lane that holds an entry's total takes the SED step (blend.py:91-93) / stores the loss (blend.py:138)
+        // the lane that holds an entry's total stores the loss (blend.py:138) / leaves the SED gradient to the worker;
+        // without a worker (not monotonic) it takes the SED step itself (blend.py:91-93)
         if (live && p == 0) {
             if (i == 0) {
                 if (it_new <= a.mse_capacity) a.mse[(size_t)s * a.mse_capacity + it_new - 1] = r;
             } else {
                 const int k = (i - 1) / B, b = (i - 1) - k * B;
-                const float curv = sed_s[k * BM + b];
-                const bool fixed = a.fix_sed && a.fix_sed[(size_t)s * K + k];
-                sed_new[k * BM + b] = fixed ? curv : curv - step_sed * (float)r;
+                if (monotonic) {
+                    sed_new[k * BM + b] = (float)r;
+                } else {
+                    const float curv = sed_s[k * BM + b];
+                    const bool fixed = a.fix_sed && a.fix_sed[(size_t)s * K + k];
+                    sed_new[k * BM + b] = fixed ? curv : curv - step_sed * (float)r;
+                }
             }
         }
     }
@@ -466,7 +512,6 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
-    const int n_present = a.ncomp ? scene_ncomp(a.ncomp, s, K) : K;   // absent components: the pair skips the constraints
     const bool mine = k < n_present;
     const int c = s * K + (mine ? k : 0);
     Tile t; t.H = H; t.W = W; t.LW = LW; t.m = tiles + (mine ? k : 0) * tile_floats;
@@ -529,14 +574,18 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     }
     STAMP(8);
     if (mine) pair_sync(2, std::false_type{});                         // B1: Hankel vectors complete
+#ifndef SC_STAMP_WORKER
     STAMP(12);
+#endif
     f32x4 T[4][2];
     if (mine && mode == 1) {
         if (rank1) pair_ks_z(kg, vec + 256, zv);
         pair_ks_gemm1<true>(t, sw, kg, vec, half, T);
     }
     if (mine) pair_sync(3, std::false_type{});                         // B2: every read of X is done
+#ifndef SC_STAMP_WORKER
     STAMP(13);
+#endif
     if (mine && mode == 1) pair_ks_gemm2<true>(t, sw, kg, vec, zv, half, T, sy, rank1);
     if (mine && mode == 2 && lead) wave_flip_symmetry<float>(t, sw, false, 1.0f);
     if (mine) pair_sync(4, std::false_type{});                         // B3
@@ -567,7 +616,75 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
             lastv[j] = want ? load4(reinterpret_cast<const float *>(last4 + g), true) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
+    // sparsity thresholds (update.py:71-82) of the final pass, and of the normalisation value below
+    float l0 = (!X && a.l0_thresh >= 0.f) ? a.l0_thresh * step_morph : -1.f;
+    float l1 = (!X && a.l1_thresh >= 0.f) ? a.l1_thresh * step_morph : -1.f;
+    auto sparse = [&](float v) {
+        if (l0 >= 0.f && fabsf(v) < l0) v = 0.f;
+        if (l1 >= 0.f) {
+            const float mag = fabsf(v) - l1;
+            v = (v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f)) * (mag < 0.f ? 0.f : mag);
+        }
+        return v;
+    };
     if (mine && !lead) load_last();                 // the idle wave of the pair: before the barrier
+    if (monotonic && mine && !lead) {
+        // The partner wave has nothing to do until its lead's sweep is over.  It publishes the component's
+        // normalisation value -- the processed peak pixel, which the sweep (levels >= 1) never writes: final since B3
+        // -- and counts itself in; the wave that completes the count does the iteration's step-size work.
+        float peak = sparse(t.m[cy * LW + cx]);
+        if (peak < 0.f) peak = 0.f;
+        int arrived = 0;
+        if (lane == 0) nmax_s[k][1] = peak;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        if (lane == 0) arrived = __hip_atomic_fetch_add(&arrive_s, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (uniform(arrived) == n_present - 1) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            WSTAMP(0);
+            // L_sed (the morphology Gram's float64 combine is in mat[0] since the gradient pass started)
+            float step_w = 0.f;
+            if (lane == 0) {
+                const double L = lambda_max_charpoly4(mat[0], K, KM);
+                a.lipschitz[2 * s] = L;
+                step_w = 1.0f / (float)L;
+            }
+            step_w = read_lane(step_w, 0);
+            // SED step (blend.py:91-93), positivity and normalisation (update.py:27-32, 62-65) and the convergence
+            // sums of every present component at once: component = 16-lane row, band = lane of the row.  A row's sum
+            // pairs its lanes as wave_sum pairs lanes 0..15, whose other three rows only ever added exact zeros.
+            const int kk = lane >> 4, bb = lane & 15;
+            const bool entry = kk < n_present && bb < B;
+            double d2s = 0, n2s = 0;
+            if (entry) {
+                const float curv = sed_s[kk * BM + bb];
+                const bool fixed = a.fix_sed && a.fix_sed[(size_t)s * K + kk];
+                float v = fixed ? curv : curv - step_w * sed_new[kk * BM + bb];
+                if (v < 0.f) v = 0.f;
+                v = v * nmax_s[kk][1];
+                sed_out[kk * B + bb] = v;
+                if (P) carry_sed[kk * BM + bb] = v;
+                const float d = curv - v;
+                d2s = (double)(d * d);
+                n2s = (double)(v * v);
+            }
+            d2s = row_sum(d2s); n2s = row_sum(n2s);
+            if (entry && bb == 0) { conv_s[kk][0] = d2s; conv_s[kk][1] = n2s; }
+            if (P) {
+                // the next iteration's L_morph, from the SEDs it will start from (an absent component's carry_sed is
+                // what its sed_s is); used only if that iteration finds its tiles resident
+                wave_sync();
+                if (lane < (small_side ? K * K : B * B)) sed_gram(carry_sed, mat[1]);
+                wave_sync();
+                if (lane == 0) {
+                    const int n = small_side ? K : B, ld = small_side ? KM : BM;
+                    const double L = n <= 4 ? lambda_max_charpoly4(mat[1], n, ld) : jacobi_lambda_max(mat[1], n, ld);
+                    step_s[1] = 1.0f / (float)L;
+                    mat[1][0] = L;
+                }
+            }
+            WSTAMP(1);
+        }
+    }
     if (mine && lead) {
         int lstop = 1 << 30;                        // last sweep level computed (early exit)
         if (monotonic) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
@@ -584,16 +701,6 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     // ---- sparsity, positivity (update.py:71-82, 27-32), normalisation (update.py:62-65),
     // store, convergence sums: one pass over the LDS tile, float4 groups split between the pair
     float norm = 0.f;
-    float l0 = (!X && a.l0_thresh >= 0.f) ? a.l0_thresh * step_morph : -1.f;
-    float l1 = (!X && a.l1_thresh >= 0.f) ? a.l1_thresh * step_morph : -1.f;
-    auto sparse = [&](float v) {
-        if (l0 >= 0.f && fabsf(v) < l0) v = 0.f;
-        if (l1 >= 0.f) {
-            const float mag = fabsf(v) - l1;
-            v = (v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f)) * (mag < 0.f ? 0.f : mag);
-        }
-        return v;
-    };
     if (!monotonic) {
         float vmax = -INFINITY;
         bool anynan = false;
@@ -712,7 +819,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
             rowrange_s[k][1 - c0][0] = (short)(known ? max(cy - (lstop >> 1), 0) : 0);
             rowrange_s[k][1 - c0][1] = (short)(known ? min(cy + (lstop >> 1), H - 1) : H - 1);
         }
-        if (lead) {
+        if (lead && !monotonic) {                      // (monotonic: the worker has done this under the sweep)
             double d2s = 0, n2s = 0;
             if (lane < B) {
                 float v = sed_new[k * BM + lane];
@@ -779,6 +886,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     STAMP(6);
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 11] = (long long)__builtin_amdgcn_s_memrealtime();
 #undef STAMP
+#undef WSTAMP
     if (P) {
         // (no wait for this iteration's global stores here: what the next iteration needs of them is in LDS, the
         // previous morphology is re-read tens of thousands of cycles from now and the cached Hankel vectors by the

@@ -11,6 +11,11 @@ what the jump assumes:
     private segment     = none (no scratch: no flat-scratch / wave-offset registers)
     work-item id VGPRs  = v0 only
 
+It also guards the kernel's residency: a CU's 160 KB of LDS hold two workgroups (two scenes) only while one takes at
+most 81 920 bytes; the dynamic part (tiles and Hankel vectors) is 77 824, so the static part -- the descriptor's
+group_segment_fixed_size -- may not exceed 4 096 bytes.  One array more and a CU holds one scene: half the throughput,
+and nothing else would say so.
+
     python tools/check_reentry_abi.py scarlet_amd/csrc/libscarlet_hip.so
 """
 import os
@@ -21,6 +26,7 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 KERNEL = "k_fit2x"
+MAX_STATIC_LDS = 4096
 
 
 def elf_symbol_bytes(path, name, size):
@@ -52,6 +58,7 @@ def main():
         subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--unbundle",
                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co])
         kd = elf_symbol_bytes(co, KERNEL + ".kd", 64)
+    static_lds, = struct.unpack_from("<I", kd, 0)          # group_segment_fixed_size
     private_size, = struct.unpack_from("<I", kd, 4)
     rsrc2, = struct.unpack_from("<I", kd, 52)
     props, preload = struct.unpack_from("<HH", kd, 56)
@@ -75,7 +82,12 @@ def main():
         print("check_reentry_abi: %s's kernel descriptor is not what its re-entry jump assumes (got, wanted): %r"
               % (KERNEL, bad), file=sys.stderr)
         sys.exit(1)
-    print("check_reentry_abi: %s descriptor ok (kernarg ptr s[0:1], workgroup ids s2-s4, v0, no scratch)" % KERNEL)
+    if static_lds > MAX_STATIC_LDS:
+        print("check_reentry_abi: %s has %d bytes of static LDS, more than the %d with which two workgroups share a CU"
+              % (KERNEL, static_lds, MAX_STATIC_LDS), file=sys.stderr)
+        sys.exit(1)
+    print("check_reentry_abi: %s descriptor ok (kernarg ptr s[0:1], workgroup ids s2-s4, v0, no scratch; %d bytes of "
+          "static LDS)" % (KERNEL, static_lds))
 
 
 if __name__ == "__main__":

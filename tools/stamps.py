@@ -26,7 +26,14 @@ dt = np.diff(st[:, :7], axis=1)
 if st[:, 10].any():
     print("P2 wave0: pre-sym %d  sym %d  sweep %d  tail %d" % ((st[:, 8] - st[:, 4]).mean(), (st[:, 9] - st[:, 8]).mean(),
           (st[:, 10] - st[:, 9]).mean(), (st[:, 5] - st[:, 10]).mean()))
-if st[:, 12].any():
+if os.environ.get("STAMP_WORKER"):
+    # library built with -DSC_STAMP_WORKER: slots 12 / 13 = start / end of the worker's step-size work (fused2.h), on
+    # the worker wave; 9 / 10 = wave 0 after B3 / after B4 (its pair's sweep lies between them)
+    ok = st[:, 13] > st[:, 12]
+    print("worker: starts %d after wave 0's B3, works %d (p90 %d), ends %d before wave 0's B4; %.1f %% end after it  (n=%d)" % (
+          (st[ok, 12] - st[ok, 9]).mean(), (st[ok, 13] - st[ok, 12]).mean(), np.percentile(st[ok, 13] - st[ok, 12], 90),
+          (st[ok, 10] - st[ok, 13]).mean(), 100.0 * (st[ok, 13] > st[ok, 10]).mean(), ok.sum()))
+elif st[:, 12].any():
     ok = st[:, 12] > 0
     if st[:, 11].any():
         print("sym wave0: vectors %d  rank1 %d  gemm1 %d  gemm2 %d  (n=%d)" % ((st[ok, 12] - st[ok, 8]).mean(), (st[ok, 13] - st[ok, 12]).mean(),
