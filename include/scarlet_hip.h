@@ -96,7 +96,8 @@ const char *scarlet_last_error(void);
 /* Diagnostic switches: NO_EXACT, NO_KSCACHE, FUSED_V1, NO_FUSED, FORCE_BLOCK_UPDATE,
  * NO_HYBRID_SWEEP, PAD_LDS, STAMPS, PSF_HIPFFT, NO_BOX, NO_BOX2, NO_PSF3PASS, NO_SIDE_STREAM,
  * NO_GRAM_MFMA, NO_BIGK_FUSED, NO_PIPELINE, NO_PERSIST (one launch per iteration instead of k_fit2x),
- * PERSIST_DBG.  Each starts from the environment variable SCARLET_<NAME>, read once at first use;
+ * PERSIST_DBG, NO_PLACE (component k on waves 2k, 2k + 1 of k_fit2x / k_iterate2<4,5,64>, not placed by
+ * GEMM cost).  Each starts from the environment variable SCARLET_<NAME>, read once at first use;
  * afterwards only this call changes it.  Returns the previous value (0 / 1) or SCARLET_E_ARG for an
  * unknown name.  None changes results beyond float32 rounding.
  * PSF_HIPFFT and STAMPS decide the layout of a PSF batch's workspace: they are frozen by the first

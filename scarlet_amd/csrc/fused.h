@@ -45,6 +45,7 @@ struct FusedArgs {
     long long *stamps;               // NULL, or [S][16] shader-clock stamps (diagnostics only)
     float *kscache;                  // NULL, or [S][K][2][SC_KSC_FLOATS]: Hankel vectors of the last k-space symmetry (k_iterate2)
     const int *ncomp;                // [S] or NULL: components per scene (scene_ncomp); absent ones skip the constraints
+    int no_place;                    // k_iterate2 / k_fit2x, exact shape: component k on waves 2k, 2k + 1 (option NO_PLACE)
 };
 // Per component and wave of its pair: 64 entries of av, bv, cv (this wave's half), then the header
 // {H W cy cx, magic, dy (2 words), dx (2 words), s} the vectors were made for

@@ -154,6 +154,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     // persistent form: rows [lo, hi] outside which factor buffer 0 / 1 of component k holds exact zeros -- what this
     // launch's final passes wrote there (everything beyond the sweep's cut); [0, H - 1] until a buffer has been written
     __shared__ short rowrange_s[KM][2][2];
+    __shared__ unsigned place_s;               // persistent form: the scene's placement (below), one component index per byte
     const int tid = threadIdx.x, lane = tid & 63, wid = uniform(tid >> 6);    // wid in an SGPR: scalar branches
     float *const morph0 = a.morph[0], *const morph1 = a.morph[1], *const sed0 = a.sed[0], *const sed1 = a.sed[1];
     const float *min_g = (c0 ? morph1 : morph0) + (size_t)s * K * HW;
@@ -172,6 +173,15 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
 #else
 #define WSTAMP(i) do { } while (0)
 #endif
+    // (diagnostic build -DSC_STAMP_PAIRS: every pair's lead keeps its times after B3, after B4 and at its arrival at B5
+    // and leaves two words per component in the second half of the stamp area: the arrival, and {arrival - B4 (20 bits),
+    // B4 - B3 (20), last sweep level (8), NTR (3), NTC (3), slot (2)}; tools/stamps.py, STAMP_PAIRS=1)
+#ifdef SC_STAMP_PAIRS
+    long long pst[3] = {0, 0, 0};
+#define PSTAMP(i) do { if (a.stamps) pst[i] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define PSTAMP(i) do { } while (0)
+#endif
     STAMP(0);
     // (diagnostics: the constant 100 MHz counter beside the shader clock of stamps 0 / 6 gives the clock the chip holds)
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 7] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -184,6 +194,46 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
                                         | ((long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) << 32);   // XCC_ID
     }
     const unsigned fl_req = ks_request_lengths(tid);
+    const int n_present = a.ncomp ? scene_ncomp(a.ncomp, s, K) : K;   // absent components: the pair skips the constraints
+    // Placement (exact-shape instances).  The pair of waves 2 q, 2 q + 1 -- slot q -- sits on SIMDs {0, 1} for q = 0, 2
+    // and on {2, 3} for q = 1, 3, and a SIMD's matrix pipe is shared by the waves on it: the MFMAs of the component on
+    // the other slot of the same SIMDs come straight out of this one's stream.  The two symmetry GEMMs of a window of
+    // NTR x NTC tiles cost ~ NTR NTC (NTR + NTC) MFMAs (16 to 128 for windows of 2 to 4 tiles a side), so which
+    // component shares a pipe with which decides how long the scene's longest chain -- the one the workgroup waits for
+    // at B5 -- gets.  By cost (0: absent, or centred -- no k-space GEMM), descending, ties by index: the largest and the
+    // smallest share slots 0 and 2, the two middle ones slots 1 and 3.  The slot decides the wave's half of the pair's
+    // work, which wave leads, and the SIMD; the component decides everything that is indexed by component.
+    // Decided ONCE per scene and launch, from the centres the launch finds, and carried in LDS: inside a launch a wave
+    // re-reads from memory what the same wave stored an iteration earlier (its half of the cached Hankel vectors, the
+    // previous morphology in load_last) with no wait in between -- a placement that moved between two iterations would
+    // have one wave read another's recent stores.  Across launches the kernel boundary orders them.  The cost only
+    // steers scheduling: every wave computes the same permutation, and no result depends on which one it is.
+    const int slot = wid >> 1;
+    int kp = slot;
+    if constexpr (X) {
+        unsigned place = 0x03020100u;
+        if (P) { const unsigned lp = place_s; if (reentered) place = (unsigned)uniform((int)lp); }
+        if (!(P && reentered) && !a.no_place) {
+            int cost[KM];
+#pragma unroll
+            for (int j = 0; j < KM; ++j) {
+                const int ccy = uniform(a.centers[2 * (s * K + j)]), ccx = uniform(a.centers[2 * (s * K + j) + 1]);
+                const SymWindow w = sym_window(H, W, ccy, ccx);
+                const int ntr = round16(w.h) >> 4, ntc = round16(w.w) >> 4;
+                cost[j] = (j < n_present && !w.centered) ? ntr * ntc * (ntr + ntc) : 0;
+            }
+            place = 0;
+#pragma unroll
+            for (int j = 0; j < KM; ++j) {
+                int rank = 0;
+#pragma unroll
+                for (int i = 0; i < KM; ++i) rank += (cost[i] > cost[j] || (cost[i] == cost[j] && i < j)) ? 1 : 0;
+                place |= (unsigned)j << (8 * (rank ^ (rank >> 1)));         // ranks 0, 1, 2, 3 -> slots 0, 1, 3, 2
+            }
+        }
+        if (P && !reentered && tid == 0) place_s = place;
+        kp = (int)((place >> (8 * slot)) & (KM - 1));
+    }
     // The Hankel vectors of the k-space symmetry depend on (H, W, centre, shift) only; the shift moves
     // every fifth iteration and the centre rarely, so each wave keeps its half of the vectors of the
     // previous iteration in the workspace and recomputes them (float64 sincospi, ~4k cycles on the
@@ -192,24 +242,24 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     // after the gradient step; a load at that point would put an HBM round trip on the constraint chain)
     int pre_cy = 0, pre_cx = 0;
     double pre_dy = 0, pre_dx = 0;
-    if (X && (wid >> 1) < K) {                  // (the generic instance has no registers to spare: it loads late)
-        const int cpre = s * K + (wid >> 1);
+    if (X && kp < K) {                          // (the generic instance has no registers to spare: it loads late)
+        const int cpre = s * K + kp;
         if (!(P && reentered)) {
             pre_cy = a.centers[2 * cpre]; pre_cx = a.centers[2 * cpre + 1];
             pre_dy = a.shifts[2 * cpre]; pre_dx = a.shifts[2 * cpre + 1];
         }
         if (P) {       // (read unconditionally, selected by value: a select between an LDS and a global POINTER would
                        // turn both loads into flat loads)
-            const int lcy = carry_cen[wid >> 1][0], lcx = carry_cen[wid >> 1][1];
-            const double ldy = carry_sh[wid >> 1][0], ldx = carry_sh[wid >> 1][1];
+            const int lcy = carry_cen[kp][0], lcx = carry_cen[kp][1];
+            const double ldy = carry_sh[kp][0], ldx = carry_sh[kp][1];
             if (reentered) { pre_cy = lcy; pre_cx = lcx; pre_dy = ldy; pre_dx = ldx; }
         }
     }
     float *kcache = nullptr;
     float kc_v[3] = {0.f, 0.f, 0.f};
     unsigned kc_hdr = 0;
-    if (X && a.kscache && (wid >> 1) < K) {
-        kcache = a.kscache + ((size_t)(s * K + (wid >> 1)) * 2 + (wid & 1)) * SC_KSC_FLOATS;
+    if (X && a.kscache && kp < K) {
+        kcache = a.kscache + ((size_t)(s * K + kp) * 2 + (wid & 1)) * SC_KSC_FLOATS;
         if (P) {                               // past the L1: this wave stored them an iteration ago
             kc_v[0] = __builtin_nontemporal_load(kcache + lane); kc_v[1] = __builtin_nontemporal_load(kcache + 64 + lane);
             kc_v[2] = __builtin_nontemporal_load(kcache + 128 + lane);
@@ -277,7 +327,6 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         }
     }
     const bool small_side = (K <= B);          // nonzero spectrum of A^T A == that of A A^T
-    const int n_present = a.ncomp ? scene_ncomp(a.ncomp, s, K) : K;   // absent components: the pair skips the constraints
     // step_morph and its L_morph were left in step_s[1] / mat[1][0] by the previous iteration's worker (there is a
     // worker whenever a component is present)
     const bool carried = P && reentered && resident && monotonic && n_present > 0;
@@ -491,12 +540,13 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     __syncthreads();
     STAMP(4);
 
-    // ---------------- phase 2: constraints, one PAIR of waves (2k, 2k + 1) per component.  The two
+    // ---------------- phase 2: constraints, one PAIR of waves (slot q: waves 2q, 2q + 1) per component k (the
+    // placement above; k = q in the generic instance).  The two
     // waves sit on different SIMDs, so the MFMA work of a big window spreads over two matrix
     // pipes; the wave that also runs the sweep and the bookkeeping (`lead`) alternates so that the
     // four sweeps of a scene land on four different SIMDs.
-    const int k = wid >> 1, half = wid & 1;
-    const bool lead = half == ((k >> 1) & 1);
+    const int k = kp, half = wid & 1;
+    const bool lead = half == ((slot >> 1) & 1);
     // Synchronisation of the two waves of a pair WITHOUT the other components of the scene: each wave
     // publishes the phase it has completed (after a release fence on its LDS writes) and sleeps until
     // its partner has published the same phase.  The four components then run their chains
@@ -590,6 +640,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     if (mine && mode == 2 && lead) wave_flip_symmetry<float>(t, sw, false, 1.0f);
     if (mine) pair_sync(4, std::false_type{});                         // B3
     STAMP(9);
+    PSTAMP(0);
     // lane -> (row, float4 group) walk of the final pass without divisions: +128 groups per step
     const int dyq = (2 * SC_WAVE) / gpr, dxq = 2 * SC_WAVE - dyq * gpr;
     const int g0 = lane + SC_WAVE * half;
@@ -698,6 +749,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     }
     if (mine) pair_sync(5, std::true_type{});                         // B4: sweep done, lstop published
     STAMP(10);
+    PSTAMP(1);
     // ---- sparsity, positivity (update.py:71-82, 27-32), normalisation (update.py:62-65),
     // store, convergence sums: one pass over the LDS tile, float4 groups split between the pair
     float norm = 0.f;
@@ -835,6 +887,16 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
             if (lane == 0) { conv_s[k][0] = d2s; conv_s[k][1] = n2s; }
         }
     }
+#ifdef SC_STAMP_PAIRS
+    PSTAMP(2);
+    if (a.stamps && mine && lead && lane == 0) {
+        long long *q = a.stamps + (size_t)a.S * 16 + (size_t)s * 8 + 2 * k;
+        const int ls = lstop_s[k];
+        q[0] = pst[2];
+        q[1] = ((pst[2] - pst[1]) & 0xfffff) | (((pst[1] - pst[0]) & 0xfffff) << 20) | ((long long)(ls < 255 ? ls : 255) << 40) |
+               ((long long)kg.ntr << 48) | ((long long)kg.ntc << 51) | ((long long)slot << 54);
+    }
+#endif
     __syncthreads();                                // B5
     if (mine && norm == norm) {
         // a NaN pixel away from the peak (NaN sums with a non-NaN norm): np.max is NaN and the
@@ -887,6 +949,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 11] = (long long)__builtin_amdgcn_s_memrealtime();
 #undef STAMP
 #undef WSTAMP
+#undef PSTAMP
     if (P) {
         // (no wait for this iteration's global stores here: what the next iteration needs of them is in LDS, the
         // previous morphology is re-read tens of thousands of cycles from now and the cached Hankel vectors by the

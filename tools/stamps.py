@@ -13,11 +13,38 @@ b = BlendBatch(imgs, cen, **kw)
 b.init_extended(np.ones(5) * .1)
 b.fit(int(os.environ.get("STAMP_PRE", "3")), e_rel=0, check_every=0)
 torch.cuda.synchronize()
-b.workspace[:S * 16 * 8].zero_()
+PAIRS = bool(os.environ.get("STAMP_PAIRS"))     # library built with -DSC_STAMP_PAIRS: 8 more words per scene behind the stamps
+b.workspace[:S * (24 if PAIRS else 16) * 8].zero_()
 # STAMP_ITERS > 1: the multi-iteration kernel (k_fit2x); the stamps are those of the launch's LAST iteration
 b.fit(int(os.environ.get("STAMP_ITERS", "1")), e_rel=0, check_every=0)
 torch.cuda.synchronize()
 st = b.workspace[:S * 16 * 8].view(torch.int64).view(S, 16).cpu().numpy()
+if PAIRS:
+    # per component: the lead's arrival at B5, and {arrival - B4, B4 - B3, last sweep level, NTR, NTC, slot} (fused2.h)
+    pw = b.workspace[S * 16 * 8:S * 24 * 8].view(torch.int64).view(S, 4, 2).cpu().numpy()
+    if int(os.environ.get("STAMP_ITERS", "1")) > 1 and S > 2048: pw = pw[:S - 1024]
+    pw = pw[(pw[:, :, 0] > 0).all(axis=1)]                      # scenes with four present components
+    arr, w = pw[:, :, 0].astype(np.float64), pw[:, :, 1]
+    tail, sweep, lstop = w & 0xfffff, (w >> 20) & 0xfffff, (w >> 40) & 0xff
+    ntr, ntc, slot = (w >> 48) & 7, (w >> 51) & 7, (w >> 54) & 3
+    cost = ntr * ntc * (ntr + ntc)
+    last = arr.argmax(axis=1)
+    rows = np.arange(len(arr))
+    print("B5 arrivals (n=%d scene-iterations): last - mean %d (p90 %d)   last - first %d (p90 %d)" % (
+        len(arr), (arr.max(1) - arr.mean(1)).mean(), np.percentile(arr.max(1) - arr.mean(1), 90),
+        (arr.max(1) - arr.min(1)).mean(), np.percentile(arr.max(1) - arr.min(1), 90)))
+    print("   the last one: has the scene's largest GEMM cost in %.1f %%, its deepest sweep in %.1f %%; on slot 0/1/2/3 in %s %%" % (
+        100.0 * (cost[rows, last] == cost.max(1)).mean(), 100.0 * (lstop[rows, last] == lstop.max(1)).mean(),
+        np.round(100.0 * np.bincount(slot[rows, last], minlength=4) / len(arr), 1)))
+    print("   (NTR, NTC) of the last one: share of scene-iterations, its lead's mean B3->B4 (sweep), last level, B4->B5")
+    for a_, b_ in sorted(set(zip(ntr[rows, last].tolist(), ntc[rows, last].tolist()))):
+        m = (ntr[rows, last] == a_) & (ntc[rows, last] == b_)
+        print("      (%d, %d): %5.1f %%   sweep %6d   level %5.1f   tail %6d" % (a_, b_, 100.0 * m.mean(), sweep[rows, last][m].mean(),
+              lstop[rows, last][m].mean(), tail[rows, last][m].mean()))
+    lv = np.maximum(lstop, 1)
+    print("   all leads: sweep %d cycles, %.0f per level; B4->B5 %d;  SIMDs {0,1} pairs' cost sum %.1f, SIMDs {2,3} %.1f" % (
+        sweep.mean(), (sweep / lv).mean(), tail.mean(),
+        np.where((slot & 1) == 0, cost, 0).sum(1).mean(), np.where((slot & 1) == 1, cost, 0).sum(1).mean()))
 if int(os.environ.get("STAMP_ITERS", "1")) > 1 and S > 2048:
     # multi-iteration launch: the last iteration of the scenes that finish while the chip is still full (the last
     # ~1000 scenes of the queue finish beside emptying CUs and run faster)
