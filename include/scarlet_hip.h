@@ -383,6 +383,46 @@ int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior *p, int in
 int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
                       int check_every, void *stream);
 
+/* Components with their own constraint switches (PointSource / ExtendedSource default to symmetric=True,
+ * CombinedExtendedSource to symmetric=False, and every constructor takes symmetric= and monotonic=, source.py:340-492):
+ * the four settings of the constraint pipeline per component instead of per batch.  scarlet_batch does not change; the
+ * settings travel in a struct of their own, device memory owned by the caller, indexed like the batch.
+ *   - Rows of absent components and of inactive scenes are not read.
+ *   - A given `symmetric` array needs an odd-sized centroid_psf in the batch; otherwise the call returns SCARLET_E_ARG,
+ *     found on the host before any launch (as for the scalar b->symmetric).
+ *   - c == NULL is SCARLET_E_ARG.
+ *   - The members of one multi-component source (group >= 0) must agree on `symmetric` and `monotonic`: the source's
+ *     shared centre (k_group_centers) reads the first member's value.
+ *   - The workspace layout does not depend on the struct (nor on the batch's four scalars).
+ *   - The caller sets b->symmetric and b->monotonic to the OR over its arrays: the library uses those scalars only for
+ *     decisions that must err on the side of "some component needs it" (the centroid PSF check, the box kernels of
+ *     frames beyond 64 x 64, which serve the monotonic components and leave the others to the full-frame kernel).
+ *   - With every pointer NULL the three entry points behave exactly as scarlet_fit / scarlet_fit_prior,
+ *     scarlet_source_update / scarlet_source_update_prior and scarlet_fit_observations do.
+ * A component without `symmetric` runs no centroid and its `shifts` are not touched; one without `monotonic` is
+ * normalised by the maximum over its whole plane.  Batches that take the one-launch iteration (K <= 4, frames up to
+ * 64 x 64 with W % 4 == 0, no PSF, exact L, no prior, no group) keep it: the four-wave kernel reads each wave's own
+ * component's settings (profile class 4). */
+typedef struct scarlet_constraints {
+    const uint8_t *symmetric;   /* device [S][K], or NULL = b->symmetric for every component */
+    const uint8_t *monotonic;   /* device [S][K], or NULL = b->monotonic                     */
+    const float   *l0_thresh;   /* device [S][K], < 0 = off, or NULL = b->l0_thresh          */
+    const float   *l1_thresh;   /* device [S][K], < 0 = off, or NULL = b->l1_thresh          */
+} scarlet_constraints;          /* 32 bytes */
+
+/* scarlet_fit (p == NULL) or scarlet_fit_prior (p given) with per-component switches */
+int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p /* or NULL */,
+                            int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+/* scarlet_source_update / scarlet_source_update_prior with per-component switches.  in_iteration = 0 (the constructors'
+ * update, which ignores `active`) with any array given leaves scenes with SCARLET_STATUS_BAD_INIT or
+ * SCARLET_STATUS_BAD_COUNT untouched. */
+int scarlet_source_update_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p /* or NULL: only L_comp is read */,
+                                      int in_iteration, void *stream);
+/* scarlet_fit_observations with per-component switches on the state */
+int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                         const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                         int approximate_L, int check_every, void *stream);
+
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes
  * the stepped factors into buffer 1-cur; cur/it are NOT advanced yet                   */

@@ -91,6 +91,11 @@ class ScarletPrior(Structure):
     ]
 
 
+class ScarletConstraints(Structure):
+    """struct scarlet_constraints of include/scarlet_hip.h (field order must match)."""
+    _fields_ = [("symmetric", c_void_p), ("monotonic", c_void_p), ("l0_thresh", c_void_p), ("l1_thresh", c_void_p)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "scarlet_version": (c_char_p, []),
@@ -129,6 +134,11 @@ _SIGNATURES = {
     "scarlet_backward_step_prior": (c_int, [POINTER(ScarletBatch), POINTER(ScarletPrior), c_int, _P]),
     "scarlet_source_update_prior": (c_int, [POINTER(ScarletBatch), POINTER(ScarletPrior), c_int, _P]),
     "scarlet_fit_prior": (c_int, [POINTER(ScarletBatch), POINTER(ScarletPrior), c_int, c_double, c_int, c_int, _P]),
+    "scarlet_fit_constrained": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletPrior), c_int, c_double,
+                                        c_int, c_int, _P]),
+    "scarlet_source_update_constrained": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletPrior), c_int, _P]),
+    "scarlet_fit_observations_constrained": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints),
+                                                     POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

@@ -45,6 +45,80 @@ def pad_centers(centers, K=None):
     return out, counts
 
 
+_SWITCHES, _THRESHOLDS = ("symmetric", "monotonic"), ("l0_thresh", "l1_thresh")
+
+
+def is_scalar_setting(value):
+    """True for what BlendBatch has always taken for a constraint setting: None, a bool or a number."""
+    if value is None or isinstance(value, (bool, int, float, np.generic)):
+        return True
+    return hasattr(value, "ndim") and value.ndim == 0        # 0-d array / tensor
+
+
+def constraint_arrays(value, S, K, kind, group=None):
+    """One constraint setting of a batch as an (S, K) host array, one entry per component (no device needed).
+
+    value : a scalar (every component), a (K,) sequence (one row for all scenes), an (S, K) array, or a list of S
+        per-scene lists of at most K entries each (ragged batches, padded like `pad_centers` pads the centres: the
+        entries of absent components are "off" and never read)
+    kind : "symmetric" / "monotonic" -> uint8 0 / 1;  "l0_thresh" / "l1_thresh" -> float32, where None or a negative
+        number means off and is stored as -1
+    group : None or (S, K) integers as BlendBatch takes them: the members of one multi-component source (equal
+        group >= 0) must agree on a switch (ValueError otherwise); thresholds may differ between layers
+    A wrong shape raises ValueError."""
+    if kind not in _SWITCHES + _THRESHOLDS:
+        raise ValueError("constraint_arrays: unknown kind %r" % (kind,))
+    switch = kind in _SWITCHES
+    S, K = int(S), int(K)
+
+    def entry(v):
+        if switch:
+            if v is None:
+                raise ValueError("%s: None is not a switch value" % kind)
+            return 1 if bool(v) else 0
+        if v is None:
+            return -1.0
+        v = float(v)
+        if v != v:
+            raise ValueError("%s: NaN is not a threshold" % kind)
+        return -1.0 if v < 0 else v
+
+    dtype, off = (np.uint8, 0) if switch else (np.float32, -1.0)
+    out = np.full((S, K), off, dtype=dtype)
+    if hasattr(value, "detach"):                       # a torch tensor
+        value = value.detach().cpu().numpy()
+    if is_scalar_setting(value):
+        out[:] = entry(value if not hasattr(value, "ndim") else value.item())
+    else:
+        seq = list(value)
+        rows = [hasattr(r, "__len__") and not isinstance(r, (str, bytes)) for r in seq]
+        if any(rows):
+            if not all(rows):
+                raise ValueError("%s: a mix of per-scene rows and single entries" % kind)
+            if len(seq) != S:
+                raise ValueError("%s: %d per-scene rows for S = %d scenes" % (kind, len(seq), S))
+            for s_, r in enumerate(seq):
+                r = list(r)
+                if len(r) > K:
+                    raise ValueError("%s: scene %d has %d entries, more than K = %d" % (kind, s_, len(r), K))
+                if any(hasattr(v, "__len__") for v in r):
+                    raise ValueError("%s must be a scalar, (K,) = (%d,), (S, K) = (%d, %d) or S per-scene lists" % (kind, K, S, K))
+                out[s_, :len(r)] = [entry(v) for v in r]
+        else:
+            if len(seq) != K:
+                raise ValueError("%s: %d entries for K = %d components per scene" % (kind, len(seq), K))
+            out[:] = np.array([entry(v) for v in seq], dtype=dtype)[None, :]
+    if switch and group is not None:
+        g = np.asarray(group).reshape(S, K)
+        same = (g[:, 1:] == g[:, :-1]) & (g[:, 1:] >= 0)          # (members are adjacent components)
+        bad = same & (out[:, 1:] != out[:, :-1])
+        if bad.any():
+            s_, k = [int(v[0]) for v in np.nonzero(bad)]
+            raise ValueError("%s: components %d and %d of scene %d are layers of one multi-component source (group %d) "
+                             "and must agree" % (kind, k, k + 1, s_, int(g[s_, k])))
+    return out
+
+
 class ObservationBatch(object):
     """One observation of S scenes for `BlendBatch.from_observations` (reference Observation, observation.py:101-224,
     as one element of Blend(sources, [obs_a, obs_b])): the images cover the model channels band0 .. band0 + B - 1.
@@ -94,6 +168,13 @@ class BlendBatch(object):
     weights : None (scalar 1, reference observation.py:148-151), a Python scalar, or (S, B, H, W)
     symmetric, monotonic : constraint switches of PointSource/ExtendedSource.update
     l0_thresh, l1_thresh : None or sparsity thresholds (update.sparse_l0 / sparse_l1)
+        Each of the four is one value for the batch, or one per component (`constraint_arrays`): a (K,) sequence, an
+        (S, K) array, or per-scene lists for ragged batches -- as the reference's sources each carry their own
+        symmetric= / monotonic=.  With any of them per component the batch is `constrained` and runs the library's
+        *_constrained entry points; `symmetric` / `monotonic` then read "any component is", `l0_thresh` / `l1_thresh`
+        None.  The layers of one `group` must agree on the switches.  Initialisation switches stay per batch:
+        `init_monotonic=None` means "any component is monotonic", and the layers of a group start with the batch's
+        `symmetric`; a per-component start option is out of scope.
     centroid_weight : (P, P) float64 centroid PSF; default = reference default
     group : None, or (S, K) integers: -1 = the component is a source of its own, g >= 0 = it is a layer of
         multi-component source g of its scene (reference MultiComponentSource, source.py:538-641): the layers
@@ -176,8 +257,25 @@ class BlendBatch(object):
                     s, k = [int(v[0]) for v in np.nonzero(absent & (g >= 0))]
                     raise ValueError("group[%d][%d] = %d: an absent component must have group -1" % (s, k, g[s, k]))
             self.group = torch.as_tensor(g).to(**i32).contiguous()
-        self.symmetric, self.monotonic = bool(symmetric), bool(monotonic)
-        self.l0_thresh, self.l1_thresh = l0_thresh, l1_thresh
+        # the four settings: scalars (the entry points of old) or per component (scarlet_constraints)
+        given = dict(symmetric=symmetric, monotonic=monotonic, l0_thresh=l0_thresh, l1_thresh=l1_thresh)
+        self.constraints = {}         # name -> (S, K) device tensor, for the settings given per component
+        g_host = None if self.group is None else self.group.cpu().numpy()
+        for name, value in given.items():
+            if is_scalar_setting(value):
+                continue
+            arr = constraint_arrays(value, S, K, name, group=g_host)
+            if self.n_components is not None:          # rows of absent components: off (never read)
+                arr[~self._present().cpu().numpy()] = 0 if name in _SWITCHES else -1.0
+            self.constraints[name] = torch.as_tensor(arr).to(device=self.device).contiguous()
+            given[name] = bool(arr.any()) if name in _SWITCHES else None
+        self.symmetric, self.monotonic = bool(given["symmetric"]), bool(given["monotonic"])
+        self.l0_thresh, self.l1_thresh = given["l0_thresh"], given["l1_thresh"]
+        self._cons = None
+        if self.constraints:
+            self._cons = _lib.ScarletConstraints()
+            for name, x in self.constraints.items():
+                setattr(self._cons, name, x.data_ptr())
         cw = default_centroid_weight() if centroid_weight is None else np.asarray(centroid_weight, dtype=np.float64)
         assert cw.ndim == 2 and cw.shape[0] == cw.shape[1] and cw.shape[0] % 2 == 1
         self.centroid_weight = torch.as_tensor(cw).to(**f64).contiguous()
@@ -190,6 +288,14 @@ class BlendBatch(object):
         self._c.workspace = self.workspace.data_ptr()
 
     # ------------------------------------------------------------------ plumbing
+    @property
+    def constrained(self):
+        """True when a constraint setting was given per component: the batch runs the *_constrained entry points."""
+        return self._cons is not None
+
+    def _cons_ref(self):
+        return ctypes.byref(self._cons)
+
     def _present(self):
         """(S, K) bool device mask of the components each scene uses (all of them without n_components)."""
         k = self.torch.arange(self.K, device=self.device)
@@ -331,9 +437,11 @@ class BlendBatch(object):
         rc = _lib.lib.scarlet_init_extended(
             ctypes.byref(self._c), bg.ctypes.data_as(ctypes.c_void_p), float(thresh),
             None if sc is None else sc.ctypes.data_as(ctypes.c_void_p), int(bool(init_symmetric)),
-            int(self.monotonic if init_monotonic is None else bool(init_monotonic)), int(bool(run_update)),
-            _lib.stream_ptr())
+            int(self.monotonic if init_monotonic is None else bool(init_monotonic)),
+            int(bool(run_update) and not self.constrained), _lib.stream_ptr())
         _lib.check(rc)
+        if run_update and self.constrained:       # the constructors' update() with each component's own settings
+            self.update_sources()
         return self
 
     def init_sources(self, bg_rms, kind=None, flux_percentiles=None, obs_psfs=None, model_psf=None, thresh=1.0,
@@ -428,13 +536,20 @@ class BlendBatch(object):
         spec.thresh = float(thresh)
         spec.init_symmetric = int(bool(init_symmetric))
         spec.init_monotonic = int(self.monotonic if init_monotonic is None else bool(init_monotonic))
-        spec.run_update = int(bool(run_update))
+        spec.run_update = int(bool(run_update) and not self.constrained)
         _lib.check(_lib.lib.scarlet_init_sources(ctypes.byref(self._c), ctypes.byref(spec), _lib.stream_ptr()))
         self._init_checked = True
+        if run_update and self.constrained:
+            # the constructors' update() with each component's own settings; scenes with STATUS_BAD_INIT stay untouched
+            self.update_sources()
         return self
 
     def update_sources(self):
         """Run the constraint pipeline once with it=0 (what the source constructors do)."""
+        if self.constrained:
+            _lib.check(_lib.lib.scarlet_source_update_constrained(ctypes.byref(self._c), self._cons_ref(), None, 0,
+                                                                  _lib.stream_ptr()))
+            return self
         _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 0, _lib.stream_ptr()))
         return self
 
@@ -457,6 +572,10 @@ class BlendBatch(object):
             return self._fit_observations(max_iter, e_rel, approximate_L, check_every)
         if prior is not None:
             return self._fit_prior(prior, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every))
+        if self.constrained:
+            rc = _lib.lib.scarlet_fit_constrained(ctypes.byref(self._c), self._cons_ref(), None, int(max_iter), float(e_rel),
+                                                  int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
+            return _lib.check(rc)
         rc = _lib.lib.scarlet_fit(ctypes.byref(self._c), int(max_iter), float(e_rel),
                                   int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
         return _lib.check(rc)
@@ -479,7 +598,10 @@ class BlendBatch(object):
             return
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step(ctypes.byref(self._c), int(bool(approximate_L)), s))
-        _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 1, s))
+        if self.constrained:
+            _lib.check(_lib.lib.scarlet_source_update_constrained(ctypes.byref(self._c), self._cons_ref(), None, 1, s))
+        else:
+            _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 1, s))
         _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), float(e_rel), s))
 
     # ------------------------------------------------------------------ priors
@@ -527,7 +649,10 @@ class BlendBatch(object):
         self._set_given(ps, dicts)
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step_prior(ctypes.byref(self._c), ctypes.byref(ps), approximate_L, s))
-        _lib.check(_lib.lib.scarlet_source_update_prior(ctypes.byref(self._c), ctypes.byref(ps), 1, s))
+        if self.constrained:
+            _lib.check(_lib.lib.scarlet_source_update_constrained(ctypes.byref(self._c), self._cons_ref(), ctypes.byref(ps), 1, s))
+        else:
+            _lib.check(_lib.lib.scarlet_source_update_prior(ctypes.byref(self._c), ctypes.byref(ps), 1, s))
         _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), e_rel, s))
 
     def _fit_prior(self, prior, max_iter, e_rel, approximate_L, check_every):
@@ -536,6 +661,10 @@ class BlendBatch(object):
         if not fns:
             # nothing changes between iterations: the library's own loop
             self._set_given(ps, given)
+            if self.constrained:
+                return _lib.check(_lib.lib.scarlet_fit_constrained(ctypes.byref(self._c), self._cons_ref(), ctypes.byref(ps),
+                                                                   max_iter, e_rel, approximate_L, check_every,
+                                                                   _lib.stream_ptr()))
             return _lib.check(_lib.lib.scarlet_fit_prior(ctypes.byref(self._c), ctypes.byref(ps), max_iter, e_rel,
                                                          approximate_L, check_every, _lib.stream_ptr()))
         launched = 0
@@ -594,6 +723,11 @@ class BlendBatch(object):
         ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
         band0 = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
         self._keep = (ptrs, band0)
+        if self.constrained:
+            rc = _lib.lib.scarlet_fit_observations_constrained(
+                ctypes.byref(self._c), self._cons_ref(), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n, int(max_iter),
+                float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
+            return _lib.check(rc)
         rc = _lib.lib.scarlet_fit_observations(ctypes.byref(self._c), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n,
                                                int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every),
                                                _lib.stream_ptr())

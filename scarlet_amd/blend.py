@@ -70,9 +70,8 @@ class Blend(ComponentTree):
                 return False
             if getattr(s, "prior", None) is not None or hasattr(s, "bboxes"):
                 return False
-        sym = {bool(s.symmetric) for s in self.sources}
-        mono = {bool(s.monotonic) for s in self.sources}
-        return len(sym) == 1 and len(mono) == 1
+        # (sources may disagree on symmetric / monotonic: the batch then carries them per component)
+        return True
 
     def _ensure_batch(self):
         if self._batch is not None:
@@ -101,13 +100,21 @@ class Blend(ComponentTree):
                 cw = np.asarray(s._centroid_weight, dtype=np.float64)
                 break
         builtin = self._builtin_pipeline()
+        # each component's own switches (a layered source's value for each of its layers); one value when all agree,
+        # which keeps the scalar entry points
+        sym = [bool(src.symmetric) for src in self.sources for _ in (src.components if hasattr(src, "components") else [src])] \
+            if builtin else [False]
+        mono = [bool(src.monotonic) for src in self.sources for _ in (src.components if hasattr(src, "components") else [src])] \
+            if builtin else [False]
+        sym = sym[0] if len(set(sym)) == 1 else [sym]
+        mono = mono[0] if len(set(mono)) == 1 else [mono]
 
-        def obs_batch(o, images=None):
+        def obs_batch(o, images=None, state=True):
             ob = BlendBatch(o._images_device()[None] if images is None else images,
                             np.array(centers, dtype=np.int32)[None],
                             weights=None if (images is not None or o._weights_device() is None) else o._weights_device()[None],
-                            symmetric=bool(self.sources[0].symmetric) if builtin else False,
-                            monotonic=bool(self.sources[0].monotonic) if builtin else False,
+                            symmetric=sym if state else bool(np.any(sym)),
+                            monotonic=mono if state else bool(np.any(mono)),
                             centroid_weight=cw,
                             group=np.array(group, dtype=np.int32)[None] if (builtin and any(g >= 0 for g in group)) else None)
             if images is None:
@@ -125,7 +132,7 @@ class Blend(ComponentTree):
             # every observation has a gradient-only batch over its own channels
             C, Ny, Nx = self.frame.shape
             b = obs_batch(obs, images=torch.zeros((1, C, Ny, Nx), dtype=torch.float32, device="cuda"))
-            self._obs_batches = [(obs_batch(o), o._band_slice) for o in self.observations]
+            self._obs_batches = [(obs_batch(o, state=False), o._band_slice) for o in self.observations]
         else:
             b = obs_batch(obs)
         sed = torch.stack([c._own_sed for c in comps])[None]
@@ -206,9 +213,14 @@ class Blend(ComponentTree):
                 n = len(self._obs_batches)
                 ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for ob, _ in self._obs_batches])
                 band0 = np.array([(sl.start or 0) for _, sl in self._obs_batches], dtype=np.int32)
-                _lib.check(_lib.lib.scarlet_fit_multi(ctypes.byref(b._c), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n,
-                                                      int(max_iter), float(e_rel), int(bool(approximate_L)), 4,
-                                                      _lib.stream_ptr()))
+                if b.constrained:
+                    _lib.check(_lib.lib.scarlet_fit_observations_constrained(
+                        ctypes.byref(b._c), b._cons_ref(), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n, int(max_iter),
+                        float(e_rel), int(bool(approximate_L)), 4, _lib.stream_ptr()))
+                else:
+                    _lib.check(_lib.lib.scarlet_fit_multi(ctypes.byref(b._c), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n,
+                                                          int(max_iter), float(e_rel), int(bool(approximate_L)), 4,
+                                                          _lib.stream_ptr()))
             b.raise_on_status()
             self._sync_sources()
             return self

@@ -73,6 +73,14 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
     const int s = c / a.K;
     if (!a.force_it0 && !a.active[s]) return;
     if (c - s * a.K >= scene_ncomp(a.ncomp, s, a.K)) return;        // absent component: never listed either
+    if (update_skips_scene(a, s)) return;
+    if (!comp_monotonic(a, c)) {
+        // no sweep, no early exit to bound the footprint: the full-frame kernel takes the component (not listed for
+        // the large box either)
+        if (threadIdx.x == 0) fallback[c] = 1;
+        return;
+    }
+    const bool symmetric = comp_symmetric(a, c);
     long long *stamps = stamps_all ? stamps_all + (size_t)c * 16 : nullptr;
 #define UB_STAMP(i) do { if (stamps && threadIdx.x == 0) stamps[(i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
     UB_STAMP(0);
@@ -109,7 +117,7 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
     }
     double dy = grouped ? (double)__builtin_nanf("") : a.shifts[2 * c], dx = grouped ? dy : a.shifts[2 * c + 1];
     bool new_shift = false;
-    if (!grouped && a.symmetric && it % 5 == 0) {                            // source.py:428-429
+    if (!grouped && symmetric && it % 5 == 0) {                            // source.py:428-429
         __syncthreads();
         centroid_tile(tg, a.centroid_psf, a.centroid_P, cy, cx, red, ctr, shf, &stat);
         cy = ctr[0]; cx = ctr[1]; dy = shf[0]; dx = shf[1];
@@ -118,7 +126,7 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
     UB_STAMP(1);
     const SymWindow sw = sym_window(H, W, cy, cx);
     // 0: no symmetry, 1: k-space, 2: soft flip (no shift yet)
-    const int mode = !a.symmetric ? 0 : ((dy != dy) ? 2 : (sw.centered ? 0 : 1));
+    const int mode = !symmetric ? 0 : ((dy != dy) ? 2 : (sw.centered ? 0 : 1));
     if (mode == 2 && sw.centered) {                       // the flip about the array middle leaves the box: full path
         if (threadIdx.x == 0) fallback[c] = 1;
         return;
@@ -463,8 +471,9 @@ __device__ __forceinline__ void ub_component(const UpdateArgs &a, const int c, i
     }
     // sparse_l0 / sparse_l1, positive, normalized('morph_max') (update.py:71-82, 27-32, 62-65): as k_source_update
     const float step_morph = update_step_morph(a, s, c);
-    const float l0 = a.l0_thresh >= 0.f ? a.l0_thresh * step_morph : -1.f;
-    const float l1 = a.l1_thresh >= 0.f ? a.l1_thresh * step_morph : -1.f;
+    const float l0t = comp_l0(a, c), l1t = comp_l1(a, c);
+    const float l0 = l0t >= 0.f ? l0t * step_morph : -1.f;
+    const float l1 = l1t >= 0.f ? l1t * step_morph : -1.f;
     auto sparse_plus = [&](float v, int y, int x) {
         if (l0 >= 0.f && fabsf(v) < l0) v = 0.f;
         if (l1 >= 0.f) {

@@ -486,7 +486,20 @@ struct UpdateArgs {
                                       // shift = None (soft symmetry); -1 = a source of its own
     const int *ncomp;                 // [S] or NULL: components per scene (scene_ncomp); absent ones are skipped
     const double *L_comp;             // [S*K][2] or NULL: the constants each component stepped with (prior.h); NULL: the scene's
+    // scarlet_constraints: [S*K] each, or NULL = the batch's scalar above.  Read through comp_symmetric() .. comp_l1() only
+    const uint8_t *symmetric_c, *monotonic_c;
+    const float *l0_c, *l1_c;
+    int skip_status;                  // constructor call (force_it0): scenes with one of these status bits are left untouched
 };
+
+// The constraint switches of component c (scarlet_constraints, or the batch's scalars).  Every caller runs one component
+// per workgroup or per wave and passes a uniform c: the values are scalar loads and the branches on them scalar branches.
+__device__ __forceinline__ bool comp_symmetric(const UpdateArgs &a, int c) { return a.symmetric_c ? a.symmetric_c[c] != 0 : a.symmetric != 0; }
+__device__ __forceinline__ bool comp_monotonic(const UpdateArgs &a, int c) { return a.monotonic_c ? a.monotonic_c[c] != 0 : a.monotonic != 0; }
+__device__ __forceinline__ float comp_l0(const UpdateArgs &a, int c) { return a.l0_c ? a.l0_c[c] : a.l0_thresh; }
+__device__ __forceinline__ float comp_l1(const UpdateArgs &a, int c) { return a.l1_c ? a.l1_c[c] : a.l1_thresh; }
+// a scene the constructors' update leaves alone (SCARLET_STATUS_BAD_INIT / BAD_COUNT under scarlet_source_update_constrained)
+__device__ __forceinline__ bool update_skips_scene(const UpdateArgs &a, int s) { return a.skip_status && (a.status[s] & a.skip_status); }
 
 // the step that scales the sparse_l0 / sparse_l1 cut (update.py:71-82): 1 / L_morph of the scene, or of the component
 // itself when it stepped with a prior's constant added (component.py:177-187)
@@ -515,6 +528,8 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     if (!a.force_it0 && !a.active[s]) return;
     if (c - s * a.K >= scene_ncomp(a.ncomp, s, a.K)) return;        // absent component
     if (a.only_flagged && !a.only_flagged[c]) return;
+    if (update_skips_scene(a, s)) return;
+    const bool symmetric = comp_symmetric(a, c), monotonic = comp_monotonic(a, c);
     const int H = a.H, W = a.W, HW = H * W, B = a.B;
     const int hp = round16(H), wp = round16(W);
     Tile t; t.H = H; t.W = W;
@@ -573,7 +588,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
         max_pixel_tile(t, cy, cx, ctr, &stat);                     // source.py:414
         cy = ctr[0]; cx = ctr[1];
     }
-    if (a.symmetric) {
+    if (symmetric) {
         double dy = grouped ? (double)__builtin_nanf("") : a.shifts[2 * c], dx = grouped ? dy : a.shifts[2 * c + 1];
         if (!grouped && it % 5 == 0) {                              // source.py:428-429
             __syncthreads();
@@ -587,7 +602,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
                       false, 0.f, scr, av, bv, cv, zv, stage, GT);
     }
     int lstop = 1 << 30;          // last sweep level computed (early exit); pixels beyond are <= 0 -> 0
-    if (a.monotonic) {                                                                   // source.py:436
+    if (monotonic) {                                                                     // source.py:436
         if (!GT && a.hybrid_sweep) {
             // tile in LDS: levels 1 .. 46 on one wave without barriers (wave_ops.h; a sweep usually stops
             // before), the rest level-synchronously on the whole workgroup
@@ -637,8 +652,9 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     // normalized('morph_max') (update.py:62-65)
     const float step_morph = update_step_morph(a, s, c);
     const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * HW : nullptr;
-    const float l0 = a.l0_thresh >= 0.f ? a.l0_thresh * step_morph : -1.f;
-    const float l1 = a.l1_thresh >= 0.f ? a.l1_thresh * step_morph : -1.f;
+    const float l0t = comp_l0(a, c), l1t = comp_l1(a, c);
+    const float l0 = l0t >= 0.f ? l0t * step_morph : -1.f;
+    const float l1 = l1t >= 0.f ? l1t * step_morph : -1.f;
     auto sparse_plus = [&](float v, int y, int x) {      // update.py:71-82, 27-32 + the sweep's cut
         if (l0 >= 0.f && fabsf(v) < l0) v = 0.f;
         if (l1 >= 0.f) {
@@ -650,7 +666,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     };
     float norm;
     double d2 = 0, n2 = 0;
-    if (vec4 && a.monotonic) {
+    if (vec4 && monotonic) {
         // one pass in float4 groups; morph.max() is the processed peak pixel after a sweep (see
         // wave_pipeline below); a NaN elsewhere shows up in the sums
         __syncthreads();
@@ -741,6 +757,7 @@ __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
     extern __shared__ __align__(16) float lds[];
     const int s = blockIdx.x;
     if (!a.force_it0 && !a.active[s]) return;
+    if (update_skips_scene(a, s)) return;
     const int K = a.K, B = a.B, H = a.H, W = a.W, HW = H * W, lane = threadIdx.x;
     const int c0 = a.cur[s], wbuf = a.in_iteration ? 1 - c0 : c0;
     const int it = a.force_it0 ? 0 : a.it[s] + (a.in_iteration ? 1 : 0);
@@ -771,7 +788,7 @@ __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
         wave_max_pixel(t, ly, lx, stat);
         double dy = a.shifts[2 * (s * K + k0)], dx = a.shifts[2 * (s * K + k0) + 1];
         bool new_shift = false;
-        if (a.symmetric && it % 5 == 0) {
+        if (comp_symmetric(a, s * K + k0) && it % 5 == 0) {        // (the members agree: the first one's value)
             wave_centroid(t, a.centroid_psf, a.centroid_P, ly, lx, dy, dx, stat);
             new_shift = true;
         }
@@ -845,8 +862,9 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
     int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
     int stat = 0;
     const bool grouped = a.group && a.group[c] >= 0;               // layer of a MultiComponentSource: centre from k_group_centers
+    const bool symmetric = comp_symmetric(a, c), monotonic = comp_monotonic(a, c);
     if (!grouped) wave_max_pixel(t, cy, cx, stat);
-    if (a.symmetric) {
+    if (symmetric) {
         double dy = grouped ? (double)__builtin_nanf("") : a.shifts[2 * c], dx = grouped ? dy : a.shifts[2 * c + 1];
         if (!grouped && it % 5 == 0) {
             wave_centroid(t, a.centroid_psf, a.centroid_P, cy, cx, dy, dx, stat);
@@ -856,12 +874,13 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
         wave_symmetry(t, cy, cx, none ? SCARLET_SYM_SOFT : SCARLET_SYM_KSPACE, 1.0f, dy, dx, false, 0.f, vec);
     }
     int lstop = 1 << 30;                // last sweep level computed; pixels beyond are <= 0 -> 0
-    if (a.monotonic) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
+    if (monotonic) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
     if (lane == 0) { a.centers[2 * c] = cy; a.centers[2 * c + 1] = cx; }
     const float step_morph = update_step_morph(a, s, c);
     const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * HW : nullptr;
-    const float l0 = a.l0_thresh >= 0.f ? a.l0_thresh * step_morph : -1.f;
-    const float l1 = a.l1_thresh >= 0.f ? a.l1_thresh * step_morph : -1.f;
+    const float l0t = comp_l0(a, c), l1t = comp_l1(a, c);
+    const float l0 = l0t >= 0.f ? l0t * step_morph : -1.f;
+    const float l1 = l1t >= 0.f ? l1t * step_morph : -1.f;
     auto sparse_plus = [&](float v, int y, int x) {      // update.py:71-82, 27-32 + the sweep's cut
         if (l0 >= 0.f && fabsf(v) < l0) v = 0.f;
         if (l1 >= 0.f) {
@@ -873,7 +892,7 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
     };
     float norm;
     double d2 = 0, n2 = 0;
-    if (vec4 && a.monotonic) {
+    if (vec4 && monotonic) {
         // One pass in float4 groups.  After the sweep no pixel exceeds the peak pixel (each is capped
         // by a convex combination of pixels closer to the peak) and the maps above are monotone, so
         // morph.max() is the processed peak value; a NaN elsewhere shows up in the sums (see below).
@@ -953,10 +972,11 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w(UpdateArgs a)
 {
     extern __shared__ __align__(16) float lds[];
     const int wid = threadIdx.x / SC_WAVE;
-    const int c = blockIdx.x * SC_NWAVES + wid;
+    const int c = uniform((int)(blockIdx.x * SC_NWAVES + wid));     // (in an SGPR: the component's switches are scalar loads)
     if (c >= a.S * a.K) return;
     if (!a.force_it0 && !a.active[c / a.K]) return;
     if (c % a.K >= scene_ncomp(a.ncomp, c / a.K, a.K)) return;      // absent component
+    if (update_skips_scene(a, c / a.K)) return;
     const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;
     wave_pipeline(a, c, lds + (size_t)wid * per_wave);
 }

@@ -47,14 +47,21 @@ struct FusedArgs {
     const int *ncomp;                // [S] or NULL: components per scene (scene_ncomp); absent ones skip the constraints
     int no_place;                    // k_iterate2 / k_fit2x, exact shape: component k on waves 2k, 2k + 1 (option NO_PLACE)
 };
+// scarlet_constraints for the four-wave kernel: [S][K] each, or NULL = the batch's scalar.  k_iterate<KM, BM, FusedArgsPC>
+// reads them in phase 2, where wave k owns component k; every other instance takes FusedArgs and compiles as before.
+struct FusedArgsPC : FusedArgs {
+    const uint8_t *symmetric_c, *monotonic_c;
+    const float *l0_c, *l1_c;
+};
 // Per component and wave of its pair: 64 entries of av, bv, cv (this wave's half), then the header
 // {H W cy cx, magic, dy (2 words), dx (2 words), s} the vectors were made for
 #define SC_KSC_FLOATS 200
 #define SC_KSC_MAGIC 0x5ca71e70u
 
-template <int KM, int BM>
-__global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(FusedArgs a)
+template <int KM, int BM, class A = FusedArgs>
+__global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
 {
+    constexpr bool PC = std::is_same<A, FusedArgsPC>::value;      // per-component constraint switches
     extern __shared__ __align__(16) float lds[];
     const int s = blockIdx.x;
     if (!a.active[s]) return;
@@ -282,9 +289,15 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(FusedArgs a)
         float *vec = vecs + wid * SC_WAVE_VEC_FLOATS;
         int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
         int stat = 0;
+        // the component's switches: the batch's, or (PC) its own -- c is uniform over the wave (wid is): scalar loads.
+        // Read where they are used, so that the instances on FusedArgs stay the code they were.
+        auto c_symmetric = [&]() -> bool { if constexpr (PC) { if (a.symmetric_c) return a.symmetric_c[c] != 0; } return a.symmetric != 0; };
+        auto c_monotonic = [&]() -> bool { if constexpr (PC) { if (a.monotonic_c) return a.monotonic_c[c] != 0; } return a.monotonic != 0; };
+        auto c_l0 = [&]() -> float { if constexpr (PC) { if (a.l0_c) return a.l0_c[c]; } return a.l0_thresh; };
+        auto c_l1 = [&]() -> float { if constexpr (PC) { if (a.l1_c) return a.l1_c[c]; } return a.l1_thresh; };
         wave_max_pixel(t, cy, cx, stat);
         cy = uniform(cy); cx = uniform(cx);
-        if (a.symmetric) {
+        if (c_symmetric()) {
             double dy = a.shifts[2 * c], dx = a.shifts[2 * c + 1];
             if (it_new % 5 == 0) {
                 wave_centroid(t, a.centroid_psf, a.centroid_P, cy, cx, dy, dx, stat);
@@ -298,7 +311,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(FusedArgs a)
         }
         STAMP(9);
         int lstop = 1 << 30;            // last sweep level computed (early exit); pixels beyond are <= 0 -> 0
-        if (a.monotonic) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
+        if (c_monotonic()) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
         STAMP(10);
         if (lane == 0) { a.centers[2 * c] = cy; a.centers[2 * c + 1] = cx; }
         // ---- sparsity, positivity (update.py:71-82, 27-32), normalisation (update.py:62-65),
@@ -313,8 +326,8 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(FusedArgs a)
             lastv[j] = g < ngroups ? last4[g] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         const bool cut = lstop < (1 << 30);
-        float l0 = a.l0_thresh >= 0.f ? a.l0_thresh * step_morph : -1.f;
-        float l1 = a.l1_thresh >= 0.f ? a.l1_thresh * step_morph : -1.f;
+        float l0 = c_l0() >= 0.f ? c_l0() * step_morph : -1.f;
+        float l1 = c_l1() >= 0.f ? c_l1() * step_morph : -1.f;
         auto sparse = [&](float v) {
             if (l0 >= 0.f && fabsf(v) < l0) v = 0.f;
             if (l1 >= 0.f) {
@@ -327,7 +340,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(FusedArgs a)
         const int dyq = SC_WAVE / gpr, dxq = SC_WAVE - dyq * gpr;
         const int y0 = lane / gpr, x0 = lane - y0 * gpr;
         float norm;
-        if (a.monotonic) {
+        if (c_monotonic()) {
             // after the sweep no pixel exceeds the peak pixel (each is capped by a convex
             // combination of pixels closer to the peak) and the maps above are monotone:
             // morph.max() is the processed peak value (a NaN elsewhere: see below)

@@ -780,6 +780,29 @@ static int check_batch(const scarlet_batch *b, bool multi = false)
     return SCARLET_OK;
 }
 
+// ---- per-component constraint switches (scarlet_constraints).  Inside the library `c` may be NULL: the batch's scalars.
+static bool cons_any(const scarlet_constraints *c) { return c && (c->symmetric || c->monotonic || c->l0_thresh || c->l1_thresh); }
+// the _constrained entry points: the struct is required, and a symmetric array needs what b->symmetric needs
+static int check_constraints(const scarlet_batch *b, const scarlet_constraints *c)
+{
+    if (!b) return set_err(SCARLET_E_ARG, "null batch");
+    if (!c) return set_err(SCARLET_E_ARG, "constraints is NULL (pass a scarlet_constraints with NULL members for the batch's scalars)");
+    if (c->symmetric && (!b->centroid_psf || b->centroid_P <= 0 || !(b->centroid_P & 1)))
+        return set_err(SCARLET_E_ARG, "constraints.symmetric needs an odd-sized centroid_psf");
+    return SCARLET_OK;
+}
+// the arrays advanced to component `first` (split_views: a half-batch's first component)
+static scarlet_constraints cons_view(const scarlet_constraints *c, size_t first)
+{
+    scarlet_constraints v = {};
+    if (!c) return v;
+    v.symmetric = c->symmetric ? c->symmetric + first : nullptr;
+    v.monotonic = c->monotonic ? c->monotonic + first : nullptr;
+    v.l0_thresh = c->l0_thresh ? c->l0_thresh + first : nullptr;
+    v.l1_thresh = c->l1_thresh ? c->l1_thresh + first : nullptr;
+    return v;
+}
+
 // Ragged batches: one small kernel per call of an entry point that iterates or initialises.  A scene whose count lies
 // outside 1..K gets SCARLET_STATUS_BAD_COUNT and active = 0; the kernels then see no component of it (scene_ncomp).
 __global__ void k_check_counts(const int *ncomp, int S, int K, int *status, int *active)
@@ -1067,10 +1090,13 @@ static scarlet_batch batch_view(const scarlet_batch *b, int s0, int n, void *ws)
     v.workspace = ws;
     return v;
 }
-static void split_views(const scarlet_batch *b, const WsLayout &l, scarlet_batch v[2], WsLayout lv[2])
+static void split_views(const scarlet_batch *b, const WsLayout &l, scarlet_batch v[2], WsLayout lv[2],
+                        const scarlet_constraints *c, scarlet_constraints cv[2])
 {
     v[0] = batch_view(b, 0, l.n0, ws_at<char>(b, l.half[0]));
     v[1] = batch_view(b, l.n0, b->S - l.n0, ws_at<char>(b, l.half[1]));
+    cv[0] = cons_view(c, 0);
+    cv[1] = cons_view(c, (size_t)l.n0 * b->K);
     for (int h = 0; h < 2; ++h) lv[h] = ws_layout(&v[h], WS_HALF);
 }
 
@@ -1204,7 +1230,8 @@ extern "C" int scarlet_batch_prepare_psf(scarlet_batch *b, void *stream)
     if (rc == SCARLET_OK && l.split && l.psf_lds) {
         scarlet_batch v[2];
         WsLayout lv[2];
-        split_views(b, l, v, lv);
+        scarlet_constraints cv[2];
+        split_views(b, l, v, lv, nullptr, cv);
         for (int h = 0; h < 2 && rc == SCARLET_OK; ++h) rc = prepare_psf_impl(&v[h], lv[h], stream);
     }
     return rc;
@@ -1646,8 +1673,9 @@ extern "C" int scarlet_backward_gradients(scarlet_batch *b, int approximate_L, v
 __global__ void k_zero_int(int *p) { *p = 0; }
 
 // L_comp: the constants each component stepped with (scarlet_prior::L_comp), or NULL: the scene's
+// cons: the components' own switches, or NULL: the batch's.  skip_status: status bits of the scenes a constructor call leaves alone
 static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, int force_it0, void *stream,
-                         const double *L_comp = nullptr)
+                         const double *L_comp = nullptr, const scarlet_constraints *cons = nullptr, int skip_status = 0)
 {
     int rc = ensure_tables();
     if (rc) return rc;
@@ -1664,6 +1692,9 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.group = b->group;
     u.ncomp = b->n_components;
     u.L_comp = L_comp;
+    u.symmetric_c = cons ? cons->symmetric : nullptr; u.monotonic_c = cons ? cons->monotonic : nullptr;
+    u.l0_c = cons ? cons->l0_thresh : nullptr; u.l1_c = cons ? cons->l1_thresh : nullptr;
+    u.skip_status = skip_status;
     if (b->group) {
         // MultiComponentSource: the shared centre of every source first (one wave per scene)
         const int R = b->centroid_P / 2 + 2;
@@ -1801,7 +1832,8 @@ static bool fused_ok(const scarlet_batch *b, int approximate_L)
 }
 // n_iter > 1: that many iterations in ONE launch where the persistent form exists (k_fit2: the headline shape's
 // exact instance); *done receives the number of iterations the launch covers
-static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream, int n_iter, int *done)
+static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream, int n_iter, int *done,
+                        const scarlet_constraints *cons = nullptr)
 {
     if (done) *done = 1;
     int rc = ensure_tables();
@@ -1824,6 +1856,20 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
     // experiment knob: SCARLET_PAD_LDS=<bytes> lowers the number of co-resident workgroups
     const size_t lds = fused_lds_bytes(b) + (size_t)opt(OPT_PAD_LDS);
     hipStream_t st = (hipStream_t)stream;
+    if (cons_any(cons)) {
+        // components with their own switches: the four-wave kernel's per-component instance for every B (wave k reads
+        // component k's four settings in phase 2), never k_iterate2 / k_fit2x
+        FusedArgsPC fp;
+        static_cast<FusedArgs &>(fp) = f;
+        fp.symmetric_c = cons->symmetric; fp.monotonic_c = cons->monotonic; fp.l0_c = cons->l0_thresh; fp.l1_c = cons->l1_thresh;
+        auto kern = b->B <= 6 ? k_iterate<4, 6, FusedArgsPC> : k_iterate<4, SC_BMAX, FusedArgsPC>;
+        if ((rc = allow_lds(kern, lds))) return rc;
+        prof_start(4, st);
+        hipLaunchKernelGGL(kern, dim3(b->S), dim3(SC_BLOCK), lds, st, fp);
+        prof_stop(st);
+        HIP_TRY(hipGetLastError());
+        return SCARLET_OK;
+    }
 #define LAUNCH_ITERATE(KM_, BM_)                                                                       \
     do {                                                                                               \
         rc = allow_lds(k_iterate<KM_, BM_>, lds);                                                      \
@@ -1897,11 +1943,13 @@ __global__ void k_count_active(const int *active, int S, int *out)
     if (threadIdx.x == 0) *out = tot;
 }
 
-extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int approximate_L,
-                           int check_every, void *stream)
+// scarlet_fit / scarlet_fit_constrained (cons NULL or all-NULL: the batch's scalars, the same launches as ever)
+static int fit_impl(scarlet_batch *b, const scarlet_constraints *cons, int max_iter, double e_rel, int approximate_L,
+                    int check_every, void *stream)
 {
     int rc = check_batch(b);
     if (rc) return rc;
+    if (!cons_any(cons)) cons = nullptr;
     if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
     if ((rc = check_counts(b, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1916,7 +1964,8 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
         if (side) {
             scarlet_batch v[2];
             WsLayout lv[2];
-            split_views(b, l, v, lv);
+            scarlet_constraints cv[2];
+            split_views(b, l, v, lv, cons, cv);
             hipStream_t sv[2] = {st, side->st};
             bool forked = false;
             // (an error between fork and join: the caller's stream still gets the second stream's work ordered before
@@ -1935,7 +1984,7 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
                 for (int h = 0; h < 2; ++h) {
                     if ((rc = backward_impl(&v[h], lv[h], approximate_L, 0, sv[h]))) return bail(rc);
                     prof_start(2, sv[h]);
-                    if ((rc = launch_update(&v[h], lv[h], 1, 0, sv[h]))) return bail(rc);
+                    if ((rc = launch_update(&v[h], lv[h], 1, 0, sv[h], nullptr, cons ? &cv[h] : nullptr))) return bail(rc);
                     prof_stop(sv[h]); prof_start(3, sv[h]);
                     if ((rc = launch_converge(&v[h], lv[h], e_rel, sv[h]))) return bail(rc);
                     prof_stop(sv[h]);
@@ -1964,12 +2013,12 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
             // up to the next host check (or the end) in one launch where the persistent kernel applies
             int want = max_iter - i, did = 1;
             if (check_every > 0) { const int to_check = check_every - i % check_every; if (to_check < want) want = to_check; }
-            if ((rc = launch_fused(b, l, e_rel, stream, want, &did))) return rc;
+            if ((rc = launch_fused(b, l, e_rel, stream, want, &did, cons))) return rc;
             i += did - 1; launched += did - 1;
         } else {
             if ((rc = backward_impl(b, l, approximate_L, 0, stream))) return rc;
             prof_start(2, st);
-            if ((rc = launch_update(b, l, 1, 0, stream))) return rc;
+            if ((rc = launch_update(b, l, 1, 0, stream, nullptr, cons))) return rc;
             prof_stop(st); prof_start(3, st);
             if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
             prof_stop(st);
@@ -1984,6 +2033,12 @@ extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int app
         }
     }
     return launched;
+}
+
+extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int approximate_L,
+                           int check_every, void *stream)
+{
+    return fit_impl(b, nullptr, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
 // ---- components with a Prior (prior.h)
@@ -2036,12 +2091,13 @@ extern "C" int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior
 }
 
 // scarlet_fit's loop on the unfused path, one pipeline: gradients, prior step, constraints, convergence test
-extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
-                                 int check_every, void *stream)
+static int fit_prior_impl(scarlet_batch *b, const scarlet_constraints *cons, const scarlet_prior *p, int max_iter, double e_rel,
+                          int approximate_L, int check_every, void *stream)
 {
     int rc = check_batch(b);
     if (!rc) rc = check_prior(p);
     if (rc) return rc;
+    if (!cons_any(cons)) cons = nullptr;
     if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
     if ((rc = check_counts(b, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -2052,7 +2108,7 @@ extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int m
         if ((rc = backward_impl(b, l, approximate_L, 1, stream))) return rc;
         if ((rc = launch_prior_step(b, p, stream))) return rc;
         prof_start(2, st);
-        if ((rc = launch_update(b, l, 1, 0, stream, p->L_comp))) return rc;
+        if ((rc = launch_update(b, l, 1, 0, stream, p->L_comp, cons))) return rc;
         prof_stop(st); prof_start(3, st);
         if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
         prof_stop(st);
@@ -2066,6 +2122,38 @@ extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int m
         }
     }
     return launched;
+}
+
+extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
+                                 int check_every, void *stream)
+{
+    return fit_prior_impl(b, nullptr, p, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+// ---- components with their own constraint switches (scarlet_constraints)
+extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int max_iter,
+                                       double e_rel, int approximate_L, int check_every, void *stream)
+{
+    int rc = check_constraints(b, c);
+    if (rc) return rc;
+    return p ? fit_prior_impl(b, c, p, max_iter, e_rel, approximate_L, check_every, stream)
+             : fit_impl(b, c, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+extern "C" int scarlet_source_update_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p,
+                                                 int in_iteration, void *stream)
+{
+    int rc = check_constraints(b, c);
+    if (!rc) rc = check_batch(b);
+    if (!rc && p) rc = check_prior(p);
+    if (!rc) rc = check_counts(b, stream);
+    if (rc) return rc;
+    // the constructors' call (in_iteration = 0) ignores `active`: a scene the initialisation refused stays untouched
+    // (BAD_COUNT scenes have no present component, scene_ncomp)
+    const bool any = cons_any(c);
+    const int skip = (any && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
+    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream, p ? p->L_comp : nullptr,
+                         any ? c : nullptr, skip);
 }
 
 // ---- several observations per blend (multiobs.h)
@@ -2169,9 +2257,11 @@ static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const Grad
 }
 
 static int fit_observations_impl(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
-                                 int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+                                 int max_iter, double e_rel, int approximate_L, int check_every, void *stream,
+                                 const scarlet_constraints *cons = nullptr)
 {
     int rc;
+    if (!cons_any(cons)) cons = nullptr;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = check_counts(state, stream))) return rc;
     const WsLayout l = ws_layout(state, WS_FIX);
@@ -2229,7 +2319,7 @@ static int fit_observations_impl(scarlet_batch *state, scarlet_batch *const *obs
         hipLaunchKernelGGL(k_obs_head, dim3(m.S), dim3(SC_BLOCK), 0, st, m);
         HIP_TRY(hipGetLastError());
         prof_stop(st); prof_start(2, st);
-        if ((rc = launch_update(state, l, 1, 0, stream))) return rc;
+        if ((rc = launch_update(state, l, 1, 0, stream, nullptr, cons))) return rc;
         prof_stop(st); prof_start(3, st);
         if ((rc = launch_converge(state, l, e_rel, stream))) return rc;
         prof_stop(st);
@@ -2246,8 +2336,9 @@ static int fit_observations_impl(scarlet_batch *state, scarlet_batch *const *obs
     return launched;
 }
 
-extern "C" int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
-                                        int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+static int fit_observations_checked(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
+                                    const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
+                                    int check_every, void *stream)
 {
     (void)hipGetLastError();
     if (!state) return set_err(SCARLET_E_ARG, "null batch");
@@ -2266,7 +2357,22 @@ extern "C" int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *con
         if ((rc = check_batch(ob))) return rc;
     }
     if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
-    return fit_observations_impl(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+    return fit_observations_impl(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, cons);
+}
+
+extern "C" int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                        int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    return fit_observations_checked(state, nullptr, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+extern "C" int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                                    const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                                    int approximate_L, int check_every, void *stream)
+{
+    int rc = check_constraints(state, c);
+    if (rc) return rc;
+    return fit_observations_checked(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
 extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
