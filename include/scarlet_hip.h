@@ -442,11 +442,6 @@ int scarlet_source_update(scarlet_batch *b, int in_iteration, void *stream);
  * iteration: it += 1, cur flips, active cleared for converged scenes                   */
 int scarlet_check_convergence(scarlet_batch *b, double e_rel, void *stream);
 
-/* Per-kernel timing of scarlet_fit with hipEvents recorded on the launch stream (used by
- * bench.py for the roofline line).  begin: allocate events for up to max_iterations
- * iterations and start recording; end: synchronise, return per kernel class
- * {0 k_grad, 1 k_step, 2 k_source_update, 3 k_converge, 4 k_iterate (fused), 5 the PSF convolution chain, 6 k_prior_step, 7 unused}
- * the summed milliseconds and launch counts, and stop recording. */
 /* diagnostics (STAMPS switch on): byte offset inside b->workspace of the convolution kernel's phase stamps
  * ([S][B][32] int64 shader-clock values, written by every k_psf_conv launch), or -1 */
 int64_t scarlet_debug_psf_stamps_offset(const scarlet_batch *b);
@@ -454,6 +449,11 @@ int64_t scarlet_debug_psf_stamps_offset(const scarlet_batch *b);
  * oky, okx, image staged in LDS, exact-shape instance, LDS bytes, 0}; 0, or -1 when the batch takes another path.
  * Host-only: no device call. */
 int scarlet_debug_psf_plan(const scarlet_batch *b, int32_t *out16);
+/* Per-kernel timing of scarlet_fit with hipEvents recorded on the launch stream (used by
+ * bench.py for the roofline line).  begin: allocate events for up to max_iterations
+ * iterations and start recording; end: synchronise, return per kernel class
+ * {0 k_grad, 1 k_step, 2 k_source_update, 3 k_converge, 4 k_iterate (fused), 5 the PSF convolution chain, 6 k_prior_step, 7 unused}
+ * the summed milliseconds and launch counts, and stop recording. */
 int scarlet_profile_begin(int max_iterations);
 int scarlet_profile_end(double total_ms[8], int64_t launches[8]);
 /* the same with both counts: `iterations` = iterations covered by the class's launches (what

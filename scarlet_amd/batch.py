@@ -170,9 +170,9 @@ class BlendBatch(object):
     l0_thresh, l1_thresh : None or sparsity thresholds (update.sparse_l0 / sparse_l1)
         Each of the four is one value for the batch, or one per component (`constraint_arrays`): a (K,) sequence, an
         (S, K) array, or per-scene lists for ragged batches -- as the reference's sources each carry their own
-        symmetric= / monotonic=.  With any of them per component the batch is `constrained` and runs the library's
-        *_constrained entry points; `symmetric` / `monotonic` then read "any component is", `l0_thresh` / `l1_thresh`
-        None.  The layers of one `group` must agree on the switches.  Initialisation switches stay per batch:
+        symmetric= / monotonic=.  With any of them per component the batch is `constrained` (its scarlet_constraints
+        then carries that setting's array); `symmetric` / `monotonic` then read "any component is", `l0_thresh` /
+        `l1_thresh` None.  The layers of one `group` must agree on the switches.  Initialisation switches stay per batch:
         `init_monotonic=None` means "any component is monotonic", and the layers of a group start with the batch's
         `symmetric`; a per-component start option is out of scope.
     centroid_weight : (P, P) float64 centroid PSF; default = reference default
@@ -271,11 +271,9 @@ class BlendBatch(object):
             given[name] = bool(arr.any()) if name in _SWITCHES else None
         self.symmetric, self.monotonic = bool(given["symmetric"]), bool(given["monotonic"])
         self.l0_thresh, self.l1_thresh = given["l0_thresh"], given["l1_thresh"]
-        self._cons = None
-        if self.constraints:
-            self._cons = _lib.ScarletConstraints()
-            for name, x in self.constraints.items():
-                setattr(self._cons, name, x.data_ptr())
+        self._cons = _lib.ScarletConstraints()      # members NULL for the settings given as scalars
+        for name, x in self.constraints.items():
+            setattr(self._cons, name, x.data_ptr())
         cw = default_centroid_weight() if centroid_weight is None else np.asarray(centroid_weight, dtype=np.float64)
         assert cw.ndim == 2 and cw.shape[0] == cw.shape[1] and cw.shape[0] % 2 == 1
         self.centroid_weight = torch.as_tensor(cw).to(**f64).contiguous()
@@ -290,11 +288,30 @@ class BlendBatch(object):
     # ------------------------------------------------------------------ plumbing
     @property
     def constrained(self):
-        """True when a constraint setting was given per component: the batch runs the *_constrained entry points."""
-        return self._cons is not None
+        """True when a constraint setting was given per component."""
+        return bool(self.constraints)
 
-    def _cons_ref(self):
-        return ctypes.byref(self._cons)
+    # Every call into the library's loops goes through these three.  The *_constrained entry points with a NULL member
+    # read that setting from the batch's scalars, and with prior = NULL step without one.
+    def _lib_fit(self, ps, max_iter, e_rel, approximate_L, check_every):
+        return _lib.check(_lib.lib.scarlet_fit_constrained(
+            ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(max_iter),
+            float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
+
+    def _lib_update(self, ps, in_iteration):
+        return _lib.check(_lib.lib.scarlet_source_update_constrained(
+            ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(in_iteration),
+            _lib.stream_ptr()))
+
+    def _lib_fit_observations(self, batches, band0, max_iter, e_rel, approximate_L, check_every):
+        """`batches`: the observations' gradient batches, `band0`: their first model channels."""
+        n = len(batches)
+        ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for ob in batches])
+        band0 = np.array(band0, dtype=np.int32)
+        self._keep = (ptrs, band0)
+        return _lib.check(_lib.lib.scarlet_fit_observations_constrained(
+            ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n, int(max_iter),
+            float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
 
     def _present(self):
         """(S, K) bool device mask of the components each scene uses (all of them without n_components)."""
@@ -546,22 +563,20 @@ class BlendBatch(object):
 
     def update_sources(self):
         """Run the constraint pipeline once with it=0 (what the source constructors do)."""
-        if self.constrained:
-            _lib.check(_lib.lib.scarlet_source_update_constrained(ctypes.byref(self._c), self._cons_ref(), None, 0,
-                                                                  _lib.stream_ptr()))
-            return self
-        _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 0, _lib.stream_ptr()))
+        self._lib_update(None, 0)
         return self
 
     def fit(self, max_iter=200, e_rel=1e-2, approximate_L=False, check_every=10, prior=None):
         """Blend.fit for every scene (reference blend.py:65-102).  Scenes that reach e_rel
         stop iterating individually.  Returns the number of iterations launched.  A batch made by
-        `from_observations` fits all its observations jointly (scarlet_fit_observations).
+        `from_observations` fits all its observations jointly (scarlet_fit_observations_constrained; every other
+        batch runs scarlet_fit_constrained, with or without a prior).
 
         prior : None, or what scarlet_amd.prior describes -- a QuadraticPrior and / or constant given tensors (one
-            call of scarlet_fit_prior), a callable evaluated once per iteration on the current stream (the host looks
-            at `active` only every `check_every` iterations), or a list of these.  `L_components` then holds the
-            constants each component stepped with.  Not available for a batch made by `from_observations`."""
+            call of scarlet_fit_constrained with the prior's struct), a callable evaluated once per iteration on the
+            current stream (the host looks at `active` only every `check_every` iterations), or a list of these.
+            `L_components` then holds the constants each component stepped with.  Not available for a batch made by
+            `from_observations`."""
         if prior is not None and self._observations is not None:
             raise NotImplementedError("a batch of several observations does not take priors")
         self._ensure_mse_capacity(max_iter)
@@ -572,18 +587,12 @@ class BlendBatch(object):
             return self._fit_observations(max_iter, e_rel, approximate_L, check_every)
         if prior is not None:
             return self._fit_prior(prior, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every))
-        if self.constrained:
-            rc = _lib.lib.scarlet_fit_constrained(ctypes.byref(self._c), self._cons_ref(), None, int(max_iter), float(e_rel),
-                                                  int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
-            return _lib.check(rc)
-        rc = _lib.lib.scarlet_fit(ctypes.byref(self._c), int(max_iter), float(e_rel),
-                                  int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
-        return _lib.check(rc)
+        return self._lib_fit(None, max_iter, e_rel, approximate_L, check_every)
 
     def step(self, e_rel=1e-2, approximate_L=False, prior=None):
         """One iteration in three separately callable phases (used by tests and by the
         Python-level update() override path).  A batch made by `from_observations` runs one iteration
-        of scarlet_fit_observations.  `prior`: as in `fit`."""
+        of scarlet_fit_observations_constrained.  `prior`: as in `fit`."""
         if prior is not None and self._observations is not None:
             raise NotImplementedError("a batch of several observations does not take priors")
         self._ensure_mse_capacity(1)
@@ -598,10 +607,7 @@ class BlendBatch(object):
             return
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step(ctypes.byref(self._c), int(bool(approximate_L)), s))
-        if self.constrained:
-            _lib.check(_lib.lib.scarlet_source_update_constrained(ctypes.byref(self._c), self._cons_ref(), None, 1, s))
-        else:
-            _lib.check(_lib.lib.scarlet_source_update(ctypes.byref(self._c), 1, s))
+        self._lib_update(None, 1)
         _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), float(e_rel), s))
 
     # ------------------------------------------------------------------ priors
@@ -649,10 +655,7 @@ class BlendBatch(object):
         self._set_given(ps, dicts)
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step_prior(ctypes.byref(self._c), ctypes.byref(ps), approximate_L, s))
-        if self.constrained:
-            _lib.check(_lib.lib.scarlet_source_update_constrained(ctypes.byref(self._c), self._cons_ref(), ctypes.byref(ps), 1, s))
-        else:
-            _lib.check(_lib.lib.scarlet_source_update_prior(ctypes.byref(self._c), ctypes.byref(ps), 1, s))
+        self._lib_update(ps, 1)
         _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), e_rel, s))
 
     def _fit_prior(self, prior, max_iter, e_rel, approximate_L, check_every):
@@ -661,12 +664,7 @@ class BlendBatch(object):
         if not fns:
             # nothing changes between iterations: the library's own loop
             self._set_given(ps, given)
-            if self.constrained:
-                return _lib.check(_lib.lib.scarlet_fit_constrained(ctypes.byref(self._c), self._cons_ref(), ctypes.byref(ps),
-                                                                   max_iter, e_rel, approximate_L, check_every,
-                                                                   _lib.stream_ptr()))
-            return _lib.check(_lib.lib.scarlet_fit_prior(ctypes.byref(self._c), ctypes.byref(ps), max_iter, e_rel,
-                                                         approximate_L, check_every, _lib.stream_ptr()))
+            return self._lib_fit(ps, max_iter, e_rel, approximate_L, check_every)
         launched = 0
         for i in range(max_iter):
             self._prior_iteration(ps, given, fns, e_rel, approximate_L)
@@ -719,19 +717,8 @@ class BlendBatch(object):
                              "(CombinedExtendedSource), not init_extended / init_sources")
 
     def _fit_observations(self, max_iter, e_rel, approximate_L, check_every):
-        n = len(self._observations)
-        ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
-        band0 = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
-        self._keep = (ptrs, band0)
-        if self.constrained:
-            rc = _lib.lib.scarlet_fit_observations_constrained(
-                ctypes.byref(self._c), self._cons_ref(), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n, int(max_iter),
-                float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
-            return _lib.check(rc)
-        rc = _lib.lib.scarlet_fit_observations(ctypes.byref(self._c), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n,
-                                               int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every),
-                                               _lib.stream_ptr())
-        return _lib.check(rc)
+        return self._lib_fit_observations([ob for _, ob in self._observations], [o.band0 for o, _ in self._observations],
+                                          max_iter, e_rel, approximate_L, check_every)
 
     def init_combined(self, bg_rms, obs_idx=0, obs_psfs=None, model_psf=None, thresh=1.0, init_monotonic=None):
         """CombinedExtendedSource for every component (reference source.py:183-240, 495-536): the SED is the

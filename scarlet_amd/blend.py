@@ -210,17 +210,8 @@ class Blend(ComponentTree):
                 # observation, their sum, L * n_obs, step, constraints and convergence in one device loop
                 b._ensure_mse_capacity(max_iter)
                 b.active.fill_(1)
-                n = len(self._obs_batches)
-                ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for ob, _ in self._obs_batches])
-                band0 = np.array([(sl.start or 0) for _, sl in self._obs_batches], dtype=np.int32)
-                if b.constrained:
-                    _lib.check(_lib.lib.scarlet_fit_observations_constrained(
-                        ctypes.byref(b._c), b._cons_ref(), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n, int(max_iter),
-                        float(e_rel), int(bool(approximate_L)), 4, _lib.stream_ptr()))
-                else:
-                    _lib.check(_lib.lib.scarlet_fit_multi(ctypes.byref(b._c), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n,
-                                                          int(max_iter), float(e_rel), int(bool(approximate_L)), 4,
-                                                          _lib.stream_ptr()))
+                b._lib_fit_observations([ob for ob, _ in self._obs_batches], [sl.start or 0 for _, sl in self._obs_batches],
+                                        max_iter, e_rel, approximate_L, 4)
             b.raise_on_status()
             self._sync_sources()
             return self

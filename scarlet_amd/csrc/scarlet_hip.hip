@@ -757,11 +757,9 @@ extern "C" int scarlet_profile_end(double total_ms[SC_NCLASS], int64_t launches[
     return scarlet_profile_end_ex(total_ms, launches, nullptr);
 }
 
-static int check_batch(const scarlet_batch *b, bool multi = false)
+// shape and limits alone: nothing here reads a pointer of the batch
+static int check_shape(const scarlet_batch *b)
 {
-    // Every entry point ends with a look at hipGetLastError(); that value is per thread and keeps whatever an EARLIER HIP
-    // call of the thread left there.  Start from a clean slate: what is reported is ours.
-    (void)hipGetLastError();
     if (!b) return set_err(SCARLET_E_ARG, "null batch");
     if (b->S <= 0 || b->K <= 0 || b->B <= 0 || b->H <= 0 || b->W <= 0) return set_err(SCARLET_E_ARG, "bad batch shape");
     if (b->K > SCARLET_MAX_COMPONENTS)
@@ -770,8 +768,15 @@ static int check_batch(const scarlet_batch *b, bool multi = false)
         return set_err(SCARLET_E_NOTIMPL, "B > 8 bands is not supported by this build of the gradient kernels");
     if (b->H > SCARLET_MAX_SIDE || b->W > SCARLET_MAX_SIDE)
         return set_err(SCARLET_E_TOO_LARGE, "frames larger than 1024 x 1024 (SCARLET_MAX_SIDE) are not supported");
-    if (multi && b->n_components)
-        return set_err(SCARLET_E_NOTIMPL, "scarlet_fit_multi does not take n_components (ragged batches): pass NULL");
+    return SCARLET_OK;
+}
+static int check_batch(const scarlet_batch *b)
+{
+    // Every entry point ends with a look at hipGetLastError(); that value is per thread and keeps whatever an EARLIER HIP
+    // call of the thread left there.  Start from a clean slate: what is reported is ours.
+    (void)hipGetLastError();
+    const int rc = check_shape(b);
+    if (rc) return rc;
     if (!b->images || !b->sed[0] || !b->sed[1] || !b->morph[0] || !b->morph[1] || !b->cur || !b->centers ||
         !b->shifts || !b->flags || !b->lipschitz || !b->mse || !b->it || !b->active || !b->status || !b->workspace)
         return set_err(SCARLET_E_ARG, "null pointer in batch");
@@ -782,14 +787,29 @@ static int check_batch(const scarlet_batch *b, bool multi = false)
 
 // ---- per-component constraint switches (scarlet_constraints).  Inside the library `c` may be NULL: the batch's scalars.
 static bool cons_any(const scarlet_constraints *c) { return c && (c->symmetric || c->monotonic || c->l0_thresh || c->l1_thresh); }
-// the _constrained entry points: the struct is required, and a symmetric array needs what b->symmetric needs
-static int check_constraints(const scarlet_batch *b, const scarlet_constraints *c)
+static int check_prior(const scarlet_prior *p)
+{
+    if (!p) return set_err(SCARLET_E_ARG, "null prior");
+    if (!p->L_comp) return set_err(SCARLET_E_ARG, "prior: L_comp is NULL (required output)");
+    if (p->quad_sed_target && !p->quad_sed_weight) return set_err(SCARLET_E_ARG, "prior: quad_sed_target without quad_sed_weight");
+    if (p->quad_morph_target && !p->quad_morph_weight)
+        return set_err(SCARLET_E_ARG, "prior: quad_morph_target without quad_morph_weight");
+    return SCARLET_OK;
+}
+// The host-side check of every entry point that steps, updates or fits, before anything is launched.
+// need_c: a _constrained entry point (the struct is required, and a symmetric array needs what b->symmetric needs);
+// need_p: a _prior entry point (`p` is checked whenever it is given);  max_iter: of the loops, 0 elsewhere
+static int check_call(const scarlet_batch *b, bool need_c, const scarlet_constraints *c, bool need_p, const scarlet_prior *p,
+                      int max_iter = 0)
 {
     if (!b) return set_err(SCARLET_E_ARG, "null batch");
-    if (!c) return set_err(SCARLET_E_ARG, "constraints is NULL (pass a scarlet_constraints with NULL members for the batch's scalars)");
-    if (c->symmetric && (!b->centroid_psf || b->centroid_P <= 0 || !(b->centroid_P & 1)))
+    if (need_c && !c) return set_err(SCARLET_E_ARG, "constraints is NULL (pass a scarlet_constraints with NULL members for the batch's scalars)");
+    if (need_c && c->symmetric && (!b->centroid_psf || b->centroid_P <= 0 || !(b->centroid_P & 1)))
         return set_err(SCARLET_E_ARG, "constraints.symmetric needs an odd-sized centroid_psf");
-    return SCARLET_OK;
+    int rc = check_batch(b);
+    if (!rc && (need_p || p)) rc = check_prior(p);
+    if (!rc && max_iter < 0) rc = set_err(SCARLET_E_ARG, "max_iter < 0");
+    return rc;
 }
 // the arrays advanced to component `first` (split_views: a half-batch's first component)
 static scarlet_constraints cons_view(const scarlet_constraints *c, size_t first)
@@ -1656,26 +1676,13 @@ static int backward_impl(scarlet_batch *b, const WsLayout &l, int approximate_L,
     return SCARLET_OK;
 }
 
-extern "C" int scarlet_backward_step(scarlet_batch *b, int approximate_L, void *stream)
-{
-    int rc = check_batch(b);
-    if (!rc) rc = check_counts(b, stream);
-    return rc ? rc : backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 0, stream);
-}
-
-extern "C" int scarlet_backward_gradients(scarlet_batch *b, int approximate_L, void *stream)
-{
-    int rc = check_batch(b);
-    if (!rc) rc = check_counts(b, stream);
-    return rc ? rc : backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 1, stream);
-}
-
 __global__ void k_zero_int(int *p) { *p = 0; }
 
 // L_comp: the constants each component stepped with (scarlet_prior::L_comp), or NULL: the scene's
 // cons: the components' own switches, or NULL: the batch's.  skip_status: status bits of the scenes a constructor call leaves alone
-static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, int force_it0, void *stream,
-                         const double *L_comp = nullptr, const scarlet_constraints *cons = nullptr, int skip_status = 0)
+struct UpdateOpts { const double *L_comp; const scarlet_constraints *cons; int skip_status; };
+// in_iteration = 0: the constructors' call (UpdateArgs::force_it0)
+static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, void *stream, const UpdateOpts &o)
 {
     int rc = ensure_tables();
     if (rc) return rc;
@@ -1686,15 +1693,15 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.centers = b->centers; u.shifts = b->shifts; u.lipschitz = b->lipschitz; u.it = b->it; u.active = b->active;
     u.status = b->status; u.symmetric = b->symmetric; u.monotonic = b->monotonic;
     u.l0_thresh = b->l0_thresh; u.l1_thresh = b->l1_thresh;
-    u.centroid_psf = b->centroid_psf; u.centroid_P = b->centroid_P; u.conv = ws_at<double>(b, l.conv); u.force_it0 = force_it0;
+    u.centroid_psf = b->centroid_psf; u.centroid_P = b->centroid_P; u.conv = ws_at<double>(b, l.conv); u.force_it0 = !in_iteration;
     u.gscratch = nullptr;
     u.only_flagged = nullptr;
     u.group = b->group;
     u.ncomp = b->n_components;
-    u.L_comp = L_comp;
-    u.symmetric_c = cons ? cons->symmetric : nullptr; u.monotonic_c = cons ? cons->monotonic : nullptr;
-    u.l0_c = cons ? cons->l0_thresh : nullptr; u.l1_c = cons ? cons->l1_thresh : nullptr;
-    u.skip_status = skip_status;
+    u.L_comp = o.L_comp;
+    u.symmetric_c = o.cons ? o.cons->symmetric : nullptr; u.monotonic_c = o.cons ? o.cons->monotonic : nullptr;
+    u.l0_c = o.cons ? o.cons->l0_thresh : nullptr; u.l1_c = o.cons ? o.cons->l1_thresh : nullptr;
+    u.skip_status = o.skip_status;
     if (b->group) {
         // MultiComponentSource: the shared centre of every source first (one wave per scene)
         const int R = b->centroid_P / 2 + 2;
@@ -1773,14 +1780,6 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     return SCARLET_OK;
 }
 
-extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *stream)
-{
-    int rc = check_batch(b);
-    if (!rc) rc = check_counts(b, stream);
-    if (rc) return rc;
-    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream);
-}
-
 static int launch_converge(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream)
 {
     hipLaunchKernelGGL(k_converge, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
@@ -1807,7 +1806,8 @@ static int fit2x_resident_workgroups(size_t lds, int *out)
     if (dev < 0 || dev >= 64) return set_err(SCARLET_E_HIP, "device index out of range");
     std::lock_guard<std::mutex> lock(mu);
     if (!cached[dev] || cached_lds[dev] != lds) {
-        int per_cu = 0, cus = 0;
+        int per_cu = 0, cus = 0, rc = allow_lds(k_fit2x, lds);        // (the query counts with the LDS the launch will ask for)
+        if (rc) return rc;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fit2x, SC_FB2, lds));
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         if (per_cu < 1) per_cu = 1;
@@ -1833,7 +1833,7 @@ static bool fused_ok(const scarlet_batch *b, int approximate_L)
 // n_iter > 1: that many iterations in ONE launch where the persistent form exists (k_fit2: the headline shape's
 // exact instance); *done receives the number of iterations the launch covers
 static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream, int n_iter, int *done,
-                        const scarlet_constraints *cons = nullptr)
+                        const scarlet_constraints *cons)
 {
     if (done) *done = 1;
     int rc = ensure_tables();
@@ -1856,41 +1856,29 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
     // experiment knob: SCARLET_PAD_LDS=<bytes> lowers the number of co-resident workgroups
     const size_t lds = fused_lds_bytes(b) + (size_t)opt(OPT_PAD_LDS);
     hipStream_t st = (hipStream_t)stream;
+    // allow the LDS, profile class 4 (weight: the iterations the launch covers), launch
+    auto run = [&](auto kern, int grid, int block, size_t bytes, int weight, const auto &... args) -> int {
+        int r = allow_lds(kern, bytes);
+        if (r) return r;
+        prof_start(4, st, weight);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), bytes, st, args...);
+        prof_stop(st);
+        HIP_TRY(hipGetLastError());
+        return SCARLET_OK;
+    };
     if (cons_any(cons)) {
         // components with their own switches: the four-wave kernel's per-component instance for every B (wave k reads
         // component k's four settings in phase 2), never k_iterate2 / k_fit2x
         FusedArgsPC fp;
         static_cast<FusedArgs &>(fp) = f;
         fp.symmetric_c = cons->symmetric; fp.monotonic_c = cons->monotonic; fp.l0_c = cons->l0_thresh; fp.l1_c = cons->l1_thresh;
-        auto kern = b->B <= 6 ? k_iterate<4, 6, FusedArgsPC> : k_iterate<4, SC_BMAX, FusedArgsPC>;
-        if ((rc = allow_lds(kern, lds))) return rc;
-        prof_start(4, st);
-        hipLaunchKernelGGL(kern, dim3(b->S), dim3(SC_BLOCK), lds, st, fp);
-        prof_stop(st);
-        HIP_TRY(hipGetLastError());
-        return SCARLET_OK;
+        return run(b->B <= 6 ? k_iterate<4, 6, FusedArgsPC> : k_iterate<4, SC_BMAX, FusedArgsPC>, b->S, SC_BLOCK, lds, 1, fp);
     }
-#define LAUNCH_ITERATE(KM_, BM_)                                                                       \
-    do {                                                                                               \
-        rc = allow_lds(k_iterate<KM_, BM_>, lds);                                                      \
-        if (rc) return rc;                                                                             \
-        prof_start(4, st);                                                                             \
-        hipLaunchKernelGGL((k_iterate<KM_, BM_>), dim3(b->S), dim3(SC_BLOCK), lds, st, f);             \
-        prof_stop(st);                                                                                 \
-    } while (0)
     // K <= 4, B <= 5: eight waves per scene, a pair of waves per component (fused2.h; its 128-VGPR
     // budget does not hold a sixth band's accumulators)
     if (b->K <= 4 && b->B <= 5 && !opt(OPT_FUSED_V1)) {
         const size_t lds2 = sizeof(float) * ((size_t)b->K * b->H * tile_stride(b->W) + (size_t)b->K * SC_PAIR_VEC_FLOATS) +
                             (size_t)opt(OPT_PAD_LDS);
-#define LAUNCH_ITERATE2(BM_)                                                                           \
-    do {                                                                                               \
-        rc = allow_lds(k_iterate2<4, BM_>, lds2);                                                      \
-        if (rc) return rc;                                                                             \
-        prof_start(4, st);                                                                             \
-        hipLaunchKernelGGL((k_iterate2<4, BM_>), dim3(b->S), dim3(SC_FB2), lds2, st, f);               \
-        prof_stop(st);                                                                                 \
-    } while (0)
         // the headline shape (BASELINE configs[1]/[3]: 4 sources, 5 bands, 64 x 64, default pipeline) has
         // an instance with every shape and switch folded at compile time
         const bool exact64 = b->K == 4 && b->B == 5 && b->H == 64 && b->W == 64 && !b->weights && b->weight_scalar == 1.0f && b->symmetric &&
@@ -1899,8 +1887,6 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
         const size_t lds2x = sizeof(float) * ((size_t)4 * 64 * SC_XS_STRIDE + (size_t)4 * SC_PAIR_VEC_FLOATS) + (size_t)opt(OPT_PAD_LDS);
         if (n_iter > 0xffffff) n_iter = 0xffffff;
         if (exact64 && (n_iter > 1 || (opt(OPT_PERSIST_DBG) & 2)) && !opt(OPT_NO_PERSIST)) {
-            rc = allow_lds(k_fit2x, lds2x);
-            if (rc) return rc;
             // as many workgroups as the chip keeps resident; the scenes beyond them come from the launch's queue
             // (a counter in the workspace, zeroed on the stream in front of the launch)
             int n_wg = 0;
@@ -1908,26 +1894,13 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
             if (n_wg > b->S || (opt(OPT_PERSIST_DBG) & 4)) n_wg = b->S;            // (4: diagnostic, one workgroup per scene)
             int *queue = ws_at<int>(b, l.fit2x_queue);
             HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), st));
-            prof_start(4, st, n_iter);
-            hipLaunchKernelGGL(k_fit2x, dim3(n_wg), dim3(SC_FB2), lds2x, st, f, n_iter | ((opt(OPT_PERSIST_DBG) & 1) << 30), queue, n_wg);
-            prof_stop(st);
             if (done) *done = n_iter;
-        } else if (exact64) {
-            rc = allow_lds(k_iterate2<4, 5, 64>, lds2x);
-            if (rc) return rc;
-            prof_start(4, st);
-            hipLaunchKernelGGL((k_iterate2<4, 5, 64>), dim3(b->S), dim3(SC_FB2), lds2x, st, f);
-            prof_stop(st);
-        } else
-            LAUNCH_ITERATE2(5);
-#undef LAUNCH_ITERATE2
-        HIP_TRY(hipGetLastError());
-        return SCARLET_OK;
+            return run(k_fit2x, n_wg, SC_FB2, lds2x, n_iter, f, n_iter | ((opt(OPT_PERSIST_DBG) & 1) << 30), queue, n_wg);
+        }
+        if (exact64) return run(k_iterate2<4, 5, 64>, b->S, SC_FB2, lds2x, 1, f);
+        return run(k_iterate2<4, 5>, b->S, SC_FB2, lds2, 1, f);
     }
-    if (b->B <= 6) LAUNCH_ITERATE(4, 6); else LAUNCH_ITERATE(4, SC_BMAX);
-#undef LAUNCH_ITERATE
-    HIP_TRY(hipGetLastError());
-    return SCARLET_OK;
+    return b->B <= 6 ? run(k_iterate<4, 6>, b->S, SC_BLOCK, lds, 1, f) : run(k_iterate<4, SC_BMAX>, b->S, SC_BLOCK, lds, 1, f);
 }
 
 __global__ void k_count_active(const int *active, int S, int *out)
@@ -1943,89 +1916,23 @@ __global__ void k_count_active(const int *active, int S, int *out)
     if (threadIdx.x == 0) *out = tot;
 }
 
-// scarlet_fit / scarlet_fit_constrained (cons NULL or all-NULL: the batch's scalars, the same launches as ever)
-static int fit_impl(scarlet_batch *b, const scarlet_constraints *cons, int max_iter, double e_rel, int approximate_L,
-                    int check_every, void *stream)
+// ---- the iteration driver.  Every fit entry point is fit_loop around a front half -- the fused launch, the general
+// step, the prior step or the observation step -- that ends in iteration_tail (the fused kernels hold theirs).
+// iterate(want, join, &did) runs at least one iteration: `want` is the number up to the next host look or the end (only
+// the persistent k_fit2x launch covers more than one and says so in `did`); `join`: the look or the end comes next,
+// so everything must be ordered on the caller's stream when it returns.  Returns the iterations launched.
+template <typename Iterate>
+static int fit_loop(const scarlet_batch *b, const WsLayout &l, int max_iter, int check_every, hipStream_t st, Iterate iterate)
 {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!cons_any(cons)) cons = nullptr;
-    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
-    if ((rc = check_counts(b, stream))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int launched = 0;
-    const WsLayout l = ws_layout(b, WS_FIX);
-    int *d_count = ws_at<int>(b, l.active_count);
-    const bool fused = fused_ok(b, approximate_L);
-    if (!fused && two_pipelines(l)) {
-        // two half-batches, two streams (see split_views)
-        SideStream *side = nullptr;
-        if ((rc = side_stream(&side))) return rc;
-        if (side) {
-            scarlet_batch v[2];
-            WsLayout lv[2];
-            scarlet_constraints cv[2];
-            split_views(b, l, v, lv, cons, cv);
-            hipStream_t sv[2] = {st, side->st};
-            bool forked = false;
-            // (an error between fork and join: the caller's stream still gets the second stream's work ordered before
-            // anything it enqueues next)
-            auto bail = [&](int code) {
-                if (forked && hipEventRecord(side->ev[1], side->st) == hipSuccess) (void)hipStreamWaitEvent(st, side->ev[1], 0);
-                return code;
-            };
-            for (int i = 0; i < max_iter; ++i) {
-#define HIP_TRY_BAIL(expr) do { if ((expr) != hipSuccess) { set_err(SCARLET_E_HIP, "HIP call failed in the two-pipeline loop: " #expr); return bail(SCARLET_E_HIP); } } while (0)
-                if (!forked) {
-                    HIP_TRY(hipEventRecord(side->ev[0], st));
-                    HIP_TRY_BAIL(hipStreamWaitEvent(side->st, side->ev[0], 0));
-                    forked = true;
-                }
-                for (int h = 0; h < 2; ++h) {
-                    if ((rc = backward_impl(&v[h], lv[h], approximate_L, 0, sv[h]))) return bail(rc);
-                    prof_start(2, sv[h]);
-                    if ((rc = launch_update(&v[h], lv[h], 1, 0, sv[h], nullptr, cons ? &cv[h] : nullptr))) return bail(rc);
-                    prof_stop(sv[h]); prof_start(3, sv[h]);
-                    if ((rc = launch_converge(&v[h], lv[h], e_rel, sv[h]))) return bail(rc);
-                    prof_stop(sv[h]);
-                }
-                ++launched;
-                const bool check = check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter;
-                if (check || i + 1 == max_iter) {
-                    HIP_TRY_BAIL(hipEventRecord(side->ev[1], side->st));
-                    HIP_TRY_BAIL(hipStreamWaitEvent(st, side->ev[1], 0));
-                    forked = false;
-                }
-                if (check) {
-                    int h_count = 0;
-                    hipLaunchKernelGGL(k_count_active, dim3(1), dim3(SC_BLOCK), 0, st, b->active, b->S, d_count);
-                    HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(int), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                    if (h_count == 0) break;
-                }
-            }
-#undef HIP_TRY_BAIL
-            return launched;
-        }
-    }
-    for (int i = 0; i < max_iter; ++i) {
-        if (fused) {
-            // up to the next host check (or the end) in one launch where the persistent kernel applies
-            int want = max_iter - i, did = 1;
-            if (check_every > 0) { const int to_check = check_every - i % check_every; if (to_check < want) want = to_check; }
-            if ((rc = launch_fused(b, l, e_rel, stream, want, &did, cons))) return rc;
-            i += did - 1; launched += did - 1;
-        } else {
-            if ((rc = backward_impl(b, l, approximate_L, 0, stream))) return rc;
-            prof_start(2, st);
-            if ((rc = launch_update(b, l, 1, 0, stream, nullptr, cons))) return rc;
-            prof_stop(st); prof_start(3, st);
-            if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
-            prof_stop(st);
-        }
-        ++launched;
-        if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter) {
-            int h_count = 0;
+    int rc, launched = 0;
+    while (launched < max_iter) {
+        int want = max_iter - launched, did = 1;
+        if (check_every > 0 && check_every - launched % check_every < want) want = check_every - launched % check_every;
+        if ((rc = iterate(want, want == 1, &did))) return rc;
+        launched += did;
+        if (check_every > 0 && launched % check_every == 0 && launched < max_iter) {
+            // the host's look at `active`: every scene converged ends the call
+            int h_count = 0, *d_count = ws_at<int>(b, l.active_count);
             hipLaunchKernelGGL(k_count_active, dim3(1), dim3(SC_BLOCK), 0, st, b->active, b->S, d_count);
             HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(int), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
@@ -2034,23 +1941,20 @@ static int fit_impl(scarlet_batch *b, const scarlet_constraints *cons, int max_i
     }
     return launched;
 }
-
-extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int approximate_L,
-                           int check_every, void *stream)
+// the constraint pipeline and the convergence test of one iteration
+static int iteration_tail(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream, const UpdateOpts &o)
 {
-    return fit_impl(b, nullptr, max_iter, e_rel, approximate_L, check_every, stream);
+    int rc;
+    hipStream_t st = (hipStream_t)stream;
+    prof_start(2, st);
+    if ((rc = launch_update(b, l, 1, stream, o))) return rc;
+    prof_stop(st); prof_start(3, st);
+    if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
+    prof_stop(st);
+    return SCARLET_OK;
 }
 
 // ---- components with a Prior (prior.h)
-static int check_prior(const scarlet_prior *p)
-{
-    if (!p) return set_err(SCARLET_E_ARG, "null prior");
-    if (!p->L_comp) return set_err(SCARLET_E_ARG, "prior: L_comp is NULL (required output)");
-    if (p->quad_sed_target && !p->quad_sed_weight) return set_err(SCARLET_E_ARG, "prior: quad_sed_target without quad_sed_weight");
-    if (p->quad_morph_target && !p->quad_morph_weight)
-        return set_err(SCARLET_E_ARG, "prior: quad_morph_target without quad_morph_weight");
-    return SCARLET_OK;
-}
 // buffer 1-cur holds the raw gradients (backward_impl with raw_gradient = 1): step them in place
 static int launch_prior_step(const scarlet_batch *b, const scarlet_prior *p, void *stream)
 {
@@ -2072,88 +1976,131 @@ static int launch_prior_step(const scarlet_batch *b, const scarlet_prior *p, voi
     return SCARLET_OK;
 }
 
+
+// The bodies of the entry points, each behind check_call.  `p` NULL: no prior; `c` NULL or all-NULL: the batch's scalars.
+// raw_gradient = 1 with a prior: buffer 1-cur receives the gradients, the prior's step turns them into the stepped factors
+static int backward_call(scarlet_batch *b, const scarlet_prior *p, int approximate_L, int raw_gradient, void *stream)
+{
+    int rc = check_counts(b, stream);
+    if (!rc) rc = backward_impl(b, ws_layout(b, WS_FIX), approximate_L, raw_gradient, stream);
+    return rc || !p ? rc : launch_prior_step(b, p, stream);
+}
+extern "C" int scarlet_backward_step(scarlet_batch *b, int approximate_L, void *stream)
+{
+    const int rc = check_call(b, false, nullptr, false, nullptr);
+    return rc ? rc : backward_call(b, nullptr, approximate_L, 0, stream);
+}
+extern "C" int scarlet_backward_gradients(scarlet_batch *b, int approximate_L, void *stream)
+{
+    const int rc = check_call(b, false, nullptr, false, nullptr);
+    return rc ? rc : backward_call(b, nullptr, approximate_L, 1, stream);
+}
 extern "C" int scarlet_backward_step_prior(scarlet_batch *b, const scarlet_prior *p, int approximate_L, void *stream)
 {
-    int rc = check_batch(b);
-    if (!rc) rc = check_prior(p);
-    if (!rc) rc = check_counts(b, stream);
-    if (!rc) rc = backward_impl(b, ws_layout(b, WS_FIX), approximate_L, 1, stream);
-    return rc ? rc : launch_prior_step(b, p, stream);
+    const int rc = check_call(b, false, nullptr, true, p);
+    return rc ? rc : backward_call(b, p, approximate_L, 1, stream);
 }
 
-extern "C" int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior *p, int in_iteration, void *stream)
+static int update_call(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int in_iteration, void *stream)
 {
-    int rc = check_batch(b);
-    if (!rc) rc = check_prior(p);
-    if (!rc) rc = check_counts(b, stream);
-    if (rc) return rc;
-    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream, p->L_comp);
-}
-
-// scarlet_fit's loop on the unfused path, one pipeline: gradients, prior step, constraints, convergence test
-static int fit_prior_impl(scarlet_batch *b, const scarlet_constraints *cons, const scarlet_prior *p, int max_iter, double e_rel,
-                          int approximate_L, int check_every, void *stream)
-{
-    int rc = check_batch(b);
-    if (!rc) rc = check_prior(p);
-    if (rc) return rc;
-    if (!cons_any(cons)) cons = nullptr;
-    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
-    if ((rc = check_counts(b, stream))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const WsLayout l = ws_layout(b, WS_FIX);
-    int *d_count = ws_at<int>(b, l.active_count);
-    int launched = 0;
-    for (int i = 0; i < max_iter; ++i) {
-        if ((rc = backward_impl(b, l, approximate_L, 1, stream))) return rc;
-        if ((rc = launch_prior_step(b, p, stream))) return rc;
-        prof_start(2, st);
-        if ((rc = launch_update(b, l, 1, 0, stream, p->L_comp, cons))) return rc;
-        prof_stop(st); prof_start(3, st);
-        if ((rc = launch_converge(b, l, e_rel, stream))) return rc;
-        prof_stop(st);
-        ++launched;
-        if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter) {
-            int h_count = 0;
-            hipLaunchKernelGGL(k_count_active, dim3(1), dim3(SC_BLOCK), 0, st, b->active, b->S, d_count);
-            HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(int), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (h_count == 0) break;
-        }
-    }
-    return launched;
-}
-
-extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
-                                 int check_every, void *stream)
-{
-    return fit_prior_impl(b, nullptr, p, max_iter, e_rel, approximate_L, check_every, stream);
-}
-
-// ---- components with their own constraint switches (scarlet_constraints)
-extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int max_iter,
-                                       double e_rel, int approximate_L, int check_every, void *stream)
-{
-    int rc = check_constraints(b, c);
-    if (rc) return rc;
-    return p ? fit_prior_impl(b, c, p, max_iter, e_rel, approximate_L, check_every, stream)
-             : fit_impl(b, c, max_iter, e_rel, approximate_L, check_every, stream);
-}
-
-extern "C" int scarlet_source_update_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p,
-                                                 int in_iteration, void *stream)
-{
-    int rc = check_constraints(b, c);
-    if (!rc) rc = check_batch(b);
-    if (!rc && p) rc = check_prior(p);
-    if (!rc) rc = check_counts(b, stream);
+    const int rc = check_counts(b, stream);
     if (rc) return rc;
     // the constructors' call (in_iteration = 0) ignores `active`: a scene the initialisation refused stays untouched
     // (BAD_COUNT scenes have no present component, scene_ncomp)
     const bool any = cons_any(c);
     const int skip = (any && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
-    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, in_iteration ? 0 : 1, stream, p ? p->L_comp : nullptr,
-                         any ? c : nullptr, skip);
+    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, stream, {p ? p->L_comp : nullptr, any ? c : nullptr, skip});
+}
+extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *stream)
+{
+    const int rc = check_call(b, false, nullptr, false, nullptr);
+    return rc ? rc : update_call(b, nullptr, nullptr, in_iteration, stream);
+}
+extern "C" int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior *p, int in_iteration, void *stream)
+{
+    const int rc = check_call(b, false, nullptr, true, p);
+    return rc ? rc : update_call(b, nullptr, p, in_iteration, stream);
+}
+extern "C" int scarlet_source_update_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p,
+                                                 int in_iteration, void *stream)
+{
+    const int rc = check_call(b, true, c, false, p);
+    return rc ? rc : update_call(b, c, p, in_iteration, stream);
+}
+
+// One observation: the fused launch where it applies (never with a prior), two half-batches on two streams where the
+// layout splits the batch (see split_views; never with a prior), the general step otherwise.
+static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const scarlet_prior *p, int max_iter, double e_rel,
+                    int approximate_L, int check_every, void *stream)
+{
+    int rc;
+    if (!cons_any(cons)) cons = nullptr;
+    if ((rc = check_counts(b, stream))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const WsLayout l = ws_layout(b, WS_FIX);
+    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0};
+    if (p)       // gradients, prior step, constraints, convergence test
+        return fit_loop(b, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
+            int r = backward_impl(b, l, approximate_L, 1, stream);
+            if (!r) r = launch_prior_step(b, p, stream);
+            return r ? r : iteration_tail(b, l, e_rel, stream, uo);
+        });
+    if (fused_ok(b, approximate_L))      // up to the next host look in one launch where the persistent kernel applies
+        return fit_loop(b, l, max_iter, check_every, st,
+                        [&](int want, bool, int *did) { return launch_fused(b, l, e_rel, stream, want, did, cons); });
+    SideStream *side = nullptr;
+    if (two_pipelines(l) && (rc = side_stream(&side))) return rc;
+    if (!side)
+        return fit_loop(b, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
+            const int r = backward_impl(b, l, approximate_L, 0, stream);
+            return r ? r : iteration_tail(b, l, e_rel, stream, uo);
+        });
+    scarlet_batch v[2];
+    WsLayout lv[2];
+    scarlet_constraints cv[2];
+    split_views(b, l, v, lv, cons, cv);
+    hipStream_t sv[2] = {st, side->st};
+    bool forked = false;
+    // the second stream's work ordered into the caller's (after an error too: whatever the caller enqueues next waits)
+    auto join_side = [&]() {
+        const bool ok = hipEventRecord(side->ev[1], side->st) == hipSuccess && hipStreamWaitEvent(st, side->ev[1], 0) == hipSuccess;
+        forked = false;
+        return ok;
+    };
+    auto bail = [&](int code) { if (forked) (void)join_side(); return code; };
+    return fit_loop(b, l, max_iter, check_every, st, [&](int, bool join, int *) -> int {
+        int r;
+        if (!forked) {
+            HIP_TRY(hipEventRecord(side->ev[0], st));
+            HIP_TRY(hipStreamWaitEvent(side->st, side->ev[0], 0));
+            forked = true;          // (from here on an error joins)
+        }
+        for (int h = 0; h < 2; ++h) {
+            const UpdateOpts uh = {nullptr, cons ? &cv[h] : nullptr, 0};
+            if ((r = backward_impl(&v[h], lv[h], approximate_L, 0, sv[h])) || (r = iteration_tail(&v[h], lv[h], e_rel, sv[h], uh)))
+                return bail(r);
+        }
+        if (join && !join_side()) return set_err(SCARLET_E_HIP, "HIP call failed in the two-pipeline loop: join");
+        return SCARLET_OK;
+    });
+}
+extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int approximate_L,
+                           int check_every, void *stream)
+{
+    const int rc = check_call(b, false, nullptr, false, nullptr, max_iter);
+    return rc ? rc : fit_call(b, nullptr, nullptr, max_iter, e_rel, approximate_L, check_every, stream);
+}
+extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
+                                 int check_every, void *stream)
+{
+    const int rc = check_call(b, false, nullptr, true, p, max_iter);
+    return rc ? rc : fit_call(b, nullptr, p, max_iter, e_rel, approximate_L, check_every, stream);
+}
+extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int max_iter,
+                                       double e_rel, int approximate_L, int check_every, void *stream)
+{
+    const int rc = check_call(b, true, c, false, p, max_iter);
+    return rc ? rc : fit_call(b, c, p, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
 // ---- several observations per blend (multiobs.h)
@@ -2256,9 +2203,11 @@ static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const Grad
     return SCARLET_OK;
 }
 
-static int fit_observations_impl(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
-                                 int max_iter, double e_rel, int approximate_L, int check_every, void *stream,
-                                 const scarlet_constraints *cons = nullptr)
+// Several observations: one pipeline, every iteration the observation step (the observations' G planes, the contraction
+// over them, L x n_obs, the step) and the tail
+static int fit_observations_call(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
+                                 const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
+                                 int check_every, void *stream)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
@@ -2292,9 +2241,8 @@ static int fit_observations_impl(scarlet_batch *state, scarlet_batch *const *obs
     const size_t lds = obs_contract_lds(state->K);
     if ((rc = allow_lds(contract, lds))) return rc;
     const dim3 grid(m.T, m.S);
-    int *d_count = ws_at<int>(state, l.active_count);
-    int launched = 0;
-    for (int i = 0; i < max_iter; ++i) {
+    const UpdateOpts uo = {nullptr, cons, 0};
+    return fit_loop(state, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
         prof_start(0, st);
         for (int o = 0; o < n_obs; ++o) {
             if (!lo[o].psf) continue;
@@ -2318,78 +2266,63 @@ static int fit_observations_impl(scarlet_batch *state, scarlet_batch *const *obs
         }
         hipLaunchKernelGGL(k_obs_head, dim3(m.S), dim3(SC_BLOCK), 0, st, m);
         HIP_TRY(hipGetLastError());
-        prof_stop(st); prof_start(2, st);
-        if ((rc = launch_update(state, l, 1, 0, stream, nullptr, cons))) return rc;
-        prof_stop(st); prof_start(3, st);
-        if ((rc = launch_converge(state, l, e_rel, stream))) return rc;
         prof_stop(st);
-        ++launched;
-        if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < max_iter) {
-            int h_count = 0;
-            hipLaunchKernelGGL(k_count_active, dim3(1), dim3(SC_BLOCK), 0, st, state->active, state->S, d_count);
-            HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(int), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (h_count == 0) break;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return launched;
+        return iteration_tail(state, l, e_rel, stream, uo);
+    });
 }
 
-static int fit_observations_checked(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
-                                    const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
-                                    int check_every, void *stream)
+// the one check of the observation entry points: the list, the state (check_call), every observation against it
+static int check_observations(const scarlet_batch *state, bool need_c, const scarlet_constraints *c, scarlet_batch *const *obs,
+                              const int32_t *band0, int n_obs, int max_iter)
 {
-    (void)hipGetLastError();
-    if (!state) return set_err(SCARLET_E_ARG, "null batch");
     if (n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
     if (!obs || !band0) return set_err(SCARLET_E_ARG, "null observation list");
-    int rc = check_batch(state);
-    if (rc) return rc;
-    for (int o = 0; o < n_obs; ++o) {
+    int rc = check_call(state, need_c, c, false, nullptr, max_iter);
+    for (int o = 0; !rc && o < n_obs; ++o) {
         const scarlet_batch *ob = obs[o];
         if (!ob) return set_err(SCARLET_E_ARG, "null observation batch");
         if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || ob->B < 1 ||
-            band0[o] < 0 || band0[o] + ob->B > state->B)
+            band0[o] < 0 || band0[o] + ob->B > state->B || ob->mse_capacity < 1)
             return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
         if (ob->n_components)
             return set_err(SCARLET_E_ARG, "an observation batch takes no n_components: the state's counts govern every observation");
-        if ((rc = check_batch(ob))) return rc;
+        rc = check_batch(ob);
     }
-    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
-    return fit_observations_impl(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, cons);
+    return rc;
 }
 
 extern "C" int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
                                         int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
 {
-    return fit_observations_checked(state, nullptr, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+    const int rc = check_observations(state, false, nullptr, obs, band0, n_obs, max_iter);
+    return rc ? rc : fit_observations_call(state, nullptr, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
 extern "C" int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
                                                     const int32_t *band0, int n_obs, int max_iter, double e_rel,
                                                     int approximate_L, int check_every, void *stream)
 {
-    int rc = check_constraints(state, c);
-    if (rc) return rc;
-    return fit_observations_checked(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+    const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
+// scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused
+// right after the shape checks, before any pointer of the batches is looked at
+static int refuse_counts(const scarlet_batch *b)
+{
+    const int rc = check_shape(b);
+    if (!rc && b->n_components)
+        return set_err(SCARLET_E_NOTIMPL, "scarlet_fit_multi does not take n_components (ragged batches): pass NULL");
+    return rc;
+}
 extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
                                  int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
 {
-    int rc = check_batch(state, true);
-    if (rc) return rc;
-    if (!obs || !band0 || n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
-    if (max_iter < 0) return set_err(SCARLET_E_ARG, "max_iter < 0");
-    for (int o = 0; o < n_obs; ++o) {
-        if ((rc = check_batch(obs[o], true))) return rc;
-        const scarlet_batch *ob = obs[o];
-        if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || band0[o] < 0 ||
-            band0[o] + ob->B > state->B || ob->mse_capacity < 1)
-            return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
-    }
-    return fit_observations_impl(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+    int rc = refuse_counts(state);
+    if (obs && n_obs <= SCARLET_MAX_OBSERVATIONS)
+        for (int o = 0; !rc && o < n_obs; ++o)
+            if (obs[o]) rc = refuse_counts(obs[o]);
+    return rc ? rc : scarlet_fit_observations(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
 extern "C" int scarlet_init_combined_sed(scarlet_batch *state, const float *images, int B, int band0,
@@ -2521,7 +2454,7 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     }
     HIP_TRY(hipGetLastError());
-    return run_update ? launch_update(b, ws_layout(b, WS_PEEK), 0, 1, stream) : SCARLET_OK;   // constructor's self.update()
+    return run_update ? launch_update(b, ws_layout(b, WS_PEEK), 0, stream, {}) : SCARLET_OK;   // constructor's self.update()
 }
 
 // ---- scarlet_init_sources (initsrc.h): every stock source type, per-scene noise and PSF peaks
@@ -2570,7 +2503,7 @@ extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *s
     if (spec->run_update) {                          // the constructors' self.update(), on the scenes initialised here
         scarlet_batch c = *b;
         c.n_components = a.ncomp;
-        if ((rc = launch_update(&c, ws_layout(b, WS_PEEK), 0, 1, stream))) {
+        if ((rc = launch_update(&c, ws_layout(b, WS_PEEK), 0, stream, {}))) {
             (void)hipStreamSynchronize(st);
             return rc;
         }
