@@ -97,7 +97,7 @@ const char *scarlet_last_error(void);
  * NO_HYBRID_SWEEP, PAD_LDS, STAMPS, PSF_HIPFFT, NO_BOX, NO_BOX2, NO_PSF3PASS, NO_SIDE_STREAM,
  * NO_GRAM_MFMA, NO_BIGK_FUSED, NO_PIPELINE, NO_PERSIST (one launch per iteration instead of k_fit2x),
  * PERSIST_DBG, NO_PLACE (component k on waves 2k, 2k + 1 of k_fit2x / k_iterate2<4,5,64>, not placed by
- * GEMM cost).  Each starts from the environment variable SCARLET_<NAME>, read once at first use;
+ * GEMM cost), NO_LOWRES_MFMA (the GEMMs of a low-resolution observation as plain FMA chains, bit-identical).  Each starts from the environment variable SCARLET_<NAME>, read once at first use;
  * afterwards only this call changes it.  Returns the previous value (0 / 1) or SCARLET_E_ARG for an
  * unknown name.  None changes results beyond float32 rounding.
  * PSF_HIPFFT and STAMPS decide the layout of a PSF batch's workspace: they are frozen by the first
@@ -422,6 +422,60 @@ int scarlet_source_update_constrained(scarlet_batch *b, const scarlet_constraint
 int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
                                          const int32_t *band0, int n_obs, int max_iter, double e_rel,
                                          int approximate_L, int check_every, void *stream);
+
+/* A LOW-RESOLUTION observation of the model frame (reference LowResObservation, observation.py:242-599): a second data
+ * set with coarser pixels and its own PSFs, fitted jointly with the others.  For frames that are not rotated against
+ * each other the reference's resample-and-convolve operator, restricted to the frequencies its sinc cut keeps, is
+ *     out_c = Re( Vy . ( Dhat_c o (Uy . model_c . Ux^T) ) . Vx^T )        (o: elementwise product)
+ * with five small complex matrices that the caller computes once per geometry (scarlet_amd/resampling.py) and passes as
+ * device float32 (re, im) pairs.  The struct travels beside the observation's scarlet_batch; every pointer is device
+ * memory owned by the caller.
+ * Limit: the four factor matrices, the B band spectra [2][nfy][nfx] and one model plane with its projection stay in
+ * LDS: about 4 (2 nfy H + 2 nfx W + 2 h nfy + 2 w nfx + 2 B nfy nfx + 4 nfy nfx + H (W + 2 nfx)) bytes (rows padded to
+ * odd lengths) against 159 KiB.  With an 11-pixel model PSF and images of half the model's side: a 64 x 64 model frame
+ * (72-point padded plane, nfy = 19, nfx = 37) with 32 x 32 images takes 133 KiB at B = 8 bands; 72 x 72 with 36 x 36
+ * still fits at B = 8 (145 KiB), 76 x 76 up to B = 6, 84 x 84 up to B = 2; beyond: SCARLET_E_NOTIMPL. */
+typedef struct scarlet_lowres {
+    int32_t h, w;               /* the observation's pixel grid: images and weights are [S][B][h][w]                */
+    int32_t nfy, nfx;           /* retained frequencies per axis (rows of uy / ux)                                  */
+    int32_t B;                  /* bands of the observation = of dhat = of its scarlet_batch                        */
+    const float *uy;            /* [nfy][H][2]   model rows    -> frequencies (placement phase included)            */
+    const float *ux;            /* [nfx][W][2]   model columns -> frequencies                                       */
+    const float *vy;            /* [h][nfy][2], or [S][h][nfy][2] when v_per_scene: frequencies -> observed rows    */
+    const float *vx;            /* [w][nfx][2], or [S][w][nfx][2] when v_per_scene                                  */
+    const float *dhat;          /* [B][nfy][nfx][2], or [S][B][nfy][nfx][2] when dhat_per_scene: the difference
+                                   kernels' spectra times (observed pixel / model pixel)^2                          */
+    int32_t v_per_scene;        /* scenes cut at different sub-pixel phases carry their own vy / vx                 */
+    int32_t dhat_per_scene;
+    void *workspace;            /* scarlet_lowres_workspace_bytes() bytes: the gradient planes [S][B][H][W] and the
+                                   per-plane losses [S][B] (float64); scratch of the fit, no need to zero it        */
+} scarlet_lowres;               /* 80 bytes */
+
+/* bytes of `lr->workspace` for this state (S, H, W) and observation batch (B); < 0: an error code */
+int64_t scarlet_lowres_workspace_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr);
+
+/* scarlet_fit_observations_constrained where some observations are low-resolution: `lowres` is an array of n_obs pointers,
+ * NULL = that observation shares the model's grid and is handled exactly as before; with every entry NULL the call IS
+ * scarlet_fit_observations_constrained.  A low-resolution obs[i] has H = lowres[i]->h, W = lowres[i]->w, B = lowres[i]->B,
+ * images and weights [S][B][h][w], the state's S and K, and no diff_kernel (SCARLET_E_ARG).  Per iteration and scene one
+ * workgroup (k_lowres_planes) projects every present component's morphology once, forms the band spectra from the
+ * state's SEDs, renders, takes the weighted residual and its loss (float64 sums) and writes the adjoint as gradient
+ * planes over the model frame; the contraction, both Lipschitz constants (n_obs x the eigenvalues as in the reference:
+ * the operator's norm is not in them), the step, the constraint pipeline and the convergence test are those of
+ * scarlet_fit_observations.  Ragged counts, per-component constraints, fix_sed / fix_morph and approximate_L work as
+ * there.  Shapes, null factor pointers and the LDS limit are checked on the host before any launch. */
+int scarlet_fit_observations_lowres(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                    const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs, int max_iter,
+                                    double e_rel, int approximate_L, int check_every, void *stream);
+
+/* LowResObservation.render and its adjoint for n planes (also what the tests compare with float64): plane p uses the
+ * difference kernel of band[p] (device int32 [n], values in 0 .. lr->B - 1; NULL: band 0) and, with v_per_scene /
+ * dhat_per_scene, the factors of scene[p] (device int32 [n]; NULL: scene 0).  render: model [n][H][W] -> out [n][h][w];
+ * adjoint: resid [n][h][w] -> out [n][H][W].  lr->workspace is not used. */
+int scarlet_lowres_render(const float *model, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                          const int32_t *scene, float *out, void *stream);
+int scarlet_lowres_adjoint(const float *resid, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                           const int32_t *scene, float *out, void *stream);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

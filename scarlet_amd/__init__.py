@@ -10,6 +10,7 @@ from . import psf
 from . import fft
 from . import measurement
 from . import interpolation
+from . import resampling
 from . import update as _update_module
 from .bbox import Box, trim, flux_at_edge
 from .cache import Cache
@@ -20,9 +21,9 @@ from .source import (SourceInitError, get_pixel_sed, get_psf_sed, get_best_fit_s
                      build_detection_coadd, init_extended_source, init_combined_extended_source,
                      init_multicomponent_source, PointSource, CombinedExtendedSource,
                      ExtendedSource, MultiComponentSource, RandomSource)
-from .observation import Frame, Observation
+from .observation import Frame, Observation, LowResObservation
 from .blend import Blend
-from .batch import BlendBatch, ObservationBatch
+from .batch import BlendBatch, ObservationBatch, LowResObservationBatch
 from .prior import QuadraticPrior
 from . import bbox, cache, component, source, observation, blend, batch, synth, distributed, io, prior
 

@@ -96,6 +96,13 @@ class ScarletConstraints(Structure):
     _fields_ = [("symmetric", c_void_p), ("monotonic", c_void_p), ("l0_thresh", c_void_p), ("l1_thresh", c_void_p)]
 
 
+class ScarletLowres(Structure):
+    """struct scarlet_lowres of include/scarlet_hip.h (field order must match)."""
+    _fields_ = [("h", c_int32), ("w", c_int32), ("nfy", c_int32), ("nfx", c_int32), ("B", c_int32),
+                ("uy", c_void_p), ("ux", c_void_p), ("vy", c_void_p), ("vx", c_void_p), ("dhat", c_void_p),
+                ("v_per_scene", c_int32), ("dhat_per_scene", c_int32), ("workspace", c_void_p)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "scarlet_version": (c_char_p, []),
@@ -139,6 +146,11 @@ _SIGNATURES = {
     "scarlet_source_update_constrained": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletPrior), c_int, _P]),
     "scarlet_fit_observations_constrained": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints),
                                                      POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
+    "scarlet_lowres_workspace_bytes": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres)]),
+    "scarlet_fit_observations_lowres": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(POINTER(ScarletBatch)),
+                                                POINTER(POINTER(ScarletLowres)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
+    "scarlet_lowres_render": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P]),
+    "scarlet_lowres_adjoint": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

@@ -157,6 +157,73 @@ class ObservationBatch(object):
         return self
 
 
+class LowResObservationBatch(ObservationBatch):
+    """One LOW-RESOLUTION observation of S scenes for `BlendBatch.from_observations` (reference LowResObservation as one
+    element of Blend(sources, [obs_hr, obs_lr])): images on a coarser pixel grid than the model frame, with their own
+    PSFs, covering the model channels band0 .. band0 + B - 1.
+
+    images : (S, B, h, w) array or tensor
+    geometry : a `LowResObservation` matched to the model frame -- one for every scene -- or a list of S of them (scenes
+        cut at different sub-pixel phases or observed with different PSFs; they must share the model frame, its PSF and
+        the observation's shape).  Only its geometry is read (factor matrices, band count), not its images.
+    weights : None (scalar 1), a Python scalar, or (S, B, h, w)
+
+    Every pixel of the observation must lie inside the model frame (ValueError otherwise); a geometry that was not
+    matched raises ValueError too."""
+
+    def __init__(self, images, band0=0, geometry=None, weights=None):
+        ObservationBatch.__init__(self, images, band0=band0, weights=weights)
+        S, B, h, w = self.shape
+        geoms = list(geometry) if isinstance(geometry, (list, tuple)) else [geometry]
+        if isinstance(geometry, (list, tuple)) and len(geoms) != S:
+            raise ValueError("LowResObservationBatch: %d geometries for S = %d scenes" % (len(geoms), S))
+        for g in geoms:
+            if not hasattr(g, "factors_f32") or getattr(g, "model_shape", None) is None:
+                raise ValueError("LowResObservationBatch: geometry must be a LowResObservation after match(model_frame)")
+            if not g.covers:
+                raise ValueError("LowResObservationBatch: only %s of the observation's %s pixels lie inside the model frame; "
+                                 "every low-resolution pixel must" % (g.lr_shape, tuple(g.frame.shape[1:])))
+        self.per_scene = isinstance(geometry, (list, tuple))
+        self.geometries = geoms
+        self.model_shape = tuple(geoms[0].model_shape)
+        f0 = geoms[0].factors_f32()
+        if f0["dhat"].shape[0] != B or (f0["vy"].shape[0], f0["vx"].shape[0]) != (h, w):
+            raise ValueError("LowResObservationBatch: images are %s, the geometry describes %s"
+                             % (self.shape[1:], (f0["dhat"].shape[0], f0["vy"].shape[0], f0["vx"].shape[0])))
+        fs = [f0] + [g.factors_f32() for g in geoms[1:]]
+        for f in fs[1:]:
+            if tuple(g.model_shape) != self.model_shape or any(f[k].shape != f0[k].shape for k in f0) or \
+                    not (np.array_equal(f["uy"], f0["uy"]) and np.array_equal(f["ux"], f0["ux"])):
+                raise ValueError("LowResObservationBatch: the scenes' geometries must share the model frame, its PSF and "
+                                 "the observation's shape")
+        self.host_factors = dict(uy=f0["uy"], ux=f0["ux"])
+        for k in ("vy", "vx", "dhat"):
+            self.host_factors[k] = np.stack([f[k] for f in fs]) if self.per_scene else f0[k]
+
+    def pixels_of(self, centers):
+        """(..., 2) model-frame centres (torch, integer) -> the observation's pixels under them, truncated as
+        Frame.get_pixel does; scene s uses its own geometry."""
+        import torch
+        t = centers.to(dtype=torch.float64)
+        S = self.shape[0]
+        geoms = self.geometries if self.per_scene else self.geometries * S
+        org = t.new_tensor([g.origin for g in geoms]).view(S, 1, 2)
+        stp = t.new_tensor([g.step for g in geoms]).view(S, 1, 2)
+        return ((t - org) / stp).trunc().to(dtype=centers.dtype)
+
+    def lowres_struct(self, device):
+        """(struct scarlet_lowres without a workspace, the device tensors it points to)"""
+        import torch
+        t = {k: torch.as_tensor(v).to(device).contiguous() for k, v in self.host_factors.items()}
+        lr = _lib.ScarletLowres()
+        lr.h, lr.w, lr.B = self.shape[2], self.shape[3], self.shape[1]
+        lr.nfy, lr.nfx = t["uy"].shape[0], t["ux"].shape[0]
+        for k, v in t.items():
+            setattr(lr, k, v.data_ptr())
+        lr.v_per_scene = lr.dhat_per_scene = int(self.per_scene)
+        return lr, t
+
+
 class BlendBatch(object):
     """S scenes x K components x B bands x H x W pixels, all float32 on one device.
 
@@ -303,12 +370,20 @@ class BlendBatch(object):
             ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(in_iteration),
             _lib.stream_ptr()))
 
-    def _lib_fit_observations(self, batches, band0, max_iter, e_rel, approximate_L, check_every):
-        """`batches`: the observations' gradient batches, `band0`: their first model channels."""
+    def _lib_fit_observations(self, batches, band0, max_iter, e_rel, approximate_L, check_every, lowres=None):
+        """`batches`: the observations' gradient batches, `band0`: their first model channels, `lowres`: None, or per
+        observation None / (scarlet_lowres, ...) for a low-resolution one (scarlet_fit_observations_lowres)."""
         n = len(batches)
         ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for ob in batches])
         band0 = np.array(band0, dtype=np.int32)
         self._keep = (ptrs, band0)
+        if lowres is not None and any(x is not None for x in lowres):
+            lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[ctypes.pointer(x[0]) if x is not None else
+                                                              ctypes.POINTER(_lib.ScarletLowres)() for x in lowres])
+            self._keep += (lows,)
+            return _lib.check(_lib.lib.scarlet_fit_observations_lowres(
+                ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, lows, band0.ctypes.data_as(ctypes.c_void_p), n,
+                int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
         return _lib.check(_lib.lib.scarlet_fit_observations_constrained(
             ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n, int(max_iter),
             float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
@@ -683,10 +758,18 @@ class BlendBatch(object):
         obs = list(observations)
         if not 1 <= len(obs) <= _lib.MAX_OBSERVATIONS:
             raise ValueError("from_observations: 1 to %d observations, not %d" % (_lib.MAX_OBSERVATIONS, len(obs)))
-        if not all(isinstance(o, ObservationBatch) for o in obs):
+        if not all(isinstance(o, ObservationBatch) for o in obs):      # (a LowResObservationBatch is one)
             raise ValueError("from_observations: every observation must be an ObservationBatch")
-        S, _, H, W = obs[0].shape
+        same_grid = [o for o in obs if not isinstance(o, LowResObservationBatch)]
+        S = obs[0].shape[0]
+        H, W = same_grid[0].shape[2:] if same_grid else obs[0].model_shape
         for i, o in enumerate(obs):
+            if isinstance(o, LowResObservationBatch):
+                if o.shape[0] != S or o.model_shape != (H, W):
+                    raise ValueError("from_observations: low-resolution observation %d has %d scenes and was matched to a "
+                                     "%d x %d model frame, the batch has %d scenes of %d x %d"
+                                     % ((i, o.shape[0]) + o.model_shape + (S, H, W)))
+                continue
             if (o.shape[0], o.shape[2], o.shape[3]) != (S, H, W):
                 raise ValueError("from_observations: observation %d has %d scenes of %d x %d, observation 0 %d of %d x %d"
                                  % (i, o.shape[0], o.shape[2], o.shape[3], S, H, W))
@@ -699,17 +782,52 @@ class BlendBatch(object):
         state = cls(None, centers, _frame=(S, C, H, W), **kwargs)
         torch, f32 = state.torch, dict(dtype=state.torch.float32, device=state.device)
         batches = []
-        for o in obs:
-            ob = cls(o.images, state.centers, weights=o.weights, symmetric=False, monotonic=False, mse_capacity=1,
-                     centroid_weight=state.centroid_weight.cpu().numpy(), device=state.device)
+        state._lowres = [None] * len(obs)        # per observation: None, or (scarlet_lowres, what it points to)
+        for i, o in enumerate(obs):
+            low = isinstance(o, LowResObservationBatch)
+            # (a low-resolution batch lives on its own pixel grid: the model-frame centres mean nothing there)
+            ob = cls(o.images, torch.zeros_like(state.centers) if low else state.centers, weights=o.weights, symmetric=False,
+                     monotonic=False, mse_capacity=1, centroid_weight=state.centroid_weight.cpu().numpy(), device=state.device)
             # the fit reads the state's morphologies: the observation's own planes are not used
             ob.morph = [torch.zeros((1,), **f32) for _ in range(2)]
             ob._fill_struct()
-            if o.diff_kernel is not None:
+            if low:
+                lr, keep = o.lowres_struct(state.device)
+                nbytes = _lib.check(_lib.lib.scarlet_lowres_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c),
+                                                                            ctypes.byref(lr)))
+                keep["workspace"] = torch.empty((int(nbytes),), dtype=torch.uint8, device=state.device)
+                lr.workspace = keep["workspace"].data_ptr()
+                state._lowres[i] = (lr, keep)
+            elif o.diff_kernel is not None:
                 ob.set_diff_kernel(o.diff_kernel)
             batches.append((o, ob))
         state._observations = batches
         return state
+
+    def _init_lowres_sed(self, o, ob, peak, mmax):
+        """The SED slice a low-resolution observation contributes to init_combined (get_psf_sed, source.py:41-71): its
+        pixel under every present component's centre (the geometry's map, truncated as Frame.get_pixel does), divided by
+        the observation's PSF peaks and multiplied by the model PSF's max.  Written to both buffers' channels of the
+        scenes init_sources accepted; plain indexing, no kernel."""
+        t = self.torch
+        pix = o.pixels_of(self.centers).long()
+        h, w = o.shape[2:]
+        present = self._present() & ((self.status & _lib.STATUS_BAD_INIT) == 0).view(-1, 1)
+        bad = present & ((pix[..., 0] < 0) | (pix[..., 0] >= h) | (pix[..., 1] < 0) | (pix[..., 1] >= w))
+        if bool(bad.any().item()):
+            s, k = [int(v[0]) for v in t.nonzero(bad, as_tuple=True)]
+            raise ValueError("init_combined: source %d of scene %d lies outside the low-resolution observation" % (k, s))
+        pix = pix.clamp(min=0)
+        py, px = pix[..., 0].clamp(max=h - 1), pix[..., 1].clamp(max=w - 1)
+        sidx = t.arange(self.S, device=self.device).view(-1, 1).expand(self.S, self.K)
+        sed = ob.images[sidx, :, py, px]                                  # (S, K, B)
+        if peak is not None:
+            sed = sed / (peak.view(self.S, 1, o.B) if peak.ndim == 2 else peak.view(1, 1, o.B))
+        if mmax is not None:
+            sed = sed * mmax
+        for b in range(2):
+            dst = self.sed[b][:, :, o.band0:o.band0 + o.B]
+            dst.copy_(t.where(present.view(self.S, self.K, 1), sed.to(dst.dtype), dst))
 
     def _refuse_single_init(self):
         if self._observations is not None:
@@ -718,7 +836,7 @@ class BlendBatch(object):
 
     def _fit_observations(self, max_iter, e_rel, approximate_L, check_every):
         return self._lib_fit_observations([ob for _, ob in self._observations], [o.band0 for o, _ in self._observations],
-                                          max_iter, e_rel, approximate_L, check_every)
+                                          max_iter, e_rel, approximate_L, check_every, lowres=getattr(self, "_lowres", None))
 
     def init_combined(self, bg_rms, obs_idx=0, obs_psfs=None, model_psf=None, thresh=1.0, init_monotonic=None):
         """CombinedExtendedSource for every component (reference source.py:183-240, 495-536): the SED is the
@@ -746,6 +864,9 @@ class BlendBatch(object):
         if not 0 <= int(obs_idx) < n:
             raise ValueError("init_combined: obs_idx = %d, there are %d observations" % (obs_idx, n))
         obs_idx = int(obs_idx)
+        if isinstance(obs[obs_idx][0], LowResObservationBatch):
+            raise ValueError("init_combined: obs_idx = %d names a low-resolution observation; the morphology starts from "
+                             "an observation on the model's pixel grid" % obs_idx)
         if len(bg_rms) != n:
             raise ValueError("init_combined: one bg_rms per observation (%d), not %d" % (n, len(bg_rms)))
         if obs_psfs is not None and len(obs_psfs) != n:
@@ -760,7 +881,7 @@ class BlendBatch(object):
         peaks = []
         for i, (o, _) in enumerate(obs):
             bg = np.shape(bg_rms[i])
-            if tuple(bg) not in ((o.B,), (self.S, o.B)):
+            if tuple(bg) not in ((o.B,), (self.S, o.B)) and not (isinstance(o, LowResObservationBatch) and bg_rms[i] is None):
                 raise ValueError("init_combined: bg_rms[%d] must be (%d,) or (%d, %d), not %s" % (i, o.B, self.S, o.B, tuple(bg)))
             p = None if obs_psfs is None else obs_psfs[i]
             if p is not None:
@@ -794,6 +915,9 @@ class BlendBatch(object):
             ob._fill_struct()
         for i, (o, ob) in enumerate(obs):
             p = peaks[i]
+            if isinstance(o, LowResObservationBatch):
+                self._init_lowres_sed(o, ob, p, mmax)
+                continue
             _lib.check(_lib.lib.scarlet_init_combined_sed(
                 ctypes.byref(self._c), ob.images.data_ptr(), int(o.B), int(o.band0), None if p is None else p.data_ptr(),
                 int(p is not None and p.ndim == 2), None if mmax is None else mmax.data_ptr(), _lib.stream_ptr()))

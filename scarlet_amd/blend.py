@@ -78,7 +78,9 @@ class Blend(ComponentTree):
             return self._batch
         torch = _lib.require_gpu()
         from .batch import BlendBatch
-        multi = len(self.observations) != 1 or self.observations[0]._band_slice != slice(None)
+        from .observation import LowResObservation as _Low
+        multi = len(self.observations) != 1 or self.observations[0]._band_slice != slice(None) or \
+            isinstance(self.observations[0], _Low)
         obs = self.observations[0]
         comps = self.components
         from .source import MultiComponentSource
@@ -109,9 +111,13 @@ class Blend(ComponentTree):
         sym = sym[0] if len(set(sym)) == 1 else [sym]
         mono = mono[0] if len(set(mono)) == 1 else [mono]
 
+        from .observation import LowResObservation
+
         def obs_batch(o, images=None, state=True):
+            low = images is None and isinstance(o, LowResObservation)
             ob = BlendBatch(o._images_device()[None] if images is None else images,
-                            np.array(centers, dtype=np.int32)[None],
+                            # (a low-resolution batch lives on its own pixel grid: the model-frame centres mean nothing there)
+                            np.zeros((1, len(centers), 2), dtype=np.int32) if low else np.array(centers, dtype=np.int32)[None],
                             weights=None if (images is not None or o._weights_device() is None) else o._weights_device()[None],
                             symmetric=sym if state else bool(np.any(sym)),
                             monotonic=mono if state else bool(np.any(mono)),
@@ -121,11 +127,23 @@ class Blend(ComponentTree):
                 if type(o.weights) is not np.ndarray and o.weights != 1:
                     ob.weight_scalar = float(o.weights)
                     ob._fill_struct()
-                if o._diff_kernels is not None:
+                if o._diff_kernels is not None and not low:
                     ob.set_diff_kernel(np.asarray(o._diff_kernels.image, dtype=np.float32))
             return ob
 
-        self._obs_batches = None
+        def lowres_of(o, ob, state):
+            """None for an observation on the model's grid; (scarlet_lowres with its workspace, what it points to) for a
+            LowResObservation, which goes through LowResObservationBatch's checks as a batch of one scene"""
+            if not isinstance(o, LowResObservation):
+                return None
+            from .batch import LowResObservationBatch
+            lr, keep = LowResObservationBatch(o.images[None], band0=o._band_slice.start or 0, geometry=o).lowres_struct(state.device)
+            nbytes = _lib.check(_lib.lib.scarlet_lowres_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c), ctypes.byref(lr)))
+            keep["workspace"] = torch.empty((int(nbytes),), dtype=torch.uint8, device=state.device)
+            lr.workspace = keep["workspace"].data_ptr()
+            return lr, keep
+
+        self._obs_batches, self._lowres = None, None
         if multi:
             # several observations and / or band slices (reference blend.py:120-139, 219-220): the state
             # (factors, centres, flags, convergence) lives in a batch over the model frame's channels,
@@ -133,6 +151,7 @@ class Blend(ComponentTree):
             C, Ny, Nx = self.frame.shape
             b = obs_batch(obs, images=torch.zeros((1, C, Ny, Nx), dtype=torch.float32, device="cuda"))
             self._obs_batches = [(obs_batch(o, state=False), o._band_slice) for o in self.observations]
+            self._lowres = [lowres_of(o, ob, b) for o, (ob, _) in zip(self.observations, self._obs_batches)]
         else:
             b = obs_batch(obs)
         sed = torch.stack([c._own_sed for c in comps])[None]
@@ -211,11 +230,13 @@ class Blend(ComponentTree):
                 b._ensure_mse_capacity(max_iter)
                 b.active.fill_(1)
                 b._lib_fit_observations([ob for ob, _ in self._obs_batches], [sl.start or 0 for _, sl in self._obs_batches],
-                                        max_iter, e_rel, approximate_L, 4)
+                                        max_iter, e_rel, approximate_L, 4, lowres=self._lowres)
             b.raise_on_status()
             self._sync_sources()
             return self
         # Python pipeline: device gradient step, Python update() per source, device check
+        if self._lowres is not None and any(x is not None for x in self._lowres):
+            raise NotImplementedError("a LowResObservation needs the built-in update() of every source (the fit stays on the device)")
         s = _lib.stream_ptr
         b._ensure_mse_capacity(max_iter)
         b.active.fill_(1)

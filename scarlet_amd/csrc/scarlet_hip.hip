@@ -27,6 +27,7 @@
 #include "extras.h"
 #include "initsrc.h"
 #include "multiobs.h"
+#include "lowres.h"
 #include "prior.h"
 
 __constant__ unsigned short sc_nfl_table[SC_NFL_MAX];
@@ -53,10 +54,10 @@ extern "C" const char *scarlet_version(void) { return "scarlet_amd-hip 0.2 (gfx9
 // environment (SCARLET_<NAME>) at first use and changed afterwards only through scarlet_set_option.
 // None of them changes results beyond float32 rounding.
 enum { OPT_NO_EXACT = 0, OPT_NO_KSCACHE, OPT_FUSED_V1, OPT_NO_FUSED, OPT_FORCE_BLOCK_UPDATE, OPT_NO_HYBRID_SWEEP,
-       OPT_PAD_LDS, OPT_STAMPS, OPT_PSF_HIPFFT, OPT_NO_BOX, OPT_NO_BOX2, OPT_NO_PSF3PASS, OPT_NO_SIDE_STREAM, OPT_NO_GRAM_MFMA, OPT_NO_BIGK_FUSED, OPT_NO_PIPELINE, OPT_NO_PERSIST, OPT_PERSIST_DBG, OPT_FORCE_HUGEK, OPT_NO_PLACE, OPT_COUNT };
+       OPT_PAD_LDS, OPT_STAMPS, OPT_PSF_HIPFFT, OPT_NO_BOX, OPT_NO_BOX2, OPT_NO_PSF3PASS, OPT_NO_SIDE_STREAM, OPT_NO_GRAM_MFMA, OPT_NO_BIGK_FUSED, OPT_NO_PIPELINE, OPT_NO_PERSIST, OPT_PERSIST_DBG, OPT_FORCE_HUGEK, OPT_NO_PLACE, OPT_NO_LOWRES_MFMA, OPT_COUNT };
 static const char *const g_opt_names[OPT_COUNT] = {"NO_EXACT", "NO_KSCACHE", "FUSED_V1", "NO_FUSED", "FORCE_BLOCK_UPDATE",
                                                    "NO_HYBRID_SWEEP", "PAD_LDS", "STAMPS", "PSF_HIPFFT", "NO_BOX", "NO_BOX2",
-                                                   "NO_PSF3PASS", "NO_SIDE_STREAM", "NO_GRAM_MFMA", "NO_BIGK_FUSED", "NO_PIPELINE", "NO_PERSIST", "PERSIST_DBG", "FORCE_HUGEK", "NO_PLACE"};
+                                                   "NO_PSF3PASS", "NO_SIDE_STREAM", "NO_GRAM_MFMA", "NO_BIGK_FUSED", "NO_PIPELINE", "NO_PERSIST", "PERSIST_DBG", "FORCE_HUGEK", "NO_PLACE", "NO_LOWRES_MFMA"};
 static std::atomic<int> g_opt[OPT_COUNT];
 static std::once_flag g_opt_once;
 static void options_init(void)
@@ -2103,6 +2104,87 @@ extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constrain
     return rc ? rc : fit_call(b, c, p, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
+// ---- a low-resolution observation (lowres.h): the shapes, the workspace and the host checks
+static LowresDims lowres_dims(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr)
+{
+    LowresDims d;
+    d.H = state->H; d.W = state->W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = ob->B;
+    return d;
+}
+static LowresFactors lowres_factors(const scarlet_lowres *lr)
+{
+    LowresFactors f;
+    f.uy = (const float2 *)lr->uy; f.ux = (const float2 *)lr->ux; f.vy = (const float2 *)lr->vy; f.vx = (const float2 *)lr->vx;
+    f.dhat = (const float2 *)lr->dhat; f.v_per_scene = lr->v_per_scene; f.dhat_per_scene = lr->dhat_per_scene;
+    return f;
+}
+// the G planes [S][B][H][W] come first, the per-plane losses [S][B] (float64) after them, 16-byte aligned
+static int64_t lowres_loss_offset(const scarlet_batch *state, const scarlet_batch *ob)
+{
+    const int64_t g = (int64_t)state->S * ob->B * state->H * state->W * (int64_t)sizeof(float);
+    return (g + 15) & ~(int64_t)15;
+}
+// shapes, pointers and limits of one scarlet_lowres for a model frame of H x W and B bands; no device call
+static int check_lowres(const scarlet_lowres *lr, int H, int W, int B, bool need_workspace)
+{
+    if (!lr) return set_err(SCARLET_E_ARG, "null scarlet_lowres");
+    if (lr->h < 1 || lr->w < 1 || lr->nfy < 1 || lr->nfx < 1 || H < 1 || W < 1 || B < 1 || lr->B != B)
+        return set_err(SCARLET_E_ARG, "scarlet_lowres: bad shape");
+    if (!lr->uy || !lr->ux || !lr->vy || !lr->vx || !lr->dhat)
+        return set_err(SCARLET_E_ARG, "scarlet_lowres: null factor matrix");
+    if (need_workspace && !lr->workspace) return set_err(SCARLET_E_ARG, "scarlet_lowres: null workspace");
+    if (B > SC_BMAX) return set_err(SCARLET_E_NOTIMPL, "B > 8 bands is not supported by this build of the gradient kernels");
+    if (H > SCARLET_MAX_SIDE || W > SCARLET_MAX_SIDE || lr->h > SCARLET_MAX_SIDE || lr->w > SCARLET_MAX_SIDE ||
+        lr->nfy > SCARLET_MAX_SIDE || lr->nfx > 2 * SCARLET_MAX_SIDE)
+        return set_err(SCARLET_E_NOTIMPL, "scarlet_lowres: the factor matrices and one model plane do not fit LDS");
+    LowresDims d;
+    d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = B;
+    if (lowres_lds_bytes(d) > LDS_LIMIT)
+        return set_err(SCARLET_E_NOTIMPL, "scarlet_lowres: the factor matrices and one model plane do not fit LDS");
+    return SCARLET_OK;
+}
+
+extern "C" int64_t scarlet_lowres_workspace_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr)
+{
+    if (check_shape(state) || check_shape(obs)) return SCARLET_E_ARG;
+    if (int rc = check_lowres(lr, state->H, state->W, obs->B, false)) return rc;
+    return lowres_loss_offset(state, obs) + (int64_t)state->S * obs->B * (int64_t)sizeof(double);
+}
+
+static int lowres_op(bool adjoint, const float *in, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                     const int32_t *scene, float *out, void *stream)
+{
+    (void)hipGetLastError();
+    if (n < 0) return set_err(SCARLET_E_ARG, "n < 0");
+    if (int rc = check_lowres(lr, H, W, lr ? lr->B : 0, false)) return rc;
+    if (!in || !out) return set_err(SCARLET_E_ARG, "null plane pointer");
+    if (n == 0) return SCARLET_OK;
+    LowresOpArgs a = {};
+    a.d.H = H; a.d.W = W; a.d.h = lr->h; a.d.w = lr->w; a.d.nfy = lr->nfy; a.d.nfx = lr->nfx; a.d.B = lr->B;
+    a.f = lowres_factors(lr); a.in = in; a.out = out; a.band = band; a.scene = scene; a.mfma = !opt(OPT_NO_LOWRES_MFMA);
+    const size_t lds = lowres_lds_bytes(a.d);
+    int rc;
+    if (adjoint) {
+        if ((rc = allow_lds(k_lowres_adjoint, lds))) return rc;
+        hipLaunchKernelGGL(k_lowres_adjoint, dim3(n), dim3(SC_BLOCK), lds, (hipStream_t)stream, a);
+    } else {
+        if ((rc = allow_lds(k_lowres_render, lds))) return rc;
+        hipLaunchKernelGGL(k_lowres_render, dim3(n), dim3(SC_BLOCK), lds, (hipStream_t)stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+extern "C" int scarlet_lowres_render(const float *model, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                                     const int32_t *scene, float *out, void *stream)
+{
+    return lowres_op(false, model, n, H, W, lr, band, scene, out, stream);
+}
+extern "C" int scarlet_lowres_adjoint(const float *resid, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                                      const int32_t *scene, float *out, void *stream)
+{
+    return lowres_op(true, resid, n, H, W, lr, band, scene, out, stream);
+}
+
 // ---- several observations per blend (multiobs.h)
 // G planes of an observation with a PSF: model planes from the STATE's morphologies and the observation's band slice
 // of the SEDs (its own buffer sed[0], filled by k_obs_slice), then the convolution chain of backward_step_psf up to the
@@ -2207,7 +2289,7 @@ static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const Grad
 // over them, L x n_obs, the step) and the tail
 static int fit_observations_call(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
                                  const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
-                                 int check_every, void *stream)
+                                 int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
@@ -2232,6 +2314,26 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         v.B = ob->B; v.band0 = band0[o];
         if (ob->diff_kernel && !lo[o].psf) return set_err(SCARLET_E_ARG, "diff_kernel without psf_h, psf_w");
     }
+    // low-resolution observations (lowres.h): their G planes and per-plane losses lie in the scarlet_lowres workspace
+    LowresArgs la[SC_MAX_OBS] = {};
+    size_t la_lds[SC_MAX_OBS] = {};
+    for (int o = 0; o < n_obs; ++o) {
+        const scarlet_lowres *lr = lowres ? lowres[o] : nullptr;
+        if (!lr) continue;
+        LowresArgs &a = la[o];
+        a.d = lowres_dims(state, obs[o], lr); a.f = lowres_factors(lr);
+        a.S = state->S; a.K = state->K; a.C = state->B; a.band0 = band0[o];
+        a.sed[0] = state->sed[0]; a.sed[1] = state->sed[1]; a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
+        a.cur = state->cur; a.active = state->active; a.ncomp = state->n_components;
+        a.images = obs[o]->images; a.weights = obs[o]->weights; a.weight_scalar = obs[o]->weight_scalar;
+        a.G = (float *)lr->workspace;
+        a.loss_part = (double *)((char *)lr->workspace + lowres_loss_offset(state, obs[o]));
+        a.mfma = !opt(OPT_NO_LOWRES_MFMA);
+        la_lds[o] = lowres_lds_bytes(a.d);
+        if ((rc = allow_lds(k_lowres_planes, la_lds[o]))) return rc;
+        ObsView &v = m.obs[o];
+        v.G = a.G; v.loss_part = a.loss_part; v.Fy = state->H; v.Fx = state->W; v.oy = v.ox = 0;
+    }
     // the state's gradient arguments: its partials (engine.h layout over the C channels) feed the Gram / lambda_max code
     const GradArgs ga = grad_args(state, l, approximate_L, 0);
     // K <= 8: the contraction also sums the Gram matrix (no Gram pass); its lambda_max is found in k_obs_head
@@ -2245,6 +2347,10 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
     return fit_loop(state, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
         prof_start(0, st);
         for (int o = 0; o < n_obs; ++o) {
+            if (lowres && lowres[o]) {
+                hipLaunchKernelGGL(k_lowres_planes, dim3(m.S), dim3(SC_BLOCK), la_lds[o], st, la[o]);
+                continue;
+            }
             if (!lo[o].psf) continue;
             hipLaunchKernelGGL(k_obs_slice, dim3(m.S), dim3(SC_BLOCK), 0, st, m, band0[o], obs[o]->B, obs[o]->sed[0]);
             if ((rc = obs_psf_planes(obs[o], lo[o], state, st, &m.obs[o]))) return rc;
@@ -2273,7 +2379,7 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
 
 // the one check of the observation entry points: the list, the state (check_call), every observation against it
 static int check_observations(const scarlet_batch *state, bool need_c, const scarlet_constraints *c, scarlet_batch *const *obs,
-                              const int32_t *band0, int n_obs, int max_iter)
+                              const int32_t *band0, int n_obs, int max_iter, const scarlet_lowres *const *lowres = nullptr)
 {
     if (n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
     if (!obs || !band0) return set_err(SCARLET_E_ARG, "null observation list");
@@ -2281,6 +2387,19 @@ static int check_observations(const scarlet_batch *state, bool need_c, const sca
     for (int o = 0; !rc && o < n_obs; ++o) {
         const scarlet_batch *ob = obs[o];
         if (!ob) return set_err(SCARLET_E_ARG, "null observation batch");
+        const scarlet_lowres *lr = lowres ? lowres[o] : nullptr;
+        if (lr) {
+            // a low-resolution observation: its batch has the observation's own h x w and no difference kernel
+            if (ob->S != state->S || ob->K != state->K || ob->H != lr->h || ob->W != lr->w || ob->B < 1 || band0[o] < 0 ||
+                band0[o] + ob->B > state->B || ob->mse_capacity < 1)
+                return set_err(SCARLET_E_ARG, "a low-resolution observation does not fit the model frame or its scarlet_lowres");
+            if (ob->diff_kernel)
+                return set_err(SCARLET_E_ARG, "a low-resolution observation takes no diff_kernel: its PSFs are in dhat");
+            if (ob->n_components)
+                return set_err(SCARLET_E_ARG, "an observation batch takes no n_components: the state's counts govern every observation");
+            if ((rc = check_lowres(lr, state->H, state->W, ob->B, true)) || (rc = check_batch(ob))) return rc;
+            continue;
+        }
         if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || ob->B < 1 ||
             band0[o] < 0 || band0[o] + ob->B > state->B || ob->mse_capacity < 1)
             return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
@@ -2304,6 +2423,15 @@ extern "C" int scarlet_fit_observations_constrained(scarlet_batch *state, const 
 {
     const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter);
     return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+extern "C" int scarlet_fit_observations_lowres(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                               const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                               int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
+    const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter, lowres);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, lowres);
 }
 
 // scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused

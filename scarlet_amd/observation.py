@@ -1,4 +1,4 @@
-"""Frame and Observation (reference ``scarlet/observation.py:13-239`` API).
+"""Frame, Observation and LowResObservation (reference ``scarlet/observation.py`` API).
 
 `Frame` describes the model (shape, PSF, channels, dtype); `Observation` holds the data
 (images, weights, PSFs) and, after ``match(model_frame)``, the band slice and the PSF
@@ -7,6 +7,7 @@ the engine computes in float32: a float64 DATA frame is cast to the model frame'
 (as in the reference), a float64 MODEL frame is accepted with one warning -- the factors are stored in float32
 (component._require_float32_frame; a strict opt-in refuses it).
 """
+import ctypes
 import logging
 
 import numpy as np
@@ -147,6 +148,142 @@ class Observation(object):
         m = m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m)).cuda()
         w = self._weights_device()
         d = m.to(torch.float32) - self._images_device()
+        if w is not None:
+            d = w * d
+        elif self.weights != 1:
+            d = float(self.weights) * d
+        return 0.5 * (d.double() ** 2).sum()
+
+
+class LowResObservation(Observation):
+    """A data set with coarser pixels than the model frame and its own PSFs, fitted jointly with the others
+    (reference observation.py:242-599): ``Blend(sources, [obs_hr, obs_lr])``.
+
+    images : (B, h, w);  wcs : required, any object `scarlet_amd.resampling` can read (astropy's WCS, or
+    `resampling.AffineWCS`);  psfs : required, (B, p, p) on the observation's own pixel grid
+    operator : 'exact', 'bilinear' or 'SVD' -- accepted and ignored, as in the reference
+
+    Scope: frames that are not rotated against each other (a rotated pair raises NotImplementedError in `match`); pixel
+    ratios need not be integers and the grids may be offset by fractions of a pixel.  The batch classes further need
+    every low-resolution pixel inside the model frame (`covers`).
+    """
+
+    def __init__(self, images, wcs=None, psfs=None, weights=None, channels=None, padding=3, operator='exact'):
+        assert wcs is not None, "WCS is necessary for LowResObservation"
+        assert psfs is not None, "PSFs are necessary for LowResObservation"
+        assert operator in ['exact', 'bilinear', 'SVD']
+        Observation.__init__(self, images, psfs=psfs, weights=weights, wcs=wcs, channels=channels, padding=padding)
+        self._factors = None
+
+    def match(self, model_frame):
+        """Dtype and band slice as `Observation.match`; then the geometry (reference observation.py:405-521): the
+        overlap of the two grids, the PSFs matched at the model's resolution and their difference kernels, and from them
+        the five factor matrices of the operator (`resampling.lowres_factors`).
+
+        Sets ``lr_shape`` (the rows and columns of the observation that lie inside the model frame), ``covers`` (they
+        are all of them), ``_band_slice``, ``origin`` / ``step`` (the model-frame position of pixel (0, 0) and the pixel
+        ratio per axis) and ``factors`` (complex128; `factors_f32` and the device tensors derive from it)."""
+        from . import resampling as rs
+        if self.frame.dtype != model_frame.dtype:
+            msg = "Dtypes of model and observation different. Casting observation to {}"
+            logger.warning(msg.format(model_frame.dtype))
+            self.frame.dtype = model_frame.dtype
+            self.images = self.images.astype(model_frame.dtype)
+            if type(self.weights) is np.ndarray:
+                self.weights = self.weights.astype(model_frame.dtype)
+            self.frame.psfs.update_dtype(model_frame.dtype)
+        self._band_slice = slice(None)
+        if self.frame.channels is not model_frame.channels:
+            assert self.frame.channels is not None and model_frame.channels is not None
+            bmin = list(model_frame.channels).index(self.frame.channels[0])
+            bmax = list(model_frame.channels).index(self.frame.channels[-1])
+            self._band_slice = slice(bmin, bmax + 1)
+        assert model_frame.wcs is not None and model_frame.psfs is not None, "the model frame needs a WCS and a PSF"
+        a_obs, a_model = rs.affine(self.frame.wcs), rs.affine(model_frame.wcs)
+        self.sin_rot, self.cos_rot, self.isrot = rs.rotation(a_obs, a_model)
+        if self.isrot:
+            raise NotImplementedError("LowResObservation: frames rotated against each other are not supported (the "
+                                      "operator does not separate per axis)")
+        self.sin_rot, self.cos_rot = 0, 1
+        H, W = model_frame.Ny, model_frame.Nx
+        h, w = self.frame.Ny, self.frame.Nx
+        m = rs.match_patches((H, W), (h, w), model_frame.wcs, self.frame.wcs)
+        (iy, ix), (y_at, x_at) = m["lr_in"], m["lr_at"]
+        self._coord_lr, self._coord_hr = (iy, ix), (y_at, x_at)
+        self.lr_shape = (int(iy.max() - iy.min() + 1), int(ix.max() - ix.min() + 1))
+        self.covers = self.lr_shape == (h, w)
+        self.small_axis = w <= h
+        self.model_shape = (H, W)
+        self.origin = (float(y_at[0]), float(x_at[0]))       # (of the first pixel inside: pixel (0, 0) when `covers`)
+        self.step = (float(y_at[1] - y_at[0]) if len(y_at) > 1 else 1.0, float(x_at[1] - x_at[0]) if len(x_at) > 1 else 1.0)
+        model_psf = np.asarray(model_frame.psfs.image)[0]
+        fine, coarse = rs.match_psfs(model_psf, np.asarray(self.frame.psfs.image), model_frame.wcs, self.frame.wcs)
+        self._diff_kernels = rs.difference_kernel(coarse, fine)
+        self._factors = None
+        if self.covers:
+            area = (rs.pixel_scale(a_obs) / rs.pixel_scale(a_model)) ** 2
+            self._factors = rs.lowres_factors((H, W), (h, w), model_psf.shape, self._diff_kernels, y_at, x_at, area)
+            self._fft_shape = self._factors["fft_shape"]
+        self._device = {}
+        return self
+
+    @property
+    def factors(self):
+        """dict(uy, ux, vy, vx, dhat) complex128 of the matched geometry."""
+        if self._factors is None:
+            raise ValueError("LowResObservation: match() a model frame that contains every pixel of the observation first "
+                             "(lr_shape = %s of %s)" % (getattr(self, "lr_shape", None), self.frame.shape[1:]))
+        return self._factors
+
+    def factors_f32(self):
+        """The five matrices as float32 arrays whose last axis is (re, im): what the library reads."""
+        f = self.factors
+        return {k: np.ascontiguousarray(np.stack([f[k].real, f[k].imag], axis=-1), dtype=np.float32)
+                for k in ("uy", "ux", "vy", "vx", "dhat")}
+
+    def pixel_of(self, y, x):
+        """The observation's pixel (row, column) under model-frame position (y, x), truncated as Frame.get_pixel does."""
+        return int((y - self.origin[0]) / self.step[0]), int((x - self.origin[1]) / self.step[1])
+
+    def _lowres_struct(self):
+        """(struct scarlet_lowres without a workspace, the device tensors it points to)"""
+        torch = _lib.require_gpu()
+        if "lowres" not in self._device:
+            t = {k: torch.as_tensor(v).cuda() for k, v in self.factors_f32().items()}
+            lr = _lib.ScarletLowres()
+            lr.h, lr.w = self.frame.Ny, self.frame.Nx
+            lr.nfy, lr.nfx, lr.B = t["uy"].shape[0], t["ux"].shape[0], t["dhat"].shape[0]
+            for k, v in t.items():
+                setattr(lr, k, v.data_ptr())
+            self._device["lowres"] = (lr, t)
+        return self._device["lowres"]
+
+    def _render(self, model):
+        """The model's band slice resampled and convolved into the observation's pixels, on the device: (B, h, w)."""
+        torch = _lib.require_gpu()
+        lr, _keep = self._lowres_struct()
+        m = model if torch.is_tensor(model) else torch.as_tensor(np.asarray(model))
+        m = m[self._band_slice].to(device="cuda", dtype=torch.float32).contiguous()
+        B, H, W = m.shape
+        if (H, W) != tuple(self.model_shape) or B != lr.B:
+            raise ValueError("LowResObservation.render: the model's band slice is %s, matched was %s"
+                             % (tuple(m.shape), (lr.B,) + tuple(self.model_shape)))
+        band = torch.arange(B, dtype=torch.int32, device="cuda")
+        out = torch.empty((B, lr.h, lr.w), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.lib.scarlet_lowres_render(m.data_ptr(), B, H, W, ctypes.byref(lr), band.data_ptr(), None,
+                                                  out.data_ptr(), _lib.stream_ptr()))
+        return out
+
+    def render(self, model):
+        """The model as this observation sees it (reference observation.py:561-578; every pixel lies inside the model
+        frame, so the rendered patch is the whole image)."""
+        return self._render(model)
+
+    def get_loss(self, model):
+        """0.5 * sum (weights * (render(model) - images))^2 (reference observation.py:580-599)."""
+        torch = _lib.require_gpu()
+        d = self._render(model) - self._images_device()
+        w = self._weights_device()
         if w is not None:
             d = w * d
         elif self.weights != 1:
