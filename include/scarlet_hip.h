@@ -434,7 +434,8 @@ int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_con
  * LDS: about 4 (2 nfy H + 2 nfx W + 2 h nfy + 2 w nfx + 2 B nfy nfx + 4 nfy nfx + H (W + 2 nfx)) bytes (rows padded to
  * odd lengths) against 159 KiB.  With an 11-pixel model PSF and images of half the model's side: a 64 x 64 model frame
  * (72-point padded plane, nfy = 19, nfx = 37) with 32 x 32 images takes 133 KiB at B = 8 bands; 72 x 72 with 36 x 36
- * still fits at B = 8 (145 KiB), 76 x 76 up to B = 6, 84 x 84 up to B = 2; beyond: SCARLET_E_NOTIMPL. */
+ * (75 x 80-point plane, nfy = 19, nfx = 41) still fits at B = 8 (156 KiB), 76 x 76 with 38 x 38 up to B = 6 (158 KiB),
+ * 84 x 84 with 42 x 42 up to B = 2 (158 KiB); beyond: SCARLET_E_NOTIMPL. */
 typedef struct scarlet_lowres {
     int32_t h, w;               /* the observation's pixel grid: images and weights are [S][B][h][w]                */
     int32_t nfy, nfx;           /* retained frequencies per axis (rows of uy / ux)                                  */

@@ -187,7 +187,8 @@ __device__ inline double jacobi_lambda_max(double *A, int n, int ld)
 // p, p', p'' > 0 to the right of the largest one, so Newton's iteration started at the
 // trace (>= lambda_max) decreases monotonically onto it.  ~10 x fewer dependent
 // instructions than a Jacobi sweep; the root's conditioning is that of the eigenvalue
-// (error ~1e-16 separated, ~1e-8 relative for a double top eigenvalue).
+// (error ~1e-16 separated, ~1e-8 relative for a double top eigenvalue; a cluster of three or four is returned from
+// above, within the start's distance or ~2e-5, whichever is smaller).
 // Replaces np.linalg.eigvals(...).max() of blend.py:216-218.
 __device__ inline double lambda_max_charpoly4(const double *A, int n, int ld)
 {
@@ -224,7 +225,12 @@ __device__ inline double lambda_max_charpoly4(const double *A, int n, int ld)
     for (int it = 0; it < 64; ++it) {
         const double pv = (((x - c1) * x + c2) * x - c3) * x + c4;
         const double dv = ((4.0 * x - 3.0 * c1) * x + 2.0 * c2) * x - c3;
-        if (!(pv > 0.0) || !(dv > 0.0)) break;                 // at (or, by rounding, just past) the root
+        // at the root to within the rounding of pv itself (a few times 1e-16 x^4): a step taken from there divides noise
+        // by a dv that vanishes at a multiple root -- K equal, well separated morphologies make a triple or quadruple one
+        // -- and lands far BELOW the root (4 I: 9 % low).  Stopping on the floor keeps x an upper bound; the start is
+        // within the off-diagonal sums of the root, so such a matrix is solved by its start.
+        const double x2 = x * x;
+        if (!(pv > 0x1p-47 * (x2 * x2)) || !(dv > 0.0)) break;
         // pv / dv by one refinement of the hardware reciprocal (relative error ~1e-16: far inside the
         // step's own tolerance, and without the IEEE division's dozen dependent instructions)
         double rc = __builtin_amdgcn_rcp(dv);

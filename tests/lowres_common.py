@@ -39,16 +39,88 @@ def geometry(g, name, model_channels=("r", "i"), channels=("r", "i"), origin=Non
     return obs.match(frame), frame
 
 
+# Geometries at the limits of the low-resolution kernels (tests/golden/lowres_limits.npz holds what the reference says
+# to d .. h): name -> (model (H, W), observation (h, w), pixel ratio, model-frame position (y, x) of observation pixel
+# (0, 0), (model PSF, observation PSF) side in pixels, the bands B the device tests run it with).
+#   d, g, f, e  the shapes scarlet_hip.h promises, at their largest B: dynamic LDS of 133 - 158 KiB, the opt-in range
+#   h           pixel ratio near 1: the only one whose scratch buffers are sized by h x ldw (`scratch_terms`)
+#   i           non-square frame and observation past 48 KiB
+#   j           every GEMM dimension off 16 and off 4 (H, W, h, w, 2 nfy, 2 nfx = 17, 23, 5, 7, 10, 30)
+LIMITS = {
+    "d": ((64, 64), (32, 32), 2.0, (0.0, 0.0), (11, 9), 8),
+    "e": ((84, 84), (42, 42), 2.0, (0.0, 0.0), (11, 9), 2),
+    "f": ((76, 76), (24, 24), 3.0, (1.2, 2.1), (11, 9), 6),
+    "g": ((72, 72), (36, 36), 2.0, (0.0, 0.0), (11, 9), 8),
+    "h": ((40, 40), (36, 36), 1.1, (0.2, 0.2), (11, 9), 2),
+    "i": ((48, 64), (18, 26), 2.4, (1.3, 0.6), (11, 9), 3),
+    "j": ((17, 23), (5, 7), 3.0, (1.0, 1.0), (5, 5), 3),
+}
+LIMIT_CHANNELS = ["c%d" % c for c in range(8)]
+
+
+def gauss(n, sigma, dy=0.0, dx=0.0):
+    y, x = np.mgrid[:n, :n] - (n // 2)
+    g = np.exp(-((y - dy) ** 2 + (x - dx) ** 2) / (2 * sigma ** 2))
+    return g / g.sum()
+
+
+def limit_psfs(psf_px, B):
+    """(model PSF (1, P, P), the observation's PSFs (B, p, p)) of a LIMITS geometry, the fixture's for B = 2"""
+    return (gauss(psf_px[0], 0.9)[None].astype(np.float32),
+            np.array([gauss(psf_px[1], 0.9 + 0.15 * b, 0.2, -0.1) for b in range(B)]).astype(np.float32))
+
+
+def limit_geometry(name, B=2, origin=None, lr_shape=None, band0=0, C=None, weights=None):
+    """Geometry `name` of LIMITS as a matched scarlet_amd.LowResObservation of B bands (zero images) that covers the
+    model channels band0 .. band0 + B - 1 of C, and its model frame."""
+    import scarlet_amd as scarlet
+    (H, W), hw, ratio, org, psf_px, _ = LIMITS[name] if isinstance(name, str) else name       # (or such a tuple itself)
+    h, w = hw if lr_shape is None else lr_shape
+    wm, wl = wcs_pair((H, W), (h, w), ratio, org if origin is None else origin)
+    model_psf, lr_psfs = limit_psfs(psf_px, B)
+    model_channels = LIMIT_CHANNELS[:band0 + B if C is None else C]
+    channels = model_channels[band0:band0 + B]
+    if channels == model_channels:
+        channels = model_channels
+    frame = scarlet.Frame((len(model_channels), H, W), wcs=wm, psfs=model_psf, channels=model_channels)
+    obs = scarlet.LowResObservation(np.zeros((B, h, w), np.float32), wcs=wl, psfs=lr_psfs, weights=weights, channels=channels)
+    return obs.match(frame), frame
+
+
+def scratch_terms(H, W, h, w, nfy, nfx):
+    """lowres.h's lowres_lds restated: the four products whose largest sizes the scratch buffers X and Y (floats), and
+    the footprint in bytes without the B band spectra, which take 8 nfy nfx bytes each."""
+    odd = lambda n: n | 1
+    ny2, nx2 = 2 * nfy, 2 * nfx
+    terms = {"2nfy x ld2x": ny2 * odd(nx2), "2nfy x ldw": ny2 * odd(w), "h x ldw": h * odd(w), "2nfy x ldW": ny2 * odd(W)}
+    sz = max(terms.values())
+    proj = H * odd(W) + H * odd(nx2)
+    fixed = ny2 * odd(H) + nx2 * odd(W) + h * odd(ny2) + w * odd(nx2) + sz + max(proj, sz)
+    return terms, 4 * fixed
+
+
+def apply_by_matmul(f, model):
+    """resampling.apply_factors as four matrix products (float64; the fits call it every iteration, and the three-operand
+    einsum there takes 0.1 s per call at 8 bands of 72 x 72); tests/test_lowres_host.py holds the two together"""
+    spec = (f["uy"] @ np.asarray(model, dtype=np.float64) @ f["ux"].T) * f["dhat"]
+    return np.real(f["vy"] @ spec @ f["vx"].T)
+
+
+def adjoint_by_matmul(f, resid):
+    """resampling.adjoint_factors likewise"""
+    spec = (f["vy"].T @ np.asarray(resid, dtype=np.float64) @ f["vx"]) * f["dhat"]
+    return np.real(f["uy"].T @ spec @ f["ux"])
+
+
 def lowres_loss_and_gradients(seds, morphs, ob):
     """pgm.loss_and_gradients for a low-resolution observation: the operator and its adjoint in float64
-    (resampling.apply_factors / adjoint_factors), the gradients in the factors' dtype."""
-    from scarlet_amd import resampling as rs
+    (resampling.apply_factors / adjoint_factors as matrix products), the gradients in the factors' dtype."""
     dt = seds[0].dtype
     images = np.asarray(ob["images"], dtype=np.float64)
     model = pgm.scene_model(seds, morphs, (len(seds[0]),) + morphs[0].shape, np.float64)
     w = ob.get("weights", 1)
-    d = w * (rs.apply_factors(ob["factors"], model) - images)
-    G = rs.adjoint_factors(ob["factors"], w * d)
+    d = w * (apply_by_matmul(ob["factors"], model) - images)
+    G = adjoint_by_matmul(ob["factors"], w * d)
     return (0.5 * np.sum(d ** 2), [(G * m[None]).sum(axis=(1, 2)).astype(dt) for m in morphs],
             [(G * s[:, None, None]).sum(axis=0).astype(dt) for s in seds])
 

@@ -1,7 +1,8 @@
 """CPU: the host set-up of a low-resolution observation (scarlet_amd.LowResObservation.match, resampling.py) against
-what the reference computed (tests/golden/lowres.npz, tools/gen_lowres_golden.py), the float restatement of the joint
-fit against the reference's fit, and the C ABI with its argument checks.  Every library call below returns before a
-launch."""
+what the reference computed (tests/golden/lowres.npz, tools/gen_lowres_golden.py; at the geometries that fill LDS
+tests/golden/lowres_limits.npz, tools/gen_lowres_limits_golden.py), the float restatement of the joint fit against the
+reference's fit, and the C ABI with its argument checks and its LDS boundary.  Every library call below returns before
+a launch."""
 import ctypes
 import os
 import re
@@ -11,7 +12,7 @@ import numpy as np
 import pytest
 
 import lowres_common as lc
-from conftest import rel_err
+from conftest import load_golden, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "scarlet_hip.h")
@@ -73,6 +74,88 @@ def test_sandwich_is_the_reference_algorithm_and_its_adjoint(g, name):
     lhs, rhs = np.sum(out * y), np.sum(model * rs.adjoint_factors(obs.factors, y))
     assert abs(lhs - rhs) <= 1e-12 * max(abs(lhs), 1.0)
     assert "broadcast" in str(g["c_reference_error"])
+
+
+@pytest.fixture(scope="module")
+def gl():
+    return load_golden("lowres_limits")
+
+
+@pytest.mark.parametrize("name", ["d", "e", "f"])
+def test_host_factors_reproduce_the_reference_at_the_limits(gl, name):
+    """the geometries that fill LDS (lowres_common.LIMITS), where the reference still runs: 1.3e-7 .. 1.5e-7, the
+    float32 cast of the reference's result (profiles/lowres_rel_err.txt)"""
+    from scarlet_amd import resampling as rs
+    (H, W), (h, w), ratio, origin, psf_px, _ = lc.LIMITS[name]
+    assert (tuple(gl[name + "_model_shape"]), tuple(gl[name + "_lr_shape"])) == ((H, W), (h, w))
+    assert float(gl[name + "_ratio"]) == ratio and tuple(gl[name + "_origin"]) == origin
+    for got, want in zip(lc.limit_psfs(psf_px, 2), (gl[name + "_model_psf"], gl[name + "_lr_psfs"])):
+        np.testing.assert_array_equal(got, want)
+    obs, _ = lc.limit_geometry(name, B=2)
+    assert obs.covers and obs.lr_shape == (h, w)
+    assert list(obs._fft_shape) == list(gl[name + "_fft_shape"])
+    model = gl[name + "_models"][0]
+    out = rs.apply_factors(obs.factors, model)
+    err = rel_err(out, gl[name + "_renders"][0])
+    print("geometry %s: render rel err %.3e" % (name, err))
+    assert err <= HOST_TOL
+    wgt, img = gl[name + "_weights_lr"].astype(np.float64), gl[name + "_images_lr"].astype(np.float64)
+    loss = 0.5 * np.sum((wgt * (out - img)) ** 2)
+    assert abs(loss - gl[name + "_losses"][0]) <= HOST_TOL * gl[name + "_losses"][0]
+
+
+@pytest.mark.parametrize("name", sorted(lc.LIMITS))
+def test_sandwich_is_the_reference_algorithm_at_the_limits(gl, name):
+    """as test_sandwich_is_the_reference_algorithm_and_its_adjoint, on d .. j.  g and h pad to planes that are not
+    square (75 x 80, 45 x 48), which the reference refuses as it refuses c: its messages are in the fixture."""
+    from scarlet_amd import resampling as rs
+    (H, W), (h, w) = lc.LIMITS[name][:2]
+    obs, _ = lc.limit_geometry(name, B=2)
+    assert obs.covers and obs.small_axis == (w <= h)
+    rng = np.random.default_rng(5)
+    model = rng.random((2, H, W))
+    out = rs.apply_factors(obs.factors, model)
+    err = rel_err(out, lc.render_by_planes(obs, model))
+    print("geometry %s: sandwich vs planes %.3e" % (name, err))
+    assert err <= 1e-12
+    y = rng.standard_normal(out.shape)
+    back = rs.adjoint_factors(obs.factors, y)
+    lhs, rhs = np.sum(out * y), np.sum(model * back)
+    assert abs(lhs - rhs) <= 1e-12 * max(abs(lhs), 1.0)
+    # (the form the float restatement of the fit uses)
+    assert rel_err(lc.apply_by_matmul(obs.factors, model), out) <= 1e-12
+    assert rel_err(lc.adjoint_by_matmul(obs.factors, y), back) <= 1e-12
+    if name in "gh":
+        assert obs._fft_shape[0] != obs._fft_shape[1]
+        assert str(gl[name + "_reference_error"]).startswith("ValueError") and "inhomogeneous" in str(gl[name + "_reference_error"])
+
+
+def _dims(obs):
+    (H, W), (h, w) = obs.model_shape, obs.frame.shape[1:]
+    return H, W, h, w, obs.factors["uy"].shape[0], obs.factors["ux"].shape[0]
+
+
+def test_scratch_layouts_of_the_geometries(g):
+    """Which product sizes lowres.h's scratch buffers: 2 nfy x ld2x at a .. g, i and j, h x ldw at h alone (pixel ratio
+    1.1) -- the only geometry in the suite that runs the other layout, so it must stay in it.  Pure sizes; the footprints
+    are those of the table in profiles/lowres_rel_err.txt."""
+    largest, kib = {}, {}
+    for name in "abc":
+        terms, _ = lc.scratch_terms(*_dims(lc.geometry(g, name)[0]))
+        largest[name] = max(terms, key=terms.get)
+    for name, B in (("d", 8), ("e", 2), ("g", 8), ("h", 1), ("i", 3), ("j", 1), ("f", 6)):
+        d = _dims(lc.limit_geometry(name)[0])
+        terms, fixed = lc.scratch_terms(*d)
+        largest[name] = max(terms, key=terms.get)
+        kib[name] = round((fixed + B * 8 * d[4] * d[5]) / 1024.0, 1)
+        assert sorted(terms.values())[-1] > sorted(terms.values())[-2]          # no tie decides a layout
+    assert largest.pop("h") == "h x ldw"
+    assert set(largest.values()) == {"2nfy x ld2x"} and len(largest) == 9
+    assert (kib["d"], kib["e"], kib["g"], kib["h"], kib["i"], kib["j"]) == (132.8, 158.1, 156.3, 43.7, 80.4, 9.8)
+    assert kib["f"] < kib["e"]
+    terms, _ = lc.scratch_terms(*_dims(lc.limit_geometry("h")[0]))
+    assert (terms["h x ldw"], terms["2nfy x ld2x"]) == (1332, 1122)
+    assert _dims(lc.limit_geometry("j")[0]) == (17, 23, 5, 7, 5, 15)             # every GEMM dimension off 16 and 4
 
 
 @pytest.mark.parametrize("name", ["a", "b"])
@@ -224,7 +307,7 @@ def test_argument_errors_come_back_before_any_launch():
     assert "LDS" in _lib.last_error()
     # the limit the header promises: 64 x 64 with 32 x 32 images, an 11-pixel PSF (72-point plane) and 8 bands is sized
     st8, lo8 = _batch(3, 2, 8, 64, 64), _batch(3, 2, 8, 32, 32)
-    lr8 = _lowres(h=32, w=32, nfy=18, nfx=35, B=8)
+    lr8 = _lowres(h=32, w=32, nfy=19, nfx=37, B=8)           # (nfy, nfx as match() makes them: geometry d)
     n = _lib.lib.scarlet_lowres_workspace_bytes(ctypes.byref(st8), ctypes.byref(lo8), ctypes.byref(lr8))
     assert n == 3 * 8 * 64 * 64 * 4 + 3 * 8 * 8
     assert _lib.lib.scarlet_lowres_workspace_bytes(ctypes.byref(big), ctypes.byref(big_lo),
@@ -238,3 +321,34 @@ def test_argument_errors_come_back_before_any_launch():
         assert fn(FAKE, 1, 32, 32, ctypes.byref(_lowres(ux=None)), None, None, FAKE, None) == _lib.E_ARG
         assert fn(FAKE, 1, 1024, 1024, ctypes.byref(lr), None, None, FAKE, None) == _lib.E_NOTIMPL
         assert fn(FAKE, 0, 32, 32, ctypes.byref(lr), None, None, FAKE, None) == 0
+
+
+def _half(side):
+    """side x side model frame, images of half its side on the same corner, 11- and 9-pixel PSFs: the header's family"""
+    return ((side, side), (side // 2, side // 2), 2.0, (0.0, 0.0), (11, 9), None)
+
+
+@pytest.mark.parametrize("side,nf,accepted,refused", [(64, (19, 37), 8, None), (72, (19, 41), 8, None), (76, (21, 41), 6, 7),
+                                                      (84, (23, 45), 2, 3), (88, (25, 49), None, 1)])
+def test_lds_boundary_is_where_the_header_says(side, nf, accepted, refused):
+    """scarlet_hip.h: "64 x 64 ... at B = 8 bands; 72 x 72 with 36 x 36 still fits at B = 8, 76 x 76 up to B = 6,
+    84 x 84 up to B = 2; beyond: SCARLET_E_NOTIMPL", with the frequencies match() gives.  The restated footprint
+    (lowres_common.scratch_terms) sits on the same side of 159 KiB as the library's answer."""
+    from scarlet_amd import _lib
+    obs, _ = lc.limit_geometry(_half(side))
+    d = _dims(obs)
+    assert d[4:] == nf
+    _, fixed = lc.scratch_terms(*d)
+    for B, ok in ((accepted, True), (refused, False)):
+        if B is None:
+            continue
+        st, lo = _batch(3, 2, B, side, side), _batch(3, 2, B, side // 2, side // 2)
+        lr = _lowres(h=side // 2, w=side // 2, nfy=nf[0], nfx=nf[1], B=B)
+        n = _lib.lib.scarlet_lowres_workspace_bytes(ctypes.byref(st), ctypes.byref(lo), ctypes.byref(lr))
+        lds = fixed + B * 8 * nf[0] * nf[1]
+        print("%d x %d, B = %d: %.1f KiB" % (side, side, B, lds / 1024.0))
+        assert (lds <= 159 * 1024) == ok
+        if ok:
+            assert n == (3 * B * side * side * 4 + 15) // 16 * 16 + 3 * B * 8
+        else:
+            assert n == _lib.E_NOTIMPL and "LDS" in _lib.last_error()
