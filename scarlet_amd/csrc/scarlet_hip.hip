@@ -1207,6 +1207,24 @@ static int fft_c2r(const FftPlans &p, float2 *in, float *out, hipStream_t st)
 }
 static unsigned grid_for(int64_t n) { int64_t g = (n + SC_BLOCK - 1) / SC_BLOCK; return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); }
 
+// One hipFFT convolution of `planes` planes, in place: real -> spec, times K-hat (adjoint: its conjugate) and `scale`,
+// -> real.  `before_mul` enqueues what the product needs besides the planes' spectrum (scarlet_convolve_same: K-hat).
+template <typename BeforeMul>
+static int hipfft_convolve(const FftPlans &p, float *real, float2 *spec, const float2 *khat, int nk, int64_t planes,
+                           int plane_elems, int adjoint, float scale, hipStream_t st, BeforeMul before_mul)
+{
+    int rc;
+    if ((rc = fft_r2c(p, real, spec, st)) || (rc = before_mul())) return rc;
+    hipLaunchKernelGGL(k_spec_mul, dim3(grid_for(planes * plane_elems)), dim3(SC_BLOCK), 0, st, spec, khat, nk, plane_elems,
+                       planes * plane_elems, adjoint, scale);
+    return fft_c2r(p, spec, real, st);
+}
+static int hipfft_convolve(const FftPlans &p, float *real, float2 *spec, const float2 *khat, int nk, int64_t planes,
+                           int plane_elems, int adjoint, float scale, hipStream_t st)
+{
+    return hipfft_convolve(p, real, spec, khat, nk, planes, plane_elems, adjoint, scale, st, [] { return (int)SCARLET_OK; });
+}
+
 static int prepare_psf_impl(scarlet_batch *b, const WsLayout &l, void *stream)
 {
     const PsfGeom &g = l.geom;
@@ -1306,25 +1324,73 @@ static void launch_bigk_step(const GradArgs &a, int nch, const float *resid, hip
     else hipLaunchKernelGGL((k_bigk_step<SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a, resid);
 }
 
-// The gradient step for K > SC_KBIG (hugek.h).  Without a PSF it starts from the morphologies (k_bigk_resid); with one,
-// `psf_resid` holds the compact gradient planes G [S][B][H][W] and `psf_loss` the per-plane loss sums.
-static int backward_hugek(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, const float *psf_resid,
-                          const double *psf_loss, hipStream_t st)
+// the Gram matrix and lambda_max of the many-component path on one stream; `mode` is k_bigk_lipschitz's
+static void launch_bigk_lipschitz(const GradArgs &a, int nch, int mode, hipStream_t st)
 {
-    const GradArgs a = grad_args(b, l, approximate_L, raw_gradient);
+    launch_bigk_gram(a, nch, st);
+    hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, st, a, mode);
+}
+
+// The same on the second stream, beside what `st` does from here on.  `precede` enqueues on `st` what k_bigk_lipschitz
+// has to wait for and says whether there was anything: the residual (whose loss it reads) in the chunked form, nothing
+// in the fused form.  The SED step joins on ev[2].
+template <typename Precede>
+static int bigk_lipschitz_beside(SideStream *side, const GradArgs &a, int nch, int mode, hipStream_t st, Precede precede)
+{
+    HIP_TRY(hipEventRecord(side->ev[0], st));
+    HIP_TRY(hipStreamWaitEvent(side->st, side->ev[0], 0));
+    launch_bigk_gram(a, nch, side->st);
+    if (precede()) {
+        HIP_TRY(hipEventRecord(side->ev[1], st));
+        HIP_TRY(hipStreamWaitEvent(side->st, side->ev[1], 0));
+    }
+    hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, side->st, a, mode);
+    HIP_TRY(hipEventRecord(side->ev[2], side->st));
+    return SCARLET_OK;
+}
+
+// the morphology step and the SED step (class 1); `join`: the SED step waits for the second stream's lambda_max
+static int bigk_step_sed(const GradArgs &a, int nch, const float *resid, SideStream *join, hipStream_t st)
+{
+    prof_start(1, st);
+    launch_bigk_step(a, nch, resid, st);
+    if (join) HIP_TRY(hipStreamWaitEvent(st, join->ev[2], 0));
+    hipLaunchKernelGGL(k_bigk_sed, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 0);
+    prof_stop(st);
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
+// ---- K > SC_KBIG (hugek.h).  Its functions stand in the order of their passes: the code object lists a template kernel
+// where the host code first names it, and a host-only change keeps that order.
+// The residual planes and the loss record.  Without a PSF k_bigk_resid makes both from the morphologies; with one,
+// `psf_planes` holds the compact gradient planes G [S][B][H][W], which serve as they are, and `psf_loss` the per-plane
+// loss sums.
+static const float *huge_resid(const scarlet_batch *b, const WsLayout &l, const GradArgs &a, const float *psf_planes,
+                               const double *psf_loss, hipStream_t st)
+{
+    if (psf_planes) {
+        hipLaunchKernelGGL(k_bigk_loss_from_planes, dim3((a.S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a, psf_loss);
+        return psf_planes;
+    }
+    float *resid = ws_at<float>(b, l.gplanes);
+    hipLaunchKernelGGL((k_bigk_resid<SC_KHUGE>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a, resid);
+    return resid;
+}
+
+static HugeArgs huge_args(const scarlet_batch *b, const WsLayout &l)
+{
     HugeArgs h;
     h.C = huge_nchunks(b->H * b->W);
     h.gpart = ws_at<double>(b, l.gpart); h.gram = ws_at<double>(b, l.gram);
     h.msq[0] = ws_at<double>(b, l.msq[0]); h.msq[1] = ws_at<double>(b, l.msq[1]);
-    const int nb = huge_nblk(b->K), npairs = huge_npairs(b->K), nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
-    const float *resid = psf_resid;
-    prof_start(0, st);
-    if (psf_resid)
-        hipLaunchKernelGGL(k_bigk_loss_from_planes, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a, psf_loss);
-    else {
-        resid = ws_at<float>(b, l.gplanes);
-        hipLaunchKernelGGL((k_bigk_resid<SC_KHUGE>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a, ws_at<float>(b, l.gplanes));
-    }
+    return h;
+}
+
+// the Gram matrix of K > SC_KBIG components (hugek.h) and its lambda_max: by repeated squaring, or its trace
+static void launch_huge_lipschitz(const GradArgs &a, const HugeArgs &h, int approximate_L, hipStream_t st)
+{
+    const int nb = huge_nblk(a.K), npairs = huge_npairs(a.K);
     if ((a.HW & 3) == 0) hipLaunchKernelGGL((k_huge_gram<true>), dim3(h.C, npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
     else hipLaunchKernelGGL((k_huge_gram<false>), dim3(h.C, npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
     hipLaunchKernelGGL(k_huge_gram_reduce, dim3(npairs, a.S), dim3(SC_BLOCK), 0, st, a, h);
@@ -1335,159 +1401,169 @@ static int backward_hugek(scarlet_batch *b, const WsLayout &l, int approximate_L
             last = h.msq[q & 1];
         }
     hipLaunchKernelGGL(k_huge_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, st, a, h, last);
-    hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
-    prof_stop(st); prof_start(1, st);
-    launch_bigk_step(a, nch, resid, st);
-    hipLaunchKernelGGL(k_bigk_sed, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 0);
-    prof_stop(st);
-    HIP_TRY(hipGetLastError());
-    return SCARLET_OK;
 }
 
-static int backward_step_psf(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, void *stream)
+// The gradient step for K > SC_KBIG; psf_planes, psf_loss: as huge_resid takes them
+static int backward_hugek(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, const float *psf_planes,
+                          const double *psf_loss, hipStream_t st)
+{
+    const GradArgs a = grad_args(b, l, approximate_L, raw_gradient);
+    prof_start(0, st);
+    const float *resid = huge_resid(b, l, a, psf_planes, psf_loss, st);
+    launch_huge_lipschitz(a, huge_args(b, l), approximate_L, st);
+    hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
+    prof_stop(st);
+    return bigk_step_sed(a, (b->K + SC_CHUNK - 1) / SC_CHUNK, resid, nullptr, st);
+}
+
+// The arguments of one PSF chain.  `ob` owns the images, weights, PSF workspace and lipschitz / mse; `state` owns morph,
+// cur, active and it (a single-observation fit passes one batch for both).  sed0, sed1: the SED buffers the model planes
+// are built from.
+static PsfArgs psf_args(const scarlet_batch *ob, const WsLayout &l, const scarlet_batch *state, float *sed0, float *sed1,
+                        const uint8_t *fix_sed, const uint8_t *fix_morph, int approximate_L, int raw_gradient)
+{
+    PsfArgs a = {};
+    a.S = ob->S; a.K = ob->K; a.B = ob->B; a.T = n_tiles(ob); a.g = l.geom;
+    a.images = ob->images; a.weights = ob->weights; a.weight_scalar = ob->weight_scalar;
+    a.sed[0] = sed0; a.sed[1] = sed1; a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
+    a.cur = state->cur; a.fix_sed = fix_sed; a.fix_morph = fix_morph;
+    a.real = ws_at<float>(ob, l.real);
+    a.spec = ws_at<float2>(ob, l.spec);
+    a.khat = ws_at<const float2>(ob, l.psf_lds ? l.lds_khat : l.khat);
+    a.khat_per_scene = ob->diff_kernel_per_scene;
+    a.partials = ws_at<double>(ob, l.partials); a.loss_part = ws_at<double>(ob, l.loss);
+    a.lipschitz = ob->lipschitz; a.mse = ob->mse; a.mse_capacity = ob->mse_capacity;
+    a.it = state->it; a.active = state->active; a.approximate_L = approximate_L; a.raw_gradient = raw_gradient;
+    return a;
+}
+
+// The gradient planes of one PSF chain: model planes, render, residual + loss, adjoint.  On return G lies in a.real as
+// planes [S][B][a.g.Fy][a.g.Fx] with the image at offset (a.g.oy, a.g.ox), and a.loss_part holds the per-plane losses:
+// compact planes (Fy = H, Fx = W, no offset) from the LDS-resident form, the padded hipFFT planes otherwise.  a.g is
+// also the geometry the gradient kernels after the stage read G through.
+// `model`: which kernel writes the model planes.  PSF_MODEL_GRAM is the three-pass form's k_psf_model4g, which also leaves
+// the Gram partials (K <= SC_KMAX, LDS-resident form, H W % 4 == 0: the caller's choice); PSF_MODEL_PLAIN takes
+// k_psf_model4 or k_psf_model by H W % 4 and the K range.  Opens no profiler class: the callers bracket it.
+enum PsfModel { PSF_MODEL_PLAIN, PSF_MODEL_GRAM };
+static int psf_gradient_planes(const scarlet_batch *b, const WsLayout &l, PsfArgs &a, PsfModel model, hipStream_t st)
 {
     const PsfGeom &g = l.geom;
-    hipStream_t st = (hipStream_t)stream;
-    PsfArgs a;
-    a.S = b->S; a.K = b->K; a.B = b->B; a.T = n_tiles(b); a.g = g;
-    a.images = b->images; a.weights = b->weights; a.weight_scalar = b->weight_scalar;
-    a.sed[0] = b->sed[0]; a.sed[1] = b->sed[1]; a.morph[0] = b->morph[0]; a.morph[1] = b->morph[1];
-    a.cur = b->cur; a.fix_sed = b->fix_sed; a.fix_morph = b->fix_morph;
-    a.real = ws_at<float>(b, l.real);
-    a.spec = ws_at<float2>(b, l.spec);
-    a.khat = ws_at<const float2>(b, l.khat);
-    a.partials = ws_at<double>(b, l.partials); a.loss_part = ws_at<double>(b, l.loss);
-    a.lipschitz = b->lipschitz; a.mse = b->mse; a.mse_capacity = b->mse_capacity;
-    a.it = b->it; a.active = b->active; a.approximate_L = approximate_L; a.raw_gradient = raw_gradient;
-    const int planes = b->S * b->B;
-    const int plane_elems = g.Fy * g.Fxh;
-    const float scale = 1.0f / ((float)g.Fy * (float)g.Fx);
-    const int nkh = b->diff_kernel_per_scene ? planes : b->B;
-    a.khat_per_scene = b->diff_kernel_per_scene;
+    const int HW = b->H * b->W, planes = b->S * b->B;
+    const bool huge = b->K > SC_KBIG;
     int rc;
-    FftPlan fp = l.plan;
-    const bool lds_path = l.psf_lds;
-    const bool three_pass = lds_path && (b->H * b->W) % 4 == 0 && l.grad == GRAD_SMALL && !opt(OPT_NO_PSF3PASS);
-    if (lds_path) {
-        // one kernel: model, render, residual + loss, adjoint -> compact gradient planes G [S][B][H][W] in `real`
+    if (l.psf_lds) {
+        // one kernel after the model's: render, residual + loss, adjoint
+        FftPlan fp = l.plan;
         fp.tables = ws_at<const float2>(b, l.lds_tables);
-        a.khat = ws_at<const float2>(b, l.lds_khat);
         const bool x128 = psf_conv_finish_plan(b, &fp);
         const size_t lds = fft_lds_bytes(fp.Fy, fp.M, fp.RS, b->H, b->W, fp.dma_image != 0);
         if ((rc = allow_lds(k_psf_conv, lds))) return rc;
-        const int groups = (b->S + 7) / 8;
-        prof_start(5, st);
         // model planes, compact [S][B][H][W], into `real` (k_psf_model with the geometry of an unpadded plane)
         a.g.Fy = b->H; a.g.Fx = b->W; a.g.Fxh = b->W / 2 + 1; a.g.oy = 0; a.g.ox = 0;
-        if (b->K > SC_KBIG) {
-            if ((b->H * b->W) % 4 == 0)
-                hipLaunchKernelGGL(k_psf_model4<SC_KHUGE>, dim3(((b->H * b->W) / 4 + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
-            else
-                hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, dim3((b->H * b->W + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
-        } else if (three_pass) {
-            // model planes + Gram partials in one pass (psf_path.h, "three-pass form")
-            if (b->K <= 4) hipLaunchKernelGGL((k_psf_model4g<4>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a);
-            else hipLaunchKernelGGL((k_psf_model4g<SC_KMAX>), dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a);
-        } else if ((b->H * b->W) % 4 == 0)
-            hipLaunchKernelGGL(k_psf_model4<SC_KBIG>, dim3(((b->H * b->W) / 4 + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
-        else
-            hipLaunchKernelGGL(k_psf_model<SC_KBIG>, dim3((b->H * b->W + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+        auto plain = [&](void (*k4)(PsfArgs), void (*k1)(PsfArgs)) {      // (four pixels per lane where the plane allows)
+            if (HW % 4 == 0) hipLaunchKernelGGL(k4, dim3((HW / 4 + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+            else hipLaunchKernelGGL(k1, dim3((HW + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
+        };
+        if (huge) plain(k_psf_model4<SC_KHUGE>, k_psf_model<SC_KHUGE>);
+        else if (model == PSF_MODEL_GRAM)
+            hipLaunchKernelGGL(b->K <= 4 ? k_psf_model4g<4> : k_psf_model4g<SC_KMAX>, dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a);
+        else plain(k_psf_model4<SC_KBIG>, k_psf_model<SC_KBIG>);
         long long *stamps = opt(OPT_STAMPS) ? ws_at<long long>(b, l.stamps) : nullptr;
         fp.stagger_wgs = 0;
+        const int groups = (b->S + 7) / 8;
         if (x128) {
             // (the instance keeps the image in registers unless built with SC_X128_DMA: plane + tables only)
             const size_t lds_x = fft_lds_bytes(fp.Fy, fp.M, fp.RS, b->H, b->W, SC_X128_DMA != 0);
             if ((rc = allow_lds(k_psf_conv_x128, lds_x))) return rc;
             hipLaunchKernelGGL(k_psf_conv_x128, dim3(groups * 8 * b->B), dim3(SC_FFT_NT_X), lds_x, st, a, fp, a.real, stamps);
         } else
-        hipLaunchKernelGGL(k_psf_conv, dim3(groups * 8 * b->B), dim3(SC_FFT_NT), lds, st, a, fp, a.real, stamps);
-        prof_stop(st);
-        // (the gradient kernels below read G through the same geometry struct: compact planes, no offset)
+            hipLaunchKernelGGL(k_psf_conv, dim3(groups * 8 * b->B), dim3(SC_FFT_NT), lds, st, a, fp, a.real, stamps);
     } else {
-    FftPlans p;
-    rc = get_plans(g.Fy, g.Fx, planes, &p);
-    if (rc) return rc;
-    prof_start(5, st);
-    if (b->K > SC_KBIG) hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, dim3((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL(k_psf_model<SC_KBIG>, dim3((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, b->S), dim3(SC_BLOCK), 0, st, a);
-    if ((rc = fft_r2c(p, a.real, a.spec, st))) return rc;
-    hipLaunchKernelGGL(k_spec_mul, dim3(grid_for((int64_t)planes * plane_elems)), dim3(SC_BLOCK), 0, st,
-                       a.spec, a.khat, nkh, plane_elems, (int64_t)planes * plane_elems, 0, scale);
-    if ((rc = fft_c2r(p, a.spec, a.real, st))) return rc;
-    hipLaunchKernelGGL(k_psf_resid, dim3(planes), dim3(SC_BLOCK), 0, st, a);
-    if ((rc = fft_r2c(p, a.real, a.spec, st))) return rc;
-    hipLaunchKernelGGL(k_spec_mul, dim3(grid_for((int64_t)planes * plane_elems)), dim3(SC_BLOCK), 0, st,
-                       a.spec, a.khat, nkh, plane_elems, (int64_t)planes * plane_elems, 1, scale);
-    if ((rc = fft_c2r(p, a.spec, a.real, st))) return rc;
+        FftPlans p;
+        if ((rc = get_plans(g.Fy, g.Fx, planes, &p))) return rc;
+        const int plane_elems = g.Fy * g.Fxh, nkh = b->diff_kernel_per_scene ? planes : b->B;
+        const float scale = 1.0f / ((float)g.Fy * (float)g.Fx);
+        const dim3 grid((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, b->S);
+        if (huge) hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, grid, dim3(SC_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL(k_psf_model<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a);
+        if ((rc = hipfft_convolve(p, a.real, a.spec, a.khat, nkh, planes, plane_elems, 0, scale, st))) return rc;
+        hipLaunchKernelGGL(k_psf_resid, dim3(planes), dim3(SC_BLOCK), 0, st, a);
+        if ((rc = hipfft_convolve(p, a.real, a.spec, a.khat, nkh, planes, plane_elems, 1, scale, st))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
+// G as the many-component passes read it, compact [S][B][H][W]: where the stage left it (LDS-resident form), or cropped
+// out of the hipFFT planes once
+static const float *psf_compact_planes(const scarlet_batch *b, const WsLayout &l, const PsfArgs &a, hipStream_t st)
+{
+    if (l.psf_lds) return a.real;
+    float *out = ws_at<float>(b, l.gplanes);
+    hipLaunchKernelGGL(k_plane_crop, dim3(grid_for((int64_t)a.S * a.B * b->H * b->W)), dim3(SC_BLOCK), 0, st,
+                       (const float *)a.real, a.S * a.B, b->H, b->W, a.g.Fy, a.g.Fx, a.g.oy, a.g.ox, out);
+    return out;
+}
+
+// the pair "gradient kernel, step kernel" over the tiles of every scene, each under its profiler class
+template <typename Args>
+static void launch_grad_step(void (*grad)(Args), void (*step)(Args), const Args &a, hipStream_t st)
+{
+    const dim3 grid(a.T, a.S);
+    prof_start(0, st);
+    hipLaunchKernelGGL(grad, grid, dim3(SC_BLOCK), 0, st, a);
+    prof_stop(st); prof_start(1, st);
+    hipLaunchKernelGGL(step, grid, dim3(SC_BLOCK), 0, st, a);
     prof_stop(st);
-    }
-    dim3 grid(a.T, a.S);
-    if (l.grad == GRAD_HUGEK) {
-        float *resid = lds_path ? a.real : ws_at<float>(b, l.gplanes);
-        if (!lds_path)
-            hipLaunchKernelGGL(k_plane_crop, dim3(grid_for((int64_t)planes * b->H * b->W)), dim3(SC_BLOCK), 0, st,
-                               (const float *)a.real, planes, b->H, b->W, g.Fy, g.Fx, g.oy, g.ox, resid);
-        return backward_hugek(b, l, approximate_L, raw_gradient, resid, (const double *)a.loss_part, st);
-    }
+}
+
+static int backward_step_psf(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    PsfArgs a = psf_args(b, l, b, b->sed[0], b->sed[1], b->fix_sed, b->fix_morph, approximate_L, raw_gradient);
+    const bool vec4 = l.psf_lds && (b->H * b->W) % 4 == 0;         // compact gradient planes: 16 B per lane
+    // three-pass form (psf_path.h): the model pass also leaves the Gram partials
+    const bool three_pass = vec4 && l.grad == GRAD_SMALL && !opt(OPT_NO_PSF3PASS);
+    int rc;
+    prof_start(5, st);
+    if ((rc = psf_gradient_planes(b, l, a, three_pass ? PSF_MODEL_GRAM : PSF_MODEL_PLAIN, st))) return rc;
+    prof_stop(st);
+    if (l.grad == GRAD_HUGEK)
+        return backward_hugek(b, l, approximate_L, raw_gradient, psf_compact_planes(b, l, a, st), a.loss_part, st);
     if (l.grad == GRAD_BIGK) {
-        // many components: G is cropped out of the FFT buffers once (the LDS path's planes are compact already),
-        // then the chunked passes of bigk.h
-        GradArgs ga = grad_args(b, l, approximate_L, raw_gradient);
-        float *resid = lds_path ? a.real : ws_at<float>(b, l.gplanes);
+        // many components: the chunked passes of bigk.h over the compact planes, on the one stream
+        const GradArgs ga = grad_args(b, l, approximate_L, raw_gradient);
         const int nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
         prof_start(0, st);
-        if (!lds_path)
-            hipLaunchKernelGGL(k_plane_crop, dim3(grid_for((int64_t)planes * b->H * b->W)), dim3(SC_BLOCK), 0, st,
-                               (const float *)a.real, planes, b->H, b->W, g.Fy, g.Fx, g.oy, g.ox, resid);
+        const float *resid = psf_compact_planes(b, l, a, st);
         hipLaunchKernelGGL(k_bigk_loss_from_planes, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, ga,
                            (const double *)a.loss_part);
-        launch_bigk_gram(ga, nch, st);
-        hipLaunchKernelGGL(k_bigk_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, 0);
-        prof_stop(st); prof_start(1, st);
-        launch_bigk_step(ga, nch, resid, st);
-        hipLaunchKernelGGL(k_bigk_sed, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, 0);
+        launch_bigk_lipschitz(ga, nch, 0, st);
         prof_stop(st);
-        HIP_TRY(hipGetLastError());
-        return SCARLET_OK;
+        return bigk_step_sed(ga, nch, resid, nullptr, st);
     }
     if (three_pass) {
         // morphology step + SED-gradient partials in one pass over G, then the per-scene scalar head
-        prof_start(1, st);
-        // (instances by band count: the accumulators of absent bands would cost occupancy)
-        if (b->K <= 4) {
-            if (b->B <= 4) hipLaunchKernelGGL((k_step_psf4f<4, 4>), grid, dim3(SC_BLOCK), 0, st, a);
-            else if (b->B <= 6) hipLaunchKernelGGL((k_step_psf4f<4, 6>), grid, dim3(SC_BLOCK), 0, st, a);
-            else hipLaunchKernelGGL((k_step_psf4f<4, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-            hipLaunchKernelGGL((k_sed_step<4, SC_BMAX>), dim3(a.S), dim3(SC_BLOCK), 0, st, a);
-        } else {
-            if (b->B <= 4) hipLaunchKernelGGL((k_step_psf4f<SC_KMAX, 4>), grid, dim3(SC_BLOCK), 0, st, a);
-            else if (b->B <= 6) hipLaunchKernelGGL((k_step_psf4f<SC_KMAX, 6>), grid, dim3(SC_BLOCK), 0, st, a);
-            else hipLaunchKernelGGL((k_step_psf4f<SC_KMAX, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-            hipLaunchKernelGGL((k_sed_step<SC_KMAX, SC_BMAX>), dim3(a.S), dim3(SC_BLOCK), 0, st, a);
-        }
-        prof_stop(st);
-    } else if (lds_path && (b->H * b->W) % 4 == 0) {
-        // compact gradient planes: 16 B per lane
-        prof_start(0, st);
-        if (b->K <= 4) hipLaunchKernelGGL((k_grad_psf4<4, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_grad_psf4<SC_KMAX, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st); prof_start(1, st);
-        if (b->K <= 4) hipLaunchKernelGGL((k_step_psf4<4, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_step_psf4<SC_KMAX, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st);
-    } else if (b->K <= 4) {
-        prof_start(0, st);
-        hipLaunchKernelGGL((k_grad_psf<4, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st); prof_start(1, st);
-        hipLaunchKernelGGL((k_step_psf<4, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st);
-    } else {
-        prof_start(0, st);
-        hipLaunchKernelGGL((k_grad_psf<SC_KMAX, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st); prof_start(1, st);
-        hipLaunchKernelGGL((k_step_psf<SC_KMAX, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st);
-    }
+        auto step = [&](auto kc) {
+            constexpr int KC = decltype(kc)::value;
+            const dim3 grid(a.T, a.S);
+            prof_start(1, st);
+            // (instances by band count: the accumulators of absent bands would cost occupancy)
+            if (b->B <= 4) hipLaunchKernelGGL((k_step_psf4f<KC, 4>), grid, dim3(SC_BLOCK), 0, st, a);
+            else if (b->B <= 6) hipLaunchKernelGGL((k_step_psf4f<KC, 6>), grid, dim3(SC_BLOCK), 0, st, a);
+            else hipLaunchKernelGGL((k_step_psf4f<KC, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
+            hipLaunchKernelGGL((k_sed_step<KC, SC_BMAX>), dim3(a.S), dim3(SC_BLOCK), 0, st, a);
+            prof_stop(st);
+        };
+        if (b->K <= 4) step(std::integral_constant<int, 4>{});
+        else step(std::integral_constant<int, SC_KMAX>{});
+    } else if (vec4)
+        launch_grad_step(b->K <= 4 ? k_grad_psf4<4, SC_BMAX> : k_grad_psf4<SC_KMAX, SC_BMAX>,
+                         b->K <= 4 ? k_step_psf4<4, SC_BMAX> : k_step_psf4<SC_KMAX, SC_BMAX>, a, st);
+    else if (b->K <= 4)
+        launch_grad_step(k_grad_psf<4, SC_BMAX>, k_step_psf<4, SC_BMAX>, a, st);
+    else
+        launch_grad_step(k_grad_psf<SC_KMAX, SC_BMAX>, k_step_psf<SC_KMAX, SC_BMAX>, a, st);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
@@ -1570,109 +1646,75 @@ extern "C" int scarlet_convolve_same(const float *model, int n, int H, int W, co
     FftPlans pm, pk;
     int rc;
     if ((rc = get_plans(g.Fy, g.Fx, n, &pm)) == SCARLET_OK && (rc = get_plans(g.Fy, g.Fx, nk, &pk)) == SCARLET_OK &&
-        (rc = fft_r2c(pm, real, spec, st)) == SCARLET_OK && (rc = fft_r2c(pk, kreal, kspec, st)) == SCARLET_OK) {
-        hipLaunchKernelGGL(k_spec_mul, dim3(grid_for(n * splane)), dim3(SC_BLOCK), 0, st, spec, kspec, nk, (int)splane,
-                           n * splane, 0, 1.0f / ((float)g.Fy * (float)g.Fx));
-        if ((rc = fft_c2r(pm, spec, real, st)) == SCARLET_OK)
-            hipLaunchKernelGGL(k_plane_crop, dim3(grid_for((int64_t)n * H * W)), dim3(SC_BLOCK), 0, st, real, n, H, W,
-                               g.Fy, g.Fx, g.oy, g.ox, out);
-    }
+        (rc = hipfft_convolve(pm, real, spec, kspec, nk, n, (int)splane, 0, 1.0f / ((float)g.Fy * (float)g.Fx), st,
+                              [&] { return fft_r2c(pk, kreal, kspec, st); })) == SCARLET_OK)
+        hipLaunchKernelGGL(k_plane_crop, dim3(grid_for((int64_t)n * H * W)), dim3(SC_BLOCK), 0, st, real, n, H, W,
+                           g.Fy, g.Fx, g.oy, g.ox, out);
     const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);    // buffers outlive the kernels
     if (rc) return rc;
     HIP_TRY(e1); HIP_TRY(e2);
     return SCARLET_OK;
 }
 
-// raw_gradient = 0: buffer 1-cur receives the stepped factors; 1: the gradients themselves
-static int backward_impl(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, void *stream)
+// The gradient step for SC_KMAX < K <= SC_KBIG without a PSF: passes over chunks of eight components (bigk.h), in one of
+// three forms
+static int backward_bigk(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, hipStream_t st)
 {
+    const GradArgs a = grad_args(b, l, approximate_L, raw_gradient);
+    const int nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
+    float *resid = ws_at<float>(b, l.gplanes);
     int rc;
-    if (b->diff_kernel)            // (a kernel without a size has no PSF area in the workspace)
-        return l.psf ? backward_step_psf(b, l, approximate_L, raw_gradient, stream)
-                     : set_err(SCARLET_E_ARG, "diff_kernel without psf_h, psf_w");
-    GradArgs a = grad_args(b, l, approximate_L, raw_gradient);
-    dim3 grid(a.T, a.S);
-    hipStream_t st = (hipStream_t)stream;
-    if (l.grad == GRAD_HUGEK) return backward_hugek(b, l, approximate_L, raw_gradient, nullptr, nullptr, st);
-    if (l.grad == GRAD_BIGK) {
-        // many components per scene: passes over chunks of eight (bigk.h)
-        const int nch = (b->K + SC_CHUNK - 1) / SC_CHUNK;
-        float *resid = ws_at<float>(b, l.gplanes);
-        SideStream *side = nullptr;
-        if (!opt(OPT_NO_SIDE_STREAM) && (rc = side_stream(&side))) return rc;
-        if (!approximate_L && (a.HW & 63) == 0 && !opt(OPT_NO_BIGK_FUSED)) {
-            // residual + morphology step + SED-gradient sums in one pass on the matrix cores (k_bigk_fused); the Gram
-            // matrix and its eigenvalue beside it on the second stream:
-            //   stream : lmorph . fused ..... (join) sed (+ loss record)
-            //   side   : gram . lipschitz           (exact constants do not need the loss)
-            if (side) {
-                HIP_TRY(hipEventRecord(side->ev[0], st));
-                HIP_TRY(hipStreamWaitEvent(side->st, side->ev[0], 0));
-                launch_bigk_gram(a, nch, side->st);
-                hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, side->st, a, 2);
-                HIP_TRY(hipEventRecord(side->ev[2], side->st));
-            }
-            prof_start(0, st);
-            hipLaunchKernelGGL(k_bigk_lmorph<SC_KBIG>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
-            prof_stop(st); prof_start(1, st);
-            hipLaunchKernelGGL(k_bigk_fused, grid, dim3(SC_BLOCK), 0, st, a);
-            if (side) HIP_TRY(hipStreamWaitEvent(st, side->ev[2], 0));
-            else {
-                launch_bigk_gram(a, nch, st);
-                hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 2);
-            }
-            hipLaunchKernelGGL(k_bigk_sed, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 1);
-            prof_stop(st);
-            HIP_TRY(hipGetLastError());
-            return SCARLET_OK;
-        }
-        if (side) {
-            // The morphology step needs the residual planes and lambda_max(A^T A) only; the Gram matrix S S^T and
-            // its largest eigenvalue (for the SED step) run beside it on a second stream:
-            //   stream : resid . lmorph . step ............ (join) sed
-            //   side   : gram ......... (after resid: loss) lipschitz
-            HIP_TRY(hipEventRecord(side->ev[0], st));
-            HIP_TRY(hipStreamWaitEvent(side->st, side->ev[0], 0));
-            launch_bigk_gram(a, nch, side->st);
-            prof_start(0, st);
-            hipLaunchKernelGGL(k_bigk_resid<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a, resid);
-            HIP_TRY(hipEventRecord(side->ev[1], st));
-            HIP_TRY(hipStreamWaitEvent(side->st, side->ev[1], 0));
-            hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, side->st, a, 1);
-            HIP_TRY(hipEventRecord(side->ev[2], side->st));
-            hipLaunchKernelGGL(k_bigk_lmorph<SC_KBIG>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
-            prof_stop(st); prof_start(1, st);
-            launch_bigk_step(a, nch, resid, st);
-            HIP_TRY(hipStreamWaitEvent(st, side->ev[2], 0));
-            hipLaunchKernelGGL(k_bigk_sed, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 0);
-            prof_stop(st);
-            HIP_TRY(hipGetLastError());
-            return SCARLET_OK;
-        }
+    SideStream *side = nullptr;
+    if (!opt(OPT_NO_SIDE_STREAM) && (rc = side_stream(&side))) return rc;
+    if (!approximate_L && (a.HW & 63) == 0 && !opt(OPT_NO_BIGK_FUSED)) {
+        // residual + morphology step + SED-gradient sums in one pass on the matrix cores (k_bigk_fused); the Gram
+        // matrix and its eigenvalue beside it on the second stream:
+        //   stream : lmorph . fused ..... (join) sed (+ loss record)
+        //   side   : gram . lipschitz           (exact constants do not need the loss)
+        if (side && (rc = bigk_lipschitz_beside(side, a, nch, 2, st, [] { return false; }))) return rc;
         prof_start(0, st);
-        hipLaunchKernelGGL(k_bigk_resid<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a, resid);
-        launch_bigk_gram(a, nch, st);
-        hipLaunchKernelGGL(k_bigk_lipschitz, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 0);
+        hipLaunchKernelGGL(k_bigk_lmorph<SC_KBIG>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
         prof_stop(st); prof_start(1, st);
-        launch_bigk_step(a, nch, resid, st);
-        hipLaunchKernelGGL(k_bigk_sed, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 0);
+        hipLaunchKernelGGL(k_bigk_fused, dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a);
+        if (side) HIP_TRY(hipStreamWaitEvent(st, side->ev[2], 0));
+        else launch_bigk_lipschitz(a, nch, 2, st);
+        hipLaunchKernelGGL(k_bigk_sed, dim3(a.S), dim3(SC_BLOCK), 0, st, a, 1);
         prof_stop(st);
         HIP_TRY(hipGetLastError());
         return SCARLET_OK;
     }
-    if (b->K <= 4) {
-        prof_start(0, st);
-        hipLaunchKernelGGL((k_grad<4, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st); prof_start(1, st);
-        hipLaunchKernelGGL((k_step<4, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st);
+    auto launch_resid = [&] {
+        hipLaunchKernelGGL(k_bigk_resid<SC_KBIG>, dim3(a.T, a.S), dim3(SC_BLOCK), 0, st, a, resid);
+        return true;
+    };
+    prof_start(0, st);
+    if (side) {
+        // The morphology step needs the residual planes and lambda_max(A^T A) only; the Gram matrix S S^T and
+        // its largest eigenvalue (for the SED step) run beside it on a second stream:
+        //   stream : resid . lmorph . step ............ (join) sed
+        //   side   : gram ......... (after resid: loss) lipschitz
+        if ((rc = bigk_lipschitz_beside(side, a, nch, 1, st, launch_resid))) return rc;
+        hipLaunchKernelGGL(k_bigk_lmorph<SC_KBIG>, dim3(a.S), dim3(SC_WAVE), 0, st, a);
     } else {
-        prof_start(0, st);
-        hipLaunchKernelGGL((k_grad<SC_KMAX, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st); prof_start(1, st);
-        hipLaunchKernelGGL((k_step<SC_KMAX, SC_BMAX>), grid, dim3(SC_BLOCK), 0, st, a);
-        prof_stop(st);
+        launch_resid();
+        launch_bigk_lipschitz(a, nch, 0, st);
     }
+    prof_stop(st);
+    return bigk_step_sed(a, nch, resid, side, st);
+}
+
+// raw_gradient = 0: buffer 1-cur receives the stepped factors; 1: the gradients themselves
+static int backward_impl(scarlet_batch *b, const WsLayout &l, int approximate_L, int raw_gradient, void *stream)
+{
+    if (b->diff_kernel)            // (a kernel without a size has no PSF area in the workspace)
+        return l.psf ? backward_step_psf(b, l, approximate_L, raw_gradient, stream)
+                     : set_err(SCARLET_E_ARG, "diff_kernel without psf_h, psf_w");
+    hipStream_t st = (hipStream_t)stream;
+    if (l.grad == GRAD_HUGEK) return backward_hugek(b, l, approximate_L, raw_gradient, nullptr, nullptr, st);
+    if (l.grad == GRAD_BIGK) return backward_bigk(b, l, approximate_L, raw_gradient, st);
+    const GradArgs a = grad_args(b, l, approximate_L, raw_gradient);
+    if (b->K <= 4) launch_grad_step(k_grad<4, SC_BMAX>, k_step<4, SC_BMAX>, a, st);
+    else launch_grad_step(k_grad<SC_KMAX, SC_BMAX>, k_step<SC_KMAX, SC_BMAX>, a, st);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
@@ -2186,101 +2228,12 @@ extern "C" int scarlet_lowres_adjoint(const float *resid, int n, int H, int W, c
 }
 
 // ---- several observations per blend (multiobs.h)
-// G planes of an observation with a PSF: model planes from the STATE's morphologies and the observation's band slice
-// of the SEDs (its own buffer sed[0], filled by k_obs_slice), then the convolution chain of backward_step_psf up to the
-// adjoint.  `v` receives where the planes and the per-plane losses lie.
-static int obs_psf_planes(scarlet_batch *ob, const WsLayout &l, const scarlet_batch *state, hipStream_t st, ObsView *v)
-{
-    const PsfGeom &g = l.geom;
-    PsfArgs a = {};
-    a.S = ob->S; a.K = ob->K; a.B = ob->B; a.T = n_tiles(ob); a.g = g;
-    a.images = ob->images; a.weights = ob->weights; a.weight_scalar = ob->weight_scalar;
-    a.sed[0] = a.sed[1] = ob->sed[0];
-    a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
-    a.cur = state->cur; a.active = state->active; a.it = state->it;
-    a.real = ws_at<float>(ob, l.real); a.spec = ws_at<float2>(ob, l.spec); a.khat = ws_at<const float2>(ob, l.khat);
-    a.partials = ws_at<double>(ob, l.partials); a.loss_part = ws_at<double>(ob, l.loss);
-    a.lipschitz = ob->lipschitz; a.mse = ob->mse; a.mse_capacity = ob->mse_capacity;
-    a.khat_per_scene = ob->diff_kernel_per_scene;
-    const int HW = ob->H * ob->W, planes = ob->S * ob->B;
-    const bool huge = ob->K > SC_KBIG;
-    int rc;
-    v->G = a.real; v->loss_part = a.loss_part;
-    if (l.psf_lds) {
-        FftPlan fp = l.plan;
-        fp.tables = ws_at<const float2>(ob, l.lds_tables);
-        a.khat = ws_at<const float2>(ob, l.lds_khat);
-        const bool x128 = psf_conv_finish_plan(ob, &fp);
-        const size_t lds = fft_lds_bytes(fp.Fy, fp.M, fp.RS, ob->H, ob->W, fp.dma_image != 0);
-        if ((rc = allow_lds(k_psf_conv, lds))) return rc;
-        a.g.Fy = ob->H; a.g.Fx = ob->W; a.g.Fxh = ob->W / 2 + 1; a.g.oy = 0; a.g.ox = 0;
-        if (HW % 4 == 0) {
-            const dim3 grid((HW / 4 + SC_BLOCK - 1) / SC_BLOCK, ob->S);
-            if (huge) hipLaunchKernelGGL(k_psf_model4<SC_KHUGE>, grid, dim3(SC_BLOCK), 0, st, a);
-            else hipLaunchKernelGGL(k_psf_model4<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a);
-        } else {
-            const dim3 grid((HW + SC_BLOCK - 1) / SC_BLOCK, ob->S);
-            if (huge) hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, grid, dim3(SC_BLOCK), 0, st, a);
-            else hipLaunchKernelGGL(k_psf_model<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a);
-        }
-        long long *stamps = opt(OPT_STAMPS) ? ws_at<long long>(ob, l.stamps) : nullptr;
-        fp.stagger_wgs = 0;
-        const int groups = (ob->S + 7) / 8;
-        if (x128) {
-            const size_t lds_x = fft_lds_bytes(fp.Fy, fp.M, fp.RS, ob->H, ob->W, SC_X128_DMA != 0);
-            if ((rc = allow_lds(k_psf_conv_x128, lds_x))) return rc;
-            hipLaunchKernelGGL(k_psf_conv_x128, dim3(groups * 8 * ob->B), dim3(SC_FFT_NT_X), lds_x, st, a, fp, a.real, stamps);
-        } else
-            hipLaunchKernelGGL(k_psf_conv, dim3(groups * 8 * ob->B), dim3(SC_FFT_NT), lds, st, a, fp, a.real, stamps);
-        v->Fy = ob->H; v->Fx = ob->W; v->oy = 0; v->ox = 0;
-    } else {
-        FftPlans p;
-        if ((rc = get_plans(g.Fy, g.Fx, planes, &p))) return rc;
-        const int plane_elems = g.Fy * g.Fxh;
-        const float scale = 1.0f / ((float)g.Fy * (float)g.Fx);
-        const int nkh = ob->diff_kernel_per_scene ? planes : ob->B;
-        const dim3 grid((g.Fy * g.Fx + SC_BLOCK - 1) / SC_BLOCK, ob->S);
-        if (huge) hipLaunchKernelGGL(k_psf_model<SC_KHUGE>, grid, dim3(SC_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL(k_psf_model<SC_KBIG>, grid, dim3(SC_BLOCK), 0, st, a);
-        if ((rc = fft_r2c(p, a.real, a.spec, st))) return rc;
-        hipLaunchKernelGGL(k_spec_mul, dim3(grid_for((int64_t)planes * plane_elems)), dim3(SC_BLOCK), 0, st,
-                           a.spec, a.khat, nkh, plane_elems, (int64_t)planes * plane_elems, 0, scale);
-        if ((rc = fft_c2r(p, a.spec, a.real, st))) return rc;
-        hipLaunchKernelGGL(k_psf_resid, dim3(planes), dim3(SC_BLOCK), 0, st, a);
-        if ((rc = fft_r2c(p, a.real, a.spec, st))) return rc;
-        hipLaunchKernelGGL(k_spec_mul, dim3(grid_for((int64_t)planes * plane_elems)), dim3(SC_BLOCK), 0, st,
-                           a.spec, a.khat, nkh, plane_elems, (int64_t)planes * plane_elems, 1, scale);
-        if ((rc = fft_c2r(p, a.spec, a.real, st))) return rc;
-        v->Fy = g.Fy; v->Fx = g.Fx; v->oy = g.oy; v->ox = g.ox;
-    }
-    HIP_TRY(hipGetLastError());
-    return SCARLET_OK;
-}
-
 // L_sed of the state's current morphologies (blend.py:186-218, before the factor n_obs): the Gram matrix and its largest
 // eigenvalue by the existing code of the K range, or its trace with approximate constants
 static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const GradArgs &ga, int approximate_L, hipStream_t st)
 {
-    if (l.grad == GRAD_HUGEK) {
-        HugeArgs h;
-        h.C = huge_nchunks(state->H * state->W);
-        h.gpart = ws_at<double>(state, l.gpart); h.gram = ws_at<double>(state, l.gram);
-        h.msq[0] = ws_at<double>(state, l.msq[0]); h.msq[1] = ws_at<double>(state, l.msq[1]);
-        const int nb = huge_nblk(state->K), npairs = huge_npairs(state->K);
-        if ((ga.HW & 3) == 0) hipLaunchKernelGGL((k_huge_gram<true>), dim3(h.C, npairs, ga.S), dim3(SC_BLOCK), 0, st, ga, h);
-        else hipLaunchKernelGGL((k_huge_gram<false>), dim3(h.C, npairs, ga.S), dim3(SC_BLOCK), 0, st, ga, h);
-        hipLaunchKernelGGL(k_huge_gram_reduce, dim3(npairs, ga.S), dim3(SC_BLOCK), 0, st, ga, h);
-        const double *last = h.gram;
-        if (!approximate_L)
-            for (int q = 0; q < SC_HUGE_SQUARINGS; ++q) {
-                hipLaunchKernelGGL(k_huge_square, dim3(nb, nb, ga.S), dim3(SC_BLOCK), 0, st, ga, last, h.msq[q & 1]);
-                last = h.msq[q & 1];
-            }
-        hipLaunchKernelGGL(k_huge_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, h, last);
-    } else {
-        launch_bigk_gram(ga, (state->K + SC_CHUNK - 1) / SC_CHUNK, st);
-        hipLaunchKernelGGL(k_bigk_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, approximate_L ? 1 : 2);
-    }
+    if (l.grad == GRAD_HUGEK) launch_huge_lipschitz(ga, huge_args(state, l), approximate_L, st);
+    else launch_bigk_lipschitz(ga, (state->K + SC_CHUNK - 1) / SC_CHUNK, approximate_L ? 1 : 2, st);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
@@ -2353,7 +2306,11 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
             }
             if (!lo[o].psf) continue;
             hipLaunchKernelGGL(k_obs_slice, dim3(m.S), dim3(SC_BLOCK), 0, st, m, band0[o], obs[o]->B, obs[o]->sed[0]);
-            if ((rc = obs_psf_planes(obs[o], lo[o], state, st, &m.obs[o]))) return rc;
+            // model planes from the STATE's morphologies and the observation's band slice of the SEDs (its own sed[0])
+            PsfArgs a = psf_args(obs[o], lo[o], state, obs[o]->sed[0], obs[o]->sed[0], nullptr, nullptr, 0, 0);
+            if ((rc = psf_gradient_planes(obs[o], lo[o], a, PSF_MODEL_PLAIN, st))) return rc;
+            ObsView &v = m.obs[o];
+            v.G = a.real; v.loss_part = a.loss_part; v.Fy = a.g.Fy; v.Fx = a.g.Fx; v.oy = a.g.oy; v.ox = a.g.ox;
         }
         prof_stop(st); prof_start(1, st);
         if (!approximate_L) {

@@ -72,10 +72,11 @@ def oracle_fit(args):
     from oracle import pgm
     images, sed0, morph0, cen0, sh0, iters, e_rel, dt, okw = args
     okw = dict(okw)
+    approx = okw.pop("approximate_L", False)
     if okw.get("diff_kernel") is not None:
         okw["diff_kernel"] = okw["diff_kernel"].astype(dt)
     sc = pgm.scene_from_state(images.astype(dt), sed0.astype(dt), morph0.astype(dt), cen0, sh0, **okw)
-    pgm.fit(sc, iters, e_rel=e_rel)
+    pgm.fit(sc, iters, e_rel=e_rel, approximate_L=approx)
     return (np.array([s.sed for s in sc.sources]), np.array([s.morph for s in sc.sources]), np.array(sc.mse),
             np.array([s.center for s in sc.sources]), len(sc.mse), [int(s.flags) for s in sc.sources])
 
@@ -84,13 +85,14 @@ def oracle_trace(images, sed0, morph0, cen0, sh0, iters, dt, okw):
     """per-iteration (morph after the iteration, morph as prox_plus saw it) of one scene"""
     from oracle import pgm
     okw = dict(okw)
+    approx = okw.pop("approximate_L", False)
     if okw.get("diff_kernel") is not None:
         okw["diff_kernel"] = okw["diff_kernel"].astype(dt)
     sc = pgm.scene_from_state(images.astype(dt), sed0.astype(dt), morph0.astype(dt), cen0, sh0, **okw)
     for s in sc.sources:
         s.trace = dict(step=[], pre_plus=[])
     post = []
-    pgm.fit(sc, iters, e_rel=0, callback=lambda scn: post.append(np.array([s.morph.copy() for s in scn.sources])))
+    pgm.fit(sc, iters, e_rel=0, approximate_L=approx, callback=lambda scn: post.append(np.array([s.morph.copy() for s in scn.sources])))
     pre = [(np.array([s.trace["step"][t] for s in sc.sources]), np.array([s.trace["pre_plus"][t] for s in sc.sources]))
            for t in range(iters)]
     return post, pre
@@ -101,12 +103,13 @@ def gpu_fit(scarlet, wl, images, centers, iters, e_rel, per_iteration=False, che
     b = wl.batch(scarlet, images, centers, iters + 1)
     st0 = [t.cpu().numpy() for t in (b.sed_current, b.morph_current, b.centers, b.shifts)]
     snaps = []
+    approx = bool(wl.oracle_kwargs().get("approximate_L"))       # (a workload may ask for the approximate constants)
     if per_iteration:
         for _ in range(iters):
-            b.fit(1, e_rel=e_rel)
+            b.fit(1, e_rel=e_rel, approximate_L=approx)
             snaps.append(b.morph_current.cpu().numpy().copy())
     else:
-        b.fit(iters, e_rel=e_rel, check_every=check_every)
+        b.fit(iters, e_rel=e_rel, approximate_L=approx, check_every=check_every)
     torch.cuda.synchronize()
     out = dict(sed=b.sed_current.cpu().numpy(), morph=b.morph_current.cpu().numpy(), cen=b.centers.cpu().numpy(),
                it=b.it.cpu().numpy(), flags=b.flags.cpu().numpy(), mse=b.mse_buf.cpu().numpy(), snaps=snaps,
