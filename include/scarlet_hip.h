@@ -97,7 +97,10 @@ const char *scarlet_last_error(void);
  * NO_HYBRID_SWEEP, PAD_LDS, STAMPS, PSF_HIPFFT, NO_BOX, NO_BOX2, NO_PSF3PASS, NO_SIDE_STREAM,
  * NO_GRAM_MFMA, NO_BIGK_FUSED, NO_PIPELINE, NO_PERSIST (one launch per iteration instead of k_fit2x),
  * PERSIST_DBG, NO_PLACE (component k on waves 2k, 2k + 1 of k_fit2x / k_iterate2<4,5,64>, not placed by
- * GEMM cost), NO_LOWRES_MFMA (the GEMMs of a low-resolution observation as plain FMA chains, bit-identical).  Each starts from the environment variable SCARLET_<NAME>, read once at first use;
+ * GEMM cost), NO_LOWRES_MFMA (the GEMMs of a low-resolution observation as plain FMA chains, bit-identical),
+ * LOWRES_STREAMED (the *_large low-resolution entry points take the streamed form for shapes that fit LDS as well),
+ * LOWRES_CHUNK (planes per chunk of the streamed form, 0 = automatic; it can only lower the chunk; the one switch whose
+ * value is a count: scarlet_set_option returns its previous value, negative values are SCARLET_E_ARG).  Each starts from the environment variable SCARLET_<NAME>, read once at first use;
  * afterwards only this call changes it.  Returns the previous value (0 / 1) or SCARLET_E_ARG for an
  * unknown name.  None changes results beyond float32 rounding.
  * PSF_HIPFFT and STAMPS decide the layout of a PSF batch's workspace: they are frozen by the first
@@ -435,7 +438,8 @@ int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_con
  * odd lengths) against 159 KiB.  With an 11-pixel model PSF and images of half the model's side: a 64 x 64 model frame
  * (72-point padded plane, nfy = 19, nfx = 37) with 32 x 32 images takes 133 KiB at B = 8 bands; 72 x 72 with 36 x 36
  * (75 x 80-point plane, nfy = 19, nfx = 41) still fits at B = 8 (156 KiB), 76 x 76 with 38 x 38 up to B = 6 (158 KiB),
- * 84 x 84 with 42 x 42 up to B = 2 (158 KiB); beyond: SCARLET_E_NOTIMPL. */
+ * 84 x 84 with 42 x 42 up to B = 2 (158 KiB); beyond: SCARLET_E_NOTIMPL from the LDS-resident entry points, the
+ * streamed form from the *_large ones (below). */
 typedef struct scarlet_lowres {
     int32_t h, w;               /* the observation's pixel grid: images and weights are [S][B][h][w]                */
     int32_t nfy, nfx;           /* retained frequencies per axis (rows of uy / ux)                                  */
@@ -477,6 +481,35 @@ int scarlet_lowres_render(const float *model, int n, int H, int W, const scarlet
                           const int32_t *scene, float *out, void *stream);
 int scarlet_lowres_adjoint(const float *resid, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
                            const int32_t *scene, float *out, void *stream);
+
+/* The four entry points above are the LDS-RESIDENT form: they end where the factor matrices and one model plane leave
+ * LDS (SCARLET_E_NOTIMPL).  The *_large entry points below take every shape those take and every larger one up to
+ * SCARLET_MAX_SIDE a side.  Where the shape fits LDS (and the LOWRES_STREAMED switch is off) they launch the same
+ * kernels, bit-identical to the calls above; beyond, the STREAMED form (csrc/lowres_stream.h): the same sandwich on the
+ * same stacked real operands with the same k-ordered float32 sums as a chain of batched GEMMs over many planes at once
+ * (k_lrs_gemm: v_mfma_f32_16x16x4_f32, operands staged through LDS in K-steps, grid = (output tiles, planes)), the
+ * intermediates in a scratch area in HBM, planes taken in chunks that keep the scratch below 256 MiB.  A fit projects
+ * the B band models sum_k sed[k][c] m_k instead of the K components, so its cost does not depend on K.
+ *
+ * bytes of `lr->workspace` for scarlet_fit_observations_lowres_large: the gradient planes, the per-plane losses and
+ * ALWAYS the scratch of the streamed form (a switch changed between sizing and fitting cannot write past it); < 0: an
+ * error code */
+int64_t scarlet_lowres_large_workspace_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr);
+/* scarlet_fit_observations_lowres without the LDS limit; every lowres[i]->workspace holds
+ * scarlet_lowres_large_workspace_bytes().  Shapes, null pointers, B <= 8 and sides <= SCARLET_MAX_SIDE are checked on
+ * the host before any launch. */
+int scarlet_fit_observations_lowres_large(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                          const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                          int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+/* bytes of device scratch scarlet_lowres_render_large / _adjoint_large need for n planes: 0 where the LDS form runs;
+ * < 0: an error code */
+int64_t scarlet_lowres_op_scratch_bytes(int n, int H, int W, const scarlet_lowres *lr);
+/* scarlet_lowres_render / _adjoint without the LDS limit; `scratch` (device, scratch_bytes long; may be NULL when
+ * scarlet_lowres_op_scratch_bytes() is 0).  A scratch that is too small is SCARLET_E_ARG before any launch. */
+int scarlet_lowres_render_large(const float *model, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                                const int32_t *scene, float *out, void *scratch, int64_t scratch_bytes, void *stream);
+int scarlet_lowres_adjoint_large(const float *resid, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                                 const int32_t *scene, float *out, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

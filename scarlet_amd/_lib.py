@@ -151,6 +151,12 @@ _SIGNATURES = {
                                                 POINTER(POINTER(ScarletLowres)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
     "scarlet_lowres_render": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P]),
     "scarlet_lowres_adjoint": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P]),
+    "scarlet_lowres_large_workspace_bytes": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres)]),
+    "scarlet_fit_observations_lowres_large": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(POINTER(ScarletBatch)),
+                                                      POINTER(POINTER(ScarletLowres)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
+    "scarlet_lowres_op_scratch_bytes": (c_int64, [c_int, c_int, c_int, POINTER(ScarletLowres)]),
+    "scarlet_lowres_render_large": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P, c_int64, _P]),
+    "scarlet_lowres_adjoint_large": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P, c_int64, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

@@ -372,7 +372,8 @@ class BlendBatch(object):
 
     def _lib_fit_observations(self, batches, band0, max_iter, e_rel, approximate_L, check_every, lowres=None):
         """`batches`: the observations' gradient batches, `band0`: their first model channels, `lowres`: None, or per
-        observation None / (scarlet_lowres, ...) for a low-resolution one (scarlet_fit_observations_lowres)."""
+        observation None / (scarlet_lowres, ...) for a low-resolution one (scarlet_fit_observations_lowres_large: the
+        LDS-resident kernels where the model frame lets them, the streamed form beyond)."""
         n = len(batches)
         ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for ob in batches])
         band0 = np.array(band0, dtype=np.int32)
@@ -381,7 +382,7 @@ class BlendBatch(object):
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[ctypes.pointer(x[0]) if x is not None else
                                                               ctypes.POINTER(_lib.ScarletLowres)() for x in lowres])
             self._keep += (lows,)
-            return _lib.check(_lib.lib.scarlet_fit_observations_lowres(
+            return _lib.check(_lib.lib.scarlet_fit_observations_lowres_large(
                 ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, lows, band0.ctypes.data_as(ctypes.c_void_p), n,
                 int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
         return _lib.check(_lib.lib.scarlet_fit_observations_constrained(
@@ -793,8 +794,8 @@ class BlendBatch(object):
             ob._fill_struct()
             if low:
                 lr, keep = o.lowres_struct(state.device)
-                nbytes = _lib.check(_lib.lib.scarlet_lowres_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c),
-                                                                            ctypes.byref(lr)))
+                nbytes = _lib.check(_lib.lib.scarlet_lowres_large_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c),
+                                                                                  ctypes.byref(lr)))
                 keep["workspace"] = torch.empty((int(nbytes),), dtype=torch.uint8, device=state.device)
                 lr.workspace = keep["workspace"].data_ptr()
                 state._lowres[i] = (lr, keep)

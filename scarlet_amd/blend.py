@@ -138,7 +138,7 @@ class Blend(ComponentTree):
                 return None
             from .batch import LowResObservationBatch
             lr, keep = LowResObservationBatch(o.images[None], band0=o._band_slice.start or 0, geometry=o).lowres_struct(state.device)
-            nbytes = _lib.check(_lib.lib.scarlet_lowres_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c), ctypes.byref(lr)))
+            nbytes = _lib.check(_lib.lib.scarlet_lowres_large_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c), ctypes.byref(lr)))
             keep["workspace"] = torch.empty((int(nbytes),), dtype=torch.uint8, device=state.device)
             lr.workspace = keep["workspace"].data_ptr()
             return lr, keep

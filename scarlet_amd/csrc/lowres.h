@@ -21,7 +21,8 @@
 // in turn; operands outside the matrices are read as zero, so ragged edges need no second code path.  The
 // NO_LOWRES_MFMA switch runs the same sums as plain FMA chains (bit-identical; diagnostics).
 // All factor matrices and intermediates stay in LDS; leading dimensions are odd so that the 16 lanes that walk a column
-// fall on different banks.
+// fall on different banks.  This is the LDS-RESIDENT form, up to 64 x 64 model frames at 8 bands (84 x 84 at 2); beyond,
+// the *_large entry points run the STREAMED form of lowres_stream.h: the same sums as batched GEMMs through HBM scratch.
 #pragma once
 #include "common.h"
 

@@ -28,6 +28,7 @@
 #include "initsrc.h"
 #include "multiobs.h"
 #include "lowres.h"
+#include "lowres_stream.h"
 #include "prior.h"
 
 __constant__ unsigned short sc_nfl_table[SC_NFL_MAX];
@@ -54,10 +55,10 @@ extern "C" const char *scarlet_version(void) { return "scarlet_amd-hip 0.2 (gfx9
 // environment (SCARLET_<NAME>) at first use and changed afterwards only through scarlet_set_option.
 // None of them changes results beyond float32 rounding.
 enum { OPT_NO_EXACT = 0, OPT_NO_KSCACHE, OPT_FUSED_V1, OPT_NO_FUSED, OPT_FORCE_BLOCK_UPDATE, OPT_NO_HYBRID_SWEEP,
-       OPT_PAD_LDS, OPT_STAMPS, OPT_PSF_HIPFFT, OPT_NO_BOX, OPT_NO_BOX2, OPT_NO_PSF3PASS, OPT_NO_SIDE_STREAM, OPT_NO_GRAM_MFMA, OPT_NO_BIGK_FUSED, OPT_NO_PIPELINE, OPT_NO_PERSIST, OPT_PERSIST_DBG, OPT_FORCE_HUGEK, OPT_NO_PLACE, OPT_NO_LOWRES_MFMA, OPT_COUNT };
+       OPT_PAD_LDS, OPT_STAMPS, OPT_PSF_HIPFFT, OPT_NO_BOX, OPT_NO_BOX2, OPT_NO_PSF3PASS, OPT_NO_SIDE_STREAM, OPT_NO_GRAM_MFMA, OPT_NO_BIGK_FUSED, OPT_NO_PIPELINE, OPT_NO_PERSIST, OPT_PERSIST_DBG, OPT_FORCE_HUGEK, OPT_NO_PLACE, OPT_NO_LOWRES_MFMA, OPT_LOWRES_STREAMED, OPT_LOWRES_CHUNK, OPT_COUNT };
 static const char *const g_opt_names[OPT_COUNT] = {"NO_EXACT", "NO_KSCACHE", "FUSED_V1", "NO_FUSED", "FORCE_BLOCK_UPDATE",
                                                    "NO_HYBRID_SWEEP", "PAD_LDS", "STAMPS", "PSF_HIPFFT", "NO_BOX", "NO_BOX2",
-                                                   "NO_PSF3PASS", "NO_SIDE_STREAM", "NO_GRAM_MFMA", "NO_BIGK_FUSED", "NO_PIPELINE", "NO_PERSIST", "PERSIST_DBG", "FORCE_HUGEK", "NO_PLACE", "NO_LOWRES_MFMA"};
+                                                   "NO_PSF3PASS", "NO_SIDE_STREAM", "NO_GRAM_MFMA", "NO_BIGK_FUSED", "NO_PIPELINE", "NO_PERSIST", "PERSIST_DBG", "FORCE_HUGEK", "NO_PLACE", "NO_LOWRES_MFMA", "LOWRES_STREAMED", "LOWRES_CHUNK"};
 static std::atomic<int> g_opt[OPT_COUNT];
 static std::once_flag g_opt_once;
 static void options_init(void)
@@ -95,6 +96,10 @@ extern "C" int scarlet_set_option(const char *name, int value)
             if ((i == OPT_PSF_HIPFFT || i == OPT_STAMPS) && g_layout_frozen.load() && (g_opt[i].load() != 0) != (value != 0))
                 return set_err(SCARLET_E_ARG, "PSF_HIPFFT / STAMPS fix the workspace layout of PSF batches: they cannot change "
                                               "after the first PSF workspace of the process was sized");
+            if (i == OPT_LOWRES_CHUNK) {            // (the one switch that is a count: planes per chunk, 0 = automatic)
+                if (value < 0) return set_err(SCARLET_E_ARG, "LOWRES_CHUNK: planes per chunk, 0 = automatic");
+                return g_opt[i].exchange(value);
+            }
             return g_opt[i].exchange(value) != 0 ? 1 : 0;
         }
     return set_err(SCARLET_E_ARG, "unknown option");
@@ -2167,7 +2172,7 @@ static int64_t lowres_loss_offset(const scarlet_batch *state, const scarlet_batc
     return (g + 15) & ~(int64_t)15;
 }
 // shapes, pointers and limits of one scarlet_lowres for a model frame of H x W and B bands; no device call
-static int check_lowres(const scarlet_lowres *lr, int H, int W, int B, bool need_workspace)
+static int check_lowres(const scarlet_lowres *lr, int H, int W, int B, bool need_workspace, bool large = false)
 {
     if (!lr) return set_err(SCARLET_E_ARG, "null scarlet_lowres");
     if (lr->h < 1 || lr->w < 1 || lr->nfy < 1 || lr->nfx < 1 || H < 1 || W < 1 || B < 1 || lr->B != B)
@@ -2176,8 +2181,11 @@ static int check_lowres(const scarlet_lowres *lr, int H, int W, int B, bool need
         return set_err(SCARLET_E_ARG, "scarlet_lowres: null factor matrix");
     if (need_workspace && !lr->workspace) return set_err(SCARLET_E_ARG, "scarlet_lowres: null workspace");
     if (B > SC_BMAX) return set_err(SCARLET_E_NOTIMPL, "B > 8 bands is not supported by this build of the gradient kernels");
-    if (H > SCARLET_MAX_SIDE || W > SCARLET_MAX_SIDE || lr->h > SCARLET_MAX_SIDE || lr->w > SCARLET_MAX_SIDE ||
-        lr->nfy > SCARLET_MAX_SIDE || lr->nfx > 2 * SCARLET_MAX_SIDE)
+    const bool sides = H > SCARLET_MAX_SIDE || W > SCARLET_MAX_SIDE || lr->h > SCARLET_MAX_SIDE || lr->w > SCARLET_MAX_SIDE ||
+                       lr->nfy > SCARLET_MAX_SIDE || lr->nfx > 2 * SCARLET_MAX_SIDE;
+    if (large)           // (the streamed form of lowres_stream.h takes over where LDS ends)
+        return sides ? set_err(SCARLET_E_NOTIMPL, "scarlet_lowres: sides above SCARLET_MAX_SIDE are not supported") : SCARLET_OK;
+    if (sides)
         return set_err(SCARLET_E_NOTIMPL, "scarlet_lowres: the factor matrices and one model plane do not fit LDS");
     LowresDims d;
     d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = B;
@@ -2227,6 +2235,183 @@ extern "C" int scarlet_lowres_adjoint(const float *resid, int n, int H, int W, c
     return lowres_op(true, resid, n, H, W, lr, band, scene, out, stream);
 }
 
+// ---- the streamed form (lowres_stream.h): one launch per product over the planes of a chunk
+static bool lowres_fits_lds(const LowresDims &d) { return lowres_lds_bytes(d) <= LDS_LIMIT; }
+// the form a call of the *_large entry points takes: the LDS-resident kernels wherever they fit, unless LOWRES_STREAMED
+static bool lowres_streamed(const LowresDims &d) { return opt(OPT_LOWRES_STREAMED) || !lowres_fits_lds(d); }
+static LrsOperand lrs_real(const float *p, int rs, int cs, size_t plane)
+{
+    LrsOperand o = {p, rs, cs, 0, 0, plane, 0};
+    return o;
+}
+// a factor matrix of (re, im) pairs with strides in pairs, stacked along its first (1) or second (2) index
+static LrsOperand lrs_factor(const float2 *p, int rs, int cs, int stack, int n, size_t scene)
+{
+    LrsOperand o = {(const float *)p, 2 * rs, 2 * cs, stack, n, 0, 2 * scene};
+    return o;
+}
+static void lrs_gemm(hipStream_t st, bool mfma, const LrsOperand &a, const LrsOperand &b, float *c, int ldc, size_t c_plane,
+                     int M, int N, int K, const LrsPlanes &pl, int planes)
+{
+    LrsGemm g = {a, b, c, ldc, c_plane, M, N, K, pl};
+    const dim3 grid(((M + LRS_BM - 1) / LRS_BM) * ((N + LRS_BN - 1) / LRS_BN), planes);
+    if (mfma) hipLaunchKernelGGL(k_lrs_gemm<true>, grid, dim3(SC_BLOCK), 0, st, g);
+    else hipLaunchKernelGGL(k_lrs_gemm<false>, grid, dim3(SC_BLOCK), 0, st, g);
+}
+// the buffers of one chunk inside the scratch: the loss partials (float64) first, then M, A, B, Z, D
+struct LrsBuffers {
+    double *partials;
+    float *m, *a, *b, *z, *d;
+};
+static LrsBuffers lrs_buffers(void *scratch, const LrsScratch &s, int chunk, bool fit)
+{
+    LrsBuffers u;
+    u.partials = (double *)scratch;
+    u.m = (float *)(u.partials + (fit ? (size_t)chunk * LRS_LOSS_BLOCKS : 0));
+    u.a = u.m + chunk * s.m; u.b = u.a + chunk * s.a; u.z = u.b + chunk * s.b; u.d = u.z + chunk * s.b;
+    return u;
+}
+static void lrs_expand(hipStream_t st, const LowresDims &d, const LowresFactors &f, const LrsBuffers &u, const LrsScratch &s,
+                       const LrsPlanes &pl, int planes)
+{
+    LrsExpand e = {u.b, u.z, s.b, d.nfy, d.nfx, d.B, f, pl};
+    hipLaunchKernelGGL(k_lrs_expand, dim3((d.nfy * d.nfx + SC_BLOCK - 1) / SC_BLOCK, planes), dim3(SC_BLOCK), 0, st, e);
+}
+// render of the chunk's planes: model [planes][H][W] -> out [planes][h][w]
+static void lrs_forward(hipStream_t st, bool mfma, const LowresDims &d, const LowresFactors &f, const LrsBuffers &u,
+                        const LrsScratch &s, const LrsPlanes &pl, int planes, const float *model, float *out)
+{
+    const int ny2 = 2 * d.nfy, nx2 = 2 * d.nfx;
+    const size_t vy_scene = f.v_per_scene ? (size_t)d.h * d.nfy : 0, vx_scene = f.v_per_scene ? (size_t)d.w * d.nfx : 0;
+    // T [H][2 nfx] = m [H][W] . (Re Ux | Im Ux)^T
+    lrs_gemm(st, mfma, lrs_real(model, d.W, 1, (size_t)d.H * d.W), lrs_factor(f.ux, 1, d.W, 2, d.nfx, 0), u.a, nx2, s.a,
+             d.H, nx2, d.W, pl, planes);
+    // C [2 nfy][2 nfx] = (Re Uy; Im Uy) [2 nfy][H] . T
+    lrs_gemm(st, mfma, lrs_factor(f.uy, d.H, 1, 1, d.nfy, 0), lrs_real(u.a, nx2, 1, s.a), u.b, nx2, s.b, ny2, nx2, d.H, pl, planes);
+    lrs_expand(st, d, f, u, s, pl, planes);
+    // R [2 nfy][w] = Z [2 nfy][2 nfx] . (Re Vx | Im Vx)^T = [Re R; -Im R]
+    lrs_gemm(st, mfma, lrs_real(u.z, nx2, 1, s.b), lrs_factor(f.vx, 1, d.nfx, 1, d.nfx, vx_scene), u.a, d.w, s.a, ny2, d.w, nx2,
+             pl, planes);
+    // out [h][w] = (Re Vy | Im Vy) [h][2 nfy] . R
+    lrs_gemm(st, mfma, lrs_factor(f.vy, d.nfy, 1, 2, d.nfy, vy_scene), lrs_real(u.a, d.w, 1, s.a), out, d.w, (size_t)d.h * d.w,
+             d.h, d.w, ny2, pl, planes);
+}
+// adjoint of the chunk's planes: resid [planes][h][w] -> out [planes][H][W]
+static void lrs_backward(hipStream_t st, bool mfma, const LowresDims &d, const LowresFactors &f, const LrsBuffers &u,
+                         const LrsScratch &s, const LrsPlanes &pl, int planes, const float *resid, float *out)
+{
+    const int ny2 = 2 * d.nfy, nx2 = 2 * d.nfx;
+    const size_t vy_scene = f.v_per_scene ? (size_t)d.h * d.nfy : 0, vx_scene = f.v_per_scene ? (size_t)d.w * d.nfx : 0;
+    // A1 [2 nfy][w] = (Re Vy | Im Vy)^T . E
+    lrs_gemm(st, mfma, lrs_factor(f.vy, 1, d.nfy, 1, d.nfy, vy_scene), lrs_real(resid, d.w, 1, (size_t)d.h * d.w), u.a, d.w, s.a,
+             ny2, d.w, d.h, pl, planes);
+    // C2 [2 nfy][2 nfx] = A1 . (Re Vx | Im Vx)
+    lrs_gemm(st, mfma, lrs_real(u.a, d.w, 1, s.a), lrs_factor(f.vx, d.nfx, 1, 2, d.nfx, vx_scene), u.b, nx2, s.b, ny2, nx2, d.w,
+             pl, planes);
+    lrs_expand(st, d, f, u, s, pl, planes);
+    // G1 [2 nfy][W] = Z [2 nfy][2 nfx] . (Re Ux; Im Ux) = [Re G1; -Im G1]
+    lrs_gemm(st, mfma, lrs_real(u.z, nx2, 1, s.b), lrs_factor(f.ux, d.W, 1, 1, d.nfx, 0), u.a, d.W, s.a, ny2, d.W, nx2, pl, planes);
+    // G [H][W] = (Re Uy; Im Uy)^T . G1
+    lrs_gemm(st, mfma, lrs_factor(f.uy, 1, d.H, 2, d.nfy, 0), lrs_real(u.a, d.W, 1, s.a), out, d.W, (size_t)d.H * d.W, d.H, d.W,
+             ny2, pl, planes);
+}
+// planes per chunk of a call: what the scratch was sized for, lowered by LOWRES_CHUNK (never raised)
+static int lrs_chunk_now(const LrsScratch &s, int planes)
+{
+    const int sized = lrs_chunk(s, planes), asked = opt(OPT_LOWRES_CHUNK);
+    return asked > 0 && asked < sized ? asked : sized;
+}
+// what one low-resolution observation of a fit runs per iteration in the streamed form
+struct LrsFit {
+    LowresArgs a;
+    LrsScratch s;
+    void *scratch;
+};
+static void lrs_fit_planes(hipStream_t st, const LrsFit &f)
+{
+    const LowresArgs &a = f.a;
+    const LowresDims &d = a.d;
+    const int planes = a.S * d.B, sized = lrs_chunk(f.s, planes), chunk = lrs_chunk_now(f.s, planes);
+    const LrsBuffers u = lrs_buffers(f.scratch, f.s, sized, true);
+    const size_t HW = (size_t)d.H * d.W;
+    for (int p0 = 0; p0 < planes; p0 += chunk) {
+        const int n = planes - p0 < chunk ? planes - p0 : chunk;
+        const LrsPlanes pl = {nullptr, nullptr, a.active, d.B, p0};
+        LrsModel m = {{a.sed[0], a.sed[1]}, {a.morph[0], a.morph[1]}, a.cur, a.ncomp, a.K, a.C, a.band0, (int)HW, u.m, f.s.m, pl};
+        const int mblocks = (int)((HW + SC_BLOCK - 1) / SC_BLOCK);
+        hipLaunchKernelGGL(k_lrs_model, dim3(mblocks < 1024 ? mblocks : 1024, n), dim3(SC_BLOCK), 0, st, m);
+        lrs_forward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, u.m, u.d);
+        LrsResid r = {u.d, f.s.d, a.images, a.weights, a.weight_scalar, d.h * d.w, u.partials, a.loss_part, pl};
+        hipLaunchKernelGGL(k_lrs_resid, dim3(LRS_LOSS_BLOCKS, n), dim3(SC_BLOCK), 0, st, r);
+        hipLaunchKernelGGL(k_lrs_loss, dim3((n + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, r, n);
+        lrs_backward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, u.d, a.G + (size_t)p0 * HW);
+    }
+}
+static int64_t lowres_scratch_offset(const scarlet_batch *state, const scarlet_batch *ob)
+{
+    const int64_t o = lowres_loss_offset(state, ob) + (int64_t)state->S * ob->B * (int64_t)sizeof(double);
+    return (o + 15) & ~(int64_t)15;
+}
+
+extern "C" int64_t scarlet_lowres_large_workspace_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr)
+{
+    if (check_shape(state) || check_shape(obs)) return SCARLET_E_ARG;
+    if (int rc = check_lowres(lr, state->H, state->W, obs->B, false, true)) return rc;
+    // (the scratch of the streamed form always: an option changed between sizing and fitting cannot write past it)
+    const LrsScratch s = lrs_scratch(lowres_dims(state, obs, lr), true);
+    return lowres_scratch_offset(state, obs) + (int64_t)lrs_chunk(s, state->S * obs->B) * (int64_t)s.per_plane;
+}
+
+extern "C" int64_t scarlet_lowres_op_scratch_bytes(int n, int H, int W, const scarlet_lowres *lr)
+{
+    if (n < 0) return set_err(SCARLET_E_ARG, "n < 0");
+    if (int rc = check_lowres(lr, H, W, lr ? lr->B : 0, false, true)) return rc;
+    LowresDims d;
+    d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = lr->B;
+    if (n == 0 || !lowres_streamed(d)) return 0;
+    const LrsScratch s = lrs_scratch(d, false);
+    return (int64_t)lrs_chunk(s, n) * (int64_t)s.per_plane;
+}
+
+static int lowres_op_large(bool adjoint, const float *in, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                           const int32_t *scene, float *out, void *scratch, int64_t scratch_bytes, void *stream)
+{
+    (void)hipGetLastError();
+    const int64_t need = scarlet_lowres_op_scratch_bytes(n, H, W, lr);
+    if (need < 0) return (int)need;
+    if (!in || !out) return set_err(SCARLET_E_ARG, "null plane pointer");
+    if (need > 0 && (!scratch || scratch_bytes < need))
+        return set_err(SCARLET_E_ARG, "scarlet_lowres: the scratch is smaller than scarlet_lowres_op_scratch_bytes()");
+    if (n == 0) return SCARLET_OK;
+    if (need == 0) return lowres_op(adjoint, in, n, H, W, lr, band, scene, out, stream);
+    LowresDims d;
+    d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = lr->B;
+    const LowresFactors f = lowres_factors(lr);
+    const LrsScratch s = lrs_scratch(d, false);
+    const int sized = lrs_chunk(s, n), chunk = lrs_chunk_now(s, n);
+    const LrsBuffers u = lrs_buffers(scratch, s, sized, false);
+    const bool mfma = !opt(OPT_NO_LOWRES_MFMA);
+    const size_t HW = (size_t)H * W, hw = (size_t)d.h * d.w;
+    for (int p0 = 0; p0 < n; p0 += chunk) {
+        const int m = n - p0 < chunk ? n - p0 : chunk;
+        const LrsPlanes pl = {band, scene, nullptr, 0, p0};
+        if (adjoint) lrs_backward((hipStream_t)stream, mfma, d, f, u, s, pl, m, in + p0 * hw, out + p0 * HW);
+        else lrs_forward((hipStream_t)stream, mfma, d, f, u, s, pl, m, in + p0 * HW, out + p0 * hw);
+    }
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+extern "C" int scarlet_lowres_render_large(const float *model, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                                           const int32_t *scene, float *out, void *scratch, int64_t scratch_bytes, void *stream)
+{
+    return lowres_op_large(false, model, n, H, W, lr, band, scene, out, scratch, scratch_bytes, stream);
+}
+extern "C" int scarlet_lowres_adjoint_large(const float *resid, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
+                                            const int32_t *scene, float *out, void *scratch, int64_t scratch_bytes, void *stream)
+{
+    return lowres_op_large(true, resid, n, H, W, lr, band, scene, out, scratch, scratch_bytes, stream);
+}
+
 // ---- several observations per blend (multiobs.h)
 // L_sed of the state's current morphologies (blend.py:186-218, before the factor n_obs): the Gram matrix and its largest
 // eigenvalue by the existing code of the K range, or its trace with approximate constants
@@ -2242,7 +2427,8 @@ static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const Grad
 // over them, L x n_obs, the step) and the tail
 static int fit_observations_call(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
                                  const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
-                                 int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr)
+                                 int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr,
+                                 bool large = false)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
@@ -2268,8 +2454,11 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         if (ob->diff_kernel && !lo[o].psf) return set_err(SCARLET_E_ARG, "diff_kernel without psf_h, psf_w");
     }
     // low-resolution observations (lowres.h): their G planes and per-plane losses lie in the scarlet_lowres workspace
+    // (`large`, scarlet_fit_observations_lowres_large: those that do not fit LDS take the streamed form, lowres_stream.h)
     LowresArgs la[SC_MAX_OBS] = {};
     size_t la_lds[SC_MAX_OBS] = {};
+    LrsFit ls[SC_MAX_OBS] = {};
+    bool streamed[SC_MAX_OBS] = {};
     for (int o = 0; o < n_obs; ++o) {
         const scarlet_lowres *lr = lowres ? lowres[o] : nullptr;
         if (!lr) continue;
@@ -2282,8 +2471,14 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         a.G = (float *)lr->workspace;
         a.loss_part = (double *)((char *)lr->workspace + lowres_loss_offset(state, obs[o]));
         a.mfma = !opt(OPT_NO_LOWRES_MFMA);
-        la_lds[o] = lowres_lds_bytes(a.d);
-        if ((rc = allow_lds(k_lowres_planes, la_lds[o]))) return rc;
+        streamed[o] = large && lowres_streamed(a.d);
+        if (streamed[o]) {
+            ls[o].a = a; ls[o].s = lrs_scratch(a.d, true);
+            ls[o].scratch = (char *)lr->workspace + lowres_scratch_offset(state, obs[o]);
+        } else {
+            la_lds[o] = lowres_lds_bytes(a.d);
+            if ((rc = allow_lds(k_lowres_planes, la_lds[o]))) return rc;
+        }
         ObsView &v = m.obs[o];
         v.G = a.G; v.loss_part = a.loss_part; v.Fy = state->H; v.Fx = state->W; v.oy = v.ox = 0;
     }
@@ -2301,7 +2496,8 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         prof_start(0, st);
         for (int o = 0; o < n_obs; ++o) {
             if (lowres && lowres[o]) {
-                hipLaunchKernelGGL(k_lowres_planes, dim3(m.S), dim3(SC_BLOCK), la_lds[o], st, la[o]);
+                if (streamed[o]) lrs_fit_planes(st, ls[o]);
+                else hipLaunchKernelGGL(k_lowres_planes, dim3(m.S), dim3(SC_BLOCK), la_lds[o], st, la[o]);
                 continue;
             }
             if (!lo[o].psf) continue;
@@ -2336,7 +2532,8 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
 
 // the one check of the observation entry points: the list, the state (check_call), every observation against it
 static int check_observations(const scarlet_batch *state, bool need_c, const scarlet_constraints *c, scarlet_batch *const *obs,
-                              const int32_t *band0, int n_obs, int max_iter, const scarlet_lowres *const *lowres = nullptr)
+                              const int32_t *band0, int n_obs, int max_iter, const scarlet_lowres *const *lowres = nullptr,
+                              bool large = false)
 {
     if (n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
     if (!obs || !band0) return set_err(SCARLET_E_ARG, "null observation list");
@@ -2354,7 +2551,7 @@ static int check_observations(const scarlet_batch *state, bool need_c, const sca
                 return set_err(SCARLET_E_ARG, "a low-resolution observation takes no diff_kernel: its PSFs are in dhat");
             if (ob->n_components)
                 return set_err(SCARLET_E_ARG, "an observation batch takes no n_components: the state's counts govern every observation");
-            if ((rc = check_lowres(lr, state->H, state->W, ob->B, true)) || (rc = check_batch(ob))) return rc;
+            if ((rc = check_lowres(lr, state->H, state->W, ob->B, true, large)) || (rc = check_batch(ob))) return rc;
             continue;
         }
         if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || ob->B < 1 ||
@@ -2389,6 +2586,15 @@ extern "C" int scarlet_fit_observations_lowres(scarlet_batch *state, const scarl
     if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
     const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter, lowres);
     return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, lowres);
+}
+
+extern "C" int scarlet_fit_observations_lowres_large(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                                     const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                                     int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
+    const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter, lowres, true);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, lowres, true);
 }
 
 // scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused

@@ -270,8 +270,11 @@ class LowResObservation(Observation):
                              % (tuple(m.shape), (lr.B,) + tuple(self.model_shape)))
         band = torch.arange(B, dtype=torch.int32, device="cuda")
         out = torch.empty((B, lr.h, lr.w), dtype=torch.float32, device="cuda")
-        _lib.check(_lib.lib.scarlet_lowres_render(m.data_ptr(), B, H, W, ctypes.byref(lr), band.data_ptr(), None,
-                                                  out.data_ptr(), _lib.stream_ptr()))
+        # (0 bytes where the model frame lets the LDS-resident kernel run)
+        nbytes = int(_lib.check(_lib.lib.scarlet_lowres_op_scratch_bytes(B, H, W, ctypes.byref(lr))))
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device="cuda") if nbytes else None
+        _lib.check(_lib.lib.scarlet_lowres_render_large(m.data_ptr(), B, H, W, ctypes.byref(lr), band.data_ptr(), None,
+                                                        out.data_ptr(), _lib.ptr(scratch), nbytes, _lib.stream_ptr()))
         return out
 
     def render(self, model):

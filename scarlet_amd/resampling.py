@@ -296,20 +296,23 @@ def lowres_factors(model_shape, lr_shape, psf_shape, diff_psf, y_at, x_at, area_
         vx = vx[::-1]
     else:
         vy = vy[::-1]
-    D = pad_center(np.asarray(diff_psf, dtype=np.float64), F)
-    ey = np.exp(-2j * np.pi * sgn_y * fy[:, None] * (np.arange(ny)[None, :] - cy) / ny)
-    ex = np.exp(-2j * np.pi * sgn_x * fx[:, None] * (np.arange(nx)[None, :] - cx) / nx)
-    dhat = area_ratio * np.einsum("fa,bax,gx->bfg", ey, D, ex)
+    # the spectra of the kernels padded into the plane (pad_center): only the kernels' own rows and columns are not zero,
+    # so the two transforms run over those alone, as matrix products
+    D = np.asarray(diff_psf, dtype=np.float64)
+    py, px = np.arange(D.shape[-2]) + pad_start(D.shape[-2], ny), np.arange(D.shape[-1]) + pad_start(D.shape[-1], nx)
+    ey = np.exp(-2j * np.pi * sgn_y * fy[:, None] * (py[None, :] - cy) / ny)
+    ex = np.exp(-2j * np.pi * sgn_x * fx[:, None] * (px[None, :] - cx) / nx)
+    dhat = area_ratio * (ey @ D @ ex.T)
     return dict(uy=uy, ux=ux, vy=np.ascontiguousarray(vy), vx=np.ascontiguousarray(vx), dhat=dhat, fft_shape=F)
 
 
 def apply_factors(f, model):
     """The operator in float64: model (B, H, W) -> (B, h, w)."""
-    spec = np.einsum("fy,byx,gx->bfg", f["uy"], np.asarray(model, dtype=np.float64), f["ux"]) * f["dhat"]
-    return np.real(np.einsum("if,bfg,jg->bij", f["vy"], spec, f["vx"]))
+    spec = (f["uy"] @ np.asarray(model, dtype=np.float64) @ f["ux"].T) * f["dhat"]
+    return np.real(f["vy"] @ spec @ f["vx"].T)
 
 
 def adjoint_factors(f, resid):
     """Its adjoint in float64: (B, h, w) -> (B, H, W)."""
-    spec = np.einsum("if,bij,jg->bfg", f["vy"], np.asarray(resid, dtype=np.float64), f["vx"]) * f["dhat"]
-    return np.real(np.einsum("fy,bfg,gx->byx", f["uy"], spec, f["ux"]))
+    spec = (f["vy"].T @ np.asarray(resid, dtype=np.float64) @ f["vx"]) * f["dhat"]
+    return np.real(f["uy"].T @ spec @ f["ux"])
