@@ -553,6 +553,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
         scr = lds + H * t.LW;
         av = scr + hp * scratch_stride(wp);
     }
+    // (sized by update_lds_bytes, tile_stage_lds_bytes, plane_lds_bytes for MODE 0, 1, 2: prox_ops.h)
     float *bv = av + 2 * hp, *cv = bv + 2 * wp, *zv = cv + 2 * wp;
     float *stage = MODE == 0 ? nullptr : zv + wp;   // LDS staging of the operands that live in HBM
     __shared__ double red[SC_NWAVES];
@@ -758,6 +759,11 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
 // PSF-weighted centroid.  _morph is materialised only on the patch both windows can touch (the centroid's radius
 // + 2 around the previous centre, clipped to the frame: inside it every bounds decision equals the frame's).
 // The new centre (and shift) is written to EVERY layer of the source; the update kernels take it as given.
+__host__ __device__ inline size_t group_centers_lds_bytes(int centroid_P)
+{
+    const int R = centroid_P / 2 + 2;                 // the patch: 2 R + 1 rows of stride PW = 2 R + 2
+    return sizeof(float) * (size_t)(2 * R + 1) * (2 * R + 2);
+}
 __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
 {
     extern __shared__ __align__(16) float lds[];
@@ -983,6 +989,6 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w(UpdateArgs a)
     if (!a.force_it0 && !a.active[c / a.K]) return;
     if (c % a.K >= scene_ncomp(a.ncomp, c / a.K, a.K)) return;      // absent component
     if (update_skips_scene(a, c / a.K)) return;
-    const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;
+    const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;      // wave_tile_floats (wave_ops.h)
     wave_pipeline(a, c, lds + (size_t)wid * per_wave);
 }

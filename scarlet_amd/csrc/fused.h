@@ -58,6 +58,11 @@ struct FusedArgsPC : FusedArgs {
 #define SC_KSC_FLOATS 200
 #define SC_KSC_MAGIC 0x5ca71e70u
 
+// dynamic LDS of k_iterate: the K tiles, then one set of vectors per wave
+__host__ __device__ inline size_t fused_lds_bytes(int K, int H, int W)
+{
+    return sizeof(float) * ((size_t)K * H * tile_stride(W) + SC_NWAVES * SC_WAVE_VEC_FLOATS);
+}
 template <int KM, int BM, class A = FusedArgs>
 __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
 {
@@ -68,7 +73,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
     const int K = a.K, B = a.B, H = a.H, W = a.W, HW = H * W, LW = tile_stride(W);
     const int tile_floats = H * LW;
     float *tiles = lds;
-    float *vecs = lds + (size_t)K * tile_floats;
+    float *vecs = lds + (size_t)K * tile_floats;             // (fused_lds_bytes)
     constexpr int NG = KM * (KM + 1) / 2;
     constexpr int NP = 1 + KM * BM;
     constexpr int GPT = 4;                       // float4 groups per thread (H, W <= 64)

@@ -24,6 +24,16 @@
 #define SC_FB2 512
 #define SC_NW2 (SC_FB2 / SC_WAVE)
 #define SC_PAIR_VEC_FLOATS 512       // av, bv, cv (128 each) + one zv (64) per wave of the pair
+// dynamic LDS of k_iterate2: the K tiles, then one set of vectors per pair of waves; the exact-shape instances
+// (k_iterate2<KM, BM, XS>, k_fit2x) with their own tile stride (common.h SC_XS_STRIDE)
+__host__ __device__ inline size_t fused2_lds_bytes(int K, int H, int W)
+{
+    return sizeof(float) * ((size_t)K * H * tile_stride(W) + (size_t)K * SC_PAIR_VEC_FLOATS);
+}
+__host__ __device__ inline size_t fused2_exact_lds_bytes(int KM, int XS)
+{
+    return sizeof(float) * ((size_t)KM * XS * SC_XS_STRIDE + (size_t)KM * SC_PAIR_VEC_FLOATS);
+}
 
 // FFT lengths of a window of half-size r (h = 2 r + 1): fl[0][r] = next_fast_len(2 h + 10) and
 // fl[1][r] = the first EVEN fast length from there (fft.py:95-115 via operator.py:253-288).  The
@@ -131,7 +141,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     };
     const bool symmetric = X ? true : a.symmetric != 0, monotonic = X ? true : a.monotonic != 0;
     float *tiles = lds;
-    float *vecs = lds + (size_t)K * tile_floats;
+    float *vecs = lds + (size_t)K * tile_floats;             // (fused2_lds_bytes, fused2_exact_lds_bytes)
     constexpr int NG = KM * (KM + 1) / 2;
     constexpr int NP = 1 + KM * BM;
     constexpr int GPT = 2;                       // float4 groups per thread in phases 0/1 (H, W <= 64)

@@ -174,6 +174,10 @@ __device__ __forceinline__ void init_scene_bg(const InitSrcArgs &a, int s, doubl
     for (int b = 0; b < SC_BMAX; ++b) bg[b] = b < a.B ? (double)a.bg_rms[(size_t)s * a.bg_stride + b] : 1.0;
 }
 
+// the float64 tile of one component (row stride W + 1), in dynamic LDS or, for GT, in a temporary HBM buffer:
+// k_init_extended, k_init_extended_rows, k_init_layers
+__host__ __device__ inline size_t init_tile_bytes(int H, int W) { return sizeof(double) * (size_t)H * (W + 1); }
+
 // ---- ExtendedSource with the scene's own noise and PSF peaks: what k_init_extended does for one row of bg_rms
 template <bool GT>
 __global__ __launch_bounds__(SC_BLOCK) void k_init_extended_rows(InitSrcArgs a, double *gtile)

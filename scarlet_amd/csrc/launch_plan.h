@@ -1,0 +1,114 @@
+// launch_plan.h -- which form of a kernel a shape takes and the dynamic LDS that form asks for, decided once.
+// Host code: pure functions of the shapes and the diagnostic switches (UpdateWants, FusedSwitches), no device call.
+// The sizes come from the functions that stand beside the kernels (prox_ops.h, wave_ops.h, boxupdate.h, fused.h,
+// fused2.h, initsrc.h); the launch sites of scarlet_hip.hip switch on the plan and compute nothing of their own.
+// tools/native/launch_forms.hip prints the shapes at which the forms begin (the table of DESIGN.md "One plan").
+#pragma once
+#include "boxupdate.h"
+#include "fused2.h"
+#include "initsrc.h"
+
+static const size_t LDS_LIMIT = 160 * 1024 - 1024;   // leave room for static __shared__
+
+// ---- the constraint update (launch_update), the stand-alone operators (launch_operator), the layout (ws_layout)
+// FORM_WAVE: one wave per component, its tile in LDS (sides up to 64).  FORM_TILE: one workgroup per component, tile
+// and GEMM scratch in LDS.  FORM_TILE_GSCRATCH: the tile in LDS, the scratch in HBM.  FORM_PLANE: both in HBM.
+enum UpdateForm { FORM_WAVE, FORM_TILE, FORM_TILE_GSCRATCH, FORM_PLANE };
+// k_source_update_box<NB, XS> and its _listed twin; BOX_STREAMED = <0, 0>, frames with a side over 256
+enum BoxInstance { BOX_NONE, BOX_STREAMED, BOX_8_128, BOX_16_256, BOX_8, BOX_16 };
+struct UpdateWants {
+    bool wave;              // the wave form is allowed (an operator without one, FORCE_BLOCK_UPDATE: false)
+    bool gscratch;          // a workspace with `gscratch` stands behind the launch (the operators have none)
+    bool box, box2, exact;  // the box stage (monotonic batches), its second box, the exact-shape instances
+};
+struct UpdatePlan {
+    int form;
+    size_t lds;             // that form's dynamic LDS
+    bool reserve_gscratch;  // the workspace holds the scratch in HBM (a function of the shape alone: ws_layout)
+    int box;                // BOX_NONE: no box stage
+    bool box2;              // the 127 x 127 box runs for what the 63 x 63 box listed
+    size_t box_lds[2];
+};
+inline UpdatePlan update_plan(int H, int W, const UpdateWants &w)
+{
+    UpdatePlan p = {};
+    const bool beyond_wave = H > 64 || W > 64;
+    // (frames up to 80 KB of LDS run two workgroups per CU without the scratch)
+    p.reserve_gscratch = beyond_wave && update_lds_bytes(H, W) > 80 * 1024;
+    if (!beyond_wave && w.wave) { p.form = FORM_WAVE; p.lds = wave_tile_lds_bytes(H, W); }
+    else if (update_lds_bytes(H, W) > LDS_LIMIT) { p.form = FORM_PLANE; p.lds = plane_lds_bytes(H, W); }
+    else if (w.gscratch && p.reserve_gscratch && tile_stage_lds_bytes(H, W) <= 78 * 1024) {
+        p.form = FORM_TILE_GSCRATCH; p.lds = tile_stage_lds_bytes(H, W);     // two workgroups per CU instead of one
+    } else { p.form = FORM_TILE; p.lds = update_lds_bytes(H, W); }
+    // the pipeline on the box around each peak (boxupdate.h): 63 x 63 for every component, 127 x 127 for those whose
+    // footprint left it; frames with a side over 256 take the streamed instance
+    const bool streamed = H > 256 || W > 256;
+    for (int i = 0; i < 2; ++i)
+        p.box_lds[i] = sizeof(float) * (streamed ? ub_lds_floats_streamed(H, W, i ? 63 : 31) : ub_lds_floats(H, W, i ? 63 : 31));
+    if (beyond_wave && w.box && p.box_lds[1] <= LDS_LIMIT) {
+        // instances: bands of X per frame height (8: up to 128 rows, 16: up to 256), and the two BASELINE frame
+        // shapes (128 x 128, 256 x 256) as compile-time constants
+        p.box = streamed ? BOX_STREAMED : (w.exact && H == 128 && W == 128) ? BOX_8_128 : (w.exact && H == 256 && W == 256) ? BOX_16_256
+                : (H <= 128 && W <= 128) ? BOX_8 : BOX_16;
+        p.box2 = w.box2;
+    }
+    return p;
+}
+
+// ---- the fused one-kernel iteration (launch_fused); FUSED_NONE: the batch takes the general path
+struct FusedSwitches {      // (scarlet_hip.hip fused_switches() reads them from the options)
+    bool no_exact, fused_v1, no_fused, no_persist;
+    int persist_dbg;
+    size_t pad_lds;
+};
+enum FusedKernel { FUSED_NONE, FUSED_PC_B6, FUSED_PC_B8,        // k_iterate<4, 6 / SC_BMAX, FusedArgsPC>
+                   FUSED_FIT2X, FUSED_ITERATE2_EXACT, FUSED_ITERATE2, // k_fit2x, k_iterate2<4, 5, 64>, k_iterate2<4, 5>
+                   FUSED_B6, FUSED_B8 };                        // k_iterate<4, 6 / SC_BMAX>
+struct FusedPlan {
+    int kernel, block;
+    size_t lds;             // what the launch asks for, PAD_LDS included
+    bool fits;              // ... is within LDS_LIMIT
+};
+// per_component: the components carry their own switches (scarlet_constraints); n_iter: the iterations wanted of
+// one launch (only k_fit2x covers more than one)
+inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_component, int n_iter, const FusedSwitches &sw)
+{
+    FusedPlan p = {FUSED_NONE, SC_BLOCK, 0, true};
+    // K > 4: eight tiles leave one workgroup per CU and the general path is faster (measured at K = 6, 8:
+    // 2.44 vs 2.58 ms and 3.25 vs 3.90 ms per iteration of 4000 scenes)
+    if (approximate_L || b->diff_kernel || b->K > 4 || b->group || sw.no_fused) return p;
+    if (b->H > 64 || b->W > 64 || (b->W & 3) || b->H < 3 || b->W < 3) return p;
+    // admission by the four-wave kernel's size; the eight-wave kernel's K <= 4 sets of vectors ask for at most 1 KB
+    // more and its exact shape for 76 KB, so without PAD_LDS every admitted launch fits
+    if (fused_lds_bytes(b->K, b->H, b->W) > LDS_LIMIT - 4096) return p;
+    // the headline shape (BASELINE configs[1]/[3]: 4 sources, 5 bands, 64 x 64, default pipeline) has an instance
+    // with every shape and switch folded at compile time
+    const bool exact64 = b->K == 4 && b->B == 5 && b->H == 64 && b->W == 64 && !b->weights && b->weight_scalar == 1.0f && b->symmetric &&
+                         b->monotonic && b->l0_thresh < 0.f && b->l1_thresh < 0.f && !sw.no_exact;
+    if (per_component) {
+        // the four-wave kernel's per-component instance for every B (wave k reads component k's four settings in
+        // phase 2), never k_iterate2 / k_fit2x
+        p.kernel = b->B <= 6 ? FUSED_PC_B6 : FUSED_PC_B8; p.lds = fused_lds_bytes(b->K, b->H, b->W);
+    } else if (b->B <= 5 && !sw.fused_v1) {
+        // K <= 4, B <= 5: eight waves per scene, a pair of waves per component (fused2.h; its 128-VGPR budget does
+        // not hold a sixth band's accumulators); persistent where more than one iteration is wanted
+        const bool persist = (n_iter > 1 || (sw.persist_dbg & 2)) && !sw.no_persist;
+        p.kernel = !exact64 ? FUSED_ITERATE2 : persist ? FUSED_FIT2X : FUSED_ITERATE2_EXACT;
+        p.block = SC_FB2;
+        p.lds = exact64 ? fused2_exact_lds_bytes(4, 64) : fused2_lds_bytes(b->K, b->H, b->W);
+    } else {
+        p.kernel = b->B <= 6 ? FUSED_B6 : FUSED_B8; p.lds = fused_lds_bytes(b->K, b->H, b->W);
+    }
+    p.lds += sw.pad_lds;    // experiment knob: SCARLET_PAD_LDS=<bytes> lowers the number of co-resident workgroups
+    p.fits = p.lds <= LDS_LIMIT;
+    return p;
+}
+
+// ---- the initialisers' float64 tile (initsrc.h): in LDS, or one per component in a temporary HBM buffer
+struct InitTilePlan { bool in_lds; size_t lds, hbm; };
+inline InitTilePlan init_tile_plan(int H, int W, size_t components)
+{
+    const size_t tile = init_tile_bytes(H, W);
+    const bool in_lds = tile <= LDS_LIMIT;
+    return {in_lds, in_lds ? tile : 0, in_lds ? 0 : tile * components};
+}

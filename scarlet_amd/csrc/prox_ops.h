@@ -457,9 +457,28 @@ __device__ inline void symmetry_tile(const Tile &t, int cy, int cx, int algorith
     }
 }
 
-// LDS floats needed by symmetry_tile for an H x W tile (worst-case window)
+// ---- the dynamic LDS of the kernels that run symmetry_tile on a workgroup (k_source_update<MODE>, k_operator<GT>):
+// [tile] [GEMM scratch] av bv cv zv [stage], each part in LDS or in HBM as the form has it.  The host sizes every
+// launch with these; the kernels carve in the same order.
+// the Hankel and rank-1 vectors: av [2 hp], bv, cv [2 wp], zv [wp]
+__host__ __device__ inline int symmetry_vec_floats(int H, int W) { return 2 * round16(H) + 2 * round16(W) + 2 * round16(W) + round16(W); }
+// LDS floats needed by symmetry_tile for an H x W tile (worst-case window): the GEMM scratch and the vectors
 __host__ __device__ inline int symmetry_lds_floats(int H, int W)
 {
-    const int hp = round16(H), wp = round16(W);
-    return hp * scratch_stride(wp) + 2 * hp + 2 * wp + 2 * wp + wp;
+    return round16(H) * scratch_stride(round16(W)) + symmetry_vec_floats(H, W);
+}
+// tile and scratch in LDS (k_source_update<0>, k_operator<false>)
+__host__ __device__ inline size_t update_lds_bytes(int H, int W)
+{
+    return sizeof(float) * ((size_t)H * tile_stride(W) + symmetry_lds_floats(H, W));
+}
+// plane and scratch in HBM (k_source_update<2>, k_operator<true>): the vectors and the stage
+__host__ __device__ inline size_t plane_lds_bytes(int H, int W)
+{
+    return sizeof(float) * (size_t)(symmetry_vec_floats(H, W) + stage_floats(round16(H), round16(W)));
+}
+// tile in LDS, scratch in HBM (k_source_update<1>): the tile, the vectors and the stage
+__host__ __device__ inline size_t tile_stage_lds_bytes(int H, int W)
+{
+    return sizeof(float) * (size_t)H * tile_stride(W) + plane_lds_bytes(H, W);
 }

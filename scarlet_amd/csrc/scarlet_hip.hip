@@ -30,6 +30,7 @@
 #include "lowres.h"
 #include "lowres_stream.h"
 #include "prior.h"
+#include "launch_plan.h"
 
 __constant__ unsigned short sc_nfl_table[SC_NFL_MAX];
 
@@ -190,19 +191,20 @@ static int device_cu_count(void)
     return n;
 }
 
-// LDS bytes of the per-component update kernel for an H x W image
-static size_t update_lds_bytes(int H, int W)
-{
-    return sizeof(float) * ((size_t)H * tile_stride(W) + symmetry_lds_floats(H, W));
-}
-static const size_t LDS_LIMIT = 160 * 1024 - 1024;   // leave room for static __shared__
-
 template <typename Kern>
 static int allow_lds(Kern k, size_t bytes)
 {
     if (bytes > LDS_LIMIT) return set_err(SCARLET_E_TOO_LARGE, "image tile does not fit in LDS");
     if (bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SCARLET_OK;
+}
+// allow the dynamic LDS, launch
+template <typename Kern, typename... Args>
+static int launch_lds(Kern k, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &... args)
+{
+    if (int rc = allow_lds(k, lds)) return rc;
+    hipLaunchKernelGGL(k, grid, block, lds, st, args...);
     return SCARLET_OK;
 }
 
@@ -232,6 +234,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_operator(OpArgs a, float *gscratch
     float *scr, *av;
     if (GT) { t.LW = W; t.m = g; scr = gscratch + (size_t)c * hp * scratch_stride(wp); av = lds; }
     else    { t.LW = tile_stride(W); t.m = lds; scr = lds + H * t.LW; av = scr + hp * scratch_stride(wp); }
+    // (sized by update_lds_bytes, or plane_lds_bytes for GT: prox_ops.h)
     float *bv = av + 2 * hp, *cv = bv + 2 * wp, *zv = cv + 2 * wp;
     float *stage = GT ? zv + wp : nullptr;
     __shared__ double red[SC_NWAVES];
@@ -287,7 +290,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_operator_w(OpArgs a)
     if (c >= a.n) return;
     const int H = a.H, W = a.W, HW = H * W;
     Tile t; t.H = H; t.W = W; t.LW = tile_stride(W);
-    t.m = lds + (size_t)wid * (H * t.LW + SC_WAVE_VEC_FLOATS);
+    t.m = lds + (size_t)wid * (H * t.LW + SC_WAVE_VEC_FLOATS);      // wave_tile_floats (wave_ops.h)
     float *vec = t.m + H * t.LW;
     float *g = a.x + (size_t)c * HW;
     for (int i = lane; i < HW; i += SC_WAVE) t.m[(i / W) * t.LW + (i % W)] = g[i];
@@ -337,29 +340,25 @@ static int launch_operator(OpArgs a, void *stream)
     if (a.n == 0) return SCARLET_OK;
     int rc = ensure_tables();
     if (rc) return rc;
-    if (a.H <= 64 && a.W <= 64 && a.op != OP_MONO_NEAREST && !opt(OPT_FORCE_BLOCK_UPDATE)) {
-        const size_t lds = sizeof(float) * SC_NWAVES * ((size_t)a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS);
-        rc = allow_lds(k_operator_w, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_operator_w, dim3((a.n + SC_NWAVES - 1) / SC_NWAVES), dim3(SC_BLOCK), lds,
-                           (hipStream_t)stream, a);
-    } else if (update_lds_bytes(a.H, a.W) <= LDS_LIMIT) {
-        const size_t lds = update_lds_bytes(a.H, a.W);
-        rc = allow_lds(k_operator<false>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_operator<false>, dim3(a.n), dim3(SC_BLOCK), lds, (hipStream_t)stream, a, (float *)nullptr);
-    } else {
-        DevBuf gscratch;                      // released on every path, after the kernel has finished
+    // the update's choice of form without a workspace behind it; the nearest-neighbour sweep has no wave form
+    const UpdatePlan p = update_plan(a.H, a.W, {a.op != OP_MONO_NEAREST && !opt(OPT_FORCE_BLOCK_UPDATE)});
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf gscratch;                          // released on every path, after the kernel has finished
+    switch (p.form) {
+    case FORM_WAVE:
+        rc = launch_lds(k_operator_w, dim3((a.n + SC_NWAVES - 1) / SC_NWAVES), dim3(SC_BLOCK), p.lds, st, a);
+        break;
+    case FORM_TILE:
+        rc = launch_lds(k_operator<false>, dim3(a.n), dim3(SC_BLOCK), p.lds, st, a, (float *)nullptr);
+        break;
+    default:
         if (a.op == OP_SYMMETRY)
             DEV_ALLOC(gscratch, sizeof(float) * (size_t)a.n * round16(a.H) * scratch_stride(round16(a.W)));
-        const size_t lds = sizeof(float) * (2 * round16(a.H) + 5 * round16(a.W) + stage_floats(round16(a.H), round16(a.W)));
-        rc = allow_lds(k_operator<true>, lds);          // (past 48 KB from ~512 columns on)
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_operator<true>, dim3(a.n), dim3(SC_BLOCK), lds, (hipStream_t)stream, a, gscratch.as<float>());
-        HIP_TRY(hipGetLastError());
-        if (gscratch.p) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        rc = launch_lds(k_operator<true>, dim3(a.n), dim3(SC_BLOCK), p.lds, st, a, gscratch.as<float>());   // (past 48 KB from ~512 columns on)
     }
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
+    if (gscratch.p) HIP_TRY(hipStreamSynchronize(st));
     return SCARLET_OK;
 }
 
@@ -1032,8 +1031,7 @@ static WsLayout ws_layout(const scarlet_batch *b, LayoutUse use)
     auto place = [&at](int64_t bytes) { const int64_t o = at; at += bytes; return o; };
     if (use == WS_FIX && K > SC_KMAX && K <= SC_KBIG) g_hugek_frozen.store(true);
     l.grad = K <= SC_KMAX ? GRAD_SMALL : (K > SC_KBIG || opt(OPT_FORCE_HUGEK)) ? GRAD_HUGEK : GRAD_BIGK;
-    // (frames up to 80 KB of LDS run two workgroups per CU without the scratch)
-    l.has_gscratch = (b->H > 64 || b->W > 64) && update_lds_bytes(b->H, b->W) > 80 * 1024;
+    l.has_gscratch = update_plan(b->H, b->W, {}).reserve_gscratch;
     l.has_kscache = K <= 4 && B <= 5 && b->H <= 64 && b->W <= 64;
     l.partials = place(sizeof(double) * S * n_tiles(b) * n_partials(b->K, b->B));
     l.conv = place(sizeof(double) * S * K * 4);
@@ -1750,80 +1748,53 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.symmetric_c = o.cons ? o.cons->symmetric : nullptr; u.monotonic_c = o.cons ? o.cons->monotonic : nullptr;
     u.l0_c = o.cons ? o.cons->l0_thresh : nullptr; u.l1_c = o.cons ? o.cons->l1_thresh : nullptr;
     u.skip_status = o.skip_status;
-    if (b->group) {
-        // MultiComponentSource: the shared centre of every source first (one wave per scene)
-        const int R = b->centroid_P / 2 + 2;
-        const size_t ldsg = sizeof(float) * (size_t)(2 * R + 1) * (2 * R + 2);
-        if ((rc = allow_lds(k_group_centers, ldsg))) return rc;
-        hipLaunchKernelGGL(k_group_centers, dim3(b->S), dim3(SC_WAVE), ldsg, (hipStream_t)stream, u);
-    }
     u.hybrid_sweep = opt(OPT_NO_HYBRID_SWEEP) ? 0 : 1;
-    // (frames with a side over 256 take the streamed instance, NB = 0)
-    const bool streamed = b->H > 256 || b->W > 256;
-    if ((b->H > 64 || b->W > 64) && b->monotonic && !opt(OPT_NO_BOX) &&
-        sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 63) : ub_lds_floats(b->H, b->W, 63)) <= LDS_LIMIT) {
-        // frames beyond the wave-level tile: the pipeline on the box around each peak (boxupdate.h) -- 63 x 63 for
-        // every component, 127 x 127 for those whose footprint left it; the kernels below then run only for the
-        // components that left the second box too
-        const size_t lds1 = sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 31) : ub_lds_floats(b->H, b->W, 31)),
-                     lds2 = sizeof(float) * (streamed ? ub_lds_floats_streamed(b->H, b->W, 63) : ub_lds_floats(b->H, b->W, 63));
+    const UpdatePlan p = update_plan(b->H, b->W, {!opt(OPT_FORCE_BLOCK_UPDATE), true, b->monotonic && !opt(OPT_NO_BOX),
+                                                  !opt(OPT_NO_BOX2), !opt(OPT_NO_EXACT)});
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(b->S * b->K), block(SC_BLOCK);
+    // MultiComponentSource: the shared centre of every source first (one wave per scene)
+    if (b->group && (rc = launch_lds(k_group_centers, dim3(b->S), dim3(SC_WAVE), group_centers_lds_bytes(b->centroid_P), st, u)))
+        return rc;
+    if (p.box != BOX_NONE) {
+        // frames beyond the wave-level tile: the pipeline on the box around each peak (boxupdate.h); the kernels below
+        // then run only for the components that left the second box too
         long long *dbg = debug_stamps((size_t)b->S * b->K * 16);
         int *fb = ws_at<int>(b, l.box_fallback), *list = ws_at<int>(b, l.box_list), *count = ws_at<int>(b, l.box_count);
-        hipStream_t st = (hipStream_t)stream;
-        const bool second = !opt(OPT_NO_BOX2);
-        if (second) hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, count);   // (a 4-byte hipMemsetAsync costs 16 us)
+        if (p.box2) hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, count);   // (a 4-byte hipMemsetAsync costs 16 us)
         // the large box: workgroup i takes list[i]
-        const int listed_grid = b->S * b->K;
-        // instances: bands of X per frame height (8: up to 128 rows, 16: up to 256, 0: streamed), and the two BASELINE frame shapes
-        // (128 x 128, 256 x 256) as compile-time constants
         auto run = [&](auto small_k, auto listed_k) -> int {
             int r2;
-            if ((r2 = allow_lds(small_k, lds1)) || (r2 = allow_lds(listed_k, lds2))) return r2;
-            hipLaunchKernelGGL(small_k, dim3(b->S * b->K), dim3(SC_BLOCK), lds1, st, u, fb, second ? list : nullptr, count, dbg);
-            if (second)
-                hipLaunchKernelGGL(listed_k, dim3(listed_grid), dim3(SC_BLOCK), lds2, st, u, fb, (const int *)list, (const int *)count, dbg);
+            if ((r2 = allow_lds(small_k, p.box_lds[0])) || (r2 = allow_lds(listed_k, p.box_lds[1]))) return r2;
+            hipLaunchKernelGGL(small_k, grid, block, p.box_lds[0], st, u, fb, p.box2 ? list : nullptr, count, dbg);
+            if (p.box2)
+                hipLaunchKernelGGL(listed_k, grid, block, p.box_lds[1], st, u, fb, (const int *)list, (const int *)count, dbg);
             return SCARLET_OK;
         };
-        const bool exact = !opt(OPT_NO_EXACT);
-        if (streamed) rc = run(k_source_update_box<0, 0>, k_source_update_box_listed<0, 0>);
-        else if (exact && b->H == 128 && b->W == 128) rc = run(k_source_update_box<8, 128>, k_source_update_box_listed<8, 128>);
-        else if (exact && b->H == 256 && b->W == 256) rc = run(k_source_update_box<16, 256>, k_source_update_box_listed<16, 256>);
-        else if (b->H <= 128 && b->W <= 128) rc = run(k_source_update_box<8, 0>, k_source_update_box_listed<8, 0>);
-        else rc = run(k_source_update_box<16, 0>, k_source_update_box_listed<16, 0>);
+        switch (p.box) {
+        case BOX_STREAMED: rc = run(k_source_update_box<0, 0>, k_source_update_box_listed<0, 0>); break;
+        case BOX_8_128: rc = run(k_source_update_box<8, 128>, k_source_update_box_listed<8, 128>); break;
+        case BOX_16_256: rc = run(k_source_update_box<16, 256>, k_source_update_box_listed<16, 256>); break;
+        case BOX_8: rc = run(k_source_update_box<8, 0>, k_source_update_box_listed<8, 0>); break;
+        default: rc = run(k_source_update_box<16, 0>, k_source_update_box_listed<16, 0>);
+        }
         if (rc) return rc;
         u.only_flagged = fb;
     }
-    if (b->H <= 64 && b->W <= 64 && !opt(OPT_FORCE_BLOCK_UPDATE)) {
-        // one wave per component, four components per workgroup (wave_ops.h)
-        const size_t lds = sizeof(float) * SC_NWAVES * ((size_t)b->H * tile_stride(b->W) + SC_WAVE_VEC_FLOATS);
-        rc = allow_lds(k_source_update_w, lds);
-        if (rc) return rc;
-        const int n = b->S * b->K;
-        hipLaunchKernelGGL(k_source_update_w, dim3((n + SC_NWAVES - 1) / SC_NWAVES), dim3(SC_BLOCK), lds,
-                           (hipStream_t)stream, u);
-    } else if (update_lds_bytes(b->H, b->W) <= LDS_LIMIT) {
-        const size_t lds = update_lds_bytes(b->H, b->W);
-        const size_t lds1 = sizeof(float) * ((size_t)b->H * tile_stride(b->W) + 2 * round16(b->H) + 5 * round16(b->W) +
-                                             stage_floats(round16(b->H), round16(b->W)));
-        if (lds > 80 * 1024 && lds1 <= 78 * 1024 && l.has_gscratch) {
-            // scratch in HBM: two workgroups per CU instead of one
-            u.gscratch = ws_at<float>(b, l.gscratch);
-            rc = allow_lds(k_source_update<1>, lds1);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_source_update<1>, dim3(b->S * b->K), dim3(SC_BLOCK), lds1, (hipStream_t)stream, u);
-        } else {
-            rc = allow_lds(k_source_update<0>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_source_update<0>, dim3(b->S * b->K), dim3(SC_BLOCK), lds, (hipStream_t)stream, u);
-        }
-    } else {
-        // frames beyond the LDS tile (up to SCARLET_MAX_SIDE): operators in place on the plane in HBM / L2
+    if (p.form == FORM_TILE_GSCRATCH || p.form == FORM_PLANE) {
+        if (!l.has_gscratch) return set_err(SCARLET_E_ARG, "the workspace layout holds no symmetry scratch for this frame");
         u.gscratch = ws_at<float>(b, l.gscratch);
-        const size_t lds = sizeof(float) * (2 * round16(b->H) + 5 * round16(b->W) +       // av, bv, cv, zv, stage
-                                            stage_floats(round16(b->H), round16(b->W)));
-        if ((rc = allow_lds(k_source_update<2>, lds))) return rc;                         // (94 KB at 1024 x 1024)
-        hipLaunchKernelGGL(k_source_update<2>, dim3(b->S * b->K), dim3(SC_BLOCK), lds, (hipStream_t)stream, u);
     }
+    switch (p.form) {
+    case FORM_WAVE:             // one wave per component, four components per workgroup (wave_ops.h)
+        rc = launch_lds(k_source_update_w, dim3((b->S * b->K + SC_NWAVES - 1) / SC_NWAVES), block, p.lds, st, u);
+        break;
+    case FORM_TILE_GSCRATCH: rc = launch_lds(k_source_update<1>, grid, block, p.lds, st, u); break;
+    case FORM_TILE: rc = launch_lds(k_source_update<0>, grid, block, p.lds, st, u); break;
+    default:                    // operators in place on the plane in HBM / L2 (94 KB at 1024 x 1024)
+        rc = launch_lds(k_source_update<2>, grid, block, p.lds, st, u);
+    }
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
@@ -1865,18 +1836,15 @@ static int fit2x_resident_workgroups(size_t lds, int *out)
     return SCARLET_OK;
 }
 
-// ---- fused one-kernel iteration (fused.h)
-static size_t fused_lds_bytes(const scarlet_batch *b)
+// ---- fused one-kernel iteration (fused.h, fused2.h): the batches fused_plan (launch_plan.h) has a kernel for
+static FusedSwitches fused_switches(void)
 {
-    return sizeof(float) * ((size_t)b->K * b->H * tile_stride(b->W) + SC_NWAVES * SC_WAVE_VEC_FLOATS);
+    return {opt(OPT_NO_EXACT) != 0, opt(OPT_FUSED_V1) != 0, opt(OPT_NO_FUSED) != 0, opt(OPT_NO_PERSIST) != 0, opt(OPT_PERSIST_DBG),
+            (size_t)opt(OPT_PAD_LDS)};
 }
 static bool fused_ok(const scarlet_batch *b, int approximate_L)
 {
-    // K > 4: eight tiles leave one workgroup per CU and the general path is faster (measured at K = 6, 8:
-    // 2.44 vs 2.58 ms and 3.25 vs 3.90 ms per iteration of 4000 scenes)
-    if (approximate_L || b->diff_kernel || b->K > 4 || b->group || opt(OPT_NO_FUSED)) return false;
-    if (b->H > 64 || b->W > 64 || (b->W & 3) || b->H < 3 || b->W < 3) return false;
-    return fused_lds_bytes(b) <= LDS_LIMIT - 4096;
+    return fused_plan(b, approximate_L, false, 1, fused_switches()).kernel != FUSED_NONE;
 }
 // n_iter > 1: that many iterations in ONE launch where the persistent form exists (k_fit2: the headline shape's
 // exact instance); *done receives the number of iterations the launch covers
@@ -1901,54 +1869,46 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
     // diagnostics: SCARLET_STAMPS=1 writes phase stamps into the (otherwise unused) partials area
     f.kscache = (!l.has_kscache || b->diff_kernel || opt(OPT_NO_KSCACHE)) ? nullptr : ws_at<float>(b, l.kscache);
     f.stamps = (opt(OPT_STAMPS) && n_partials(b->K, b->B) >= 16) ? ws_at<long long>(b, l.partials) : nullptr;
-    // experiment knob: SCARLET_PAD_LDS=<bytes> lowers the number of co-resident workgroups
-    const size_t lds = fused_lds_bytes(b) + (size_t)opt(OPT_PAD_LDS);
+    if (n_iter > 0xffffff) n_iter = 0xffffff;
+    const FusedSwitches sw = fused_switches();
+    const FusedPlan p = fused_plan(b, 0, cons_any(cons), n_iter, sw);
+    if (p.kernel == FUSED_NONE) return set_err(SCARLET_E_ARG, "no fused kernel for this batch");
+    if (!p.fits) return set_err(SCARLET_E_TOO_LARGE, "image tile does not fit in LDS");
     hipStream_t st = (hipStream_t)stream;
     // allow the LDS, profile class 4 (weight: the iterations the launch covers), launch
-    auto run = [&](auto kern, int grid, int block, size_t bytes, int weight, const auto &... args) -> int {
-        int r = allow_lds(kern, bytes);
+    auto run = [&](auto kern, int grid, int weight, const auto &... args) -> int {
+        int r = allow_lds(kern, p.lds);
         if (r) return r;
         prof_start(4, st, weight);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), bytes, st, args...);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(p.block), p.lds, st, args...);
         prof_stop(st);
         HIP_TRY(hipGetLastError());
         return SCARLET_OK;
     };
-    if (cons_any(cons)) {
-        // components with their own switches: the four-wave kernel's per-component instance for every B (wave k reads
-        // component k's four settings in phase 2), never k_iterate2 / k_fit2x
+    switch (p.kernel) {
+    case FUSED_PC_B6:
+    case FUSED_PC_B8: {
         FusedArgsPC fp;
         static_cast<FusedArgs &>(fp) = f;
         fp.symmetric_c = cons->symmetric; fp.monotonic_c = cons->monotonic; fp.l0_c = cons->l0_thresh; fp.l1_c = cons->l1_thresh;
-        return run(b->B <= 6 ? k_iterate<4, 6, FusedArgsPC> : k_iterate<4, SC_BMAX, FusedArgsPC>, b->S, SC_BLOCK, lds, 1, fp);
+        return run(p.kernel == FUSED_PC_B6 ? k_iterate<4, 6, FusedArgsPC> : k_iterate<4, SC_BMAX, FusedArgsPC>, b->S, 1, fp);
     }
-    // K <= 4, B <= 5: eight waves per scene, a pair of waves per component (fused2.h; its 128-VGPR
-    // budget does not hold a sixth band's accumulators)
-    if (b->K <= 4 && b->B <= 5 && !opt(OPT_FUSED_V1)) {
-        const size_t lds2 = sizeof(float) * ((size_t)b->K * b->H * tile_stride(b->W) + (size_t)b->K * SC_PAIR_VEC_FLOATS) +
-                            (size_t)opt(OPT_PAD_LDS);
-        // the headline shape (BASELINE configs[1]/[3]: 4 sources, 5 bands, 64 x 64, default pipeline) has
-        // an instance with every shape and switch folded at compile time
-        const bool exact64 = b->K == 4 && b->B == 5 && b->H == 64 && b->W == 64 && !b->weights && b->weight_scalar == 1.0f && b->symmetric &&
-                             b->monotonic && b->l0_thresh < 0.f && b->l1_thresh < 0.f && !opt(OPT_NO_EXACT);
-        // (the exact-shape instances use their own tile stride, common.h SC_XS_STRIDE)
-        const size_t lds2x = sizeof(float) * ((size_t)4 * 64 * SC_XS_STRIDE + (size_t)4 * SC_PAIR_VEC_FLOATS) + (size_t)opt(OPT_PAD_LDS);
-        if (n_iter > 0xffffff) n_iter = 0xffffff;
-        if (exact64 && (n_iter > 1 || (opt(OPT_PERSIST_DBG) & 2)) && !opt(OPT_NO_PERSIST)) {
-            // as many workgroups as the chip keeps resident; the scenes beyond them come from the launch's queue
-            // (a counter in the workspace, zeroed on the stream in front of the launch)
-            int n_wg = 0;
-            if ((rc = fit2x_resident_workgroups(lds2x, &n_wg))) return rc;
-            if (n_wg > b->S || (opt(OPT_PERSIST_DBG) & 4)) n_wg = b->S;            // (4: diagnostic, one workgroup per scene)
-            int *queue = ws_at<int>(b, l.fit2x_queue);
-            HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), st));
-            if (done) *done = n_iter;
-            return run(k_fit2x, n_wg, SC_FB2, lds2x, n_iter, f, n_iter | ((opt(OPT_PERSIST_DBG) & 1) << 30), queue, n_wg);
-        }
-        if (exact64) return run(k_iterate2<4, 5, 64>, b->S, SC_FB2, lds2x, 1, f);
-        return run(k_iterate2<4, 5>, b->S, SC_FB2, lds2, 1, f);
+    case FUSED_FIT2X: {
+        // as many workgroups as the chip keeps resident; the scenes beyond them come from the launch's queue
+        // (a counter in the workspace, zeroed on the stream in front of the launch)
+        int n_wg = 0;
+        if ((rc = fit2x_resident_workgroups(p.lds, &n_wg))) return rc;
+        if (n_wg > b->S || (sw.persist_dbg & 4)) n_wg = b->S;                  // (4: diagnostic, one workgroup per scene)
+        int *queue = ws_at<int>(b, l.fit2x_queue);
+        HIP_TRY(hipMemsetAsync(queue, 0, sizeof(int), st));
+        if (done) *done = n_iter;
+        return run(k_fit2x, n_wg, n_iter, f, n_iter | ((sw.persist_dbg & 1) << 30), queue, n_wg);
     }
-    return b->B <= 6 ? run(k_iterate<4, 6>, b->S, SC_BLOCK, lds, 1, f) : run(k_iterate<4, SC_BMAX>, b->S, SC_BLOCK, lds, 1, f);
+    case FUSED_ITERATE2_EXACT: return run(k_iterate2<4, 5, 64>, b->S, 1, f);
+    case FUSED_ITERATE2: return run(k_iterate2<4, 5>, b->S, 1, f);
+    case FUSED_B6: return run(k_iterate<4, 6>, b->S, 1, f);
+    default: return run(k_iterate<4, SC_BMAX>, b->S, 1, f);
+    }
 }
 
 __global__ void k_count_active(const int *active, int S, int *out)
@@ -2152,11 +2112,15 @@ extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constrain
 }
 
 // ---- a low-resolution observation (lowres.h): the shapes, the workspace and the host checks
-static LowresDims lowres_dims(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr)
+static LowresDims lowres_dims(const scarlet_lowres *lr, int H, int W, int B)
 {
     LowresDims d;
-    d.H = state->H; d.W = state->W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = ob->B;
+    d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = B;
     return d;
+}
+static LowresDims lowres_dims(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr)
+{
+    return lowres_dims(lr, state->H, state->W, ob->B);
 }
 static LowresFactors lowres_factors(const scarlet_lowres *lr)
 {
@@ -2187,9 +2151,7 @@ static int check_lowres(const scarlet_lowres *lr, int H, int W, int B, bool need
         return sides ? set_err(SCARLET_E_NOTIMPL, "scarlet_lowres: sides above SCARLET_MAX_SIDE are not supported") : SCARLET_OK;
     if (sides)
         return set_err(SCARLET_E_NOTIMPL, "scarlet_lowres: the factor matrices and one model plane do not fit LDS");
-    LowresDims d;
-    d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = B;
-    if (lowres_lds_bytes(d) > LDS_LIMIT)
+    if (lowres_lds_bytes(lowres_dims(lr, H, W, B)) > LDS_LIMIT)
         return set_err(SCARLET_E_NOTIMPL, "scarlet_lowres: the factor matrices and one model plane do not fit LDS");
     return SCARLET_OK;
 }
@@ -2210,8 +2172,7 @@ static int lowres_op(bool adjoint, const float *in, int n, int H, int W, const s
     if (!in || !out) return set_err(SCARLET_E_ARG, "null plane pointer");
     if (n == 0) return SCARLET_OK;
     LowresOpArgs a = {};
-    a.d.H = H; a.d.W = W; a.d.h = lr->h; a.d.w = lr->w; a.d.nfy = lr->nfy; a.d.nfx = lr->nfx; a.d.B = lr->B;
-    a.f = lowres_factors(lr); a.in = in; a.out = out; a.band = band; a.scene = scene; a.mfma = !opt(OPT_NO_LOWRES_MFMA);
+    a.d = lowres_dims(lr, H, W, lr->B); a.f = lowres_factors(lr); a.in = in; a.out = out; a.band = band; a.scene = scene; a.mfma = !opt(OPT_NO_LOWRES_MFMA);
     const size_t lds = lowres_lds_bytes(a.d);
     int rc;
     if (adjoint) {
@@ -2366,8 +2327,7 @@ extern "C" int64_t scarlet_lowres_op_scratch_bytes(int n, int H, int W, const sc
 {
     if (n < 0) return set_err(SCARLET_E_ARG, "n < 0");
     if (int rc = check_lowres(lr, H, W, lr ? lr->B : 0, false, true)) return rc;
-    LowresDims d;
-    d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = lr->B;
+    const LowresDims d = lowres_dims(lr, H, W, lr->B);
     if (n == 0 || !lowres_streamed(d)) return 0;
     const LrsScratch s = lrs_scratch(d, false);
     return (int64_t)lrs_chunk(s, n) * (int64_t)s.per_plane;
@@ -2384,8 +2344,7 @@ static int lowres_op_large(bool adjoint, const float *in, int n, int H, int W, c
         return set_err(SCARLET_E_ARG, "scarlet_lowres: the scratch is smaller than scarlet_lowres_op_scratch_bytes()");
     if (n == 0) return SCARLET_OK;
     if (need == 0) return lowres_op(adjoint, in, n, H, W, lr, band, scene, out, stream);
-    LowresDims d;
-    d.H = H; d.W = W; d.h = lr->h; d.w = lr->w; d.nfy = lr->nfy; d.nfx = lr->nfx; d.B = lr->B;
+    const LowresDims d = lowres_dims(lr, H, W, lr->B);
     const LowresFactors f = lowres_factors(lr);
     const LrsScratch s = lrs_scratch(d, false);
     const int sized = lrs_chunk(s, n), chunk = lrs_chunk_now(s, n);
@@ -2731,15 +2690,13 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
             return set_err(SCARLET_E_ARG, "bg_rms must be greater than zero in all channels");
     }
     if ((rc = check_counts(b, stream))) return rc;
-    const size_t lds = sizeof(double) * (size_t)b->H * (b->W + 1);
-    if (lds <= LDS_LIMIT) {
-        rc = allow_lds(k_init_extended<false>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_init_extended<false>, dim3(b->S * b->K), dim3(SC_BLOCK), lds, (hipStream_t)stream, a,
-                           (double *)nullptr);
+    const InitTilePlan t = init_tile_plan(b->H, b->W, (size_t)b->S * b->K);
+    if (t.in_lds) {
+        if ((rc = launch_lds(k_init_extended<false>, dim3(b->S * b->K), dim3(SC_BLOCK), t.lds, (hipStream_t)stream, a, (double *)nullptr)))
+            return rc;
     } else {
         DevBuf gtile;                                  // one-time setup: a temporary float64 tile per component
-        DEV_ALLOC(gtile, lds * (size_t)b->S * b->K);
+        DEV_ALLOC(gtile, t.hbm);
         hipLaunchKernelGGL(k_init_extended<true>, dim3(b->S * b->K), dim3(SC_BLOCK), 0, (hipStream_t)stream, a, gtile.as<double>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -2769,9 +2726,8 @@ extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *s
     a.perc = spec->flux_percentiles; a.thresh = spec->thresh;
     a.do_symmetric = spec->init_symmetric; a.do_monotonic = spec->init_monotonic; a.group_symmetric = b->symmetric;
     a.no_hybrid = opt(OPT_NO_HYBRID_SWEEP) ? 1 : 0;
-    const size_t lds = sizeof(double) * (size_t)b->H * (b->W + 1);
-    if (lds <= LDS_LIMIT &&
-        ((rc = allow_lds(k_init_extended_rows<false>, lds)) || (rc = allow_lds(k_init_layers<false>, lds))))
+    const InitTilePlan t = init_tile_plan(b->H, b->W, (size_t)b->S * b->K);
+    if (t.in_lds && ((rc = allow_lds(k_init_extended_rows<false>, t.lds)) || (rc = allow_lds(k_init_layers<false>, t.lds))))
         return rc;
     if ((rc = check_counts(b, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -2781,11 +2737,11 @@ extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *s
     a.ncomp = ncomp.as<int>();
     hipLaunchKernelGGL(k_init_check, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a);
     const dim3 grid(b->S * b->K);
-    if (lds <= LDS_LIMIT) {
-        hipLaunchKernelGGL(k_init_extended_rows<false>, grid, dim3(SC_BLOCK), lds, st, a, (double *)nullptr);
-        if (b->group) hipLaunchKernelGGL(k_init_layers<false>, grid, dim3(SC_BLOCK), lds, st, a, (double *)nullptr);
+    if (t.in_lds) {
+        hipLaunchKernelGGL(k_init_extended_rows<false>, grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
+        if (b->group) hipLaunchKernelGGL(k_init_layers<false>, grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
     } else {
-        DEV_ALLOC(gtile, lds * (size_t)b->S * b->K);
+        DEV_ALLOC(gtile, t.hbm);
         hipLaunchKernelGGL(k_init_extended_rows<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
         if (b->group) hipLaunchKernelGGL(k_init_layers<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
     }

@@ -749,3 +749,6 @@ __device__ inline void wave_symmetry(const Tile &t, int cy, int cx, int algorith
 }
 
 #define SC_WAVE_VEC_FLOATS 448       // av, bv, cv (128 each) + zv (64)
+// the wave-tile form (k_source_update_w, k_operator_w; H, W <= 64): per wave its tile, then its vectors
+__host__ __device__ inline size_t wave_tile_floats(int H, int W) { return (size_t)H * tile_stride(W) + SC_WAVE_VEC_FLOATS; }
+__host__ __device__ inline size_t wave_tile_lds_bytes(int H, int W) { return sizeof(float) * SC_NWAVES * wave_tile_floats(H, W); }

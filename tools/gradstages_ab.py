@@ -1,5 +1,6 @@
 """Build-against-build comparison of the gradient step's launch stages, in the manner of tools/dump_fit.py: the cases
-of tests/gradient_stage_cases.py with two builds of the library (SCARLET_LIB_PATH, tools/ab_variants.sh).
+of tests/gradient_stage_cases.py with two builds of the library (SCARLET_LIB_PATH, tools/ab_variants.sh).  In front of
+the command, `--cases MODULE` takes another table with that module's interface (tests/launch_form_cases.py).
 
     python tools/gradstages_ab.py dump DIR            # 3 iterations of every case: DIR/<case>/<array>.npy
     python tools/gradstages_ab.py compare DIR_A DIR_B # every array byte for byte; lists them; exit status 1 if one differs
@@ -21,14 +22,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import gradient_stage_cases as gs        # noqa: E402
+import importlib                         # noqa: E402
+
+if sys.argv[1:2] == ["--cases"]:
+    gs = importlib.import_module(sys.argv[2])
+    del sys.argv[1:3]
+else:
+    import gradient_stage_cases as gs    # noqa: E402
 
 HIPFFT = os.environ.get("SCARLET_PSF_HIPFFT") == "1"
 MARK = "lgamma"
 
 
 def case_names():
-    return (gs.HIPFFT_CASES if HIPFFT else list(gs.CASES)) + ["convolve_same"]
+    return (gs.HIPFFT_CASES if HIPFFT else list(gs.CASES)) + (["convolve_same"] if hasattr(gs, "convolve_inputs") else [])
 
 
 def run_cases(iters, out=None):
@@ -49,7 +56,8 @@ def run_cases(iters, out=None):
                 b = gs.make_batch(scarlet_amd, c, *gs.scenes(c))
                 torch.cuda.synchronize()
                 torch.lgamma(mark)                      # (the constructors' launches lie between two marks: not compared)
-                assert b.fit(iters, e_rel=0, approximate_L=c.approximate_L) == iters
+                n = getattr(c, "iters", None) or iters  # (a case may fix its own number)
+                assert b.fit(n, e_rel=0, approximate_L=c.approximate_L) == n
                 arrays = gs.state(b)
         torch.cuda.synchronize()
         if out:
