@@ -119,6 +119,19 @@ def constraint_arrays(value, S, K, kind, group=None):
     return out
 
 
+def _check_obs_psfs(psfs, S, B, name, shapes="(B, P, P) or (S, B, P, P)"):
+    """The observed PSFs are one set for every scene or one per scene."""
+    if np.ndim(psfs) not in (3, 4) or tuple(np.shape(psfs)[:-2]) not in ((B,), (S, B)):
+        raise ValueError("%s must be %s, not %s" % (name, shapes, tuple(np.shape(psfs))))
+
+
+def _check_model_psf(psf, name):
+    """The model PSF is one square image with a centre pixel."""
+    shape = tuple(np.shape(psf))
+    if len(shape) != 2 or shape[0] != shape[1] or shape[0] % 2 != 1:
+        raise ValueError("%s must be (P, P) with P odd, not %s" % (name, shape))
+
+
 class ObservationBatch(object):
     """One observation of S scenes for `BlendBatch.from_observations` (reference Observation, observation.py:101-224,
     as one element of Blend(sources, [obs_a, obs_b])): the images cover the model channels band0 .. band0 + B - 1.
@@ -213,15 +226,8 @@ class LowResObservationBatch(ObservationBatch):
 
     def lowres_struct(self, device):
         """(struct scarlet_lowres without a workspace, the device tensors it points to)"""
-        import torch
-        t = {k: torch.as_tensor(v).to(device).contiguous() for k, v in self.host_factors.items()}
-        lr = _lib.ScarletLowres()
-        lr.h, lr.w, lr.B = self.shape[2], self.shape[3], self.shape[1]
-        lr.nfy, lr.nfx = t["uy"].shape[0], t["ux"].shape[0]
-        for k, v in t.items():
-            setattr(lr, k, v.data_ptr())
-        lr.v_per_scene = lr.dhat_per_scene = int(self.per_scene)
-        return lr, t
+        from .observation import lowres_struct
+        return lowres_struct(self.host_factors, self.shape[2], self.shape[3], self.shape[1], self.per_scene, device)
 
 
 class BlendBatch(object):
@@ -252,7 +258,7 @@ class BlendBatch(object):
 
     def __init__(self, images, centers, weights=None, symmetric=True, monotonic=True,
                  l0_thresh=None, l1_thresh=None, centroid_weight=None, mse_capacity=256,
-                 device=None, group=None, n_components=None, _frame=None):
+                 device=None, group=None, n_components=None, _frame=None, _morph=True):
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -294,7 +300,8 @@ class BlendBatch(object):
             self.weight_scalar, weights = float(weights), None
         self.weights = None if weights is None else torch.as_tensor(weights).to(**f32).contiguous()
         self.sed = [torch.zeros((S, K, B), **f32) for _ in range(2)]
-        self.morph = [torch.zeros((S, K, H, W), **f32) for _ in range(2)]
+        # (_morph=False: a gradient batch of from_observations, whose fit reads the state's morphologies instead)
+        self.morph = [torch.zeros((S, K, H, W) if _morph else (1,), **f32) for _ in range(2)]
         self.cur = torch.zeros((S,), **i32)
         self.shifts = torch.full((S, K, 2), float("nan"), **f64)      # NaN == reference's "no shift yet"
         self.flags = torch.full((S, K), _lib.FLAG_SED_NOT_CONVERGED | _lib.FLAG_MORPH_NOT_CONVERGED, **i32)
@@ -345,12 +352,11 @@ class BlendBatch(object):
         assert cw.ndim == 2 and cw.shape[0] == cw.shape[1] and cw.shape[0] % 2 == 1
         self.centroid_weight = torch.as_tensor(cw).to(**f64).contiguous()
         self._observations = None     # from_observations: [(ObservationBatch, its gradient batch)]
+        self._lowres = None           # ... and per observation None, or (scarlet_lowres, what it points to)
         self.L_components = None      # (S, K, 2) float64 after a fit with a prior: the constants each component stepped with
         self._c = _lib.ScarletBatch()
         self._fill_struct()
-        nbytes = _lib.lib.scarlet_batch_workspace_bytes(ctypes.byref(self._c))
-        self.workspace = torch.zeros((int(nbytes),), dtype=torch.uint8, device=self.device)
-        self._c.workspace = self.workspace.data_ptr()
+        self._alloc_workspace()
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -358,8 +364,8 @@ class BlendBatch(object):
         """True when a constraint setting was given per component."""
         return bool(self.constraints)
 
-    # Every call into the library's loops goes through these three.  The *_constrained entry points with a NULL member
-    # read that setting from the batch's scalars, and with prior = NULL step without one.
+    # Every call into the library's loops goes through these two and _fit_observations.  The *_constrained entry points
+    # with a NULL member read that setting from the batch's scalars, and with prior = NULL step without one.
     def _lib_fit(self, ps, max_iter, e_rel, approximate_L, check_every):
         return _lib.check(_lib.lib.scarlet_fit_constrained(
             ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(max_iter),
@@ -370,24 +376,12 @@ class BlendBatch(object):
             ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(in_iteration),
             _lib.stream_ptr()))
 
-    def _lib_fit_observations(self, batches, band0, max_iter, e_rel, approximate_L, check_every, lowres=None):
-        """`batches`: the observations' gradient batches, `band0`: their first model channels, `lowres`: None, or per
-        observation None / (scarlet_lowres, ...) for a low-resolution one (scarlet_fit_observations_lowres_large: the
-        LDS-resident kernels where the model frame lets them, the streamed form beyond)."""
-        n = len(batches)
-        ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for ob in batches])
-        band0 = np.array(band0, dtype=np.int32)
-        self._keep = (ptrs, band0)
-        if lowres is not None and any(x is not None for x in lowres):
-            lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[ctypes.pointer(x[0]) if x is not None else
-                                                              ctypes.POINTER(_lib.ScarletLowres)() for x in lowres])
-            self._keep += (lows,)
-            return _lib.check(_lib.lib.scarlet_fit_observations_lowres_large(
-                ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, lows, band0.ctypes.data_as(ctypes.c_void_p), n,
-                int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
-        return _lib.check(_lib.lib.scarlet_fit_observations_constrained(
-            ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, band0.ctypes.data_as(ctypes.c_void_p), n, int(max_iter),
-            float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
+    def _alloc_workspace(self):
+        """The workspace for the batch as its struct describes it now (it grows with a difference kernel); the library
+        expects it zeroed."""
+        nbytes = _lib.lib.scarlet_batch_workspace_bytes(ctypes.byref(self._c))
+        self.workspace = self.torch.zeros((int(nbytes),), dtype=self.torch.uint8, device=self.device)
+        self._c.workspace = self.workspace.data_ptr()
 
     def _present(self):
         """(S, K) bool device mask of the components each scene uses (all of them without n_components)."""
@@ -481,9 +475,7 @@ class BlendBatch(object):
         self._c.diff_kernel = self.diff_kernel.data_ptr()
         self._c.diff_kernel_per_scene = int(per_scene)
         self._c.psf_h, self._c.psf_w = int(self.diff_kernel.shape[-2]), int(self.diff_kernel.shape[-1])
-        nbytes = _lib.lib.scarlet_batch_workspace_bytes(ctypes.byref(self._c))
-        self.workspace = t.zeros((int(nbytes),), dtype=t.uint8, device=self.device)
-        self._c.workspace = self.workspace.data_ptr()
+        self._alloc_workspace()
         _lib.check(_lib.lib.scarlet_batch_prepare_psf(ctypes.byref(self._c), _lib.stream_ptr()))
         return self
 
@@ -616,15 +608,13 @@ class BlendBatch(object):
             spec.flux_percentiles = dev(perc, t.float32).data_ptr()
         if obs_psfs is not None:
             op = dev(obs_psfs, t.float32)
-            if op.ndim not in (3, 4) or tuple(op.shape[:-2]) not in ((B,), (S, B)):
-                raise ValueError("obs_psfs must be (B, P, P) or (S, B, P, P), not %s" % (tuple(op.shape),))
+            _check_obs_psfs(op, S, B, "obs_psfs")
             peak = op.amax(dim=(-2, -1)).contiguous()
             keep.append(peak)
             spec.obs_psf_peak, spec.obs_psf_peak_per_scene = peak.data_ptr(), int(op.ndim == 4)
         if model_psf is not None:
             mp = dev(model_psf, t.float32)
-            if mp.ndim != 2 or mp.shape[0] != mp.shape[1] or mp.shape[0] % 2 != 1:
-                raise ValueError("model_psf must be (P, P) with P odd, not %s" % (tuple(mp.shape),))
+            _check_model_psf(mp, "model_psf")
             spec.model_psf, spec.model_psf_P = mp.data_ptr(), int(mp.shape[0])
         spec.thresh = float(thresh)
         spec.init_symmetric = int(bool(init_symmetric))
@@ -751,11 +741,16 @@ class BlendBatch(object):
 
     # ------------------------------------------------------------------ several observations
     @classmethod
-    def from_observations(cls, observations, centers, **kwargs):
+    def from_observations(cls, observations, centers, _host_gradients=False, _channels=None, **kwargs):
         """A batch fitted jointly against several observations of every scene (reference Blend(sources, [obs_a,
         obs_b]), blend.py:24-43, 120-139, 219-220).  The factors span the model frame's C = max(band0 + B) channels
         (C <= 8); `centers` and the other keyword arguments are those of BlendBatch (ragged centre lists give
-        n_components).  Start the sources with `init_combined` (or `set_state`), then `fit` / `step`."""
+        n_components).  Start the sources with `init_combined` (or `set_state`), then `fit` / `step`.
+
+        _host_gradients : `Blend`'s Python pipeline calls scarlet_backward_gradients on the state and on every
+            observation's batch itself, so the state gets real (zero) images and the observations' batches keep their
+            own morphology planes; the joint fit reads neither.
+        _channels : the model frame's channel count where the observations need not reach its last channel (`Blend`)."""
         obs = list(observations)
         if not 1 <= len(obs) <= _lib.MAX_OBSERVATIONS:
             raise ValueError("from_observations: 1 to %d observations, not %d" % (_lib.MAX_OBSERVATIONS, len(obs)))
@@ -775,6 +770,11 @@ class BlendBatch(object):
                 raise ValueError("from_observations: observation %d has %d scenes of %d x %d, observation 0 %d of %d x %d"
                                  % (i, o.shape[0], o.shape[2], o.shape[3], S, H, W))
         C = max(o.band0 + o.B for o in obs)
+        if _channels is not None:
+            if int(_channels) < C:
+                raise ValueError("from_observations: the observations span %d model channels, the model frame has %d"
+                                 % (C, _channels))
+            C = int(_channels)
         if C > 8:
             raise ValueError("from_observations: the observations span %d model channels, at most 8 are supported" % C)
         for k in ("weights", "images"):
@@ -782,23 +782,19 @@ class BlendBatch(object):
                 raise ValueError("from_observations: %s belong to the observations" % k)
         state = cls(None, centers, _frame=(S, C, H, W), **kwargs)
         torch, f32 = state.torch, dict(dtype=state.torch.float32, device=state.device)
+        if _host_gradients:
+            state.images = torch.zeros((S, C, H, W), **f32)
+            state._fill_struct()
         batches = []
-        state._lowres = [None] * len(obs)        # per observation: None, or (scarlet_lowres, what it points to)
+        state._lowres = [None] * len(obs)
         for i, o in enumerate(obs):
             low = isinstance(o, LowResObservationBatch)
             # (a low-resolution batch lives on its own pixel grid: the model-frame centres mean nothing there)
             ob = cls(o.images, torch.zeros_like(state.centers) if low else state.centers, weights=o.weights, symmetric=False,
-                     monotonic=False, mse_capacity=1, centroid_weight=state.centroid_weight.cpu().numpy(), device=state.device)
-            # the fit reads the state's morphologies: the observation's own planes are not used
-            ob.morph = [torch.zeros((1,), **f32) for _ in range(2)]
-            ob._fill_struct()
+                     monotonic=False, mse_capacity=1, centroid_weight=state.centroid_weight.cpu().numpy(), device=state.device,
+                     _morph=_host_gradients)
             if low:
-                lr, keep = o.lowres_struct(state.device)
-                nbytes = _lib.check(_lib.lib.scarlet_lowres_large_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c),
-                                                                                  ctypes.byref(lr)))
-                keep["workspace"] = torch.empty((int(nbytes),), dtype=torch.uint8, device=state.device)
-                lr.workspace = keep["workspace"].data_ptr()
-                state._lowres[i] = (lr, keep)
+                state._lowres[i] = state._attach_lowres(o, ob)
             elif o.diff_kernel is not None:
                 ob.set_diff_kernel(o.diff_kernel)
             batches.append((o, ob))
@@ -835,9 +831,31 @@ class BlendBatch(object):
             raise ValueError("a batch of several observations starts its sources with init_combined "
                              "(CombinedExtendedSource), not init_extended / init_sources")
 
+    def _attach_lowres(self, o, ob):
+        """(scarlet_lowres with its workspace, what it points to) of the low-resolution observation `o` with gradient
+        batch `ob`, sized for this state batch"""
+        lr, keep = o.lowres_struct(self.device)
+        nbytes = _lib.check(_lib.lib.scarlet_lowres_large_workspace_bytes(ctypes.byref(self._c), ctypes.byref(ob._c), ctypes.byref(lr)))
+        keep["workspace"] = self.torch.empty((int(nbytes),), dtype=self.torch.uint8, device=self.device)
+        lr.workspace = keep["workspace"].data_ptr()
+        return lr, keep
+
     def _fit_observations(self, max_iter, e_rel, approximate_L, check_every):
-        return self._lib_fit_observations([ob for _, ob in self._observations], [o.band0 for o, _ in self._observations],
-                                          max_iter, e_rel, approximate_L, check_every, lowres=getattr(self, "_lowres", None))
+        """The joint fit against `_observations` (scarlet_fit_observations_lowres_large when one of them is
+        low-resolution: the LDS-resident kernels where the model frame lets them, the streamed form beyond).  The
+        library copies the pointer arrays into its argument structs before it launches anything."""
+        n = len(self._observations)
+        ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
+        first = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
+        band0 = first.ctypes.data_as(ctypes.c_void_p)
+        tail = (n, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
+        if any(x is not None for x in self._lowres):
+            none = ctypes.POINTER(_lib.ScarletLowres)()
+            lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+            return _lib.check(_lib.lib.scarlet_fit_observations_lowres_large(
+                ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, lows, band0, *tail))
+        return _lib.check(_lib.lib.scarlet_fit_observations_constrained(
+            ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, band0, *tail))
 
     def init_combined(self, bg_rms, obs_idx=0, obs_psfs=None, model_psf=None, thresh=1.0, init_monotonic=None):
         """CombinedExtendedSource for every component (reference source.py:183-240, 495-536): the SED is the
@@ -886,17 +904,15 @@ class BlendBatch(object):
                 raise ValueError("init_combined: bg_rms[%d] must be (%d,) or (%d, %d), not %s" % (i, o.B, self.S, o.B, tuple(bg)))
             p = None if obs_psfs is None else obs_psfs[i]
             if p is not None:
-                if np.ndim(p) not in (3, 4) or tuple(np.shape(p)[:-2]) not in ((o.B,), (self.S, o.B)):
-                    raise ValueError("init_combined: obs_psfs[%d] must be (%d, P, P) or (%d, %d, P, P), not %s"
-                                     % (i, o.B, self.S, o.B, tuple(np.shape(p))))
+                _check_obs_psfs(p, self.S, o.B, "init_combined: obs_psfs[%d]" % i,
+                                "(%d, P, P) or (%d, %d, P, P)" % (o.B, self.S, o.B))
                 p = dev(p).amax(dim=(-2, -1)).contiguous()
                 keep.append(p)
             peaks.append(p)
         mmax = None
         if model_psf is not None:
             mp = np.asarray(model_psf.cpu() if t.is_tensor(model_psf) else model_psf)
-            if mp.ndim != 2 or mp.shape[0] != mp.shape[1] or mp.shape[0] % 2 != 1:
-                raise ValueError("init_combined: model_psf must be (P, P) with P odd, not %s" % (mp.shape,))
+            _check_model_psf(mp, "init_combined: model_psf")
             mmax = dev(mp).amax().reshape(1).contiguous()
             keep.append(mmax)
         # the morphology: the extended start on observation obs_idx, written straight into the state's current buffers

@@ -2,7 +2,8 @@
 
 ``Blend(sources, observations).fit(max_iter, e_rel, approximate_L)`` runs the reference's
 iteration (blend.py:65-102) on the GPU.  A `Blend` is a batch of ONE scene on top of
-`scarlet_amd.batch.BlendBatch`; many scenes at once go through `BlendBatch` directly.
+`scarlet_amd.batch.BlendBatch` (with several observations: of `BlendBatch.from_observations`); many scenes at once
+go through `BlendBatch` directly.
 
 Two execution modes, chosen automatically:
 
@@ -49,10 +50,6 @@ class Blend(ComponentTree):
         self.L_morph = 1
 
     # ------------------------------------------------------------------ device state
-    def _source_attr(self, name, default):
-        vals = [getattr(s, name, default) for s in self.sources]
-        return vals
-
     def _builtin_pipeline(self):
         """True when every source uses the reference's stock update() (source.py:402-440)."""
         from .source import PointSource, MultiComponentSource
@@ -78,9 +75,9 @@ class Blend(ComponentTree):
             return self._batch
         torch = _lib.require_gpu()
         from .batch import BlendBatch
-        from .observation import LowResObservation as _Low
+        from .observation import LowResObservation
         multi = len(self.observations) != 1 or self.observations[0]._band_slice != slice(None) or \
-            isinstance(self.observations[0], _Low)
+            isinstance(self.observations[0], LowResObservation)
         obs = self.observations[0]
         comps = self.components
         from .source import MultiComponentSource
@@ -111,49 +108,18 @@ class Blend(ComponentTree):
         sym = sym[0] if len(set(sym)) == 1 else [sym]
         mono = mono[0] if len(set(mono)) == 1 else [mono]
 
-        from .observation import LowResObservation
-
-        def obs_batch(o, images=None, state=True):
-            low = images is None and isinstance(o, LowResObservation)
-            ob = BlendBatch(o._images_device()[None] if images is None else images,
-                            # (a low-resolution batch lives on its own pixel grid: the model-frame centres mean nothing there)
-                            np.zeros((1, len(centers), 2), dtype=np.int32) if low else np.array(centers, dtype=np.int32)[None],
-                            weights=None if (images is not None or o._weights_device() is None) else o._weights_device()[None],
-                            symmetric=sym if state else bool(np.any(sym)),
-                            monotonic=mono if state else bool(np.any(mono)),
-                            centroid_weight=cw,
-                            group=np.array(group, dtype=np.int32)[None] if (builtin and any(g >= 0 for g in group)) else None)
-            if images is None:
-                if type(o.weights) is not np.ndarray and o.weights != 1:
-                    ob.weight_scalar = float(o.weights)
-                    ob._fill_struct()
-                if o._diff_kernels is not None and not low:
-                    ob.set_diff_kernel(np.asarray(o._diff_kernels.image, dtype=np.float32))
-            return ob
-
-        def lowres_of(o, ob, state):
-            """None for an observation on the model's grid; (scarlet_lowres with its workspace, what it points to) for a
-            LowResObservation, which goes through LowResObservationBatch's checks as a batch of one scene"""
-            if not isinstance(o, LowResObservation):
-                return None
-            from .batch import LowResObservationBatch
-            lr, keep = LowResObservationBatch(o.images[None], band0=o._band_slice.start or 0, geometry=o).lowres_struct(state.device)
-            nbytes = _lib.check(_lib.lib.scarlet_lowres_large_workspace_bytes(ctypes.byref(state._c), ctypes.byref(ob._c), ctypes.byref(lr)))
-            keep["workspace"] = torch.empty((int(nbytes),), dtype=torch.uint8, device=state.device)
-            lr.workspace = keep["workspace"].data_ptr()
-            return lr, keep
-
-        self._obs_batches, self._lowres = None, None
+        kw = dict(symmetric=sym, monotonic=mono, centroid_weight=cw,
+                  group=np.array(group, dtype=np.int32)[None] if (builtin and any(g >= 0 for g in group)) else None)
         if multi:
-            # several observations and / or band slices (reference blend.py:120-139, 219-220): the state
-            # (factors, centres, flags, convergence) lives in a batch over the model frame's channels,
-            # every observation has a gradient-only batch over its own channels
-            C, Ny, Nx = self.frame.shape
-            b = obs_batch(obs, images=torch.zeros((1, C, Ny, Nx), dtype=torch.float32, device="cuda"))
-            self._obs_batches = [(obs_batch(o, state=False), o._band_slice) for o in self.observations]
-            self._lowres = [lowres_of(o, ob, b) for o, (ob, _) in zip(self.observations, self._obs_batches)]
+            # several observations, band slices, a low-resolution observation (reference blend.py:120-139, 219-220):
+            # the batch of one scene that BlendBatch.from_observations makes of them, over all the frame's channels.
+            # The batch outlives a change of pipeline (a prior set between two fits), so it is always built for both.
+            b = BlendBatch.from_observations([o.as_batch() for o in self.observations], np.array(centers, dtype=np.int32)[None],
+                                             _host_gradients=True, _channels=self.frame.C, **kw)
         else:
-            b = obs_batch(obs)
+            b = BlendBatch(obs._images_device()[None], np.array(centers, dtype=np.int32)[None], weights=obs._batch_weights(), **kw)
+            if obs._diff_kernels is not None:
+                b.set_diff_kernel(np.asarray(obs._diff_kernels.image, dtype=np.float32))
         sed = torch.stack([c._own_sed for c in comps])[None]
         morph = torch.stack([c._own_morph for c in comps])[None]
         shifts = np.full((1, len(comps), 2), np.nan)
@@ -222,25 +188,19 @@ class Blend(ComponentTree):
         """Fit the model of every source to the data (reference blend.py:65-102)."""
         b = self._ensure_batch()
         if self._builtin_pipeline():
-            if self._obs_batches is None:
-                b.fit(max_iter, e_rel=e_rel, approximate_L=approximate_L, check_every=4)
-            else:
-                # several observations / band slices (reference blend.py:120-139, 219-220): gradients of every
-                # observation, their sum, L * n_obs, step, constraints and convergence in one device loop
-                b._ensure_mse_capacity(max_iter)
-                b.active.fill_(1)
-                b._lib_fit_observations([ob for ob, _ in self._obs_batches], [sl.start or 0 for _, sl in self._obs_batches],
-                                        max_iter, e_rel, approximate_L, 4, lowres=self._lowres)
+            # (several observations: gradients of every observation, their sum, L * n_obs, step, constraints and
+            # convergence in one device loop, as for a batch of many scenes)
+            b.fit(max_iter, e_rel=e_rel, approximate_L=approximate_L, check_every=4)
             b.raise_on_status()
             self._sync_sources()
             return self
         # Python pipeline: device gradient step, Python update() per source, device check
-        if self._lowres is not None and any(x is not None for x in self._lowres):
+        if b._lowres is not None and any(x is not None for x in b._lowres):
             raise NotImplementedError("a LowResObservation needs the built-in update() of every source (the fit stays on the device)")
         s = _lib.stream_ptr
         b._ensure_mse_capacity(max_iter)
         b.active.fill_(1)
-        multi = self._obs_batches is not None
+        multi = b._observations is not None
         for _ in range(max_iter):
             cur = int(b.cur[0].item())
             # Prior hooks (reference blend.py:86-90, component.py:177-187) run on the factors
@@ -271,7 +231,8 @@ class Blend(ComponentTree):
                 if multi:
                     g_sed = torch.zeros_like(x_sed); g_morph = torch.zeros_like(x_morph)
                     loss = 0.0
-                    for ob, sl in self._obs_batches:
+                    for o, ob in b._observations:
+                        sl = slice(o.band0, o.band0 + o.B)
                         ob.sed[0][0].copy_(x_sed[:, sl]); ob.morph[0][0].copy_(x_morph)
                         ob.cur.zero_(); ob.it.zero_(); ob.active.fill_(1)
                         _lib.check(_lib.lib.scarlet_backward_gradients(ctypes.byref(ob._c), 0, s()))

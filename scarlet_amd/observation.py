@@ -78,6 +78,50 @@ class Frame(object):
         return tuple(int(coord) for coord in sky_coord)
 
 
+def lowres_struct(factors, h, w, B, per_scene, device):
+    """(struct scarlet_lowres without a workspace, the device tensors it points to) from the host factor matrices:
+    `factors_f32()` of one geometry, or the dict whose vy / vx / dhat are stacked per scene (`per_scene`)."""
+    torch = _lib.require_gpu()
+    t = {k: torch.as_tensor(v).to(device).contiguous() for k, v in factors.items()}
+    lr = _lib.ScarletLowres()
+    lr.h, lr.w, lr.B = int(h), int(w), int(B)
+    lr.nfy, lr.nfx = t["uy"].shape[0], t["ux"].shape[0]
+    for k, v in t.items():
+        setattr(lr, k, v.data_ptr())
+    lr.v_per_scene = lr.dhat_per_scene = int(per_scene)
+    return lr, t
+
+
+def _match_dtype_and_bands(obs, model_frame):
+    """What both `match` methods begin with (reference observation.py:155-180): the data cast to the model frame's
+    dtype, and the band slice from the two frames' channels."""
+    if obs.frame.dtype != model_frame.dtype:
+        msg = "Dtypes of model and observation different. Casting observation to {}"
+        logger.warning(msg.format(model_frame.dtype))
+        obs.frame.dtype = model_frame.dtype
+        obs.images = obs.images.astype(model_frame.dtype)
+        if type(obs.weights) is np.ndarray:
+            obs.weights = obs.weights.astype(model_frame.dtype)
+        if obs.frame._psfs is not None:
+            obs.frame.psfs.update_dtype(model_frame.dtype)
+    obs._band_slice = slice(None)
+    if obs.frame.channels is not model_frame.channels:
+        assert obs.frame.channels is not None and model_frame.channels is not None
+        bmin = list(model_frame.channels).index(obs.frame.channels[0])
+        bmax = list(model_frame.channels).index(obs.frame.channels[-1])
+        obs._band_slice = slice(bmin, bmax + 1)
+
+
+def _weighted_loss(obs, d):
+    """0.5 * sum (weights * d)^2 for the residual d on the device: array weights, a scalar other than 1, or none."""
+    w = obs._weights_device()
+    if w is not None:
+        d = w * d
+    elif obs.weights != 1:
+        d = float(obs.weights) * d
+    return 0.5 * (d.double() ** 2).sum()
+
+
 class Observation(object):
     """Images, weights and PSFs of one data set (reference observation.py:102-239)."""
 
@@ -94,21 +138,7 @@ class Observation(object):
     def match(self, model_frame):
         """Set up the mapping from the model frame to this observation: dtype, band slice and
         PSF difference kernel (reference observation.py:155-196)."""
-        if self.frame.dtype != model_frame.dtype:
-            msg = "Dtypes of model and observation different. Casting observation to {}"
-            logger.warning(msg.format(model_frame.dtype))
-            self.frame.dtype = model_frame.dtype
-            self.images = self.images.astype(model_frame.dtype)
-            if type(self.weights) is np.ndarray:
-                self.weights = self.weights.astype(model_frame.dtype)
-            if self.frame._psfs is not None:
-                self.frame.psfs.update_dtype(model_frame.dtype)
-        self._band_slice = slice(None)
-        if self.frame.channels is not model_frame.channels:
-            assert self.frame.channels is not None and model_frame.channels is not None
-            bmin = list(model_frame.channels).index(self.frame.channels[0])
-            bmax = list(model_frame.channels).index(self.frame.channels[-1])
-            self._band_slice = slice(bmin, bmax + 1)
+        _match_dtype_and_bands(self, model_frame)
         self._diff_kernels = None
         if self.frame.psfs is not model_frame.psfs:
             assert self.frame.psfs is not None and model_frame.psfs is not None
@@ -146,13 +176,20 @@ class Observation(object):
         torch = _lib.require_gpu()
         m = self.render(model)
         m = m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m)).cuda()
+        return _weighted_loss(self, m.to(torch.float32) - self._images_device())
+
+    def as_batch(self):
+        """This observation as the one-scene `ObservationBatch` that `BlendBatch.from_observations` takes."""
+        from .batch import ObservationBatch
+        ob = ObservationBatch(self._images_device()[None], band0=self._band_slice.start or 0, weights=self._batch_weights())
+        if self._diff_kernels is not None:
+            ob.set_diff_kernel(np.asarray(self._diff_kernels.image, dtype=np.float32))
+        return ob
+
+    def _batch_weights(self):
+        """the weights as a batch of one scene takes them: (1, B, H, W) on the device, or the Python scalar"""
         w = self._weights_device()
-        d = m.to(torch.float32) - self._images_device()
-        if w is not None:
-            d = w * d
-        elif self.weights != 1:
-            d = float(self.weights) * d
-        return 0.5 * (d.double() ** 2).sum()
+        return self.weights if w is None else w[None]
 
 
 class LowResObservation(Observation):
@@ -184,20 +221,7 @@ class LowResObservation(Observation):
         are all of them), ``_band_slice``, ``origin`` / ``step`` (the model-frame position of pixel (0, 0) and the pixel
         ratio per axis) and ``factors`` (complex128; `factors_f32` and the device tensors derive from it)."""
         from . import resampling as rs
-        if self.frame.dtype != model_frame.dtype:
-            msg = "Dtypes of model and observation different. Casting observation to {}"
-            logger.warning(msg.format(model_frame.dtype))
-            self.frame.dtype = model_frame.dtype
-            self.images = self.images.astype(model_frame.dtype)
-            if type(self.weights) is np.ndarray:
-                self.weights = self.weights.astype(model_frame.dtype)
-            self.frame.psfs.update_dtype(model_frame.dtype)
-        self._band_slice = slice(None)
-        if self.frame.channels is not model_frame.channels:
-            assert self.frame.channels is not None and model_frame.channels is not None
-            bmin = list(model_frame.channels).index(self.frame.channels[0])
-            bmax = list(model_frame.channels).index(self.frame.channels[-1])
-            self._band_slice = slice(bmin, bmax + 1)
+        _match_dtype_and_bands(self, model_frame)
         assert model_frame.wcs is not None and model_frame.psfs is not None, "the model frame needs a WCS and a PSF"
         a_obs, a_model = rs.affine(self.frame.wcs), rs.affine(model_frame.wcs)
         self.sin_rot, self.cos_rot, self.isrot = rs.rotation(a_obs, a_model)
@@ -247,15 +271,9 @@ class LowResObservation(Observation):
 
     def _lowres_struct(self):
         """(struct scarlet_lowres without a workspace, the device tensors it points to)"""
-        torch = _lib.require_gpu()
         if "lowres" not in self._device:
-            t = {k: torch.as_tensor(v).cuda() for k, v in self.factors_f32().items()}
-            lr = _lib.ScarletLowres()
-            lr.h, lr.w = self.frame.Ny, self.frame.Nx
-            lr.nfy, lr.nfx, lr.B = t["uy"].shape[0], t["ux"].shape[0], t["dhat"].shape[0]
-            for k, v in t.items():
-                setattr(lr, k, v.data_ptr())
-            self._device["lowres"] = (lr, t)
+            f = self.factors_f32()
+            self._device["lowres"] = lowres_struct(f, self.frame.Ny, self.frame.Nx, f["dhat"].shape[0], False, "cuda")
         return self._device["lowres"]
 
     def _render(self, model):
@@ -284,11 +302,11 @@ class LowResObservation(Observation):
 
     def get_loss(self, model):
         """0.5 * sum (weights * (render(model) - images))^2 (reference observation.py:580-599)."""
-        torch = _lib.require_gpu()
-        d = self._render(model) - self._images_device()
-        w = self._weights_device()
-        if w is not None:
-            d = w * d
-        elif self.weights != 1:
-            d = float(self.weights) * d
-        return 0.5 * (d.double() ** 2).sum()
+        return _weighted_loss(self, self._render(model) - self._images_device())
+
+    def as_batch(self):
+        """This observation as the one-scene `LowResObservationBatch` that `BlendBatch.from_observations` takes (the
+        difference kernels live in the factor matrices: the batch gets none)."""
+        from .batch import LowResObservationBatch
+        return LowResObservationBatch(self._images_device()[None], band0=self._band_slice.start or 0, geometry=self,
+                                      weights=self._batch_weights())

@@ -418,6 +418,125 @@ def test_several_observations_match_the_reference(scarlet):
             assert_array_equal(np.array([c.pixel_center for c in blend.components]), g[tag + "_center"])
 
 
+def test_blend_with_several_observations_is_the_batch_of_one(scarlet):
+    """Blend(sources, [obs_a, obs_b]) is BlendBatch.from_observations of one scene: the scene of the test above cut
+    into two band-sliced observations on the model's grid -- the first with its own PSFs (a difference kernel) and a
+    scalar weight other than 1, the second with the model's PSF and array weights.  Two sources, 5 iterations, bit for
+    bit; then the same blend through the Python pipeline, at the tolerance the two pipelines are held to above."""
+    from scarlet_amd import synth
+    scn = synth.make_scene(7)
+    images, ch = scn["images"], list("grizy")
+    y, x = np.mgrid[-5:6, -5:6]
+    gauss = lambda sigma: (lambda p: (p / p.sum()).astype(np.float32))(np.exp(-(y * y + x * x) / (2 * sigma ** 2)))
+    frame = scarlet.Frame(images.shape, psfs=gauss(0.9)[None], channels=ch)
+    full = scarlet.Observation(images, psfs=np.array([gauss(1.4 + 0.1 * b) for b in range(5)]), channels=ch).match(frame)
+    wts = np.random.default_rng(7).uniform(0.5, 1.5, size=images[3:].shape).astype(np.float32)
+
+    def blend_of(python_pipeline):
+        obs = [scarlet.Observation(images[:3], psfs=np.array([gauss(1.4 + 0.1 * b) for b in range(3)]), channels=ch[:3]).match(frame),
+               scarlet.Observation(images[3:], psfs=frame.psfs, weights=wts, channels=ch[3:]).match(frame)]
+        obs[0].weights = 0.5
+        assert obs[0]._diff_kernels is not None and obs[1]._diff_kernels is None
+        srcs = [scarlet.ExtendedSource(frame, tuple(int(v) for v in p), full, np.ones(5) * 0.1) for p in scn["centers"][:2]]
+        blend = scarlet.Blend(srcs, obs)
+        blend.python_pipeline = python_pipeline
+        assert blend._builtin_pipeline() == (not python_pipeline)
+        return blend, obs, srcs
+
+    blend, obs, srcs = blend_of(False)
+    sed0, morph0 = np.stack([npy(s.sed) for s in srcs]), np.stack([npy(s.morph) for s in srcs])
+    cen0 = np.array([s.pixel_center for s in srcs], dtype=np.int32)
+    sh0 = np.array([s.shift for s in srcs], dtype=np.float64)        # (the constructors' update() measured one)
+    cw = np.asarray(srcs[0]._centroid_weight, dtype=np.float64)
+    blend.fit(5, e_rel=0)
+    a = scarlet.ObservationBatch(images[None, :3], band0=0, weights=0.5)
+    a.set_diff_kernel(np.asarray(obs[0]._diff_kernels.image, dtype=np.float32))
+    b = scarlet.BlendBatch.from_observations([a, scarlet.ObservationBatch(images[None, 3:], band0=3, weights=wts[None])],
+                                             cen0[None], centroid_weight=cw)
+    b.set_state(sed0[None], morph0[None], shifts=sh0[None])
+    assert b.fit(5, e_rel=0) == 5
+    assert_array_equal(np.stack([npy(s.sed) for s in srcs]), npy(b.sed_current[0]))
+    assert_array_equal(np.stack([npy(s.morph) for s in srcs]), npy(b.morph_current[0]))
+    assert_array_equal(np.array([s.pixel_center for s in srcs]), npy(b.centers[0]))
+    assert_array_equal(np.array([s.shift for s in srcs]), npy(b.shifts[0]))
+    assert blend.mse == b.mse(0) and len(blend.mse) == 5
+
+    blend_p, _, srcs_p = blend_of(True)
+    blend_p.fit(5, e_rel=0)
+    assert blend_p.it == 5
+    assert rel_err(blend_p.mse, blend.mse) < 1e-5
+    assert rel_err(np.stack([npy(s.morph) for s in srcs_p]), np.stack([npy(s.morph) for s in srcs])) < 1e-5
+    assert rel_err(np.stack([npy(s.sed) for s in srcs_p]), np.stack([npy(s.sed) for s in srcs])) < 1e-5
+    assert_array_equal(np.array([s.pixel_center for s in srcs_p]), np.array([s.pixel_center for s in srcs]))
+
+
+def test_blend_with_two_observations_changes_pipeline_between_fits(scarlet):
+    """The batch a Blend builds at its first fit serves every later one: three built-in iterations, then a source gets
+    a prior hook (or the pipeline is forced), then three through the Python pipeline -- against the Python pipeline
+    from the start, at the tolerance the two pipelines are held to above."""
+    from scarlet_amd import synth
+    scn = synth.make_scene(7)
+    images, ch = scn["images"], list("grizy")
+    frame = scarlet.Frame(images.shape, channels=ch)
+    full = scarlet.Observation(images, channels=ch).match(frame)
+
+    class NoPrior(object):               # (a hook that adds nothing: what it changes is the pipeline alone)
+        L_sed = L_morph = 0.0
+
+        def compute_grad(self, component):
+            self.sed_grad, self.morph_grad = torch.zeros_like(component.sed), torch.zeros_like(component.morph)
+
+    def blend_of():
+        obs = [scarlet.Observation(images[:3], channels=ch[:3]).match(frame),
+               scarlet.Observation(images[3:], channels=ch[3:]).match(frame)]
+        srcs = [scarlet.ExtendedSource(frame, tuple(int(v) for v in p), full, np.ones(5) * 0.1) for p in scn["centers"][:2]]
+        return scarlet.Blend(srcs, obs)
+
+    ref = blend_of()
+    ref.python_pipeline = True
+    ref.fit(3, e_rel=0).fit(3, e_rel=0)
+    for how in ("prior", "forced"):
+        blend = blend_of()
+        assert blend._builtin_pipeline()
+        blend.fit(3, e_rel=0)
+        if how == "prior":
+            blend.sources[0].prior = NoPrior()
+        else:
+            blend.python_pipeline = True
+        assert not blend._builtin_pipeline()
+        blend.fit(3, e_rel=0)
+        assert blend.it == ref.it == 6
+        assert rel_err(blend.mse, ref.mse) < 1e-5
+        assert rel_err(np.stack([npy(c.morph) for c in blend.components]), np.stack([npy(c.morph) for c in ref.components])) < 1e-5
+        assert rel_err(np.stack([npy(c.sed) for c in blend.components]), np.stack([npy(c.sed) for c in ref.components])) < 1e-5
+        assert_array_equal(np.array([c.pixel_center for c in blend.components]), np.array([c.pixel_center for c in ref.components]))
+
+
+def test_blend_whose_observation_stops_short_of_the_last_channel(scarlet):
+    """Blend(sources, obs_gri) in a grizy model frame: the state spans the frame's five channels, the observation
+    its first three.  The same loss stated on the model's grid: all five channels with weight 0 on the last two (the
+    fused single-observation path), at the project's 1e-5."""
+    from scarlet_amd import synth
+    scn = synth.make_scene(7)
+    images, ch = scn["images"], list("grizy")
+    frame = scarlet.Frame(images.shape, channels=ch)
+    full = scarlet.Observation(images, channels=ch).match(frame)
+    weights = np.ones_like(images)
+    weights[3:] = 0
+    fits = []
+    for obs in (scarlet.Observation(images[:3], channels=ch[:3]).match(frame),
+                scarlet.Observation(images, weights=weights, channels=ch).match(frame)):
+        srcs = [scarlet.ExtendedSource(frame, tuple(int(v) for v in p), full, np.ones(5) * 0.1) for p in scn["centers"][:2]]
+        blend = scarlet.Blend(srcs, obs).fit(5, e_rel=0)
+        assert blend.it == 5 and blend._batch.B == 5
+        fits.append((blend.mse, np.stack([npy(c.sed) for c in srcs]), np.stack([npy(c.morph) for c in srcs]),
+                     np.array([c.pixel_center for c in srcs])))
+    (mse, sed, morph, cen), (mse_w, sed_w, morph_w, cen_w) = fits
+    assert (blend._batch._observations is None) and rel_err(mse, mse_w) < 1e-5
+    assert rel_err(sed, sed_w) < 1e-5 and rel_err(morph, morph_w) < 1e-5
+    assert_array_equal(cen, cen_w)
+
+
 def test_approximate_L_with_two_observations(scarlet):
     """fit(approximate_L=True) on a blend with two observations (reference blend.py:189-201,
     219-220), against a fixture generated by the reference (gen_fit_extras2)."""

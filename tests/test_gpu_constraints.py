@@ -488,7 +488,7 @@ def test_blend_of_sources_that_disagree_with_two_observations(scarlet):
     assert dev._builtin_pipeline() and not ref._builtin_pipeline()
     dev.fit(10, e_rel=0)
     ref.fit(10, e_rel=0)
-    assert dev._batch.constrained and dev._obs_batches is not None and len(dev.mse) == len(ref.mse) == 10
+    assert dev._batch.constrained and dev._batch._observations is not None and len(dev.mse) == len(ref.mse) == 10
     assert rel_err(dev.mse, ref.mse) <= TOL
     for a, b in zip(dev.components, ref.components):
         assert rel_err(npy(a.sed), npy(b.sed)) <= TOL and rel_err(npy(a.morph), npy(b.morph)) <= TOL

@@ -112,6 +112,8 @@ def test_observation_batch_argument_errors():
         BlendBatch.from_observations([a, ObservationBatch(np.zeros((3, 2, 8, 8)), band0=3)], cen)
     with pytest.raises(ValueError, match="8"):
         BlendBatch.from_observations([a, ObservationBatch(np.zeros((2, 2, 8, 8)), band0=7)], cen)
+    with pytest.raises(ValueError, match="the model frame has 2"):      # (the frame's channel count, as Blend passes it)
+        BlendBatch.from_observations([a], cen, _channels=2)
 
 
 def test_init_combined_argument_errors():
