@@ -101,6 +101,22 @@ __device__ __forceinline__ KsGeom ks_geom(const SymWindow &s, const unsigned sho
 // previous morphology for the convergence sums, the cached Hankel vectors -- are loaded past the L1 (non-temporal
 // loads, L2-served).
 //
+// The start of an iteration.  Rule: on the path a launch runs all the time -- re-entered, tiles resident -- every load
+// is waited for only where its value is used.  The images are requested by the iteration's first instructions (their
+// addresses need the scene and the thread, nothing from LDS), the cached Hankel vectors right behind them, and the
+// first s_waitcnt that counts vector-memory loads stands in front of the gradient pass's first FMA on an image; the
+// first group waits for its own five loads only (the exact instances know tid < 512: no lane-masked loads).  Nothing
+// LDS still holds is fetched again: SEDs, centres, shifts, the placement and the scene's component count (place_s),
+// the FFT length table (fl_s).  The waits the hardware executes are placed by the compiler per REGISTER, with one
+// counter for all loads in issue order: a register that is the target of a global load on one way into a block and
+// of an LDS read on another is waited for with `vmcnt` on both, and that wait covers every load issued before it
+// -- with one body for all starts of an iteration, wave 0 drained its image loads before the first barrier (SED
+// staging: sed_in or carry_sed), every wave waited for its cached vectors before reading the tiles (mreg: planes or
+// tiles), and wave 0 waited for the length table in front of all of it (profiles/prologue_notes.md).  Separate
+// variables do not help, they meet in a phi.  So phase 0 exists twice (`phase0` below, FAST or not), chosen by a
+// wave-uniform branch, and the two ways meet behind the last use of a tile register; what is still pending at the join is
+// the first image group on both ways and, on the FAST one, the cached vectors requested behind it.
+//
 // Step sizes (monotonic pipelines; the exact instance always is one).  The SED step needs 1 / lambda_max of the
 // morphology Gram, but its result is read only after the sweep; the morphology step needs 1 / lambda_max(S S^T) of
 // the SEDs the iteration starts from, which the PREVIOUS iteration has already produced.  Neither solve has to
@@ -166,6 +182,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     __shared__ short rowrange_s[KM][2][2];
     __shared__ unsigned place_s;               // persistent form: the scene's placement (below), one component index per byte
     const int tid = threadIdx.x, lane = tid & 63, wid = uniform(tid >> 6);    // wid in an SGPR: scalar branches
+    if constexpr (X) __builtin_assume(tid >= 0 && tid < SC_FB2);        // (the exact instances' `g < ngroups` guards fold away: no exec-masked loads)
     float *const morph0 = a.morph[0], *const morph1 = a.morph[1], *const sed0 = a.sed[0], *const sed1 = a.sed[1];
     const float *min_g = (c0 ? morph1 : morph0) + (size_t)s * K * HW;
     float *mout_g = (c0 ? morph0 : morph1) + (size_t)s * K * HW;
@@ -192,6 +209,19 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
 #else
 #define PSTAMP(i) do { } while (0)
 #endif
+    // (diagnostic build -DSC_STAMP_PROLOGUE: slots 12 / 13 / 14 hold wave 0's times after its SED staging, after the
+    // iteration's first barrier and in front of the gradient pass's first use of an image register -- the first phase
+    // split into wait and work -- instead of B1 / B2 and the launch's start; tools/stamps.py, STAMP_PROLOGUE=1)
+#ifdef SC_STAMP_PROLOGUE
+#define QSTAMP(i) STAMP(12 + (i))
+#else
+#define QSTAMP(i) do { } while (0)
+#endif
+    // absent components: the pair skips the constraints.  The per-scene word is read here, in front of every store of the
+    // iteration, so that it is a scalar load beside the launch's other per-scene words; a re-entered iteration takes it
+    // from place_s (below)
+    int n_present = K;
+    if (X && a.ncomp && !(P && reentered)) n_present = scene_ncomp(a.ncomp, s, K);
     STAMP(0);
     // (diagnostics: the constant 100 MHz counter beside the shader clock of stamps 0 / 6 gives the clock the chip holds)
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 7] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -199,12 +229,49 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     if (P && a.stamps && tid == 0) a.stamps[(size_t)a.S * 16 + (size_t)s * 2 + (it_new & 1)] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
     if (P && a.stamps && tid == 0 && !reentered) {     // launch-level diagnostics: when and where this workgroup started
+#ifndef SC_STAMP_PROLOGUE
         a.stamps[(size_t)s * 16 + 14] = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
         a.stamps[(size_t)s * 16 + 15] = (long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11))        // HW_ID
                                         | ((long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) << 32);   // XCC_ID
     }
-    const unsigned fl_req = ks_request_lengths(tid);
-    const int n_present = a.ncomp ? scene_ncomp(a.ncomp, s, K) : K;   // absent components: the pair skips the constraints
+    // What the iteration's first phase leaves to the rest: the pair's component, its centre and shift, its half of the
+    // cached Hankel vectors, the first group's images and (in LDS) the tiles, the SEDs and the Gram partials.
+    const int slot = wid >> 1;
+    int kp = slot;
+    int pre_cy = 0, pre_cx = 0;
+    double pre_dy = 0, pre_dx = 0;
+    float *kcache = nullptr;
+    float kc_v[3] = {0.f, 0.f, 0.f};
+    unsigned kc_hdr = 0;
+    // images: the first group's are requested at the top of the iteration, the second group's when the Gram is done
+    // (under the gradient pass's first group) -- 128 VGPRs do not hold both next to the tile registers
+    float4 ireg[GPT][BM];
+    auto load_images = [&](int j) {
+        const int g = tid + j * SC_FB2;
+#pragma unroll
+        for (int b = 0; b < BM; ++b)
+            ireg[j][b] = (g < ngroups && b < B) ? reinterpret_cast<const float4 *>(img + (size_t)b * HW)[g]
+                                               : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    auto load4 = [&](const float *p, bool past_l1) {
+        if (P && past_l1) {
+            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
+            return make_float4(v[0], v[1], v[2], v[3]);
+        }
+        return *reinterpret_cast<const float4 *>(p);
+    };
+    // ---------------- phase 0: issue every global load, tiles -> LDS, Gram.  Two instances of the same statements:
+    // FAST is the re-entered iteration with resident tiles (`reent`, `resid` are compile-time facts in it), the other
+    // one every other start of an iteration (see the comment above this function).
+    auto phase0 = [&](auto fast_c) {
+    constexpr bool FAST = P && decltype(fast_c)::value;
+    const bool reent = FAST || reentered, resid = FAST || resident;
+    // FAST: the images depend on the scene and the thread only -- requested in front of the first LDS read
+    if (FAST) load_images(0);
+    // (the 128-byte table is still in fl_s on re-entry: LDS survives the jump)
+    const unsigned fl_req = (P && reent) ? 0u : ks_request_lengths(tid);
+    if (!X && a.ncomp) n_present = scene_ncomp(a.ncomp, s, K);      // (the generic instance has no SGPR to hold it any longer)
     // Placement (exact-shape instances).  The pair of waves 2 q, 2 q + 1 -- slot q -- sits on SIMDs {0, 1} for q = 0, 2
     // and on {2, 3} for q = 1, 3, and a SIMD's matrix pipe is shared by the waves on it: the MFMAs of the component on
     // the other slot of the same SIMDs come straight out of this one's stream.  The two symmetry GEMMs of a window of
@@ -218,12 +285,14 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     // previous morphology in load_last) with no wait in between -- a placement that moved between two iterations would
     // have one wave read another's recent stores.  Across launches the kernel boundary orders them.  The cost only
     // steers scheduling: every wave computes the same permutation, and no result depends on which one it is.
-    const int slot = wid >> 1;
-    int kp = slot;
+    // place_s carries the scene's component count beside the placement (bits 4..6: a slot's byte uses two bits)
     if constexpr (X) {
         unsigned place = 0x03020100u;
-        if (P) { const unsigned lp = place_s; if (reentered) place = (unsigned)uniform((int)lp); }
-        if (!(P && reentered) && !a.no_place) {
+        if (FAST) {
+            place = (unsigned)uniform((int)place_s);
+        } else if (P) { const unsigned lp = place_s; if (reent) place = (unsigned)uniform((int)lp); }
+        if (P && reent && a.ncomp) n_present = (int)((place >> 4) & 7u);
+        if (!(P && reent) && !a.no_place) {
             int cost[KM];
 #pragma unroll
             for (int j = 0; j < KM; ++j) {
@@ -241,7 +310,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
                 place |= (unsigned)j << (8 * (rank ^ (rank >> 1)));         // ranks 0, 1, 2, 3 -> slots 0, 1, 3, 2
             }
         }
-        if (P && !reentered && tid == 0) place_s = place;
+        if (P && !reent && tid == 0) place_s = place | ((unsigned)n_present << 4);
         kp = (int)((place >> (8 * slot)) & (KM - 1));
     }
     // The Hankel vectors of the k-space symmetry depend on (H, W, centre, shift) only; the shift moves
@@ -250,24 +319,24 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     // constraint chain) only when that key changed.  Requested here, under everything else.
     // centre and shift of this pair's component: requested here as well (they are read again only
     // after the gradient step; a load at that point would put an HBM round trip on the constraint chain)
-    int pre_cy = 0, pre_cx = 0;
-    double pre_dy = 0, pre_dx = 0;
     if (X && kp < K) {                          // (the generic instance has no registers to spare: it loads late)
         const int cpre = s * K + kp;
-        if (!(P && reentered)) {
-            pre_cy = a.centers[2 * cpre]; pre_cx = a.centers[2 * cpre + 1];
-            pre_dy = a.shifts[2 * cpre]; pre_dx = a.shifts[2 * cpre + 1];
-        }
-        if (P) {       // (read unconditionally, selected by value: a select between an LDS and a global POINTER would
+        if (FAST) {
+            pre_cy = carry_cen[kp][0]; pre_cx = carry_cen[kp][1];
+            pre_dy = carry_sh[kp][0]; pre_dx = carry_sh[kp][1];
+        } else {
+            if (!(P && reent)) {
+                pre_cy = a.centers[2 * cpre]; pre_cx = a.centers[2 * cpre + 1];
+                pre_dy = a.shifts[2 * cpre]; pre_dx = a.shifts[2 * cpre + 1];
+            }
+            if (P) {   // (read unconditionally, selected by value: a select between an LDS and a global POINTER would
                        // turn both loads into flat loads)
-            const int lcy = carry_cen[kp][0], lcx = carry_cen[kp][1];
-            const double ldy = carry_sh[kp][0], ldx = carry_sh[kp][1];
-            if (reentered) { pre_cy = lcy; pre_cx = lcx; pre_dy = ldy; pre_dx = ldx; }
+                const int lcy = carry_cen[kp][0], lcx = carry_cen[kp][1];
+                const double ldy = carry_sh[kp][0], ldx = carry_sh[kp][1];
+                if (reent) { pre_cy = lcy; pre_cx = lcx; pre_dy = ldy; pre_dx = ldx; }
+            }
         }
     }
-    float *kcache = nullptr;
-    float kc_v[3] = {0.f, 0.f, 0.f};
-    unsigned kc_hdr = 0;
     if (X && a.kscache && kp < K) {
         kcache = a.kscache + ((size_t)(s * K + kp) * 2 + (wid & 1)) * SC_KSC_FLOATS;
         if (P) {                               // past the L1: this wave stored them an iteration ago
@@ -280,16 +349,8 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         }
     }
 
-    // ---------------- phase 0: issue every global load, tiles -> LDS, Gram
     float4 mreg[GPT][KM];
-    auto load4 = [&](const float *p, bool past_l1) {
-        if (P && past_l1) {
-            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
-            return make_float4(v[0], v[1], v[2], v[3]);
-        }
-        return *reinterpret_cast<const float4 *>(p);
-    };
-    if (!P || !resident) {
+    if (!P || !resid) {
         // (re-entered without resident tiles -- after a NaN result, or the diagnostic switch: the planes were stored
         // by this workgroup an iteration ago, read them past the L1)
 #pragma unroll
@@ -297,35 +358,30 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
             const int g = tid + j * SC_FB2;
 #pragma unroll
             for (int k = 0; k < KM; ++k)
-                mreg[j][k] = (g < ngroups && k < K) ? load4(min_g + (size_t)k * HW + 4 * (size_t)g, reentered)
+                mreg[j][k] = (g < ngroups && k < K) ? load4(min_g + (size_t)k * HW + 4 * (size_t)g, reent)
                                                    : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    // images: the first group's are requested now, the second group's when phase 1 starts
-    // (under the first group's arithmetic) -- 128 VGPRs do not hold both next to the accumulators
-    float4 ireg[GPT][BM];
-    auto load_images = [&](int j) {
-        const int g = tid + j * SC_FB2;
-#pragma unroll
-        for (int b = 0; b < BM; ++b)
-            ireg[j][b] = (g < ngroups && b < B) ? reinterpret_cast<const float4 *>(img + (size_t)b * HW)[g]
-                                               : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    load_images(0);
+    if (!FAST) load_images(0);
     for (int i = tid; i < K * B; i += SC_FB2) {
         float v = 0.f;
-        if (!(P && reentered)) v = sed_in[i];
-        if (P) { const float lv = carry_sed[(i / B) * BM + (i % B)]; if (reentered) v = lv; }
+        if (FAST) {
+            v = carry_sed[(i / B) * BM + (i % B)];
+        } else {
+            if (!(P && reent)) v = sed_in[i];
+            if (P) { const float lv = carry_sed[(i / B) * BM + (i % B)]; if (reent) v = lv; }
+        }
         // (a new scene: the carry starts from its SEDs -- an absent component's stays zero, nothing else writes it)
-        if (P && !reentered) carry_sed[(i / B) * BM + (i % B)] = v;
+        if (P && !reent) carry_sed[(i / B) * BM + (i % B)] = v;
         sed_s[(i / B) * BM + (i % B)] = v;
     }
-    ks_fill_lengths(fl_s, tid, fl_req);
+    QSTAMP(0);
+    if (!(P && reent)) ks_fill_lengths(fl_s, tid, fl_req);
     if (tid < 2 * KM) (&pair_flag[0][0])[tid] = 0;
     if (tid == 2 * KM) arrive_s = 0;
     if (P && tid == 0) { ctl_s[it_old & 1][0] = 1; ctl_s[it_old & 1][1] = 1; }
-    if (P && !reentered && tid < KM * 4) (&rowrange_s[0][0][0])[tid] = (short)((tid & 1) ? H - 1 : 0);
-    if (P && resident) {
+    if (P && !reent && tid < KM * 4) (&rowrange_s[0][0][0])[tid] = (short)((tid & 1) ? H - 1 : 0);
+    if (P && resid) {
         // (the previous iteration's last barrier ordered its tile writes before these reads)
 #pragma unroll
         for (int j = 0; j < GPT; ++j) {
@@ -336,6 +392,63 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
                 mreg[j][k] = (g < ngroups && k < K) ? tl4(tiles + k * tile_floats + y * LW + x) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
+    // sed_s visible.  (FAST: what has been written so far -- sed_s, the pair counters, ctl_s -- is read behind the next
+    // barrier only, and nothing written between the two is read in front of this one: no barrier here)
+    if (!FAST) __syncthreads();
+    QSTAMP(1);
+    {
+        // packed-f32 products (v_pk_fma_f32): the .x lanes of gram2 sum pixels 0 and 2 of the groups,
+        // the .y lanes pixels 1 and 3
+        f32x2 gram2[NG];
+#pragma unroll
+        for (int i = 0; i < NG; ++i) gram2[i] = (f32x2){0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < GPT; ++j) {
+            const int g = tid + j * SC_FB2;
+            if (g < ngroups) {
+                const int y = g / gpr, x = (g - y * gpr) << 2;
+#pragma unroll
+                for (int k = 0; k < KM; ++k)
+                    if (k < K && !(P && resid)) ts4(tiles + k * tile_floats + y * LW + x, mreg[j][k]);
+                int gi = 0;
+#pragma unroll
+                for (int k = 0; k < KM; ++k)
+#pragma unroll
+                    for (int k2 = k; k2 < KM; ++k2) {
+                        const float4 p = mreg[j][k], q = mreg[j][k2];
+                        const f32x2 pl = {p.x, p.y}, ph = {p.z, p.w}, ql = {q.x, q.y}, qh = {q.z, q.w};
+                        // explicit FMAs, in the order every instance has always had: left to the compiler, the first
+                        // group's sum of two products (pl ql + ph qh: either product may become the addend) is rounded
+                        // one way in one instance of this phase and the other way in the next
+                        if (j == 0 && k2 == k) {
+                            gram2[gi] = __builtin_elementwise_fma(pl, ql, ph * qh);
+                        } else {
+                            gram2[gi] = __builtin_elementwise_fma(pl, ql, gram2[gi]);
+                            gram2[gi] = __builtin_elementwise_fma(ph, qh, gram2[gi]);
+                        }
+                        ++gi;
+                    }
+            }
+        }
+        float gram[NG];
+#pragma unroll
+        for (int i = 0; i < NG; ++i) gram[i] = gram2[i].x + gram2[i].y;
+        // float partials per 16-lane row (float64 across the 4 x 8 rows): red[4 wid + row][gi], gi =
+        // packed upper-triangle index over KM x KM; lane & 3 = q holds the row sums of the entries 4 m + q
+        float gq[(NG + 3) / 4];
+        wave_rowsum_quads(gram, gq);
+        if ((lane & 12) == 12) {
+#pragma unroll
+            for (int m = 0; m < (NG + 3) / 4; ++m)
+                if (4 * m + 3 < NG || 4 * m + (lane & 3) < NG) red[4 * wid + (lane >> 4)][4 * m + (lane & 3)] = gq[m];
+        }
+    }
+    };
+    // (wave-uniform; the two instances meet again only here, behind the last use of a tile register)
+    if (P && reentered && resident) phase0(std::true_type{}); else phase0(std::false_type{});
+    // (wave-uniform on both ways here; said again, or everything that branches on them behind the join -- the sweep's
+    // loop control among it -- is compiled as lane-wise)
+    if (P) { kp = uniform(kp); n_present = uniform(n_present); }
     const bool small_side = (K <= B);          // nonzero spectrum of A^T A == that of A A^T
     // step_morph and its L_morph were left in step_s[1] / mat[1][0] by the previous iteration's worker (there is a
     // worker whenever a component is present)
@@ -354,46 +467,6 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
             m[b * BM + b2] = r;
         }
     };
-    __syncthreads();                           // sed_s visible
-    {
-        // packed-f32 products (v_pk_fma_f32): the .x lanes of gram2 sum pixels 0 and 2 of the groups,
-        // the .y lanes pixels 1 and 3
-        f32x2 gram2[NG];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) gram2[i] = (f32x2){0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < GPT; ++j) {
-            const int g = tid + j * SC_FB2;
-            if (g < ngroups) {
-                const int y = g / gpr, x = (g - y * gpr) << 2;
-#pragma unroll
-                for (int k = 0; k < KM; ++k)
-                    if (k < K && !(P && resident)) ts4(tiles + k * tile_floats + y * LW + x, mreg[j][k]);
-                int gi = 0;
-#pragma unroll
-                for (int k = 0; k < KM; ++k)
-#pragma unroll
-                    for (int k2 = k; k2 < KM; ++k2) {
-                        const float4 p = mreg[j][k], q = mreg[j][k2];
-                        gram2[gi] += (f32x2){p.x, p.y} * (f32x2){q.x, q.y};
-                        gram2[gi] += (f32x2){p.z, p.w} * (f32x2){q.z, q.w};
-                        ++gi;
-                    }
-            }
-        }
-        float gram[NG];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) gram[i] = gram2[i].x + gram2[i].y;
-        // float partials per 16-lane row (float64 across the 4 x 8 rows): red[4 wid + row][gi], gi =
-        // packed upper-triangle index over KM x KM; lane & 3 = q holds the row sums of the entries 4 m + q
-        float gq[(NG + 3) / 4];
-        wave_rowsum_quads(gram, gq);
-        if ((lane & 12) == 12) {
-#pragma unroll
-            for (int m = 0; m < (NG + 3) / 4; ++m)
-                if (4 * m + 3 < NG || 4 * m + (lane & 3) < NG) red[4 * wid + (lane >> 4)][4 * m + (lane & 3)] = gq[m];
-        }
-    }
 #pragma unroll
     for (int j = 1; j < GPT; ++j) load_images(j);       // the tile registers are free now
     __syncthreads();
@@ -470,6 +543,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
                     m2[k][0] = (f32x2){v.x, v.y}; m2[k][1] = (f32x2){v.z, v.w};
                     gm2[k][0] = (f32x2){0.f, 0.f}; gm2[k][1] = gm2[k][0];
                 }
+                if (j == 0) QSTAMP(2);
 #pragma unroll
                 for (int b = 0; b < BM; ++b) {
                     if (b < B) {
@@ -634,7 +708,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     }
     STAMP(8);
     if (mine) pair_sync(2, std::false_type{});                         // B1: Hankel vectors complete
-#ifndef SC_STAMP_WORKER
+#if !defined(SC_STAMP_WORKER) && !defined(SC_STAMP_PROLOGUE)
     STAMP(12);
 #endif
     f32x4 T[4][2];
@@ -643,7 +717,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         pair_ks_gemm1<true>(t, sw, kg, vec, half, T);
     }
     if (mine) pair_sync(3, std::false_type{});                         // B2: every read of X is done
-#ifndef SC_STAMP_WORKER
+#if !defined(SC_STAMP_WORKER) && !defined(SC_STAMP_PROLOGUE)
     STAMP(13);
 #endif
     if (mine && mode == 1) pair_ks_gemm2<true>(t, sw, kg, vec, zv, half, T, sy, rank1);
@@ -958,6 +1032,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     STAMP(6);
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 11] = (long long)__builtin_amdgcn_s_memrealtime();
 #undef STAMP
+#undef QSTAMP
 #undef WSTAMP
 #undef PSTAMP
     if (P) {
@@ -1027,6 +1102,9 @@ extern "C" __global__ __launch_bounds__(SC_FB2, 4) void SC_FIT2X_KERNEL(FusedArg
 {
     const int s = blockIdx.x;                                            // the scene (workgroup id x, rewritten on re-entry)
     const unsigned st = (unsigned)__builtin_amdgcn_workgroup_id_y();     // 0 at launch (1-D grid) and for a new scene
+    // (the arguments the iteration's first instructions need, requested with the kernel's first scalar loads: left to
+    // the compiler each is loaded where it is first used, three scalar round trips in a row in front of the image loads)
+    asm volatile("" ::"s"(a.images), "s"(a.stamps), "s"(a.ncomp));
     int c0 = 0, it = 0, left = 0;
     bool resident = false, run = true;
     if (st >> 31) {

@@ -53,7 +53,15 @@ dt = np.diff(st[:, :7], axis=1)
 if st[:, 10].any():
     print("P2 wave0: pre-sym %d  sym %d  sweep %d  tail %d" % ((st[:, 8] - st[:, 4]).mean(), (st[:, 9] - st[:, 8]).mean(),
           (st[:, 10] - st[:, 9]).mean(), (st[:, 5] - st[:, 10]).mean()))
-if os.environ.get("STAMP_WORKER"):
+if os.environ.get("STAMP_PROLOGUE"):
+    # library built with -DSC_STAMP_PROLOGUE: slots 12 / 13 / 14 = wave 0 after its SED staging, after the iteration's
+    # first barrier, in front of the gradient pass's first use of an image register (fused2.h)
+    parts = [("start -> SED staged", st[:, 12] - st[:, 0]), ("-> past the first barrier", st[:, 13] - st[:, 12]),
+             ("-> Gram stored, second barrier (stamp 1)", st[:, 1] - st[:, 13]), ("Lipschitz phase (stamp 1 -> 2)", st[:, 2] - st[:, 1]),
+             ("stamp 2 -> first use of an image", st[:, 14] - st[:, 2]), ("first use of an image -> end of the gradient pass (stamp 3)", st[:, 3] - st[:, 14])]
+    for name, v in parts:
+        print("prologue: %-62s mean %6d  p50 %6d  p90 %6d" % (name, v.mean(), np.median(v), np.percentile(v, 90)))
+elif os.environ.get("STAMP_WORKER"):
     # library built with -DSC_STAMP_WORKER: slots 12 / 13 = start / end of the worker's step-size work (fused2.h), on
     # the worker wave; 9 / 10 = wave 0 after B3 / after B4 (its pair's sweep lies between them)
     ok = st[:, 13] > st[:, 12]
