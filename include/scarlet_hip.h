@@ -511,6 +511,56 @@ int scarlet_lowres_render_large(const float *model, int n, int H, int W, const s
 int scarlet_lowres_adjoint_large(const float *resid, int n, int H, int W, const scarlet_lowres *lr, const int32_t *band,
                                  const int32_t *scene, float *out, void *scratch, int64_t scratch_bytes, void *stream);
 
+/* Products of a batch's state: what the reference reads off a fitted Blend -- blend.get_model(), observation.render(model),
+ * observation.get_loss(model), component.get_flux(), component.get_model() -- for every scene in one READ-ONLY call.
+ * Every output pointer is device memory owned by the caller and may be NULL (at least one is not); only the outputs that
+ * are given are computed.
+ *   - Each scene is read from its own buffer cur[s].  Scenes with active == 0 or with status bits set are evaluated like
+ *     the others: the products describe whatever state is there.  NaN in a scene's factors stays in that scene's outputs.
+ *   - Absent components (n_components) add nothing; their rows of `flux` and `component_models` are written as zeros.
+ *   - The call writes through `out` and `scratch` only.  Of b->workspace it reads the transformed difference kernel that
+ *     scarlet_batch_prepare_psf left there (a batch with a diff_kernel and any of rendered / residual / loss wanted must
+ *     have been prepared); sed, morph, cur, it, active, status, flags, mse and lipschitz are not touched.
+ *   - loss and flux are float64 sums in a fixed order: two calls on the same state give the same bits.
+ *   - `scratch`: scarlet_products_scratch_bytes() bytes of device memory, contents irrelevant before and after.  With a
+ *     difference kernel and no `model` output the unconvolved planes are staged there, the scenes taken in chunks that
+ *     keep the staged planes and the hipFFT chain's buffers within 256 MiB (one scene at the least).
+ *   - The planes are convolved by the LDS-resident transform wherever scarlet_debug_psf_plan reports one for the batch,
+ *     by the hipFFT chain of scarlet_convolve_same elsewhere (its plans come from the library's cache, as in a fit; a
+ *     chunk with another number of planes than the batch creates its plan pair on first use).
+ * Errors (SCARLET_E_ARG with a message, before anything is launched): b or out NULL, every output NULL, n_select < 0,
+ * component_models without a selection (n_select == 0), a selected index outside 0 .. K - 1, images NULL with residual
+ * or loss wanted, a scratch that is too small. */
+typedef struct scarlet_products {
+    float  *model;            /* [S][B][H][W]: sum_k sed[k][b] morph[k][p]  (ComponentTree.get_model, component.py:321-347) */
+    float  *rendered;         /* [S][B][H][W]: model (*) diff_kernel; = model without one (Observation.render,
+                                 observation.py:203-220)                                                                     */
+    float  *residual;         /* [S][B][H][W]: images - rendered                                                            */
+    double *loss;             /* [S][B]: 0.5 sum_p (w (rendered - image))^2 per band; its sum over b is Observation.get_loss
+                                 (observation.py:222-239)                                                                    */
+    double *flux;             /* [S][K][B]: morph[k].sum() * sed[k][b]  (Component.get_flux, component.py:172-175)            */
+    const int32_t *components; /* HOST [n_select] component indices, the same for every scene; NULL: 0 .. n_select - 1        */
+    int32_t n_select;
+    float  *component_models; /* [S][n_select][B][H][W]: sed[k][b] morph[k][p]  (Component.get_model)                         */
+} scarlet_products;           /* 64 bytes */
+
+/* bytes of `scratch` for this batch and these outputs (which pointers of `out` are NULL decides, not their values);
+   0 for NULL arguments or a batch whose shape the engine does not take */
+int64_t scarlet_products_scratch_bytes(const scarlet_batch *b, const scarlet_products *out);
+int scarlet_batch_products(const scarlet_batch *b, const scarlet_products *out, void *scratch, int64_t scratch_bytes,
+                           void *stream);
+/* The same for a batch fitted against several observations (scarlet_fit_observations): observation i sees the channels
+ * band0[i] .. band0[i] + obs[i]->B - 1 of the state's model through its own difference kernel, images and weights, and
+ * out[i] takes its rendered / residual / loss ([S][obs[i]->B]...; model, flux and component_models must be NULL there).
+ * state_out (or NULL) takes model, flux and component_models over the state's C = state->B channels; they need no
+ * observation, and rendered / residual / loss must be NULL there.  An out[i] with every pointer NULL skips that
+ * observation (a low-resolution one, whose rendering this entry point does not take: pass nothing for it).
+ * `scratch` is shared by the evaluations, which run one after the other: the largest of
+ * scarlet_products_scratch_bytes(state, state_out) and scarlet_products_scratch_bytes(obs[i], &out[i]). */
+int scarlet_observations_products(const scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                  const scarlet_products *state_out, const scarlet_products *out, void *scratch,
+                                  int64_t scratch_bytes, void *stream);
+
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes
  * the stepped factors into buffer 1-cur; cur/it are NOT advanced yet                   */

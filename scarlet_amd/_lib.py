@@ -103,6 +103,12 @@ class ScarletLowres(Structure):
                 ("v_per_scene", c_int32), ("dhat_per_scene", c_int32), ("workspace", c_void_p)]
 
 
+class ScarletProducts(Structure):
+    """struct scarlet_products of include/scarlet_hip.h (field order must match); `components` is a HOST pointer."""
+    _fields_ = [("model", c_void_p), ("rendered", c_void_p), ("residual", c_void_p), ("loss", c_void_p), ("flux", c_void_p),
+                ("components", c_void_p), ("n_select", c_int32), ("component_models", c_void_p)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "scarlet_version": (c_char_p, []),
@@ -157,6 +163,10 @@ _SIGNATURES = {
     "scarlet_lowres_op_scratch_bytes": (c_int64, [c_int, c_int, c_int, POINTER(ScarletLowres)]),
     "scarlet_lowres_render_large": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P, c_int64, _P]),
     "scarlet_lowres_adjoint_large": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P, c_int64, _P]),
+    "scarlet_products_scratch_bytes": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletProducts)]),
+    "scarlet_batch_products": (c_int, [POINTER(ScarletBatch), POINTER(ScarletProducts), _P, c_int64, _P]),
+    "scarlet_observations_products": (c_int, [POINTER(ScarletBatch), POINTER(POINTER(ScarletBatch)), _P, c_int,
+                                              POINTER(ScarletProducts), POINTER(ScarletProducts), _P, c_int64, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

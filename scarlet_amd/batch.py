@@ -230,6 +230,17 @@ class LowResObservationBatch(ObservationBatch):
         return lowres_struct(self.host_factors, self.shape[2], self.shape[3], self.shape[1], self.per_scene, device)
 
 
+class BatchProducts(object):
+    """What `BlendBatch.products` returns: device tensors, None for what was not asked for.  For a batch made by
+    `from_observations`, `rendered`, `residual` and `loss` are lists with one entry per observation.  `components`
+    holds the indices (host int32 array) that `component_models` was made for."""
+    __slots__ = ("model", "rendered", "residual", "loss", "flux", "component_models", "components")
+
+    def __init__(self):
+        for name in self.__slots__:
+            setattr(self, name, None)
+
+
 class BlendBatch(object):
     """S scenes x K components x B bands x H x W pixels, all float32 on one device.
 
@@ -509,6 +520,136 @@ class BlendBatch(object):
             raise ValueError("init_sources: bad input in scenes {} (bg_rms <= 0 in a band, a group of more than {} "
                              "components, percentiles not ascending inside (0, 100), or an empty layer); they were "
                              "left inactive".format(bad.tolist(), _lib.MAX_LAYERS))
+
+    # ------------------------------------------------------------------ products of the state
+    def products(self, model=True, rendered=True, residual=True, loss=True, flux=True, components=None, out=None, obs=None):
+        """What the reference reads off a fitted Blend, for every scene, from the current factors (read-only: the state,
+        the fit's bookkeeping and the workspace stay as they are; scarlet_batch_products, or scarlet_observations_products
+        for a batch made by `from_observations`).  One call into the library on the current stream, no host
+        synchronisation.  Returns a `BatchProducts` of device tensors (None for what was not asked for):
+
+        model : (S, C, H, W) sum_k sed[k] morph[k] over the model frame's channels (blend.get_model())
+        rendered : (S, B, H, W) the model as the data sees it, convolved with the difference kernel when there is one
+            (observation.render(model))
+        residual : (S, B, H, W) images - rendered
+        loss : (S, B) float64, 0.5 sum (weights (rendered - images))^2 per band (its sum: observation.get_loss(model))
+        flux : (S, K, C) float64 morph[k].sum() * sed[k] (component.get_flux()); zero rows for absent components
+        components : None or component indices -> component_models (S, n, C, H, W) = sed[k] morph[k] (component.get_model())
+        out : a BatchProducts of an earlier call, whose tensors are written again where their shapes fit
+        obs : (from_observations) the observations to evaluate, default all
+
+        With `from_observations`, rendered / residual / loss are lists with one entry per observation (None for those
+        left out by `obs`).  A low-resolution observation's rendered / residual / loss are not available
+        (NotImplementedError); model, flux and the other observations' products are."""
+        t = self.torch
+        S, K, C, H, W = self.S, self.K, self.B, self.H, self.W
+        res = BatchProducts() if out is None else out
+
+        def buf(old, want, shape, dtype):
+            if not want:
+                return None
+            if t.is_tensor(old) and tuple(old.shape) == shape and old.dtype == dtype and old.device == self.device \
+                    and old.is_contiguous():
+                return old
+            return t.empty(shape, dtype=dtype, device=self.device)
+
+        sel = None
+        if components is not None:
+            sel = np.ascontiguousarray(np.asarray(components, dtype=np.int32).reshape(-1))
+            if sel.size == 0 or sel.min() < 0 or sel.max() >= K:
+                raise ValueError("products: components must name 1 or more of the components 0 .. %d" % (K - 1))
+        ps = _lib.ScarletProducts()
+        res.model = buf(res.model, model, (S, C, H, W), t.float32)
+        res.flux = buf(res.flux, flux, (S, K, C), t.float64)
+        res.component_models = buf(res.component_models, sel is not None, (S, 0 if sel is None else sel.size, C, H, W), t.float32)
+        res.components = None if sel is None else sel.copy()
+        ps.model, ps.flux, ps.component_models = _lib.ptr(res.model), _lib.ptr(res.flux), _lib.ptr(res.component_models)
+        if sel is not None:
+            ps.components, ps.n_select = sel.ctypes.data, int(sel.size)
+        wants = (("rendered", rendered, t.float32), ("residual", residual, t.float32), ("loss", loss, t.float64))
+        if self._observations is None:
+            if obs not in (None, 0, [0], (0,)):
+                raise ValueError("products: this batch has one observation, obs = %r" % (obs,))
+            for name, want, dtype in wants:
+                x = buf(getattr(res, name), want, (S, C) if name == "loss" else (S, C, H, W), dtype)
+                setattr(res, name, x)
+                setattr(ps, name, _lib.ptr(x))
+            nbytes = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._c), ctypes.byref(ps))
+            scratch = self._products_scratch(nbytes)
+            _lib.check(_lib.lib.scarlet_batch_products(ctypes.byref(self._c), ctypes.byref(ps), _lib.ptr(scratch), int(nbytes),
+                                                       _lib.stream_ptr()))
+            return res
+        n = len(self._observations)
+        idx = list(range(n)) if obs is None else [int(i) for i in np.atleast_1d(obs)]
+        if any(i < 0 or i >= n for i in idx):
+            raise ValueError("products: obs = %r, there are %d observations" % (obs, n))
+        if not (rendered or residual or loss):
+            idx = []
+        for i in idx:
+            if self._lowres[i] is not None:
+                raise NotImplementedError("products: rendered, residual and loss of a low-resolution observation (observation "
+                                          "%d) are not available; model and flux are" % i)
+        outs = (_lib.ScarletProducts * n)()
+        for name, want, dtype in wants:
+            old = getattr(res, name)
+            old = old if isinstance(old, list) and len(old) == n else [None] * n
+            new = [None] * n
+            for i in idx:
+                o = self._observations[i][0]
+                new[i] = buf(old[i], want, (S, o.B) if name == "loss" else (S, o.B, H, W), dtype)
+                setattr(outs[i], name, _lib.ptr(new[i]))
+            setattr(res, name, new if want else None)
+        any_state = model or flux or sel is not None
+        nbytes = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._c), ctypes.byref(ps)) if any_state else 0
+        for i in idx:
+            nbytes = max(nbytes, _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._observations[i][1]._c),
+                                                                         ctypes.byref(outs[i])))
+        scratch = self._products_scratch(nbytes)
+        ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
+        first = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
+        _lib.check(_lib.lib.scarlet_observations_products(
+            ctypes.byref(self._c), ptrs, first.ctypes.data_as(ctypes.c_void_p), n, ctypes.byref(ps) if any_state else None, outs,
+            _lib.ptr(scratch), int(nbytes), _lib.stream_ptr()))
+        return res
+
+    def _products_scratch(self, nbytes):
+        """Device scratch of `products`, kept between calls and grown when a call needs more."""
+        old = getattr(self, "_scratch", None)
+        if nbytes and (old is None or old.numel() < nbytes):
+            self._scratch = old = self.torch.empty((int(nbytes),), dtype=self.torch.uint8, device=self.device)
+        return old if nbytes else None
+
+    def _one_product(self, name, obs=0, **kw):
+        want = dict(model=False, rendered=False, residual=False, loss=False, flux=False)
+        want[name] = True
+        x = getattr(self.products(obs=None if name in ("model", "flux") or self._observations is None else [obs], **want, **kw), name)
+        return x[obs] if isinstance(x, list) else x
+
+    def get_model(self):
+        """(S, C, H, W) model of every scene over the model frame's channels (reference blend.get_model())."""
+        return self._one_product("model")
+
+    def render(self, obs=0):
+        """(S, B, H, W) the model as observation `obs` sees it (reference observation.render(blend.get_model()))."""
+        return self._one_product("rendered", obs)
+
+    def residual(self, obs=0):
+        """(S, B, H, W) images - render of observation `obs`."""
+        return self._one_product("residual", obs)
+
+    def get_loss(self):
+        """(S,) float64 loss of every scene, summed over bands and observations as Blend._loss does: what the next
+        iteration records in `mse`."""
+        x = self.products(model=False, rendered=False, residual=False, loss=True, flux=False).loss
+        return sum(v.sum(dim=1) for v in x) if isinstance(x, list) else x.sum(dim=1)
+
+    def get_flux(self):
+        """(S, K, C) float64 flux of every component in every channel (reference component.get_flux())."""
+        return self._one_product("flux")
+
+    def component_models(self, ks):
+        """(S, len(ks), C, H, W) models sed[k] morph[k] of the components `ks` (reference component.get_model())."""
+        return self.products(model=False, rendered=False, residual=False, loss=False, flux=False, components=ks).component_models
 
     # ------------------------------------------------------------------ operations
     def init_extended(self, bg_rms, thresh=1.0, sed_scale=None, init_symmetric=True, init_monotonic=None,

@@ -7,6 +7,9 @@
 #include "boxupdate.h"
 #include "fused2.h"
 #include "initsrc.h"
+#include "lowres_stream.h"
+#include "products.h"
+#include <algorithm>
 
 static const size_t LDS_LIMIT = 160 * 1024 - 1024;   // leave room for static __shared__
 
@@ -101,6 +104,57 @@ inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_
     }
     p.lds += sw.pad_lds;    // experiment knob: SCARLET_PAD_LDS=<bytes> lowers the number of co-resident workgroups
     p.fits = p.lds <= LDS_LIMIT;
+    return p;
+}
+
+// ---- the read-only products of a batch's state (products.h, launch_products): which kernels run, the LDS of the
+// rendering one, and where each region of the caller's scratch lies.  Without a difference kernel k_products writes every
+// output itself.  With one it writes the unconvolved planes -- into the caller's `model` output when there is one,
+// otherwise into scratch, the scenes taken in chunks that keep the staged planes (and the hipFFT chain's buffers)
+// within LRS_SCRATCH_CAP, at least one scene -- and the LDS-resident transform or the hipFFT chain renders them.
+enum ProductsPsf { PRODUCTS_PSF_NONE, PRODUCTS_PSF_LDS, PRODUCTS_PSF_HIPFFT };
+struct ProductsWants {
+    bool model;             // the unconvolved planes are an output
+    bool observed;          // rendered, residual or loss: what an observation sees
+    bool loss, flux;
+};
+struct ProductsPlan {
+    int T;                  // tiles of PR_TILE_PIX pixels per scene
+    int psf;                // ProductsPsf: what renders the observed outputs
+    bool main_pass;         // k_products runs
+    bool flux_in_pass;      // ... and leaves the plane sums [S][T][K]
+    bool stage;             // the unconvolved planes go to scratch
+    int chunk;              // scenes per chunk of the rendering stage (S without one)
+    size_t conv_lds;        // dynamic LDS of k_products_conv
+    int64_t loss_part, flux_part, staged, real, spec, total;   // byte offsets into the scratch, and its size
+};
+// geom: the hipFFT chain's shape (PRODUCTS_PSF_HIPFFT); fft: the LDS-resident plan (PRODUCTS_PSF_LDS)
+inline ProductsPlan products_plan(int S, int K, int B, int H, int W, int psf, const PsfGeom &geom, const FftPlan &fft,
+                                  const ProductsWants &w)
+{
+    ProductsPlan p = {};
+    const int64_t HW = (int64_t)H * W;
+    p.T = (int)((HW + PR_TILE_PIX - 1) / PR_TILE_PIX);
+    p.psf = w.observed ? psf : PRODUCTS_PSF_NONE;
+    p.flux_in_pass = w.flux;
+    p.main_pass = w.model || w.observed || p.flux_in_pass;
+    p.stage = p.psf != PRODUCTS_PSF_NONE && !w.model;
+    p.conv_lds = p.psf == PRODUCTS_PSF_LDS ? fft_lds_bytes(fft.Fy, fft.M, fft.RS) : 0;
+    int64_t at = 0;
+    auto place = [&at](int64_t bytes) { const int64_t o = at; at += (bytes + 255) & ~(int64_t)255; return o; };
+    // the loss leaves k_products and k_products_finish as tile partials; k_products_conv owns whole planes
+    p.loss_part = place(w.loss && p.psf != PRODUCTS_PSF_LDS ? (int64_t)sizeof(double) * S * p.T * B : 0);
+    p.flux_part = place(p.flux_in_pass ? (int64_t)sizeof(double) * S * p.T * K : 0);
+    const bool fft_chain = p.psf == PRODUCTS_PSF_HIPFFT;
+    const int64_t per_scene = B * ((p.stage ? HW * (int64_t)sizeof(float) : 0) +
+                                   (fft_chain ? (int64_t)geom.Fy * geom.Fx * (int64_t)sizeof(float) +
+                                                (int64_t)geom.Fy * geom.Fxh * (int64_t)sizeof(float2) + 512 : 0));
+    p.chunk = S;
+    if (per_scene > 0 && per_scene * S > (int64_t)LRS_SCRATCH_CAP) p.chunk = (int)std::max<int64_t>(1, (int64_t)LRS_SCRATCH_CAP / per_scene);
+    p.staged = place(p.stage ? (int64_t)sizeof(float) * p.chunk * B * HW : 0);
+    p.real = place(fft_chain ? (int64_t)sizeof(float) * p.chunk * B * geom.Fy * geom.Fx : 0);
+    p.spec = place(fft_chain ? (int64_t)sizeof(float2) * p.chunk * B * geom.Fy * geom.Fxh : 0);
+    p.total = at;
     return p;
 }
 

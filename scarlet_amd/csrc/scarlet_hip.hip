@@ -2798,3 +2798,192 @@ extern "C" int scarlet_convergence_sums(scarlet_batch *b, void *stream)
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
+
+// =====================================================================================
+// 4. products of a batch's state (products.h; what runs and where the scratch's regions lie: launch_plan.h products_plan)
+// =====================================================================================
+static bool products_any(const scarlet_products *o)
+{
+    return o->model || o->rendered || o->residual || o->loss || o->flux || o->component_models;
+}
+// the plan of one evaluation: the factors of a state with K components seen through `ob` (its shape, data and PSF)
+static ProductsPlan products_plan_of(const scarlet_batch *ob, int K, const scarlet_products *o, LayoutUse use, WsLayout *layout)
+{
+    ProductsWants w = {};
+    w.model = o->model != nullptr;
+    w.observed = o->rendered || o->residual || o->loss;
+    w.loss = o->loss != nullptr;
+    w.flux = o->flux != nullptr;
+    WsLayout l = {};
+    int psf = PRODUCTS_PSF_NONE;
+    if (w.observed && has_psf(ob)) {
+        l = ws_layout(ob, use);
+        psf = l.psf_lds ? PRODUCTS_PSF_LDS : PRODUCTS_PSF_HIPFFT;
+    }
+    if (layout) *layout = l;
+    return products_plan(ob->S, K, ob->B, ob->H, ob->W, psf, l.geom, l.plan, w);
+}
+// host-side check of one evaluation, before anything is launched; band0: first channel of the state that `ob` sees
+static int check_products(const scarlet_batch *state, const scarlet_batch *ob, int band0, const scarlet_products *o)
+{
+    if (!state || !ob) return set_err(SCARLET_E_ARG, "null batch");
+    if (!o) return set_err(SCARLET_E_ARG, "products: out is NULL");
+    if (!products_any(o)) return set_err(SCARLET_E_ARG, "products: every output is NULL");
+    int rc = check_shape(state);
+    if (!rc) rc = check_shape(ob);
+    if (rc) return rc;
+    if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || band0 < 0 || band0 + ob->B > state->B)
+        return set_err(SCARLET_E_ARG, "products: the observation's S, K, H, W or channels do not fit the state");
+    if (o->n_select < 0) return set_err(SCARLET_E_ARG, "products: n_select < 0");
+    if (o->n_select > SCARLET_MAX_COMPONENTS) return set_err(SCARLET_E_ARG, "products: more than 256 selected components");
+    if (o->component_models && o->n_select == 0) return set_err(SCARLET_E_ARG, "products: component_models without a selection");
+    for (int i = 0; i < o->n_select; ++i) {
+        const int k = o->components ? o->components[i] : i;
+        if (k < 0 || k >= state->K) return set_err(SCARLET_E_ARG, "products: a selected component lies outside 0 .. K - 1");
+    }
+    if (!state->sed[0] || !state->sed[1] || !state->morph[0] || !state->morph[1] || !state->cur)
+        return set_err(SCARLET_E_ARG, "products: null factor pointer in batch");
+    if ((o->residual || o->loss) && !ob->images) return set_err(SCARLET_E_ARG, "products: residual and loss need images");
+    if ((o->rendered || o->residual || o->loss) && has_psf(ob) && !ob->workspace)
+        return set_err(SCARLET_E_ARG, "products: a batch with a diff_kernel needs its prepared workspace");
+    return SCARLET_OK;
+}
+static int check_products_scratch(const ProductsPlan &p, const void *scratch, int64_t scratch_bytes)
+{
+    if (p.total > 0 && (!scratch || scratch_bytes < p.total))
+        return set_err(SCARLET_E_ARG, "products: scratch is too small (scarlet_products_scratch_bytes)");
+    return SCARLET_OK;
+}
+
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+// one evaluation, checked before: every launch of it on `st`
+static int launch_products(const scarlet_batch *state, const scarlet_batch *ob, int band0, const scarlet_products *o,
+                           void *scratch, hipStream_t st)
+{
+    WsLayout l;
+    const ProductsPlan p = products_plan_of(ob, state->K, o, WS_FIX, &l);
+    const int S = ob->S, K = state->K, B = ob->B, HW = ob->H * ob->W;
+    char *sc = (char *)scratch;
+    const bool psf = p.psf != PRODUCTS_PSF_NONE, observed_data = o->residual || o->loss;
+    ProdArgs a = {};
+    a.S = S; a.K = K; a.B = B; a.HW = HW; a.T = p.T; a.C = state->B; a.band0 = band0;
+    a.sed[0] = state->sed[0]; a.sed[1] = state->sed[1]; a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
+    a.cur = state->cur; a.ncomp = state->n_components;
+    a.images = observed_data ? ob->images : nullptr; a.weights = ob->weights; a.weight_scalar = ob->weight_scalar;
+    a.loss_part = (o->loss && p.psf != PRODUCTS_PSF_LDS) ? (double *)(sc + p.loss_part) : nullptr;
+    a.flux_part = p.flux_in_pass ? (double *)(sc + p.flux_part) : nullptr;
+    const bool vec4 = HW % 4 == 0 && aligned16(a.morph[0]) && aligned16(a.morph[1]) && aligned16(a.images) && aligned16(a.weights) &&
+                      aligned16(o->model) && aligned16(o->rendered) && aligned16(o->residual) && aligned16(o->component_models) &&
+                      aligned16(scratch);
+    // k_products over scenes s0 .. s0 + n - 1; with a PSF it leaves only the unconvolved planes (and the plane sums)
+    auto main_pass = [&](int s0, int n, float *planes, int planes_s0) {
+        ProdArgs m = a;
+        m.s0 = s0; m.model = planes; m.model_s0 = planes_s0;
+        if (psf) m.loss_part = nullptr;
+        else { m.rendered = o->rendered; m.residual = o->residual; }
+        const dim3 grid(p.T, n);
+        auto k = vec4 ? (p.flux_in_pass ? k_products<true, true> : k_products<true, false>)
+                      : (p.flux_in_pass ? k_products<false, true> : k_products<false, false>);
+        hipLaunchKernelGGL(k, grid, dim3(SC_BLOCK), 0, st, m);
+    };
+    int rc;
+    if (p.main_pass && !p.stage) main_pass(0, S, o->model, 0);
+    if (psf) {
+        ProdObsArgs r = {};
+        r.B = B; r.HW = HW; r.T = p.T;
+        r.images = a.images; r.weights = ob->weights; r.weight_scalar = ob->weight_scalar;
+        r.rendered = o->rendered; r.residual = o->residual;
+        const int64_t kplane = p.psf == PRODUCTS_PSF_LDS ? (int64_t)l.plan.Fy * (l.plan.M + 1) : (int64_t)l.geom.Fy * l.geom.Fxh;
+        const float2 *khat = ws_at<const float2>(ob, p.psf == PRODUCTS_PSF_LDS ? l.lds_khat : l.khat);
+        for (int s0 = 0; s0 < S; s0 += p.chunk) {
+            const int n = std::min(p.chunk, S - s0), planes = n * B;
+            if (p.stage) main_pass(s0, n, (float *)(sc + p.staged), s0);
+            const float *in = p.stage ? (const float *)(sc + p.staged) : o->model + (size_t)s0 * B * HW;
+            r.plane0 = s0 * B;
+            if (p.psf == PRODUCTS_PSF_LDS) {
+                FftPlan fp = l.plan;
+                fp.tables = ws_at<const float2>(ob, l.lds_tables);
+                r.loss = o->loss;
+                if ((rc = launch_lds(k_products_conv, dim3(planes), dim3(SC_FFT_NT), p.conv_lds, st, r, in, fp, khat,
+                                     (int)ob->diff_kernel_per_scene)))
+                    return rc;
+            } else {
+                const PsfGeom &g = l.geom;
+                float *real = (float *)(sc + p.real);
+                FftPlans plans;
+                if ((rc = get_plans(g.Fy, g.Fx, planes, &plans))) return rc;
+                hipLaunchKernelGGL(k_plane_pad, dim3(grid_for((int64_t)planes * g.Fy * g.Fx)), dim3(SC_BLOCK), 0, st, in, planes,
+                                   ob->H, ob->W, g.Fy, g.Fx, g.oy, g.ox, real);
+                const bool per_scene = ob->diff_kernel_per_scene != 0;
+                if ((rc = hipfft_convolve(plans, real, (float2 *)(sc + p.spec), khat + (per_scene ? (size_t)s0 * B * kplane : 0),
+                                          per_scene ? planes : B, planes, (int)kplane, 0, 1.0f / ((float)g.Fy * (float)g.Fx), st)))
+                    return rc;
+                r.loss_part = a.loss_part;
+                hipLaunchKernelGGL(k_products_finish, dim3(planes, p.T), dim3(SC_BLOCK), 0, st, r, (const float *)real, g);
+            }
+        }
+    }
+    if (a.loss_part || a.flux_part)
+        hipLaunchKernelGGL(k_products_reduce, dim3(S), dim3(SC_BLOCK), 0, st, a, a.loss_part ? o->loss : nullptr,
+                           a.flux_part ? o->flux : nullptr);
+    if (o->component_models) {
+        ProdSelection sel;
+        sel.n = o->n_select;
+        for (int i = 0; i < sel.n; ++i) sel.k[i] = o->components ? o->components[i] : i;
+        hipLaunchKernelGGL(vec4 ? k_products_components<true> : k_products_components<false>, dim3(p.T * sel.n, S),
+                           dim3(SC_BLOCK), 0, st, a, sel, o->component_models);
+    }
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
+extern "C" int64_t scarlet_products_scratch_bytes(const scarlet_batch *b, const scarlet_products *out)
+{
+    if (!b || !out || check_shape(b)) return 0;
+    return products_plan_of(b, b->K, out, WS_PEEK, nullptr).total;
+}
+
+extern "C" int scarlet_batch_products(const scarlet_batch *b, const scarlet_products *out, void *scratch, int64_t scratch_bytes,
+                                      void *stream)
+{
+    int rc = check_products(b, b, 0, out);
+    if (!rc) rc = check_products_scratch(products_plan_of(b, b->K, out, WS_PEEK, nullptr), scratch, scratch_bytes);
+    if (rc) return rc;
+    (void)hipGetLastError();              // (what is reported at the end is ours: see check_batch)
+    return launch_products(b, b, 0, out, scratch, (hipStream_t)stream);
+}
+
+extern "C" int scarlet_observations_products(const scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                             const scarlet_products *state_out, const scarlet_products *out, void *scratch,
+                                             int64_t scratch_bytes, void *stream)
+{
+    if (!state) return set_err(SCARLET_E_ARG, "null batch");
+    if (n_obs < 0 || n_obs > SCARLET_MAX_OBSERVATIONS || (n_obs > 0 && (!obs || !band0 || !out)))
+        return set_err(SCARLET_E_ARG, "products: bad observation list");
+    bool any = state_out && products_any(state_out);
+    for (int i = 0; i < n_obs; ++i) any = any || products_any(&out[i]);
+    if (!any) return set_err(SCARLET_E_ARG, "products: every output is NULL");
+    int rc;
+    if (state_out && products_any(state_out)) {
+        if (state_out->rendered || state_out->residual || state_out->loss)
+            return set_err(SCARLET_E_ARG, "products: rendered, residual and loss belong to an observation, not to the state");
+        if ((rc = check_products(state, state, 0, state_out)) ||
+            (rc = check_products_scratch(products_plan_of(state, state->K, state_out, WS_PEEK, nullptr), scratch, scratch_bytes)))
+            return rc;
+    }
+    for (int i = 0; i < n_obs; ++i) {
+        if (!products_any(&out[i])) continue;
+        if (out[i].model || out[i].flux || out[i].component_models || out[i].n_select)
+            return set_err(SCARLET_E_ARG, "products: model, flux and component_models belong to the state, not to an observation");
+        if ((rc = check_products(state, obs[i], band0[i], &out[i])) ||
+            (rc = check_products_scratch(products_plan_of(obs[i], state->K, &out[i], WS_PEEK, nullptr), scratch, scratch_bytes)))
+            return rc;
+    }
+    (void)hipGetLastError();
+    if (state_out && products_any(state_out) && (rc = launch_products(state, state, 0, state_out, scratch, (hipStream_t)stream)))
+        return rc;
+    for (int i = 0; i < n_obs; ++i)
+        if (products_any(&out[i]) && (rc = launch_products(state, obs[i], band0[i], &out[i], scratch, (hipStream_t)stream)))
+            return rc;
+    return SCARLET_OK;
+}
