@@ -97,6 +97,35 @@ def seed_is_decided(spec, iters):
     return len(o32) == iters
 
 
+def _box_regions(b):
+    """byte offsets of the convergence sums and of the box kernels' flags in the workspace (ws_layout in
+    scarlet_hip.hip): behind the per-tile partials.  Valid for K <= 32 without a difference kernel; PSF batches and
+    K > 32 lay their workspace out differently."""
+    assert b.K <= 32 and getattr(b, "diff_kernel", None) is None, "workspace layout of K <= 32 without a difference kernel only"
+    tiles = (b.H * b.W + 4095) // 4096
+    partials = 1 + b.K * b.B + b.K * (b.K + 1) // 2
+    conv = 8 * b.S * tiles * partials
+    return conv, conv + 8 * b.S * b.K * 4
+
+
+def box_fallback(b):
+    """the per-component flags the box kernels leave in the workspace (1 = left to the full-frame kernel): the int region
+    behind the per-tile partials and the convergence sums (ws_layout in scarlet_hip.hip; K <= 32)"""
+    torch = b.torch
+    _, at = _box_regions(b)
+    torch.cuda.synchronize()
+    return b.workspace[at:at + 4 * b.S * b.K].view(torch.int32).cpu().numpy().reshape(b.S, b.K)
+
+
+def box_conv(b):
+    """the convergence sums the last in-iteration update left, directly in front of those flags: (S, K, 4) float64 =
+    {d2 sed, n2 sed, d2 morph, n2 morph}, d2 = |previous - new|^2, n2 = |new|^2"""
+    torch = b.torch
+    at, end = _box_regions(b)
+    torch.cuda.synchronize()
+    return b.workspace[at:end].view(torch.float64).cpu().numpy().reshape(b.S, b.K, 4)
+
+
 def spec_of(images, sed0, morph0, cen0, sh0, sym, mono, l0, l1, **extra):
     d = dict(images=images, sed0=sed0, morph0=morph0, cen0=cen0, sh0=sh0, sym=sym, mono=mono, l0=l0, l1=l1)
     d.update(extra)

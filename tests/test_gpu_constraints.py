@@ -22,6 +22,7 @@ import pytest
 
 from conftest import rel_err
 import constraints_common as cc
+from constraints_common import box_fallback
 import parity_common as pc
 
 pytestmark = pytest.mark.gpu
@@ -85,16 +86,6 @@ def state(b):
     return dict(sed=b.sed_current.cpu().numpy(), morph=b.morph_current.cpu().numpy(), cen=b.centers.cpu().numpy(),
                 shifts=b.shifts.cpu().numpy(), flags=b.flags.cpu().numpy(), mse=b.mse_buf.cpu().numpy(),
                 it=b.it.cpu().numpy(), status=b.status.cpu().numpy(), lipschitz=b.lipschitz.cpu().numpy())
-
-
-def box_fallback(b):
-    """the per-component flags the box kernels leave in the workspace (1 = left to the full-frame kernel): the int region
-    behind the per-tile partials and the convergence sums (ws_layout in scarlet_hip.hip; K <= 32)"""
-    tiles = (b.H * b.W + 4095) // 4096
-    partials = 1 + b.K * b.B + b.K * (b.K + 1) // 2
-    at = 8 * b.S * tiles * partials + 8 * b.S * b.K * 4
-    torch.cuda.synchronize()
-    return b.workspace[at:at + 4 * b.S * b.K].view(torch.int32).cpu().numpy().reshape(b.S, b.K)
 
 
 def assert_identical(a, b, what):
