@@ -554,12 +554,46 @@ int scarlet_batch_products(const scarlet_batch *b, const scarlet_products *out, 
  * out[i] takes its rendered / residual / loss ([S][obs[i]->B]...; model, flux and component_models must be NULL there).
  * state_out (or NULL) takes model, flux and component_models over the state's C = state->B channels; they need no
  * observation, and rendered / residual / loss must be NULL there.  An out[i] with every pointer NULL skips that
- * observation (a low-resolution one, whose rendering this entry point does not take: pass nothing for it).
+ * observation.  Every observation here lies on the model's grid; a batch with a low-resolution observation goes
+ * through scarlet_observations_products_lowres (below), which renders that one too.
  * `scratch` is shared by the evaluations, which run one after the other: the largest of
  * scarlet_products_scratch_bytes(state, state_out) and scarlet_products_scratch_bytes(obs[i], &out[i]). */
 int scarlet_observations_products(const scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
                                   const scarlet_products *state_out, const scarlet_products *out, void *scratch,
                                   int64_t scratch_bytes, void *stream);
+/* scarlet_observations_products where some observations are low-resolution (LowResObservation.render(blend.get_model()),
+ * get_loss(model), reference observation.py:561-599): `lowres` is an array of n_obs pointers, NULL = that observation
+ * shares the model's grid and is handled exactly as above; with every entry NULL the call IS
+ * scarlet_observations_products.  A low-resolution obs[i] has H = lowres[i]->h, W = lowres[i]->w, B = lowres[i]->B, the
+ * state's S and K and no diff_kernel; out[i].rendered and out[i].residual are [S][B][h][w], out[i].loss is [S][B]:
+ *   - rendered = the operator of scarlet_lowres applied to channels band0[i] .. band0[i] + B - 1 of the model planes
+ *     sum_k sed[k][c] morph[k] (the float32 FMA chain in k order that `model` holds): bit for bit what
+ *     scarlet_lowres_render_large makes of those planes; residual = images - rendered; loss as in scarlet_products,
+ *     float64 sums in a fixed order, no atomics.
+ *   - Every scene is evaluated from its own buffer cur[s], whatever `active` and `status` say; absent components add
+ *     nothing; a scene's NaN stays in its own outputs.
+ *   - Read-only: the call writes through the outputs and `scratch` only.  lowres[i]->workspace is neither read nor
+ *     written (it may be NULL), so a fit's gradient planes, losses and streamed scratch stay as they are, as does the state.
+ *   - Where the factor matrices fit LDS (the limit of the LDS-resident entry points above) one workgroup per scene
+ *     (k_lowres_products) forms each band's model in LDS, projects, renders and reads the result once; it needs no
+ *     scratch.  Beyond, up to SCARLET_MAX_SIDE a side, and everywhere under the LOWRES_STREAMED switch, the streamed
+ *     chain of GEMMs runs over the S B band planes in chunks that keep the scratch within 256 MiB (at least one plane;
+ *     LOWRES_CHUNK lowers the chunk), on the band models of k_lrs_model -- or, when state_out->model is given, on that
+ *     output -- with a finish that only reads the rendered planes.  NO_LOWRES_MFMA gives the same bits in both forms.
+ *   - `scratch`: the largest of what scarlet_observations_products asks for the state and the same-grid observations
+ *     and scarlet_lowres_products_scratch_bytes() of the low-resolution ones.
+ * Errors (SCARLET_E_ARG with a message, before anything is launched): those of scarlet_observations_products; `lowres`
+ * NULL; for a low-resolution observation shapes that do not fit the state or its scarlet_lowres, a null factor matrix,
+ * B > 8, sides above SCARLET_MAX_SIDE, a diff_kernel, images NULL with residual or loss wanted, a scratch that is too
+ * small. */
+int scarlet_observations_products_lowres(const scarlet_batch *state, scarlet_batch *const *obs,
+                                         const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                         const scarlet_products *state_out, const scarlet_products *out, void *scratch,
+                                         int64_t scratch_bytes, void *stream);
+/* bytes of `scratch` that the low-resolution observation `obs` needs there: 0 where the LDS form runs (and for an `out`
+ * that is NULL or empty), otherwise a function of the shapes alone; < 0: an error code */
+int64_t scarlet_lowres_products_scratch_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr,
+                                              const scarlet_products *out);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

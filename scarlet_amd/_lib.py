@@ -167,6 +167,11 @@ _SIGNATURES = {
     "scarlet_batch_products": (c_int, [POINTER(ScarletBatch), POINTER(ScarletProducts), _P, c_int64, _P]),
     "scarlet_observations_products": (c_int, [POINTER(ScarletBatch), POINTER(POINTER(ScarletBatch)), _P, c_int,
                                               POINTER(ScarletProducts), POINTER(ScarletProducts), _P, c_int64, _P]),
+    "scarlet_observations_products_lowres": (c_int, [POINTER(ScarletBatch), POINTER(POINTER(ScarletBatch)),
+                                                     POINTER(POINTER(ScarletLowres)), _P, c_int, POINTER(ScarletProducts),
+                                                     POINTER(ScarletProducts), _P, c_int64, _P]),
+    "scarlet_lowres_products_scratch_bytes": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres),
+                                                        POINTER(ScarletProducts)]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

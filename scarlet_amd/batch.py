@@ -364,6 +364,7 @@ class BlendBatch(object):
         self.centroid_weight = torch.as_tensor(cw).to(**f64).contiguous()
         self._observations = None     # from_observations: [(ObservationBatch, its gradient batch)]
         self._lowres = None           # ... and per observation None, or (scarlet_lowres, what it points to)
+        self._lowres_products = False  # from_observations(lowres_products=True): `products` evaluates those too
         self.L_components = None      # (S, K, 2) float64 after a fit with a prior: the constants each component stepped with
         self._c = _lib.ScarletBatch()
         self._fill_struct()
@@ -525,8 +526,9 @@ class BlendBatch(object):
     def products(self, model=True, rendered=True, residual=True, loss=True, flux=True, components=None, out=None, obs=None):
         """What the reference reads off a fitted Blend, for every scene, from the current factors (read-only: the state,
         the fit's bookkeeping and the workspace stay as they are; scarlet_batch_products, or scarlet_observations_products
-        for a batch made by `from_observations`).  One call into the library on the current stream, no host
-        synchronisation.  Returns a `BatchProducts` of device tensors (None for what was not asked for):
+        / scarlet_observations_products_lowres for a batch made by `from_observations`).  One call into the library on
+        the current stream, no host synchronisation.  Returns a `BatchProducts` of device tensors (None for what was not
+        asked for):
 
         model : (S, C, H, W) sum_k sed[k] morph[k] over the model frame's channels (blend.get_model())
         rendered : (S, B, H, W) the model as the data sees it, convolved with the difference kernel when there is one
@@ -539,8 +541,11 @@ class BlendBatch(object):
         obs : (from_observations) the observations to evaluate, default all
 
         With `from_observations`, rendered / residual / loss are lists with one entry per observation (None for those
-        left out by `obs`).  A low-resolution observation's rendered / residual / loss are not available
-        (NotImplementedError); model, flux and the other observations' products are."""
+        left out by `obs`).  A low-resolution observation's entries lie on its own pixel grid: rendered and residual are
+        (S, B, h, w) -- the model through the observation's resampling and PSFs, LowResObservation.render(model) -- and
+        loss is (S, B) (scarlet_observations_products_lowres).  They are evaluated for a batch made with
+        `from_observations(..., lowres_products=True)`; a batch made without that keyword behaves as it always did and
+        raises NotImplementedError for them (model, flux and the other observations' products are available)."""
         t = self.torch
         S, K, C, H, W = self.S, self.K, self.B, self.H, self.W
         res = BatchProducts() if out is None else out
@@ -586,9 +591,10 @@ class BlendBatch(object):
         if not (rendered or residual or loss):
             idx = []
         for i in idx:
-            if self._lowres[i] is not None:
+            if self._lowres[i] is not None and not self._lowres_products:
                 raise NotImplementedError("products: rendered, residual and loss of a low-resolution observation (observation "
-                                          "%d) are not available; model and flux are" % i)
+                                          "%d) are evaluated for a batch made with from_observations(..., "
+                                          "lowres_products=True); model and flux are available without it" % i)
         outs = (_lib.ScarletProducts * n)()
         for name, want, dtype in wants:
             old = getattr(res, name)
@@ -596,20 +602,31 @@ class BlendBatch(object):
             new = [None] * n
             for i in idx:
                 o = self._observations[i][0]
-                new[i] = buf(old[i], want, (S, o.B) if name == "loss" else (S, o.B, H, W), dtype)
+                # (a low-resolution observation's planes lie on its own pixel grid)
+                new[i] = buf(old[i], want, (S, o.B) if name == "loss" else (S, o.B) + tuple(o.shape[2:]), dtype)
                 setattr(outs[i], name, _lib.ptr(new[i]))
             setattr(res, name, new if want else None)
         any_state = model or flux or sel is not None
         nbytes = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._c), ctypes.byref(ps)) if any_state else 0
         for i in idx:
-            nbytes = max(nbytes, _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._observations[i][1]._c),
-                                                                         ctypes.byref(outs[i])))
+            ob = self._observations[i][1]
+            if self._lowres[i] is None:
+                need = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(ob._c), ctypes.byref(outs[i]))
+            else:
+                need = _lib.check(_lib.lib.scarlet_lowres_products_scratch_bytes(
+                    ctypes.byref(self._c), ctypes.byref(ob._c), ctypes.byref(self._lowres[i][0]), ctypes.byref(outs[i])))
+            nbytes = max(nbytes, need)
         scratch = self._products_scratch(nbytes)
         ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
         first = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
-        _lib.check(_lib.lib.scarlet_observations_products(
-            ctypes.byref(self._c), ptrs, first.ctypes.data_as(ctypes.c_void_p), n, ctypes.byref(ps) if any_state else None, outs,
-            _lib.ptr(scratch), int(nbytes), _lib.stream_ptr()))
+        tail = (first.ctypes.data_as(ctypes.c_void_p), n, ctypes.byref(ps) if any_state else None, outs, _lib.ptr(scratch),
+                int(nbytes), _lib.stream_ptr())
+        if any(x is not None for x in self._lowres):
+            none = ctypes.POINTER(_lib.ScarletLowres)()
+            lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+            _lib.check(_lib.lib.scarlet_observations_products_lowres(ctypes.byref(self._c), ptrs, lows, *tail))
+        else:
+            _lib.check(_lib.lib.scarlet_observations_products(ctypes.byref(self._c), ptrs, *tail))
         return res
 
     def _products_scratch(self, nbytes):
@@ -882,12 +899,15 @@ class BlendBatch(object):
 
     # ------------------------------------------------------------------ several observations
     @classmethod
-    def from_observations(cls, observations, centers, _host_gradients=False, _channels=None, **kwargs):
+    def from_observations(cls, observations, centers, _host_gradients=False, _channels=None, lowres_products=False, **kwargs):
         """A batch fitted jointly against several observations of every scene (reference Blend(sources, [obs_a,
         obs_b]), blend.py:24-43, 120-139, 219-220).  The factors span the model frame's C = max(band0 + B) channels
         (C <= 8); `centers` and the other keyword arguments are those of BlendBatch (ragged centre lists give
         n_components).  Start the sources with `init_combined` (or `set_state`), then `fit` / `step`.
 
+        lowres_products : `products`, `render`, `residual` and `get_loss` also evaluate the low-resolution observations
+            (on their own pixel grids).  Off by default: a batch made without it raises NotImplementedError for those,
+            as such batches always did.  The fit does not depend on it.
         _host_gradients : `Blend`'s Python pipeline calls scarlet_backward_gradients on the state and on every
             observation's batch itself, so the state gets real (zero) images and the observations' batches keep their
             own morphology planes; the joint fit reads neither.
@@ -928,6 +948,7 @@ class BlendBatch(object):
             state._fill_struct()
         batches = []
         state._lowres = [None] * len(obs)
+        state._lowres_products = bool(lowres_products)
         for i, o in enumerate(obs):
             low = isinstance(o, LowResObservationBatch)
             # (a low-resolution batch lives on its own pixel grid: the model-frame centres mean nothing there)

@@ -158,6 +158,41 @@ inline ProductsPlan products_plan(int S, int K, int B, int H, int W, int psf, co
     return p;
 }
 
+// ---- the read-only products of a LOW-RESOLUTION observation (launch_lowres_products): k_lowres_products, one workgroup
+// per scene with the factor matrices in LDS, wherever they fit; beyond, and everywhere under LOWRES_STREAMED, the
+// streamed chain of lowres_stream.h on the S B band planes, taken in chunks that keep the caller's scratch within
+// LRS_SCRATCH_CAP (one plane at the least; LOWRES_CHUNK lowers the chunk of the launches, never the size).
+enum LowresProductsForm { LOWRES_PRODUCTS_LDS, LOWRES_PRODUCTS_STREAMED };
+struct LowresProductsSwitches {     // (scarlet_hip.hip reads them from the options)
+    bool streamed;          // LOWRES_STREAMED
+    int chunk;              // LOWRES_CHUNK: planes per chunk, 0 = automatic
+};
+struct LowresProductsPlan {
+    int form;
+    size_t lds;             // dynamic LDS of k_lowres_products
+    int planes;             // S B
+    int sized, chunk;       // planes per chunk that the scratch holds / that a launch takes
+    bool stage_model;       // k_lrs_model writes the band models into the scratch (false: the caller's `model` output has them)
+    LrsScratch s;           // the chunk's buffers (lrs_buffers)
+    int64_t total;          // bytes of the caller's scratch
+};
+// have_model: the same call writes the state's `model` output before this evaluation runs
+inline LowresProductsPlan lowres_products_plan(int S, const LowresDims &d, bool have_model, const LowresProductsSwitches &sw)
+{
+    LowresProductsPlan p = {};
+    p.planes = S * d.B;
+    p.lds = lowres_lds_bytes(d);
+    if (!sw.streamed && p.lds <= LDS_LIMIT) { p.form = LOWRES_PRODUCTS_LDS; return p; }
+    p.form = LOWRES_PRODUCTS_STREAMED;
+    p.lds = 0;
+    p.s = lrs_products_scratch(d);
+    p.sized = std::min(lrs_chunk(p.s, p.planes), 65535);           // (the planes of a chunk are the grid's y)
+    p.chunk = sw.chunk > 0 && sw.chunk < p.sized ? sw.chunk : p.sized;
+    p.stage_model = !have_model;
+    p.total = (int64_t)p.sized * (int64_t)p.s.per_plane;
+    return p;
+}
+
 // ---- the initialisers' float64 tile (initsrc.h): in LDS, or one per component in a temporary HBM buffer
 struct InitTilePlan { bool in_lds; size_t lds, hbm; };
 inline InitTilePlan init_tile_plan(int H, int W, size_t components)

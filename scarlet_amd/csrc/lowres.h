@@ -139,13 +139,20 @@ __device__ inline void lr_load_factors(float *lds, const LowresLds &l, const Low
 // one H x W plane (global, row stride W) -> the tile of the p region, then its projection Uy m Ux^T as the four real
 // blocks C = [[Re Uy . Re T, Re Uy . Im T], [Im Uy . Re T, Im Uy . Im T]] (T = m Ux^T) in buffer X, [2 nfy][ld2x].
 // Ends with the workgroup synchronised.
+__device__ inline void lr_project_tile(float *lds, const LowresLds &l, const LowresDims &d, bool mfma);
 __device__ inline void lr_project(float *lds, const LowresLds &l, const LowresDims &d, const float *plane, bool mfma)
 {
-    float *tile = lds + l.p, *tp = lds + l.p + l.tp, *C = lds + l.x;
+    float *tile = lds + l.p;
     for (int e = threadIdx.x; e < d.H * d.W; e += SC_BLOCK) {
         const int y = e / d.W, x = e - y * d.W;
         tile[y * l.ldW + x] = plane[e];
     }
+    lr_project_tile(lds, l, d, mfma);
+}
+// ... of the plane that the workgroup has written into the tile [H][ldW] of the p region itself (no barrier needed before)
+__device__ inline void lr_project_tile(float *lds, const LowresLds &l, const LowresDims &d, bool mfma)
+{
+    float *tile = lds + l.p, *tp = lds + l.p + l.tp, *C = lds + l.x;
     __syncthreads();
     const int ld2x = l.ld2x;
     // T [H][2 nfx] = m [H][W] . (Re Ux | Im Ux)^T
@@ -272,6 +279,77 @@ __global__ __launch_bounds__(SC_BLOCK) void k_lowres_planes(LowresArgs a)
         float *G = a.G + ((size_t)s * d.B + c) * HW;
         const int W = d.W;
         lr_adjoint(lr_lds, l, d, dhat, mfma, [=](int y, int x, float v) { G[y * W + x] = v; });
+    }
+}
+
+// The read-only products of a low-resolution observation (scarlet_observations_products_lowres): what the observation
+// sees of the state, forward only.  One workgroup per scene -- every scene, whatever `active` and `status` say, from its
+// own buffer cur[s] -- loads the factors once and, band by band, forms the band model sum_k sed[k][band0 + c] m_k (the
+// float32 FMA chain in k order of k_products and k_lrs_model, absent components not read) straight in the tile of
+// lr_project, projects it, multiplies by Dhat_c as k_lowres_render does (so the rendered planes are, bit for bit, that
+// kernel's on the model planes), runs lr_forward, and reads the h x w result once for rendered, residual = image -
+// rendered and loss_c = 1/2 sum (w (rendered - image))^2 (float64, block_sum: a fixed order).  Outputs that are NULL
+// are not written; nothing of the state or of a workspace is.
+struct LowresProductsArgs {
+    LowresDims d;
+    LowresFactors f;
+    int K, C, band0;
+    const float *sed[2], *morph[2];           // the STATE's factors: sed [S][K][C], morph [S][K][H][W]
+    const int *cur, *ncomp;
+    const float *images, *weights;            // [S][B][h][w]; images NULL: rendered alone; weights NULL -> weight_scalar
+    float weight_scalar;
+    float *rendered, *residual;               // [S][B][h][w] or NULL
+    double *loss;                             // [S][B] or NULL
+    int mfma;
+};
+
+__global__ __launch_bounds__(SC_BLOCK) void k_lowres_products(LowresProductsArgs a)
+{
+    extern __shared__ __align__(16) float lr_lds[];
+    __shared__ double lred[SC_NWAVES];
+    const int s = blockIdx.x;
+    const LowresDims d = a.d;
+    const LowresLds l = lowres_lds(d);
+    const bool mfma = a.mfma != 0;
+    const int n = scene_ncomp(a.ncomp, s, a.K), c0 = a.cur[s] & 1, nf = d.nfy * d.nfx, HW = d.H * d.W, hw = d.h * d.w;
+    const int ld2x = l.ld2x, nfy = d.nfy, nfx = d.nfx;
+    float *X = lr_lds + l.x, *Y = lr_lds + l.p, *tile = lr_lds + l.p;
+    lr_load_factors(lr_lds, l, d, a.f, s);
+    const float *sed = a.sed[c0] + (size_t)s * a.K * a.C + a.band0;
+    const float *morph = a.morph[c0] + (size_t)s * a.K * HW;
+    for (int c = 0; c < d.B; ++c) {
+        // (the band before no longer reads the p region: lr_forward ended synchronised; its epilogue reads X, which is
+        // written again only behind lr_project_tile's barriers)
+        for (int e = threadIdx.x; e < HW; e += SC_BLOCK) {
+            float acc = 0.f;
+            for (int k = 0; k < n; ++k) acc = fmaf(sed[(size_t)k * a.C + c], morph[(size_t)k * HW + e], acc);
+            tile[(e / d.W) * l.ldW + e % d.W] = acc;
+        }
+        lr_project_tile(lr_lds, l, d, mfma);                       // (its first barrier also covers the factors)
+        const float2 *dhat = a.f.dhat + ((size_t)(a.f.dhat_per_scene ? s * d.B : 0) + c) * nf;
+        // (the projection sits in X, which lr_forward reads expanded: expand through Y)
+        lr_expand(Y, ld2x, nfy, nfx, dhat, [=](int f, int g) { return lr_projected(X, ld2x, nfy, nfx, f, g); });
+        __syncthreads();
+        for (int e = threadIdx.x; e < 2 * nfy * ld2x; e += SC_BLOCK) X[e] = Y[e];
+        __syncthreads();
+        lr_forward(lr_lds, l, d, mfma);
+        const size_t plane = ((size_t)s * d.B + c) * hw;
+        const float *img = a.images ? a.images + plane : nullptr;
+        const float *wgt = a.weights ? a.weights + plane : nullptr;
+        double loss = 0;
+        for (int e = threadIdx.x; e < hw; e += SC_BLOCK) {
+            const float r = X[(e / d.w) * l.ldw + e % d.w];
+            if (a.rendered) a.rendered[plane + e] = r;
+            if (!img) continue;
+            const float v = img[e];
+            if (a.residual) a.residual[plane + e] = v - r;
+            const float dw = (wgt ? wgt[e] : a.weight_scalar) * (r - v);
+            loss += (double)dw * (double)dw;
+        }
+        if (a.loss) {
+            loss = block_sum(loss, lred);
+            if (threadIdx.x == 0) a.loss[(size_t)s * d.B + c] = 0.5 * loss;
+        }
     }
 }
 

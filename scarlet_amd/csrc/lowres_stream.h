@@ -12,11 +12,13 @@
 //   render  T = m Ux^T | C = Uy T | Z = expand(C o Dhat_c) (k_lrs_expand) | R = Z Vx^T | out = Vy R
 //   fit     d = w (out - image), E = w d, loss partial sums (k_lrs_resid), loss_c = 1/2 sum d^2 (k_lrs_loss)
 //   adjoint A1 = Vy^T E | C2 = A1 Vx | Z2 = expand(C2 o Dhat_c) | G1 = Z2 Ux | G = Uy^T G1
+//   products (read-only): model_c (or the caller's `model` output) | render | rendered, residual = image - out, loss
+//           partial sums (k_lrs_products_finish, which leaves `out` as it is) | k_lrs_loss
 //
 // The factor matrices are read where the caller put them, as (re, im) pairs: an operand that is a stacked factor names
 // the index along which it is stacked (LrsOperand::stack) and the loader turns an index >= n into the imaginary part of
 // index - n.  The plane -> (band, scene) map selects dhat and, with v_per_scene, vy / vx; planes of inactive scenes
-// return at once in every kernel, so nothing of theirs is written.
+// return at once in every kernel, so nothing of theirs is written (the products pass no `active`: every scene runs).
 #pragma once
 #include "lowres.h"
 
@@ -226,6 +228,41 @@ __global__ __launch_bounds__(SC_BLOCK) void k_lrs_loss(LrsResid a, int planes)
     a.loss_part[a.pl.p0 + local] = 0.5 * loss;
 }
 
+// the finish of the read-only products (scarlet_observations_products_lowres): out[plane] [h w], the rendered image of
+// the chain, is only read -- rendered, residual = image - out (each where given) and, with `partials`, the sums of
+// k_lrs_resid in its order (block b: the elements b * 256 + t + i * 64 * 256), which k_lrs_loss adds.  Every plane is
+// evaluated: pl.active is NULL.
+struct LrsFinish {
+    const float *out;
+    size_t plane;
+    const float *images, *weights;          // [planes of the caller][h w]; images NULL: rendered alone
+    float weight_scalar;
+    int hw;
+    float *rendered, *residual;             // [planes of the caller][h w] or NULL
+    double *partials;                       // [planes of the chunk][LRS_LOSS_BLOCKS] or NULL
+    int p0;
+};
+__global__ __launch_bounds__(SC_BLOCK) void k_lrs_products_finish(LrsFinish a)
+{
+    __shared__ double lred[SC_NWAVES];
+    const size_t p = (size_t)(a.p0 + blockIdx.y) * a.hw;
+    const float *out = a.out + (size_t)blockIdx.y * a.plane;
+    const float *img = a.images ? a.images + p : nullptr, *wgt = a.weights ? a.weights + p : nullptr;
+    double loss = 0;
+    for (int e = blockIdx.x * SC_BLOCK + threadIdx.x; e < a.hw; e += LRS_LOSS_BLOCKS * SC_BLOCK) {
+        const float r = out[e];
+        if (a.rendered) a.rendered[p + e] = r;
+        if (!img) continue;
+        const float v = img[e];
+        if (a.residual) a.residual[p + e] = v - r;
+        const float dw = (wgt ? wgt[e] : a.weight_scalar) * (r - v);
+        loss += (double)dw * (double)dw;
+    }
+    if (!a.partials) return;
+    loss = block_sum(loss, lred);
+    if (threadIdx.x == 0) a.partials[(size_t)blockIdx.y * LRS_LOSS_BLOCKS + blockIdx.x] = loss;
+}
+
 // ---- the scratch of one chunk, floats per plane (host): M (the band model of a fit), A (T, R, A1, G1), B and Z (the
 // projections and their expansions), D (the rendered image and its residual of a fit), and the loss partials after them
 struct LrsScratch {
@@ -246,6 +283,10 @@ inline LrsScratch lrs_scratch(const LowresDims &d, bool fit)
     s.per_plane = (s.per_plane + 15) & ~(size_t)15;
     return s;
 }
+// ... of the read-only products: the buffers of a fit (M for the band models, D for the rendered image that the finish
+// reads, the loss partials).  One layout whatever the call wants, so that its size is a function of the shape alone; a
+// call that finds the band models in the caller's `model` output leaves M unused.
+inline LrsScratch lrs_products_scratch(const LowresDims &d) { return lrs_scratch(d, true); }
 // Planes per chunk: as many as LRS_SCRATCH_CAP bytes of scratch hold, at least one, at most all
 #define LRS_SCRATCH_CAP ((size_t)256 << 20)
 inline int lrs_chunk(const LrsScratch &s, int planes)

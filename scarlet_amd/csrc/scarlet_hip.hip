@@ -2205,6 +2205,8 @@ static LrsOperand lrs_real(const float *p, int rs, int cs, size_t plane)
     LrsOperand o = {p, rs, cs, 0, 0, plane, 0};
     return o;
 }
+// contiguous model planes [planes][H][W]
+static LrsOperand lrs_planes(const float *p, const LowresDims &d) { return lrs_real(p, d.W, 1, (size_t)d.H * d.W); }
 // a factor matrix of (re, im) pairs with strides in pairs, stacked along its first (1) or second (2) index
 static LrsOperand lrs_factor(const float2 *p, int rs, int cs, int stack, int n, size_t scene)
 {
@@ -2238,15 +2240,14 @@ static void lrs_expand(hipStream_t st, const LowresDims &d, const LowresFactors 
     LrsExpand e = {u.b, u.z, s.b, d.nfy, d.nfx, d.B, f, pl};
     hipLaunchKernelGGL(k_lrs_expand, dim3((d.nfy * d.nfx + SC_BLOCK - 1) / SC_BLOCK, planes), dim3(SC_BLOCK), 0, st, e);
 }
-// render of the chunk's planes: model [planes][H][W] -> out [planes][h][w]
+// render of the chunk's planes: model (planes of H x W, an LrsOperand: lrs_planes for [planes][H][W]) -> out [planes][h][w]
 static void lrs_forward(hipStream_t st, bool mfma, const LowresDims &d, const LowresFactors &f, const LrsBuffers &u,
-                        const LrsScratch &s, const LrsPlanes &pl, int planes, const float *model, float *out)
+                        const LrsScratch &s, const LrsPlanes &pl, int planes, const LrsOperand &model, float *out)
 {
     const int ny2 = 2 * d.nfy, nx2 = 2 * d.nfx;
     const size_t vy_scene = f.v_per_scene ? (size_t)d.h * d.nfy : 0, vx_scene = f.v_per_scene ? (size_t)d.w * d.nfx : 0;
     // T [H][2 nfx] = m [H][W] . (Re Ux | Im Ux)^T
-    lrs_gemm(st, mfma, lrs_real(model, d.W, 1, (size_t)d.H * d.W), lrs_factor(f.ux, 1, d.W, 2, d.nfx, 0), u.a, nx2, s.a,
-             d.H, nx2, d.W, pl, planes);
+    lrs_gemm(st, mfma, model, lrs_factor(f.ux, 1, d.W, 2, d.nfx, 0), u.a, nx2, s.a, d.H, nx2, d.W, pl, planes);
     // C [2 nfy][2 nfx] = (Re Uy; Im Uy) [2 nfy][H] . T
     lrs_gemm(st, mfma, lrs_factor(f.uy, d.H, 1, 1, d.nfy, 0), lrs_real(u.a, nx2, 1, s.a), u.b, nx2, s.b, ny2, nx2, d.H, pl, planes);
     lrs_expand(st, d, f, u, s, pl, planes);
@@ -2301,7 +2302,7 @@ static void lrs_fit_planes(hipStream_t st, const LrsFit &f)
         LrsModel m = {{a.sed[0], a.sed[1]}, {a.morph[0], a.morph[1]}, a.cur, a.ncomp, a.K, a.C, a.band0, (int)HW, u.m, f.s.m, pl};
         const int mblocks = (int)((HW + SC_BLOCK - 1) / SC_BLOCK);
         hipLaunchKernelGGL(k_lrs_model, dim3(mblocks < 1024 ? mblocks : 1024, n), dim3(SC_BLOCK), 0, st, m);
-        lrs_forward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, u.m, u.d);
+        lrs_forward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, lrs_planes(u.m, d), u.d);
         LrsResid r = {u.d, f.s.d, a.images, a.weights, a.weight_scalar, d.h * d.w, u.partials, a.loss_part, pl};
         hipLaunchKernelGGL(k_lrs_resid, dim3(LRS_LOSS_BLOCKS, n), dim3(SC_BLOCK), 0, st, r);
         hipLaunchKernelGGL(k_lrs_loss, dim3((n + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, r, n);
@@ -2355,7 +2356,7 @@ static int lowres_op_large(bool adjoint, const float *in, int n, int H, int W, c
         const int m = n - p0 < chunk ? n - p0 : chunk;
         const LrsPlanes pl = {band, scene, nullptr, 0, p0};
         if (adjoint) lrs_backward((hipStream_t)stream, mfma, d, f, u, s, pl, m, in + p0 * hw, out + p0 * HW);
-        else lrs_forward((hipStream_t)stream, mfma, d, f, u, s, pl, m, in + p0 * HW, out + p0 * hw);
+        else lrs_forward((hipStream_t)stream, mfma, d, f, u, s, pl, m, lrs_planes(in + p0 * HW, d), out + p0 * hw);
     }
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
@@ -2953,9 +2954,103 @@ extern "C" int scarlet_batch_products(const scarlet_batch *b, const scarlet_prod
     return launch_products(b, b, 0, out, scratch, (hipStream_t)stream);
 }
 
-extern "C" int scarlet_observations_products(const scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
-                                             const scarlet_products *state_out, const scarlet_products *out, void *scratch,
-                                             int64_t scratch_bytes, void *stream)
+// ---- rendered / residual / loss of a LOW-RESOLUTION observation (lowres.h k_lowres_products, lowres_stream.h; the form,
+// the chunks and the scratch: launch_plan.h lowres_products_plan)
+static LowresProductsPlan lowres_products_plan_of(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr,
+                                                  bool have_model)
+{
+    const LowresProductsSwitches sw = {opt(OPT_LOWRES_STREAMED) != 0, opt(OPT_LOWRES_CHUNK)};
+    return lowres_products_plan(state->S, lowres_dims(state, ob, lr), have_model, sw);
+}
+// host-side check of one such evaluation, before anything is launched (every refusal is SCARLET_E_ARG)
+static int check_lowres_products(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr, int band0,
+                                 const scarlet_products *o)
+{
+    if (!state || !ob || !lr) return set_err(SCARLET_E_ARG, "null batch");
+    if (!o) return set_err(SCARLET_E_ARG, "products: out is NULL");
+    if (ob->B > SC_BMAX || lr->B > SC_BMAX) return set_err(SCARLET_E_ARG, "products: a low-resolution observation has at most 8 bands");
+    if (state->H > SCARLET_MAX_SIDE || state->W > SCARLET_MAX_SIDE || lr->h > SCARLET_MAX_SIDE || lr->w > SCARLET_MAX_SIDE ||
+        lr->nfy > SCARLET_MAX_SIDE || lr->nfx > 2 * SCARLET_MAX_SIDE)
+        return set_err(SCARLET_E_ARG, "products: sides above SCARLET_MAX_SIDE are not supported");
+    if (int rc = check_shape(state)) return rc;
+    if (ob->S != state->S || ob->K != state->K || ob->H != lr->h || ob->W != lr->w || ob->B < 1 || band0 < 0 ||
+        band0 + ob->B > state->B)
+        return set_err(SCARLET_E_ARG, "products: a low-resolution observation does not fit the model frame or its scarlet_lowres");
+    if (ob->diff_kernel)
+        return set_err(SCARLET_E_ARG, "a low-resolution observation takes no diff_kernel: its PSFs are in dhat");
+    if (int rc = check_lowres(lr, state->H, state->W, ob->B, false, true)) return rc;
+    if (!state->sed[0] || !state->sed[1] || !state->morph[0] || !state->morph[1] || !state->cur)
+        return set_err(SCARLET_E_ARG, "products: null factor pointer in batch");
+    if ((o->residual || o->loss) && !ob->images) return set_err(SCARLET_E_ARG, "products: residual and loss need images");
+    return SCARLET_OK;
+}
+// one evaluation, checked before.  model: the state's `model` output [S][C][H][W] that this call has written, or NULL
+static int launch_lowres_products(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr, int band0,
+                                  const scarlet_products *o, const float *model, void *scratch, hipStream_t st)
+{
+    const LowresDims d = lowres_dims(state, ob, lr);
+    const LowresProductsPlan p = lowres_products_plan_of(state, ob, lr, model != nullptr);
+    const LowresFactors f = lowres_factors(lr);
+    const bool mfma = !opt(OPT_NO_LOWRES_MFMA);
+    const float *images = (o->residual || o->loss) ? ob->images : nullptr;
+    const int K = state->K, C = state->B, HW = d.H * d.W, hw = d.h * d.w;
+    int rc;
+    switch (p.form) {
+    case LOWRES_PRODUCTS_LDS: {
+        LowresProductsArgs a = {};
+        a.d = d; a.f = f; a.K = K; a.C = C; a.band0 = band0;
+        a.sed[0] = state->sed[0]; a.sed[1] = state->sed[1]; a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
+        a.cur = state->cur; a.ncomp = state->n_components;
+        a.images = images; a.weights = ob->weights; a.weight_scalar = ob->weight_scalar;
+        a.rendered = o->rendered; a.residual = o->residual; a.loss = o->loss; a.mfma = mfma;
+        if ((rc = launch_lds(k_lowres_products, dim3(state->S), dim3(SC_BLOCK), p.lds, st, a))) return rc;
+        break;
+    }
+    case LOWRES_PRODUCTS_STREAMED: {
+        const LrsBuffers u = lrs_buffers(scratch, p.s, p.sized, true);
+        for (int p0 = 0; p0 < p.planes; p0 += p.chunk) {
+            const int n = std::min(p.chunk, p.planes - p0);
+            const LrsPlanes pl = {nullptr, nullptr, nullptr, d.B, p0};           // (no `active`: every scene is evaluated)
+            LrsOperand m = lrs_planes(u.m, d);
+            if (p.stage_model) {
+                LrsModel lm = {{state->sed[0], state->sed[1]}, {state->morph[0], state->morph[1]}, state->cur, state->n_components,
+                               K, C, band0, HW, u.m, p.s.m, pl};
+                const int mblocks = (HW + SC_BLOCK - 1) / SC_BLOCK;
+                hipLaunchKernelGGL(k_lrs_model, dim3(mblocks < 1024 ? mblocks : 1024, n), dim3(SC_BLOCK), 0, st, lm);
+            } else {
+                // plane p0 + i is channel band0 + band of its scene: (band0 + p0 + i) H W floats from the start, and
+                // (C - B) H W more for every scene before
+                m = lrs_planes(model + (size_t)(band0 + p0) * HW, d);
+                m.scene = (size_t)(C - d.B) * HW;
+            }
+            lrs_forward(st, mfma, d, f, u, p.s, pl, n, m, u.d);
+            LrsFinish fin = {u.d, p.s.d, images, ob->weights, ob->weight_scalar, hw, o->rendered, o->residual,
+                             o->loss ? u.partials : nullptr, p0};
+            hipLaunchKernelGGL(k_lrs_products_finish, dim3(LRS_LOSS_BLOCKS, n), dim3(SC_BLOCK), 0, st, fin);
+            if (o->loss) {
+                LrsResid r = {nullptr, 0, nullptr, nullptr, 0.f, hw, u.partials, o->loss, pl};
+                hipLaunchKernelGGL(k_lrs_loss, dim3((n + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, r, n);
+            }
+        }
+        break;
+    }
+    }
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+
+extern "C" int64_t scarlet_lowres_products_scratch_bytes(const scarlet_batch *state, const scarlet_batch *obs,
+                                                         const scarlet_lowres *lr, const scarlet_products *out)
+{
+    if (!out || !products_any(out)) return 0;
+    if (int rc = check_lowres_products(state, obs, lr, 0, out)) return rc;
+    return lowres_products_plan_of(state, obs, lr, false).total;
+}
+
+// the evaluations of scarlet_observations_products; lowres: NULL, or n_obs pointers (NULL = on the model's grid)
+static int observations_products_call(const scarlet_batch *state, scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                      const int32_t *band0, int n_obs, const scarlet_products *state_out,
+                                      const scarlet_products *out, void *scratch, int64_t scratch_bytes, void *stream)
 {
     if (!state) return set_err(SCARLET_E_ARG, "null batch");
     if (n_obs < 0 || n_obs > SCARLET_MAX_OBSERVATIONS || (n_obs > 0 && (!obs || !band0 || !out)))
@@ -2971,10 +3066,18 @@ extern "C" int scarlet_observations_products(const scarlet_batch *state, scarlet
             (rc = check_products_scratch(products_plan_of(state, state->K, state_out, WS_PEEK, nullptr), scratch, scratch_bytes)))
             return rc;
     }
+    const float *model = state_out ? state_out->model : nullptr;
     for (int i = 0; i < n_obs; ++i) {
         if (!products_any(&out[i])) continue;
         if (out[i].model || out[i].flux || out[i].component_models || out[i].n_select)
             return set_err(SCARLET_E_ARG, "products: model, flux and component_models belong to the state, not to an observation");
+        if (lowres && lowres[i]) {
+            if ((rc = check_lowres_products(state, obs[i], lowres[i], band0[i], &out[i]))) return rc;
+            const int64_t need = lowres_products_plan_of(state, obs[i], lowres[i], model != nullptr).total;
+            if (need > 0 && (!scratch || scratch_bytes < need))
+                return set_err(SCARLET_E_ARG, "products: scratch is too small (scarlet_lowres_products_scratch_bytes)");
+            continue;
+        }
         if ((rc = check_products(state, obs[i], band0[i], &out[i])) ||
             (rc = check_products_scratch(products_plan_of(obs[i], state->K, &out[i], WS_PEEK, nullptr), scratch, scratch_bytes)))
             return rc;
@@ -2982,8 +3085,28 @@ extern "C" int scarlet_observations_products(const scarlet_batch *state, scarlet
     (void)hipGetLastError();
     if (state_out && products_any(state_out) && (rc = launch_products(state, state, 0, state_out, scratch, (hipStream_t)stream)))
         return rc;
-    for (int i = 0; i < n_obs; ++i)
-        if (products_any(&out[i]) && (rc = launch_products(state, obs[i], band0[i], &out[i], scratch, (hipStream_t)stream)))
-            return rc;
+    for (int i = 0; i < n_obs; ++i) {
+        if (!products_any(&out[i])) continue;
+        if (lowres && lowres[i])
+            rc = launch_lowres_products(state, obs[i], lowres[i], band0[i], &out[i], model, scratch, (hipStream_t)stream);
+        else rc = launch_products(state, obs[i], band0[i], &out[i], scratch, (hipStream_t)stream);
+        if (rc) return rc;
+    }
     return SCARLET_OK;
+}
+
+extern "C" int scarlet_observations_products(const scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                             const scarlet_products *state_out, const scarlet_products *out, void *scratch,
+                                             int64_t scratch_bytes, void *stream)
+{
+    return observations_products_call(state, obs, nullptr, band0, n_obs, state_out, out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int scarlet_observations_products_lowres(const scarlet_batch *state, scarlet_batch *const *obs,
+                                                    const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                                    const scarlet_products *state_out, const scarlet_products *out,
+                                                    void *scratch, int64_t scratch_bytes, void *stream)
+{
+    if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
+    return observations_products_call(state, obs, lowres, band0, n_obs, state_out, out, scratch, scratch_bytes, stream);
 }
