@@ -501,10 +501,45 @@ def gen_thresh_translate(sc):
     save("thresh_translate", **out)
 
 
+EDGE_SCENES = (("04_exact_persistent", 1, ("f32", "f64")), ("11_wave", 1, ("f32",)), ("13_box_68", 0, ("f32",)))
+
+
+def gen_fit_edges(sc):
+    """Sources on the frame's borders (tests/edge_cases.py): the 64 x 64 scene with a source in each corner and its
+    catalogue pixels one pixel inside (float32 and float64), the 16 x 20 scene of the same kind and the 68 x 68 scene
+    with the broad corner source (float32).  ExtendedSource per catalogue pixel, then the scene's own number of
+    iterations at e_rel=0; the constructors' state and the final state."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import edge_cases as ec
+    out = {}
+    for name, s, tags in EDGE_SCENES:
+        c = ec.CASES[name]
+        images32, pixels, _ = ec.scene(c, s)
+        for tag in tags:
+            dt = np.float32 if tag == "f32" else np.float64
+            images = images32.astype(dt)
+            frame = sc.Frame(images.shape, dtype=dt)
+            obs = sc.Observation(images).match(frame)
+            srcs = [sc.ExtendedSource(frame, tuple(int(v) for v in p), obs, np.ones(c.B) * ec.BG) for p in pixels]
+            pre = "%s_s%d_%s_" % (name, s, tag)
+            out[pre + "init_sed"] = np.array([x.sed for x in srcs])
+            out[pre + "init_morph"] = np.array([x.morph for x in srcs])
+            out[pre + "init_center"] = np.array([x.pixel_center for x in srcs]).astype(np.int64)
+            out[pre + "init_shift"] = np.array([x.shift for x in srcs])
+            blend = sc.Blend(srcs, obs)
+            blend.fit(ec.iterations(c), e_rel=0)
+            for k, v in _blend_state(blend).items():
+                out[pre + k] = v
+    save("fit_edges", **out)
+
+
 def main():
     sc = load_reference()
     import scarlet.cache
     sc.cache = scarlet.cache
+    if len(sys.argv) > 1 and sys.argv[1] == "edges":
+        gen_fit_edges(sc)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "thresh":
         import scarlet.interpolation
         sc.interpolation = scarlet.interpolation
@@ -537,6 +572,7 @@ def main():
     gen_fit_extras2(sc)
     gen_fit_extras3(sc)
     gen_geometry(sc)
+    gen_fit_edges(sc)
 
 
 if __name__ == "__main__":

@@ -29,7 +29,8 @@ def gaussian_psf(shape, sigma):
 
 def make_scene(index, B=5, H=64, W=64, K=4, noise=0.1, min_sep=4, psfs=None,
                dtype=np.float32):
-    """Returns dict(images (B,H,W), centers (K,2) int, true_seds (K,B), true_morphs (K,H,W))."""
+    """Returns dict(images (B,H,W), centers (K,2) int, true_seds (K,B), true_morphs (K,H,W)).  Centres stay 8 px
+    inside the frame; scenes with sources on its borders come from tests/edge_cases.py."""
     rng = np.random.Generator(np.random.PCG64(SEED0 + int(index)))
     centers = []
     while len(centers) < K:

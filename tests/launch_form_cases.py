@@ -67,7 +67,8 @@ CASES = collections.OrderedDict((c.name, c) for c in [
 
 
 def scenes(c, seeds=None):
-    """images (S, B, H, W), centers (S, K, 2): blobs at least 3 pixels apart and 4 from the edges, noise 0.1"""
+    """images (S, B, H, W), centers (S, K, 2): blobs at least 3 pixels apart and 4 from the edges, noise 0.1 (sources on
+    the borders of the same cases come from tests/edge_cases.py)"""
     rng = np.random.default_rng(seeds or [c.K, c.B, c.H, c.W])
     grouped = c.batch.get("group") is not None or c.kind == "init"
     images, centers = np.zeros((S, c.B, c.H, c.W)), np.zeros((S, c.K, 2), np.int32)

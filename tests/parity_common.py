@@ -117,15 +117,12 @@ def gpu_fit(scarlet, wl, images, centers, iters, e_rel, per_iteration=False, che
     return st0, out
 
 
-def straddles_threshold(scarlet, wl, images, centers, iters):
-    """the f64-anchored exemption of the module docstring for ONE scene; returns (ok, message)"""
-    st0, g = gpu_fit(scarlet, wl, images[None], centers[None], iters, 0.0, per_iteration=True)
-    sed0, morph0, cen0, sh0 = (a[0] for a in st0)
-    okw = wl.oracle_kwargs()
-    o32, _ = oracle_trace(images, sed0, morph0, cen0, sh0, iters, np.float32, okw)
-    o64, pre64 = oracle_trace(images, sed0, morph0, cen0, sh0, iters, np.float64, okw)
+def straddle_verdict(snaps, o32, o64, pre64, iters):
+    """conditions (i) - (iii) of the module docstring for ONE scene: snaps[t], o32[t], o64[t] its morphologies after
+    iteration t + 1 on the GPU (re-run alone, iteration by iteration) and in the two oracles, pre64[t] the float64
+    oracle's (stepped morphologies, morphologies as prox_plus saw them); returns (ok, message)"""
     for t in range(iters):
-        gm = g["snaps"][t][0]
+        gm = snaps[t]
         mismatch = (gm == 0) != (o32[t] == 0)
         close = rel_err(gm, o32[t]) <= TOL
         if mismatch.any():
@@ -144,6 +141,16 @@ def straddles_threshold(scarlet, wl, images, centers, iters):
     return False, "no divergence found when re-running the scene alone"
 
 
+def straddles_threshold(scarlet, wl, images, centers, iters):
+    """the f64-anchored exemption of the module docstring for ONE scene; returns (ok, message)"""
+    st0, g = gpu_fit(scarlet, wl, images[None], centers[None], iters, 0.0, per_iteration=True)
+    sed0, morph0, cen0, sh0 = (a[0] for a in st0)
+    okw = wl.oracle_kwargs()
+    o32, _ = oracle_trace(images, sed0, morph0, cen0, sh0, iters, np.float32, okw)
+    o64, pre64 = oracle_trace(images, sed0, morph0, cen0, sh0, iters, np.float64, okw)
+    return straddle_verdict([m[0] for m in g["snaps"]], o32, o64, pre64, iters)
+
+
 def log_exemptions(test, exempt, cap):
     line = "%s: %d of at most %d scene(s) passed through the float64-anchored threshold exemption: %s" % (
         test, len(exempt), cap, exempt)
@@ -154,6 +161,38 @@ def log_exemptions(test, exempt, cap):
             f.write("exempt    %s\n" % line)
 
 
+def compare_fixed_iterations(g, ref, iters, straddle, max_exempt, test, exempt=None, flags=False):
+    """a device run `g` (gpu_fit's result: status, it, cen, sed, morph, mse, flags; `iters` iterations at e_rel = 0)
+    against the float32 oracle's results `ref` (oracle_fit's tuples, one per scene): status 0, the iteration count,
+    centres bit-exact (and, if asked, the flags and the oracle's own count), sed / morph / loss history within TOL.
+    A scene beyond TOL must pass `straddle(i)` -> (ok, message), the exemption of the module docstring; at most
+    `max_exempt` scenes may, counted in `exempt` (a list a module can share between its tests).  Returns the worst
+    errors."""
+    S = len(ref)
+    exempt = [] if exempt is None else exempt
+    assert int(np.abs(g["status"]).sum()) == 0
+    assert (g["it"] == iters).all()
+    worst = dict(sed=0.0, morph=0.0, mse=0.0)
+    for i in range(S):
+        np.testing.assert_array_equal(g["cen"][i], ref[i][3])
+        if flags:
+            assert ref[i][4] == iters, (i, ref[i][4])
+            np.testing.assert_array_equal(g["flags"][i], ref[i][5])
+        e = dict(sed=rel_err(g["sed"][i], ref[i][0]), morph=rel_err(g["morph"][i], ref[i][1]),
+                 mse=rel_err(g["mse"][i][:iters], ref[i][2]))
+        if max(e.values()) <= TOL:
+            for k in worst:
+                worst[k] = max(worst[k], e[k])
+            continue
+        ok, msg = straddle(i)
+        assert ok, "scene %d beyond 1e-5 (%s) and not a threshold straddle: %s" % (i, e, msg)
+        exempt.append((i, e, msg))
+    log_exemptions(test, exempt, max_exempt)
+    assert len(exempt) <= max_exempt, exempt
+    print("%d iterations x %d scenes: worst errors %s" % (iters, S, worst))
+    return worst
+
+
 def check_fixed_iterations(scarlet, wl, images, centers, pool, iters, max_exempt, test):
     """`iters` iterations at e_rel = 0 of every scene against the float32 oracle; returns the worst errors"""
     S = len(images)
@@ -161,22 +200,5 @@ def check_fixed_iterations(scarlet, wl, images, centers, pool, iters, max_exempt
     okw = wl.oracle_kwargs()
     ref = pool.map(oracle_fit, [(images[i], st0[0][i], st0[1][i], st0[2][i], st0[3][i], iters, 0.0, np.float32, okw)
                                 for i in range(S)])
-    assert int(np.abs(g["status"]).sum()) == 0
-    assert (g["it"] == iters).all()
-    exempt = []
-    worst = dict(sed=0.0, morph=0.0, mse=0.0)
-    for i in range(S):
-        np.testing.assert_array_equal(g["cen"][i], ref[i][3])
-        e = dict(sed=rel_err(g["sed"][i], ref[i][0]), morph=rel_err(g["morph"][i], ref[i][1]),
-                 mse=rel_err(g["mse"][i][:iters], ref[i][2]))
-        if max(e.values()) <= TOL:
-            for k in worst:
-                worst[k] = max(worst[k], e[k])
-            continue
-        ok, msg = straddles_threshold(scarlet, wl, images[i], centers[i], iters)
-        assert ok, "scene %d beyond 1e-5 (%s) and not a threshold straddle: %s" % (i, e, msg)
-        exempt.append((i, e, msg))
-    log_exemptions(test, exempt, max_exempt)
-    assert len(exempt) <= max_exempt, exempt
-    print("%d iterations x %d scenes: worst errors %s" % (iters, S, worst))
-    return worst
+    return compare_fixed_iterations(g, ref, iters, lambda i: straddles_threshold(scarlet, wl, images[i], centers[i], iters),
+                                    max_exempt, test)

@@ -384,6 +384,36 @@ def test_fit_synth_fixture(idx, tag, dt, tol):
     assert_array_equal(np.array([s.flags for s in scene.sources]), g[pre + "flags"])
 
 
+@pytest.mark.parametrize("name,s,tag,dt,tol", [("04_exact_persistent", 1, "f64", np.float64, 1e-9),
+                                               ("04_exact_persistent", 1, "f32", np.float32, 2e-5),
+                                               ("11_wave", 1, "f32", np.float32, 2e-5),
+                                               ("13_box_68", 0, "f32", np.float32, 2e-5)])
+def test_fit_edges_fixture(name, s, tag, dt, tol):
+    """Sources on the frame's borders (tests/edge_cases.py; oracle/gen_golden.py gen_fit_edges): a source in each corner
+    of a 64 x 64 frame and a 16 x 20 frame with trackers that move from one pixel inside onto rows / columns 2 and
+    H - 1 / W - 1, and the broad source in the corner of a 68 x 68 frame whose sweep runs to its last level: the
+    constructors, then the scene's iterations.  The tolerances of test_fit_synth_fixture."""
+    import edge_cases as ec
+    g = load_golden("fit_edges")
+    c = ec.CASES[name]
+    pre = "%s_s%d_%s_" % (name, s, tag)
+    images, pixels, peaks = ec.scene(c, s)
+    scene = pgm.make_extended_scene(images.astype(dt), pixels, np.ones(c.B) * ec.BG)
+    assert rel_err(np.array([x.morph for x in scene.sources]), g[pre + "init_morph"]) <= tol
+    assert rel_err(np.array([x.sed for x in scene.sources]), g[pre + "init_sed"]) <= tol
+    assert_array_equal(np.array([x.center for x in scene.sources]), g[pre + "init_center"])
+    assert_allclose(np.array([x.shift for x in scene.sources]), g[pre + "init_shift"], rtol=0, atol=1e-6)
+    scene = _restart(scene, g, pre)
+    pgm.fit(scene, ec.iterations(c), e_rel=0)
+    assert_array_equal(np.array([x.center for x in scene.sources]), g[pre + "center"])
+    assert rel_err(np.array(scene.mse), g[pre + "mse"]) <= tol
+    assert rel_err(np.array([x.sed for x in scene.sources]), g[pre + "sed"]) <= tol
+    assert rel_err(np.array([x.morph for x in scene.sources]), g[pre + "morph"]) <= tol
+    assert_array_equal(np.array([x.flags for x in scene.sources]), g[pre + "flags"])
+    # the reference itself ended on the limits
+    assert all(ec.on_limit(c, p, q) for p, q in zip(peaks, g[pre + "center"])), g[pre + "center"]
+
+
 def test_fit_synth_ragged_and_approx():
     g = load_golden("fit_synth")
     scn = synth.make_scene(0)
