@@ -382,7 +382,7 @@ int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior *p, int in
 /* scarlet_fit with priors whose inputs do not change between iterations (the quadratic form, constant given
  * gradients): gradients, prior step, constraint pipeline, convergence test per iteration, on the general
  * (unfused, one-pipeline) path; no host synchronisation other than the check_every one, no allocation.  Returns the
- * number of iterations launched.  The several-observation entry points do not take priors. */
+ * number of iterations launched.  Several observations with priors: scarlet_fit_observations_prior (below). */
 int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
                       int check_every, void *stream);
 
@@ -501,6 +501,19 @@ int64_t scarlet_lowres_large_workspace_bytes(const scarlet_batch *state, const s
 int scarlet_fit_observations_lowres_large(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
                                           const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
                                           int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+/* The joint fit with priors (Blend.fit calls backward_prior for every component however many observations the blend
+ * has, blend.py:87-96): scarlet_fit_observations_lowres_large (c given) or its form without per-component switches
+ * (c == NULL), with `lowres` NULL or an array of n_obs pointers as there, where every present component of an active
+ * scene steps as scarlet_prior describes, L being the scene's constant times n_obs.  No pass is added: the contraction
+ * that already reads the morphologies and holds their summed gradient reads the prior's planes where a component has
+ * them (k_obs_contract<KS, true>: a weight of 0, no given plane or a fixed morphology reads none), k_obs_head steps the
+ * SEDs with the prior's terms and writes p->L_comp, and the sparse_l0 / sparse_l1 cut uses each component's own step.
+ * `lipschitz` and `mse` hold no prior.  All gradient paths (K <= 8, <= 32, <= 256; exact and approximate L) are covered.
+ * p == NULL, a NULL L_comp or a target without its weight: SCARLET_E_ARG before any launch. */
+int scarlet_fit_observations_prior(scarlet_batch *state, const scarlet_constraints *c /* or NULL */, const scarlet_prior *p,
+                                   scarlet_batch *const *obs, const scarlet_lowres *const *lowres /* or NULL */,
+                                   const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
+                                   int check_every, void *stream);
 /* bytes of device scratch scarlet_lowres_render_large / _adjoint_large need for n planes: 0 where the LDS form runs;
  * < 0: an error code */
 int64_t scarlet_lowres_op_scratch_bytes(int n, int H, int W, const scarlet_lowres *lr);

@@ -160,6 +160,9 @@ _SIGNATURES = {
     "scarlet_lowres_large_workspace_bytes": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres)]),
     "scarlet_fit_observations_lowres_large": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(POINTER(ScarletBatch)),
                                                       POINTER(POINTER(ScarletLowres)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
+    "scarlet_fit_observations_prior": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletPrior),
+                                               POINTER(POINTER(ScarletBatch)), POINTER(POINTER(ScarletLowres)), _P, c_int, c_int,
+                                               c_double, c_int, c_int, _P]),
     "scarlet_lowres_op_scratch_bytes": (c_int64, [c_int, c_int, c_int, POINTER(ScarletLowres)]),
     "scarlet_lowres_render_large": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P, c_int64, _P]),
     "scarlet_lowres_adjoint_large": (c_int, [_P, c_int, c_int, c_int, POINTER(ScarletLowres), _P, _P, _P, _P, c_int64, _P]),

@@ -793,21 +793,19 @@ class BlendBatch(object):
     def fit(self, max_iter=200, e_rel=1e-2, approximate_L=False, check_every=10, prior=None):
         """Blend.fit for every scene (reference blend.py:65-102).  Scenes that reach e_rel
         stop iterating individually.  Returns the number of iterations launched.  A batch made by
-        `from_observations` fits all its observations jointly (scarlet_fit_observations_constrained; every other
-        batch runs scarlet_fit_constrained, with or without a prior).
+        `from_observations` fits all its observations jointly (scarlet_fit_observations_constrained, with a prior
+        scarlet_fit_observations_prior; every other batch runs scarlet_fit_constrained, with or without a prior).
 
         prior : None, or what scarlet_amd.prior describes -- a QuadraticPrior and / or constant given tensors (one
-            call of scarlet_fit_constrained with the prior's struct), a callable evaluated once per iteration on the
+            call into the library with the prior's struct), a callable evaluated once per iteration on the
             current stream (the host looks at `active` only every `check_every` iterations), or a list of these.
-            `L_components` then holds the constants each component stepped with.  Not available for a batch made by
-            `from_observations`."""
-        if prior is not None and self._observations is not None:
-            raise NotImplementedError("a batch of several observations does not take priors")
+            `L_components` then holds the constants each component stepped with.  Shapes are those of this batch: for
+            one made by `from_observations` the SEDs are (S, K, C) over the model frame's C channels."""
         self._ensure_mse_capacity(max_iter)
         self.active.fill_(1)          # a new fit() call iterates again, like the reference
         if self._init_checked:        # ... except the scenes whose init_sources input was bad
             self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
-        if self._observations is not None:
+        if self._observations is not None and prior is None:
             return self._fit_observations(max_iter, e_rel, approximate_L, check_every)
         if prior is not None:
             return self._fit_prior(prior, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every))
@@ -816,15 +814,14 @@ class BlendBatch(object):
     def step(self, e_rel=1e-2, approximate_L=False, prior=None):
         """One iteration in three separately callable phases (used by tests and by the
         Python-level update() override path).  A batch made by `from_observations` runs one iteration
-        of scarlet_fit_observations_constrained.  `prior`: as in `fit`."""
-        if prior is not None and self._observations is not None:
-            raise NotImplementedError("a batch of several observations does not take priors")
+        of scarlet_fit_observations_constrained (scarlet_fit_observations_prior with one).  `prior`: as in `fit`."""
         self._ensure_mse_capacity(1)
         if self._observations is not None:
             if self._init_checked:
                 self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
-            self._fit_observations(1, e_rel, approximate_L, 0)
-            return
+            if prior is None:
+                self._fit_observations(1, e_rel, approximate_L, 0)
+                return
         if prior is not None:
             quad, given, fns = _prior.split_priors(prior)
             self._prior_iteration(self._prior_struct(quad), given, fns, float(e_rel), int(bool(approximate_L)))
@@ -877,6 +874,9 @@ class BlendBatch(object):
             sed, morph = self.sed_current, self.morph_current          # gathered copies: the callables cannot touch the state
             dicts += [fn(sed, morph) for fn in fns]
         self._set_given(ps, dicts)
+        if self._observations is not None:                             # one iteration of the joint fit, no host look
+            self._fit_observations(1, e_rel, approximate_L, 0, ps)
+            return
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step_prior(ctypes.byref(self._c), ctypes.byref(ps), approximate_L, s))
         self._lib_update(ps, 1)
@@ -888,6 +888,8 @@ class BlendBatch(object):
         if not fns:
             # nothing changes between iterations: the library's own loop
             self._set_given(ps, given)
+            if self._observations is not None:
+                return self._fit_observations(max_iter, e_rel, approximate_L, check_every, ps)
             return self._lib_fit(ps, max_iter, e_rel, approximate_L, check_every)
         launched = 0
         for i in range(max_iter):
@@ -1002,18 +1004,24 @@ class BlendBatch(object):
         lr.workspace = keep["workspace"].data_ptr()
         return lr, keep
 
-    def _fit_observations(self, max_iter, e_rel, approximate_L, check_every):
+    def _fit_observations(self, max_iter, e_rel, approximate_L, check_every, ps=None):
         """The joint fit against `_observations` (scarlet_fit_observations_lowres_large when one of them is
-        low-resolution: the LDS-resident kernels where the model frame lets them, the streamed form beyond).  The
+        low-resolution: the LDS-resident kernels where the model frame lets them, the streamed form beyond;
+        scarlet_fit_observations_prior, which takes both kinds, with the prior's struct `ps`).  The
         library copies the pointer arrays into its argument structs before it launches anything."""
         n = len(self._observations)
         ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
         first = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
         band0 = first.ctypes.data_as(ctypes.c_void_p)
         tail = (n, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
+        lows = None
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+        if ps is not None:
+            return _lib.check(_lib.lib.scarlet_fit_observations_prior(
+                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(ps), ptrs, lows, band0, *tail))
+        if lows is not None:
             return _lib.check(_lib.lib.scarlet_fit_observations_lowres_large(
                 ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, lows, band0, *tail))
         return _lib.check(_lib.lib.scarlet_fit_observations_constrained(

@@ -22,6 +22,7 @@
 #pragma once
 #include "common.h"
 #include "engine.h"
+#include "prior_ops.h"
 
 #define SC_MAX_OBS 8
 #define SC_OBS_J 4                // pixels per thread per sweep of the contraction (SC_BLOCK * SC_OBS_J per sweep)
@@ -49,6 +50,7 @@ struct ObsArgs {
     const int *it;
     int head_lsed;                    // 1: K <= 8 with exact constants: k_obs_head finds lambda_max of the Gram partials
     ObsView obs[SC_MAX_OBS];
+    scarlet_prior p;                  // read by the PRIOR instances only (scarlet_fit_observations_prior)
 };
 
 // the band slice sed[cur][s][k][band0 .. band0 + B - 1] -> out[s][k][0 .. B - 1] (the SEDs an observation's PSF chain reads)
@@ -70,7 +72,31 @@ __host__ __device__ inline size_t obs_contract_lds(int K) { return (size_t)K * S
 // twice by the same thread (the second time from cache).  KS = SC_KMAX: K <= 8, the morphologies of a pixel stay in
 // registers and the pass also sums the morphology Gram (engine.h layout, slots 1 + K C ..) -- no Gram pass for small K;
 // KS = 0: any K.
-template <int KS>
+// PRIOR (a pass that writes the step; never OBS_PARTIALS): component k steps with 1 / prior_L(L_morph n_obs, ...) and
+// its d loss / d m_k goes through prior_elem first -- the given gradient plane plus w (m - target) (prior_term: rounded
+// operation by operation), read here, in the pass that holds m and the gradient, once each and only where the component
+// has them (prior.h's rules).  The component's scalars are read at the top of its turn, under the loads of m.  The
+// prior's planes are read beside m where the registers allow it (KS = 0: all loads of a component's sweep in flight
+// together); the register-tiled instance, which holds the Gram sums as well, reads them after the sums of the sweep, all
+// SC_OBS_J loads before the first store, and so stays within 128 VGPRs (4 waves per SIMD, as without a prior).
+// m, dm, given, target: the SC_OBS_J pixels of this thread, in registers.
+template <bool GIVEN, bool QUAD>
+__device__ __forceinline__ void obs_prior_store(float *mout, const float *m, const float *dm, const float *given,
+                                                const float *target, float w, float step, int p0, int p_end)
+{
+#pragma unroll
+    for (int j = 0; j < SC_OBS_J; ++j) {
+        const int p = p0 + j * SC_BLOCK + threadIdx.x;
+        if (p >= p_end) continue;
+        if (GIVEN || QUAD) {
+            const float t = prior_term<GIVEN, QUAD>(m[j], given[j], target[j], w);
+            mout[p] = prior_elem<true, false>(m[j], dm[j], t, 0.f, 0.f, step);
+        } else
+            mout[p] = prior_elem<false, false>(m[j], dm[j], 0.f, 0.f, 0.f, step);
+    }
+}
+
+template <int KS, bool PRIOR>
 __global__ __launch_bounds__(SC_BLOCK) void k_obs_contract(ObsArgs a)
 {
     const int s = blockIdx.y, tile = blockIdx.x;
@@ -89,11 +115,13 @@ __global__ __launch_bounds__(SC_BLOCK) void k_obs_contract(ObsArgs a)
     __syncthreads();
     const int mode = a.mode;
     const float step_morph = mode == OBS_PARTIALS ? 0.f : 1.0f / (float)(a.lipschitz[2 * s + 1] * (double)a.n_obs);
+    const double L_morph = PRIOR ? a.lipschitz[2 * s + 1] * (double)a.n_obs : 0.0;    // (the scene's, before the prior's)
     const float *mor = a.morph[c0] + (size_t)s * K * HW;
     float *mout = a.morph[1 - c0] + (size_t)s * K * HW;
     const int lane = threadIdx.x & (SC_WAVE - 1), wid = threadIdx.x / SC_WAVE;
     double loss = 0;
     constexpr int NG = KS * (KS + 1) / 2 > 0 ? KS * (KS + 1) / 2 : 1;
+    constexpr bool EARLY = PRIOR && KS == 0;                         // the prior's planes are loaded beside m
     float gram[NG];
 #pragma unroll
     for (int i = 0; i < NG; ++i) gram[i] = 0.f;
@@ -152,6 +180,18 @@ __global__ __launch_bounds__(SC_BLOCK) void k_obs_contract(ObsArgs a)
         for (int k = 0; k < n; ++k) {
             const bool fixm = a.fix_morph && a.fix_morph[(size_t)s * K + k];
             float acc[SC_BMAX];
+            float mj[PRIOR ? SC_OBS_J : 1], dmj[PRIOR ? SC_OBS_J : 1], gvj[PRIOR ? SC_OBS_J : 1], tgj[PRIOR ? SC_OBS_J : 1];
+            // PRIOR: the component's own constant and the streams of its prior -- scalars of (scene, k), chosen outside
+            // the pixel loop; a fixed morphology, a weight of 0 or a missing plane reads none of the streams
+            float w = 0.f, step = step_morph;
+            const float *gg = nullptr, *tt = nullptr;
+            if (PRIOR) {
+                const size_t cc = (size_t)s * K + k;
+                w = (!fixm && a.p.quad_morph_weight) ? a.p.quad_morph_weight[cc] : 0.f;
+                step = 1.0f / (float)prior_L(L_morph, a.p.L_morph, a.p.quad_morph_weight, cc, fixm);
+                if (!fixm && a.p.grad_morph) gg = a.p.grad_morph + cc * HW;
+                if (w != 0.f && a.p.quad_morph_target) tt = a.p.quad_morph_target + cc * HW;
+            }
 #pragma unroll
             for (int c = 0; c < SC_BMAX; ++c) acc[c] = 0.f;
 #pragma unroll
@@ -159,11 +199,36 @@ __global__ __launch_bounds__(SC_BLOCK) void k_obs_contract(ObsArgs a)
                 const int p = p0 + j * SC_BLOCK + threadIdx.x;
                 if (p >= p_end) continue;
                 const float m = mor[(size_t)k * HW + p];
+                if (EARLY) { gvj[j] = gg ? gg[p] : 0.f; tgj[j] = tt ? tt[p] : 0.f; }
                 float dm = 0.f;
 #pragma unroll
                 for (int c = 0; c < SC_BMAX; ++c)
                     if (c < C) { dm += sed_s[k * SC_BMAX + c] * gs[j][c]; acc[c] += m * gs[j][c]; }
-                if (mode != OBS_PARTIALS) mout[(size_t)k * HW + p] = fixm ? m : m - step_morph * dm;
+                if (PRIOR) { mj[j] = m; dmj[j] = dm; }
+                else if (mode != OBS_PARTIALS) mout[(size_t)k * HW + p] = fixm ? m : m - step_morph * dm;
+            }
+            if (PRIOR) {
+                float *mo = mout + (size_t)k * HW;
+                const bool quad = w != 0.f, given = gg != nullptr;
+                if (!EARLY) {
+#pragma unroll
+                    for (int j = 0; j < SC_OBS_J; ++j) {
+                        const int p = p0 + j * SC_BLOCK + threadIdx.x;
+                        gvj[j] = (gg && p < p_end) ? gg[p] : 0.f;
+                        tgj[j] = (tt && p < p_end) ? tt[p] : 0.f;
+                    }
+                }
+                if (fixm) {
+#pragma unroll
+                    for (int j = 0; j < SC_OBS_J; ++j) {
+                        const int p = p0 + j * SC_BLOCK + threadIdx.x;
+                        if (p < p_end) mo[p] = mj[j];
+                    }
+                }
+                else if (given && quad) obs_prior_store<true, true>(mo, mj, dmj, gvj, tgj, w, step, p0, p_end);
+                else if (given) obs_prior_store<true, false>(mo, mj, dmj, gvj, tgj, w, step, p0, p_end);
+                else if (quad) obs_prior_store<false, true>(mo, mj, dmj, gvj, tgj, w, step, p0, p_end);
+                else obs_prior_store<false, false>(mo, mj, dmj, gvj, tgj, w, step, p0, p_end);
             }
             if (mode != OBS_STEP) {
 #pragma unroll
@@ -220,12 +285,16 @@ __global__ __launch_bounds__(SC_BLOCK) void k_obs_contract(ObsArgs a)
 }
 
 // per scene: the loss record, both Lipschitz constants times n_obs (blend.py:219-220), the SED step (blend.py:91-93)
+// PRIOR: every component's SED steps with its own constant and the prior's SED terms (k_prior_step's order), and
+// L_comp[s][k] = {L_sed,k, L_morph,k} is written for the present components; `lipschitz` and `mse` hold no prior.
+template <bool PRIOR>
 __global__ __launch_bounds__(SC_BLOCK) void k_obs_head(ObsArgs a)
 {
     const int s = blockIdx.x;
     if (!a.active[s]) return;
     const int K = a.K, C = a.C, P = n_partials(K, C), n = scene_ncomp(a.ncomp, s, K);
     __shared__ float step_s;
+    __shared__ double L_s[2];                                          // PRIOR: the scene's constants x n_obs
     __shared__ double Gm[SC_KMAX * SC_KMAX], eig[2][64], lsed;
     if (a.head_lsed) {
         // K <= 8, exact constants: lambda_max of the morphology Gram summed over the tiles (blend.py:205-218)
@@ -255,7 +324,12 @@ __global__ __launch_bounds__(SC_BLOCK) void k_obs_head(ObsArgs a)
         if (it_new <= a.mse_capacity) a.mse[(size_t)s * a.mse_capacity + it_new - 1] = loss;
         const double Ls = (a.head_lsed ? lsed : a.lipschitz[2 * s]) * (double)a.n_obs;
         a.lipschitz[2 * s] = Ls;
-        a.lipschitz[2 * s + 1] *= (double)a.n_obs;
+        if (PRIOR) {
+            const double Lm = a.lipschitz[2 * s + 1] * (double)a.n_obs;
+            a.lipschitz[2 * s + 1] = Lm;
+            L_s[0] = Ls; L_s[1] = Lm;
+        } else
+            a.lipschitz[2 * s + 1] *= (double)a.n_obs;
         step_s = 1.0f / (float)Ls;
     }
     __syncthreads();
@@ -266,8 +340,23 @@ __global__ __launch_bounds__(SC_BLOCK) void k_obs_head(ObsArgs a)
         for (int t = 0; t < a.T; ++t) g += a.partials[((size_t)s * a.T + t) * P + 1 + i];
         const float x = a.sed[c0][(size_t)s * K * C + i];
         const bool fixed = a.fix_sed && a.fix_sed[(size_t)s * K + i / C];
-        a.sed[1 - c0][(size_t)s * K * C + i] = fixed ? x : x - step_sed * (float)g;
+        if (PRIOR) {
+            // a fixed factor takes neither the step nor the prior's constant
+            const size_t cc = (size_t)s * K + i / C, e = (size_t)s * K * C + i;
+            const float step = 1.0f / (float)prior_L(L_s[0], a.p.L_sed, a.p.quad_sed_weight, cc, false);
+            bool has;
+            const float t = prior_sed_term(a.p, x, cc, e, &has);
+            const float gp = has ? (float)g + t : (float)g;
+            a.sed[1 - c0][e] = fixed ? x : x - step * gp;
+        } else
+            a.sed[1 - c0][(size_t)s * K * C + i] = fixed ? x : x - step_sed * (float)g;
     }
+    if (PRIOR)
+        for (int k = threadIdx.x; k < n; k += SC_BLOCK) {
+            const size_t cc = (size_t)s * K + k;
+            a.p.L_comp[2 * cc] = prior_L(L_s[0], a.p.L_sed, a.p.quad_sed_weight, cc, a.fix_sed && a.fix_sed[cc]);
+            a.p.L_comp[2 * cc + 1] = prior_L(L_s[1], a.p.L_morph, a.p.quad_morph_weight, cc, a.fix_morph && a.fix_morph[cc]);
+        }
 }
 
 // CombinedExtendedSource's SED (source.py:183-240 via get_psf_sed, source.py:41-71) for one observation: the pixel

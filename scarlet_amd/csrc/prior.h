@@ -18,6 +18,7 @@
 // component without a target, a weight of zero or a fixed morphology does not read the streams it does not need.
 #pragma once
 #include "common.h"
+#include "prior_ops.h"
 
 #define SC_PRIOR_GROUPS 4                                       // float4 groups per lane and stream
 #define SC_PRIOR_PIX (SC_BLOCK * 4 * SC_PRIOR_GROUPS)           // pixels per workgroup (one 64 x 64 plane)
@@ -33,26 +34,7 @@ struct PriorArgs {
     scarlet_prior p;
 };
 
-// The constant a factor steps with.  A fixed factor takes neither the step nor the prior's L (component.py:182-187);
-// without a prior the scene's constant goes through unrounded, so that L_comp then equals `lipschitz`.
-__device__ __forceinline__ double prior_L(double L, const float *given, const float *quad, size_t c, bool fixed)
-{
-    if (fixed) return L;
-    const float Lp = (given ? given[c] : 0.f) + (quad ? quad[c] : 0.f);
-    return Lp != 0.f ? (double)((float)L + Lp) : L;
-}
-
-// One element.  The prior's gradient is rounded operation by operation (no contraction), so that a caller who hands
-// the same w (x - target) in as a given gradient gets the same bits; the step itself is k_step's expression.
-template <bool GIVEN, bool QUAD>
-__device__ __forceinline__ float prior_elem(float x, float g, float given, float target, float w, float step)
-{
-    if (GIVEN && QUAD) g = __fadd_rn(g, __fadd_rn(given, __fmul_rn(w, __fsub_rn(x, target))));
-    else if (GIVEN) g = __fadd_rn(g, given);
-    else if (QUAD) g = __fadd_rn(g, __fmul_rn(w, __fsub_rn(x, target)));
-    return x - step * g;
-}
-
+// (prior_L, the constant a factor steps with, and prior_elem, one element's step: prior_ops.h)
 template <bool GIVEN, bool QUAD>
 __device__ __forceinline__ void prior_plane_vec(const float *x, float *g, const float *given, const float *target, float w,
                                                 float step, int q0, int nq)

@@ -2384,11 +2384,12 @@ static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const Grad
 }
 
 // Several observations: one pipeline, every iteration the observation step (the observations' G planes, the contraction
-// over them, L x n_obs, the step) and the tail
+// over them, L x n_obs, the step) and the tail.  `p` NULL: no prior; given: the passes that write a step are the PRIOR
+// instances (multiobs.h), which read the prior in the pass that already holds the factors and their gradients
 static int fit_observations_call(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
                                  const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
                                  int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr,
-                                 bool large = false)
+                                 bool large = false, const scarlet_prior *p = nullptr)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
@@ -2404,6 +2405,7 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
     m.fix_sed = state->fix_sed; m.fix_morph = state->fix_morph;
     m.partials = ws_at<double>(state, l.partials);
     m.lipschitz = state->lipschitz; m.mse = state->mse; m.mse_capacity = state->mse_capacity; m.it = state->it;
+    if (p) m.p = *p;
     for (int o = 0; o < n_obs; ++o) {
         const scarlet_batch *ob = obs[o];
         lo[o] = ws_layout(ob, WS_FIX);
@@ -2446,12 +2448,16 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
     const GradArgs ga = grad_args(state, l, approximate_L, 0);
     // K <= 8: the contraction also sums the Gram matrix (no Gram pass); its lambda_max is found in k_obs_head
     const bool small = state->K <= SC_KMAX && l.grad == GRAD_SMALL;
-    auto contract = small ? k_obs_contract<SC_KMAX> : k_obs_contract<0>;
+    auto contract = small ? k_obs_contract<SC_KMAX, false> : k_obs_contract<0, false>;
+    // the pass that writes the step (OBS_FULL / OBS_STEP); OBS_PARTIALS writes none and stays the plain instance
+    auto contract_step = !p ? contract : small ? k_obs_contract<SC_KMAX, true> : k_obs_contract<0, true>;
+    auto head = p ? k_obs_head<true> : k_obs_head<false>;
     m.head_lsed = small && !approximate_L;
     const size_t lds = obs_contract_lds(state->K);
-    if ((rc = allow_lds(contract, lds))) return rc;
+    if ((rc = allow_lds(contract, lds)) || (rc = allow_lds(contract_step, lds))) return rc;
     const dim3 grid(m.T, m.S);
-    const UpdateOpts uo = {nullptr, cons, 0};
+    // with a prior the sparse_l0 / sparse_l1 cut uses each component's own step (update.py:71-82)
+    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0};
     return fit_loop(state, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
         prof_start(0, st);
         for (int o = 0; o < n_obs; ++o) {
@@ -2472,7 +2478,7 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         if (!approximate_L) {
             hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
             m.mode = OBS_FULL;
-            hipLaunchKernelGGL(contract, grid, dim3(SC_BLOCK), lds, st, m);
+            hipLaunchKernelGGL(contract_step, grid, dim3(SC_BLOCK), lds, st, m);
             if (!small && (rc = obs_lipschitz_sed(state, l, ga, 0, st))) return rc;
         } else {
             m.mode = OBS_PARTIALS;
@@ -2481,9 +2487,9 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
             if (small) hipLaunchKernelGGL(k_bigk_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, 1);   // (trace of the pass's Gram)
             else if ((rc = obs_lipschitz_sed(state, l, ga, 1, st))) return rc;
             m.mode = OBS_STEP;
-            hipLaunchKernelGGL(contract, grid, dim3(SC_BLOCK), lds, st, m);
+            hipLaunchKernelGGL(contract_step, grid, dim3(SC_BLOCK), lds, st, m);
         }
-        hipLaunchKernelGGL(k_obs_head, dim3(m.S), dim3(SC_BLOCK), 0, st, m);
+        hipLaunchKernelGGL(head, dim3(m.S), dim3(SC_BLOCK), 0, st, m);
         HIP_TRY(hipGetLastError());
         prof_stop(st);
         return iteration_tail(state, l, e_rel, stream, uo);
@@ -2555,6 +2561,17 @@ extern "C" int scarlet_fit_observations_lowres_large(scarlet_batch *state, const
     if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
     const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter, lowres, true);
     return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, lowres, true);
+}
+
+extern "C" int scarlet_fit_observations_prior(scarlet_batch *state, const scarlet_constraints *c, const scarlet_prior *p,
+                                              scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                              const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                              int approximate_L, int check_every, void *stream)
+{
+    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, lowres, true);
+    if (!rc) rc = check_prior(p);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
+                                           lowres, true, p);
 }
 
 // scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused

@@ -4,7 +4,8 @@ A prior adds a gradient and a Lipschitz constant to the step of ONE component.  
 `BlendBatch.step(prior=...)` take
 
   - a `QuadraticPrior`: w/2 |x - target|^2 per component and factor, evaluated by the library (gradient w (x - target),
-    constant w) -- the whole fit is one call of scarlet_fit_constrained;
+    constant w) -- the whole fit is one call of scarlet_fit_constrained (scarlet_fit_observations_prior for a batch made
+    by `from_observations`, whose SEDs are (S, K, C) over the model frame's channels);
   - a dict of given device tensors, any subset of `GIVEN_KEYS`: constant gradients (a linear prior) and constants;
   - a callable `fn(sed, morph) -> dict` of the same keys, called once per iteration with the current factors
     ((S, K, B) and (S, K, H, W) device tensors) on the current stream;
