@@ -55,6 +55,9 @@ extern "C" {
 #define SCARLET_MAX_COMPONENTS 256
 /* most observations of scarlet_fit_observations / scarlet_fit_multi */
 #define SCARLET_MAX_OBSERVATIONS 8
+/* most channels of the model frame of a joint fit (scarlet_fit_observations_wide); one observation, and a batch fitted
+   on its own, has at most 8 bands */
+#define SCARLET_MAX_CHANNELS 32
 
 /* BlendFlag bits -- scarlet/component.py:13-36 */
 #define SCARLET_FLAG_SED_NOT_CONVERGED   1
@@ -514,6 +517,32 @@ int scarlet_fit_observations_prior(scarlet_batch *state, const scarlet_constrain
                                    scarlet_batch *const *obs, const scarlet_lowres *const *lowres /* or NULL */,
                                    const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
                                    int check_every, void *stream);
+/* The joint fit over a model frame of up to SCARLET_MAX_CHANNELS channels: surveys whose bands do not coincide (LSST
+ * ugrizy + Euclid VIS/Y/J/H = 10 channels, with Roman's 7 filters 17) exceed the 8 channels of the entry points above.
+ * The arguments are those of scarlet_fit_observations_prior, with c, p and lowres each allowed to be NULL.
+ *   - state->B <= SCARLET_MAX_CHANNELS; every obs[o]->B <= 8 as before (an instrument with more bands of its own is
+ *     split into two observations on the same grid); band0[o] + obs[o]->B <= state->B.  More channels:
+ *     SCARLET_E_NOTIMPL.  A single-observation batch keeps B <= 8.
+ *   - state->B <= 8: exactly the kernels of scarlet_fit_observations_prior (or _lowres_large / _constrained without a
+ *     prior), the same bits.
+ *   - state->B > 8: the observations' own chains are unchanged (they take the channel count as a stride); the
+ *     contraction over the observations is k_obs_contract_wide (multiobs_wide.h), lambda_max of the SED Gram
+ *     (n = min(K, C) <= 32) is k_wide_lmorph, and the morphology Gram comes from the Gram passes for every K.  No atomics:
+ *     the loss and d loss / d sed partials are float64 sums in a fixed order, a repeated fit gives the same bits.
+ *   - scarlet_batch_workspace_bytes() sizes the state's workspace for any B.  The helpers that check the state's shape
+ *     have wide siblings below: the same functions with the state's channel limit at SCARLET_MAX_CHANNELS. */
+int scarlet_fit_observations_wide(scarlet_batch *state, const scarlet_constraints *c /* or NULL */,
+                                  const scarlet_prior *p /* or NULL */, scarlet_batch *const *obs,
+                                  const scarlet_lowres *const *lowres /* or NULL */, const int32_t *band0, int n_obs,
+                                  int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+int scarlet_init_combined_sed_wide(scarlet_batch *state, const float *images, int B, int band0, const float *obs_psf_peak,
+                                   int peak_per_scene, const float *model_psf_max, void *stream);
+int64_t scarlet_lowres_large_workspace_bytes_wide(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr);
+/* diagnostics, host-only: the form of the contraction a joint fit of K components over C model channels takes
+ * (launch_plan.h contract_plan): {kernel: 1 = k_obs_contract<8>, 2 = k_obs_contract<0>, 3 = k_obs_contract_wide;
+ * channels the instance is built for; waves; threads per workgroup; dynamic LDS bytes; the LDS limit of the plans;
+ * prior; 0}.  Returns 0, or -1 where there is no form (C > SCARLET_MAX_CHANNELS, K > SCARLET_MAX_COMPONENTS). */
+int scarlet_debug_contract_plan(int K, int C, int prior, int32_t *out8);
 /* bytes of device scratch scarlet_lowres_render_large / _adjoint_large need for n planes: 0 where the LDS form runs;
  * < 0: an error code */
 int64_t scarlet_lowres_op_scratch_bytes(int n, int H, int W, const scarlet_lowres *lr);
@@ -607,6 +636,17 @@ int scarlet_observations_products_lowres(const scarlet_batch *state, scarlet_bat
  * that is NULL or empty), otherwise a function of the shapes alone; < 0: an error code */
 int64_t scarlet_lowres_products_scratch_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr,
                                               const scarlet_products *out);
+/* scarlet_observations_products_lowres for a state of up to SCARLET_MAX_CHANNELS channels (`lowres` may be NULL).  The
+ * state's model [S][C][H][W] and flux partials come from k_products in chunks of 8 channels, flux [S][K][C] and
+ * component_models [S][n_select][C][H][W] from the kernels that take any channel count; flux stays a float64 sum in a
+ * fixed order.  An observation keeps B <= 8.  The scratch sizes come from the _wide functions. */
+int scarlet_observations_products_wide(const scarlet_batch *state, scarlet_batch *const *obs,
+                                       const scarlet_lowres *const *lowres /* or NULL */, const int32_t *band0, int n_obs,
+                                       const scarlet_products *state_out, const scarlet_products *out, void *scratch,
+                                       int64_t scratch_bytes, void *stream);
+int64_t scarlet_products_scratch_bytes_wide(const scarlet_batch *state, const scarlet_products *out);
+int64_t scarlet_lowres_products_scratch_bytes_wide(const scarlet_batch *state, const scarlet_batch *obs,
+                                                   const scarlet_lowres *lr, const scarlet_products *out);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

@@ -45,6 +45,7 @@ SYM_FULL_WINDOW = 16
 NORM_SED, NORM_MORPH, NORM_MORPH_MAX = 0, 1, 2
 MAX_SIDE, MAX_COMPONENTS = 1024, 256       # SCARLET_MAX_SIDE, SCARLET_MAX_COMPONENTS
 MAX_OBSERVATIONS = 8                       # SCARLET_MAX_OBSERVATIONS
+MAX_CHANNELS = 32                          # SCARLET_MAX_CHANNELS (from_observations(..., wide=True))
 
 
 class ScarletBatch(Structure):
@@ -175,6 +176,18 @@ _SIGNATURES = {
                                                      POINTER(ScarletProducts), _P, c_int64, _P]),
     "scarlet_lowres_products_scratch_bytes": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres),
                                                         POINTER(ScarletProducts)]),
+    "scarlet_fit_observations_wide": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletPrior),
+                                              POINTER(POINTER(ScarletBatch)), POINTER(POINTER(ScarletLowres)), _P, c_int, c_int,
+                                              c_double, c_int, c_int, _P]),
+    "scarlet_init_combined_sed_wide": (c_int, [POINTER(ScarletBatch), _P, c_int, c_int, _P, c_int, _P, _P]),
+    "scarlet_lowres_large_workspace_bytes_wide": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres)]),
+    "scarlet_observations_products_wide": (c_int, [POINTER(ScarletBatch), POINTER(POINTER(ScarletBatch)),
+                                                   POINTER(POINTER(ScarletLowres)), _P, c_int, POINTER(ScarletProducts),
+                                                   POINTER(ScarletProducts), _P, c_int64, _P]),
+    "scarlet_products_scratch_bytes_wide": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletProducts)]),
+    "scarlet_lowres_products_scratch_bytes_wide": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres),
+                                                             POINTER(ScarletProducts)]),
+    "scarlet_debug_contract_plan": (c_int, [c_int, c_int, c_int, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

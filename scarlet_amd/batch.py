@@ -365,6 +365,7 @@ class BlendBatch(object):
         self._observations = None     # from_observations: [(ObservationBatch, its gradient batch)]
         self._lowres = None           # ... and per observation None, or (scarlet_lowres, what it points to)
         self._lowres_products = False  # from_observations(lowres_products=True): `products` evaluates those too
+        self._wide = False            # from_observations(wide=True): the library's _wide entry points (C <= 32)
         self.L_components = None      # (S, K, 2) float64 after a fit with a prior: the constants each component stepped with
         self._c = _lib.ScarletBatch()
         self._fill_struct()
@@ -607,13 +608,16 @@ class BlendBatch(object):
                 setattr(outs[i], name, _lib.ptr(new[i]))
             setattr(res, name, new if want else None)
         any_state = model or flux or sel is not None
-        nbytes = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._c), ctypes.byref(ps)) if any_state else 0
+        state_bytes = _lib.lib.scarlet_products_scratch_bytes_wide if self._wide else _lib.lib.scarlet_products_scratch_bytes
+        lowres_bytes = (_lib.lib.scarlet_lowres_products_scratch_bytes_wide if self._wide
+                        else _lib.lib.scarlet_lowres_products_scratch_bytes)
+        nbytes = state_bytes(ctypes.byref(self._c), ctypes.byref(ps)) if any_state else 0
         for i in idx:
             ob = self._observations[i][1]
             if self._lowres[i] is None:
                 need = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(ob._c), ctypes.byref(outs[i]))
             else:
-                need = _lib.check(_lib.lib.scarlet_lowres_products_scratch_bytes(
+                need = _lib.check(lowres_bytes(
                     ctypes.byref(self._c), ctypes.byref(ob._c), ctypes.byref(self._lowres[i][0]), ctypes.byref(outs[i])))
             nbytes = max(nbytes, need)
         scratch = self._products_scratch(nbytes)
@@ -621,9 +625,13 @@ class BlendBatch(object):
         first = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
         tail = (first.ctypes.data_as(ctypes.c_void_p), n, ctypes.byref(ps) if any_state else None, outs, _lib.ptr(scratch),
                 int(nbytes), _lib.stream_ptr())
+        lows = None
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+        if self._wide:
+            _lib.check(_lib.lib.scarlet_observations_products_wide(ctypes.byref(self._c), ptrs, lows, *tail))
+        elif lows is not None:
             _lib.check(_lib.lib.scarlet_observations_products_lowres(ctypes.byref(self._c), ptrs, lows, *tail))
         else:
             _lib.check(_lib.lib.scarlet_observations_products(ctypes.byref(self._c), ptrs, *tail))
@@ -901,11 +909,17 @@ class BlendBatch(object):
 
     # ------------------------------------------------------------------ several observations
     @classmethod
-    def from_observations(cls, observations, centers, _host_gradients=False, _channels=None, lowres_products=False, **kwargs):
+    def from_observations(cls, observations, centers, _host_gradients=False, _channels=None, lowres_products=False, wide=False,
+                          **kwargs):
         """A batch fitted jointly against several observations of every scene (reference Blend(sources, [obs_a,
         obs_b]), blend.py:24-43, 120-139, 219-220).  The factors span the model frame's C = max(band0 + B) channels
-        (C <= 8); `centers` and the other keyword arguments are those of BlendBatch (ragged centre lists give
-        n_components).  Start the sources with `init_combined` (or `set_state`), then `fit` / `step`.
+        (C <= 8, with `wide=True` C <= 32); `centers` and the other keyword arguments are those of BlendBatch (ragged
+        centre lists give n_components).  Start the sources with `init_combined` (or `set_state`), then `fit` / `step`.
+
+        wide : the model frame may span up to 32 channels (scarlet_fit_observations_wide and its siblings): instruments
+            whose bands do not coincide, each still with at most 8 bands of its own.  SEDs, `flux` and `model` then
+            have C channels.  With C <= 8 the batch is the one made without the keyword, bit for bit; without the
+            keyword nothing changes, the ValueError above 8 channels included.
 
         lowres_products : `products`, `render`, `residual` and `get_loss` also evaluate the low-resolution observations
             (on their own pixel grids).  Off by default: a batch made without it raises NotImplementedError for those,
@@ -938,12 +952,20 @@ class BlendBatch(object):
                 raise ValueError("from_observations: the observations span %d model channels, the model frame has %d"
                                  % (C, _channels))
             C = int(_channels)
-        if C > 8:
+        for i, o in enumerate(obs):
+            if wide and o.B > 8:
+                raise ValueError("from_observations: observation %d has %d bands, an observation has at most 8 (split it "
+                                 "into two observations on the same grid)" % (i, o.B))
+        if wide and C > _lib.MAX_CHANNELS:
+            raise ValueError("from_observations: the observations span %d model channels, at most %d are supported"
+                             % (C, _lib.MAX_CHANNELS))
+        if C > 8 and not wide:
             raise ValueError("from_observations: the observations span %d model channels, at most 8 are supported" % C)
         for k in ("weights", "images"):
             if k in kwargs:
                 raise ValueError("from_observations: %s belong to the observations" % k)
         state = cls(None, centers, _frame=(S, C, H, W), **kwargs)
+        state._wide = bool(wide)
         torch, f32 = state.torch, dict(dtype=state.torch.float32, device=state.device)
         if _host_gradients:
             state.images = torch.zeros((S, C, H, W), **f32)
@@ -999,7 +1021,8 @@ class BlendBatch(object):
         """(scarlet_lowres with its workspace, what it points to) of the low-resolution observation `o` with gradient
         batch `ob`, sized for this state batch"""
         lr, keep = o.lowres_struct(self.device)
-        nbytes = _lib.check(_lib.lib.scarlet_lowres_large_workspace_bytes(ctypes.byref(self._c), ctypes.byref(ob._c), ctypes.byref(lr)))
+        sizer = _lib.lib.scarlet_lowres_large_workspace_bytes_wide if self._wide else _lib.lib.scarlet_lowres_large_workspace_bytes
+        nbytes = _lib.check(sizer(ctypes.byref(self._c), ctypes.byref(ob._c), ctypes.byref(lr)))
         keep["workspace"] = self.torch.empty((int(nbytes),), dtype=self.torch.uint8, device=self.device)
         lr.workspace = keep["workspace"].data_ptr()
         return lr, keep
@@ -1018,6 +1041,9 @@ class BlendBatch(object):
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+        if self._wide:
+            return _lib.check(_lib.lib.scarlet_fit_observations_wide(
+                ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), ptrs, lows, band0, *tail))
         if ps is not None:
             return _lib.check(_lib.lib.scarlet_fit_observations_prior(
                 ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(ps), ptrs, lows, band0, *tail))
@@ -1105,7 +1131,8 @@ class BlendBatch(object):
             if isinstance(o, LowResObservationBatch):
                 self._init_lowres_sed(o, ob, p, mmax)
                 continue
-            _lib.check(_lib.lib.scarlet_init_combined_sed(
+            combined_sed = _lib.lib.scarlet_init_combined_sed_wide if self._wide else _lib.lib.scarlet_init_combined_sed
+            _lib.check(combined_sed(
                 ctypes.byref(self._c), ob.images.data_ptr(), int(o.B), int(o.band0), None if p is None else p.data_ptr(),
                 int(p is not None and p.ndim == 2), None if mmax is None else mmax.data_ptr(), _lib.stream_ptr()))
         self._init_checked = True

@@ -409,8 +409,10 @@ __global__ __launch_bounds__(SC_BLOCK) void k_bigk_lipschitz(GradArgs a, int sed
     const int tid = threadIdx.x, lane = tid & 63;
     const bool w0 = tid < SC_WAVE;                      // the scalar parts run on the first wave, as before
     const int c0 = a.cur[s];
-    for (int i = tid; i < K * B; i += SC_BLOCK)
-        sed_s[(i / B) * SC_BMAX + (i % B)] = a.sed[c0][(size_t)s * K * B + i];
+    // (the SEDs serve L_morph alone: with `sed_only` they are not staged -- a wide state's B exceeds the rows of sed_s)
+    if (!sed_only)
+        for (int i = tid; i < K * B; i += SC_BLOCK)
+            sed_s[(i / B) * SC_BMAX + (i % B)] = a.sed[c0][(size_t)s * K * B + i];
     const int n = scene_ncomp(a.ncomp, s, K);            // (absent components: zero rows and columns, not summed)
     for (int i = tid; i < SC_KBIG * SC_KBIG; i += SC_BLOCK) {
         const int k = i / SC_KBIG, k2 = i - k * SC_KBIG;
@@ -432,8 +434,10 @@ __global__ __launch_bounds__(SC_BLOCK) void k_bigk_lipschitz(GradArgs a, int sed
     double L_sed = 0, L_morph = 0;
     if (a.approximate_L) {
         double LS = 0;
-        for (int i = tid; i < K * B; i += SC_BLOCK) { const float v = sed_s[(i / B) * SC_BMAX + (i % B)]; LS += (double)v * v; }
-        LS = block_sum(LS, red);
+        if (!sed_only) {
+            for (int i = tid; i < K * B; i += SC_BLOCK) { const float v = sed_s[(i / B) * SC_BMAX + (i % B)]; LS += (double)v * v; }
+            LS = block_sum(LS, red);
+        }
         double LA = trace;
         if (it_new > 1 && loss > a.mse[(size_t)s * a.mse_capacity + it_new - 2]) { LA *= 2; LS *= 2; }
         L_sed = LA; L_morph = LS;          // (loss is valid on the first wave, which is the one that writes)

@@ -9,6 +9,7 @@
 #include "initsrc.h"
 #include "lowres_stream.h"
 #include "products.h"
+#include "multiobs_wide.h"
 #include <algorithm>
 
 static const size_t LDS_LIMIT = 160 * 1024 - 1024;   // leave room for static __shared__
@@ -104,6 +105,35 @@ inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_
     }
     p.lds += sw.pad_lds;    // experiment knob: SCARLET_PAD_LDS=<bytes> lowers the number of co-resident workgroups
     p.fits = p.lds <= LDS_LIMIT;
+    return p;
+}
+
+// ---- the contraction over the observations of a joint fit (fit_observations_call).  Up to 8 model channels: the
+// kernels of multiobs.h, register-tiled for K <= 8.  Above: k_obs_contract_wide<CW, NW> (multiobs_wide.h) for the
+// channel width that holds C, with the most waves whose float64 slots fit LDS.  CONTRACT_NONE: no form (C > 32).
+enum ContractKernel { CONTRACT_NONE, CONTRACT_K8, CONTRACT_ANYK, CONTRACT_WIDE };
+struct ContractPlan {
+    int kernel;
+    int cw, nw;             // CONTRACT_WIDE: channels the instance is built for (16, 32) and its waves (4, 2, 1)
+    int block;              // threads per workgroup
+    bool prior;             // the passes that write a step are the PRIOR instances
+    size_t lds;
+};
+inline ContractPlan contract_plan(int K, int C, bool prior)
+{
+    ContractPlan p = {CONTRACT_NONE, 0, 0, SC_BLOCK, prior, 0};
+    if (K < 1 || K > SCARLET_MAX_COMPONENTS || C < 1 || C > SC_CMAX) return p;
+    if (C <= SC_BMAX) {
+        p.kernel = K <= SC_KMAX ? CONTRACT_K8 : CONTRACT_ANYK;
+        p.nw = SC_NWAVES;
+        p.lds = obs_contract_lds(K);
+        return p;
+    }
+    p.kernel = CONTRACT_WIDE;
+    p.cw = C <= 16 ? 16 : 32;
+    for (p.nw = SC_NWAVES; p.nw > 1 && obs_contract_wide_lds(K, C, p.cw, p.nw) > LDS_LIMIT; p.nw /= 2) {}
+    p.block = p.nw * SC_WAVE;
+    p.lds = obs_contract_wide_lds(K, C, p.cw, p.nw);
     return p;
 }
 

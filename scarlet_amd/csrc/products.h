@@ -26,7 +26,8 @@ struct ProdArgs {
     const int *cur, *ncomp;
     const float *images, *weights;   // [S][B][HW]; images may be NULL when neither residual nor loss is wanted
     float weight_scalar;
-    float *model;                    // [S - model_s0][B][HW] or NULL
+    float *model;                    // [S - model_s0][model_C][HW] or NULL: the B planes go to model_b0 .. model_b0 + B - 1
+    int model_C, model_b0;           // (B, 0 but for a state of more than 8 channels, evaluated in chunks of bands)
     float *rendered, *residual;      // [S][B][HW] or NULL
     int s0, model_s0;                // first scene of the launch; scene that `model` starts at (staged chunks)
     double *loss_part;               // [S][T][B] or NULL
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_products(ProdArgs a)
     for (int b = 0; b < SC_BMAX; ++b)
         if (b < B) {
             const size_t plane = ((size_t)s * B + b) * HW;
-            if (a.model) pr_store4<VEC4>(a.model + ((size_t)(s - a.model_s0) * B + b) * HW, p0, HW, acc[b]);
+            if (a.model) pr_store4<VEC4>(a.model + ((size_t)(s - a.model_s0) * a.model_C + a.model_b0 + b) * HW, p0, HW, acc[b]);
             if (a.rendered) pr_store4<VEC4>(a.rendered + plane, p0, HW, acc[b]);
             if (observed) {
                 const float4 img = pr_load4<VEC4>(a.images + plane, p0, HW);

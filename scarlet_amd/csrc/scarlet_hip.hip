@@ -27,6 +27,7 @@
 #include "extras.h"
 #include "initsrc.h"
 #include "multiobs.h"
+#include "multiobs_wide.h"
 #include "lowres.h"
 #include "lowres_stream.h"
 #include "prior.h"
@@ -763,24 +764,26 @@ extern "C" int scarlet_profile_end(double total_ms[SC_NCLASS], int64_t launches[
 }
 
 // shape and limits alone: nothing here reads a pointer of the batch
-static int check_shape(const scarlet_batch *b)
+// bmax: SC_BMAX everywhere but for the state of a wide entry point (SC_CMAX, multiobs_wide.h)
+static int check_shape(const scarlet_batch *b, int bmax = SC_BMAX)
 {
     if (!b) return set_err(SCARLET_E_ARG, "null batch");
     if (b->S <= 0 || b->K <= 0 || b->B <= 0 || b->H <= 0 || b->W <= 0) return set_err(SCARLET_E_ARG, "bad batch shape");
     if (b->K > SCARLET_MAX_COMPONENTS)
         return set_err(SCARLET_E_NOTIMPL, "K > 256 components per scene (SCARLET_MAX_COMPONENTS) is not supported");
-    if (b->B > SC_BMAX)
-        return set_err(SCARLET_E_NOTIMPL, "B > 8 bands is not supported by this build of the gradient kernels");
+    if (b->B > bmax)
+        return set_err(SCARLET_E_NOTIMPL, bmax > SC_BMAX ? "a model frame of more than 32 channels (SCARLET_MAX_CHANNELS) is not supported"
+                                                         : "B > 8 bands is not supported by this build of the gradient kernels");
     if (b->H > SCARLET_MAX_SIDE || b->W > SCARLET_MAX_SIDE)
         return set_err(SCARLET_E_TOO_LARGE, "frames larger than 1024 x 1024 (SCARLET_MAX_SIDE) are not supported");
     return SCARLET_OK;
 }
-static int check_batch(const scarlet_batch *b)
+static int check_batch(const scarlet_batch *b, int bmax = SC_BMAX)
 {
     // Every entry point ends with a look at hipGetLastError(); that value is per thread and keeps whatever an EARLIER HIP
     // call of the thread left there.  Start from a clean slate: what is reported is ours.
     (void)hipGetLastError();
-    const int rc = check_shape(b);
+    const int rc = check_shape(b, bmax);
     if (rc) return rc;
     if (!b->images || !b->sed[0] || !b->sed[1] || !b->morph[0] || !b->morph[1] || !b->cur || !b->centers ||
         !b->shifts || !b->flags || !b->lipschitz || !b->mse || !b->it || !b->active || !b->status || !b->workspace)
@@ -805,13 +808,13 @@ static int check_prior(const scarlet_prior *p)
 // need_c: a _constrained entry point (the struct is required, and a symmetric array needs what b->symmetric needs);
 // need_p: a _prior entry point (`p` is checked whenever it is given);  max_iter: of the loops, 0 elsewhere
 static int check_call(const scarlet_batch *b, bool need_c, const scarlet_constraints *c, bool need_p, const scarlet_prior *p,
-                      int max_iter = 0)
+                      int max_iter = 0, int bmax = SC_BMAX)
 {
     if (!b) return set_err(SCARLET_E_ARG, "null batch");
     if (need_c && !c) return set_err(SCARLET_E_ARG, "constraints is NULL (pass a scarlet_constraints with NULL members for the batch's scalars)");
     if (need_c && c->symmetric && (!b->centroid_psf || b->centroid_P <= 0 || !(b->centroid_P & 1)))
         return set_err(SCARLET_E_ARG, "constraints.symmetric needs an odd-sized centroid_psf");
-    int rc = check_batch(b);
+    int rc = check_batch(b, bmax);
     if (!rc && (need_p || p)) rc = check_prior(p);
     if (!rc && max_iter < 0) rc = set_err(SCARLET_E_ARG, "max_iter < 0");
     return rc;
@@ -2315,13 +2318,22 @@ static int64_t lowres_scratch_offset(const scarlet_batch *state, const scarlet_b
     return (o + 15) & ~(int64_t)15;
 }
 
-extern "C" int64_t scarlet_lowres_large_workspace_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr)
+static int64_t lowres_large_workspace_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr, int bmax)
 {
-    if (check_shape(state) || check_shape(obs)) return SCARLET_E_ARG;
+    if (check_shape(state, bmax) || check_shape(obs)) return SCARLET_E_ARG;
     if (int rc = check_lowres(lr, state->H, state->W, obs->B, false, true)) return rc;
     // (the scratch of the streamed form always: an option changed between sizing and fitting cannot write past it)
     const LrsScratch s = lrs_scratch(lowres_dims(state, obs, lr), true);
     return lowres_scratch_offset(state, obs) + (int64_t)lrs_chunk(s, state->S * obs->B) * (int64_t)s.per_plane;
+}
+extern "C" int64_t scarlet_lowres_large_workspace_bytes(const scarlet_batch *state, const scarlet_batch *obs, const scarlet_lowres *lr)
+{
+    return lowres_large_workspace_bytes(state, obs, lr, SC_BMAX);
+}
+extern "C" int64_t scarlet_lowres_large_workspace_bytes_wide(const scarlet_batch *state, const scarlet_batch *obs,
+                                                             const scarlet_lowres *lr)
+{
+    return lowres_large_workspace_bytes(state, obs, lr, SC_CMAX);
 }
 
 extern "C" int64_t scarlet_lowres_op_scratch_bytes(int n, int H, int W, const scarlet_lowres *lr)
@@ -2381,6 +2393,19 @@ static int obs_lipschitz_sed(scarlet_batch *state, const WsLayout &l, const Grad
     else launch_bigk_lipschitz(ga, (state->K + SC_CHUNK - 1) / SC_CHUNK, approximate_L ? 1 : 2, st);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
+}
+
+// the instance of k_obs_contract_wide that contract_plan chose
+typedef void (*ObsKernel)(ObsArgs);
+template <int CW, bool PRIOR>
+static ObsKernel wide_contract_waves(int nw)
+{
+    return nw == 4 ? k_obs_contract_wide<CW, 4, PRIOR> : nw == 2 ? k_obs_contract_wide<CW, 2, PRIOR> : k_obs_contract_wide<CW, 1, PRIOR>;
+}
+static ObsKernel wide_contract_kernel(const ContractPlan &cp, bool prior)
+{
+    if (cp.cw == 16) return prior ? wide_contract_waves<16, true>(cp.nw) : wide_contract_waves<16, false>(cp.nw);
+    return prior ? wide_contract_waves<32, true>(cp.nw) : wide_contract_waves<32, false>(cp.nw);
 }
 
 // Several observations: one pipeline, every iteration the observation step (the observations' G planes, the contraction
@@ -2447,15 +2472,27 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
     // the state's gradient arguments: its partials (engine.h layout over the C channels) feed the Gram / lambda_max code
     const GradArgs ga = grad_args(state, l, approximate_L, 0);
     // K <= 8: the contraction also sums the Gram matrix (no Gram pass); its lambda_max is found in k_obs_head
-    const bool small = state->K <= SC_KMAX && l.grad == GRAD_SMALL;
-    auto contract = small ? k_obs_contract<SC_KMAX, false> : k_obs_contract<0, false>;
+    // more than 8 model channels (scarlet_fit_observations_wide): the wide contraction and lambda_max (multiobs_wide.h);
+    // the Gram comes from the Gram passes for every K
+    const bool wide = state->B > SC_BMAX;
+    const ContractPlan cp = contract_plan(state->K, state->B, p != nullptr);
+    const bool small = !wide && state->K <= SC_KMAX && l.grad == GRAD_SMALL;
+    ObsKernel contract = wide ? wide_contract_kernel(cp, false) : small ? k_obs_contract<SC_KMAX, false> : k_obs_contract<0, false>;
     // the pass that writes the step (OBS_FULL / OBS_STEP); OBS_PARTIALS writes none and stays the plain instance
-    auto contract_step = !p ? contract : small ? k_obs_contract<SC_KMAX, true> : k_obs_contract<0, true>;
+    ObsKernel contract_step = !p ? contract : wide ? wide_contract_kernel(cp, true)
+                                    : small ? k_obs_contract<SC_KMAX, true> : k_obs_contract<0, true>;
     auto head = p ? k_obs_head<true> : k_obs_head<false>;
     m.head_lsed = small && !approximate_L;
-    const size_t lds = obs_contract_lds(state->K);
+    const size_t lds = wide ? cp.lds : obs_contract_lds(state->K), lmorph_lds = wide ? wide_lmorph_lds(state->K, state->B) : 0;
+    if (wide && (cp.kernel != CONTRACT_WIDE || lds > LDS_LIMIT))
+        return set_err(SCARLET_E_NOTIMPL, "no form of the wide contraction for this K and C");
     if ((rc = allow_lds(contract, lds)) || (rc = allow_lds(contract_step, lds))) return rc;
-    const dim3 grid(m.T, m.S);
+    if (wide && (rc = allow_lds(k_wide_lmorph, lmorph_lds))) return rc;
+    const dim3 grid(m.T, m.S), block(wide ? cp.block : SC_BLOCK);
+    auto lmorph = [&]() {
+        if (wide) hipLaunchKernelGGL(k_wide_lmorph, dim3(m.S), dim3(SC_BLOCK), lmorph_lds, st, ga);
+        else hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
+    };
     // with a prior the sparse_l0 / sparse_l1 cut uses each component's own step (update.py:71-82)
     const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0};
     return fit_loop(state, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
@@ -2476,18 +2513,18 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         }
         prof_stop(st); prof_start(1, st);
         if (!approximate_L) {
-            hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
+            lmorph();
             m.mode = OBS_FULL;
-            hipLaunchKernelGGL(contract_step, grid, dim3(SC_BLOCK), lds, st, m);
+            hipLaunchKernelGGL(contract_step, grid, block, lds, st, m);
             if (!small && (rc = obs_lipschitz_sed(state, l, ga, 0, st))) return rc;
         } else {
             m.mode = OBS_PARTIALS;
-            hipLaunchKernelGGL(contract, grid, dim3(SC_BLOCK), lds, st, m);
-            hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
+            hipLaunchKernelGGL(contract, grid, block, lds, st, m);
+            lmorph();
             if (small) hipLaunchKernelGGL(k_bigk_lipschitz, dim3(ga.S), dim3(SC_BLOCK), 0, st, ga, 1);   // (trace of the pass's Gram)
             else if ((rc = obs_lipschitz_sed(state, l, ga, 1, st))) return rc;
             m.mode = OBS_STEP;
-            hipLaunchKernelGGL(contract_step, grid, dim3(SC_BLOCK), lds, st, m);
+            hipLaunchKernelGGL(contract_step, grid, block, lds, st, m);
         }
         hipLaunchKernelGGL(head, dim3(m.S), dim3(SC_BLOCK), 0, st, m);
         HIP_TRY(hipGetLastError());
@@ -2499,11 +2536,11 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
 // the one check of the observation entry points: the list, the state (check_call), every observation against it
 static int check_observations(const scarlet_batch *state, bool need_c, const scarlet_constraints *c, scarlet_batch *const *obs,
                               const int32_t *band0, int n_obs, int max_iter, const scarlet_lowres *const *lowres = nullptr,
-                              bool large = false)
+                              bool large = false, int bmax = SC_BMAX)
 {
     if (n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
     if (!obs || !band0) return set_err(SCARLET_E_ARG, "null observation list");
-    int rc = check_call(state, need_c, c, false, nullptr, max_iter);
+    int rc = check_call(state, need_c, c, false, nullptr, max_iter, bmax);
     for (int o = 0; !rc && o < n_obs; ++o) {
         const scarlet_batch *ob = obs[o];
         if (!ob) return set_err(SCARLET_E_ARG, "null observation batch");
@@ -2574,6 +2611,18 @@ extern "C" int scarlet_fit_observations_prior(scarlet_batch *state, const scarle
                                            lowres, true, p);
 }
 
+// scarlet_fit_observations_prior over a model frame of up to SCARLET_MAX_CHANNELS channels; cons, p and lowres may be NULL
+extern "C" int scarlet_fit_observations_wide(scarlet_batch *state, const scarlet_constraints *c, const scarlet_prior *p,
+                                             scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                             const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                             int approximate_L, int check_every, void *stream)
+{
+    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, lowres, true, SC_CMAX);
+    if (!rc && p) rc = check_prior(p);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
+                                           lowres, true, p);
+}
+
 // scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused
 // right after the shape checks, before any pointer of the batches is looked at
 static int refuse_counts(const scarlet_batch *b)
@@ -2593,13 +2642,12 @@ extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs
     return rc ? rc : scarlet_fit_observations(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
 }
 
-extern "C" int scarlet_init_combined_sed(scarlet_batch *state, const float *images, int B, int band0,
-                                         const float *obs_psf_peak, int peak_per_scene, const float *model_psf_max,
-                                         void *stream)
+static int init_combined_sed_call(scarlet_batch *state, const float *images, int B, int band0, const float *obs_psf_peak,
+                                  int peak_per_scene, const float *model_psf_max, void *stream, int bmax)
 {
-    int rc = check_batch(state);
+    int rc = check_batch(state, bmax);
     if (rc) return rc;
-    if (!images || B < 1 || band0 < 0 || band0 + B > state->B)
+    if (!images || B < 1 || B > SC_BMAX || band0 < 0 || band0 + B > state->B)
         return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
     const int n = state->S * state->K;
     hipLaunchKernelGGL(k_combined_sed, dim3((n + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
@@ -2608,6 +2656,18 @@ extern "C" int scarlet_init_combined_sed(scarlet_batch *state, const float *imag
                        state->sed[1], images, B, band0, obs_psf_peak, peak_per_scene ? B : 0, model_psf_max);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
+}
+extern "C" int scarlet_init_combined_sed(scarlet_batch *state, const float *images, int B, int band0,
+                                         const float *obs_psf_peak, int peak_per_scene, const float *model_psf_max,
+                                         void *stream)
+{
+    return init_combined_sed_call(state, images, B, band0, obs_psf_peak, peak_per_scene, model_psf_max, stream, SC_BMAX);
+}
+extern "C" int scarlet_init_combined_sed_wide(scarlet_batch *state, const float *images, int B, int band0,
+                                              const float *obs_psf_peak, int peak_per_scene, const float *model_psf_max,
+                                              void *stream)
+{
+    return init_combined_sed_call(state, images, B, band0, obs_psf_peak, peak_per_scene, model_psf_max, stream, SC_CMAX);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2842,13 +2902,15 @@ static ProductsPlan products_plan_of(const scarlet_batch *ob, int K, const scarl
     return products_plan(ob->S, K, ob->B, ob->H, ob->W, psf, l.geom, l.plan, w);
 }
 // host-side check of one evaluation, before anything is launched; band0: first channel of the state that `ob` sees
-static int check_products(const scarlet_batch *state, const scarlet_batch *ob, int band0, const scarlet_products *o)
+// bmax: the limit on the STATE's channels (SC_CMAX from the wide entry points); an observation keeps SC_BMAX
+static int check_products(const scarlet_batch *state, const scarlet_batch *ob, int band0, const scarlet_products *o,
+                          int bmax = SC_BMAX)
 {
     if (!state || !ob) return set_err(SCARLET_E_ARG, "null batch");
     if (!o) return set_err(SCARLET_E_ARG, "products: out is NULL");
     if (!products_any(o)) return set_err(SCARLET_E_ARG, "products: every output is NULL");
-    int rc = check_shape(state);
-    if (!rc) rc = check_shape(ob);
+    int rc = check_shape(state, bmax);
+    if (!rc) rc = check_shape(ob, ob == state ? bmax : SC_BMAX);
     if (rc) return rc;
     if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || band0 < 0 || band0 + ob->B > state->B)
         return set_err(SCARLET_E_ARG, "products: the observation's S, K, H, W or channels do not fit the state");
@@ -2885,6 +2947,7 @@ static int launch_products(const scarlet_batch *state, const scarlet_batch *ob, 
     const bool psf = p.psf != PRODUCTS_PSF_NONE, observed_data = o->residual || o->loss;
     ProdArgs a = {};
     a.S = S; a.K = K; a.B = B; a.HW = HW; a.T = p.T; a.C = state->B; a.band0 = band0;
+    a.model_C = B; a.model_b0 = 0;
     a.sed[0] = state->sed[0]; a.sed[1] = state->sed[1]; a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
     a.cur = state->cur; a.ncomp = state->n_components;
     a.images = observed_data ? ob->images : nullptr; a.weights = ob->weights; a.weight_scalar = ob->weight_scalar;
@@ -2905,7 +2968,19 @@ static int launch_products(const scarlet_batch *state, const scarlet_batch *ob, 
         hipLaunchKernelGGL(k, grid, dim3(SC_BLOCK), 0, st, m);
     };
     int rc;
-    if (p.main_pass && !p.stage) main_pass(0, S, o->model, 0);
+    if (B > SC_BMAX) {
+        // a state of more than 8 channels (scarlet_observations_products_wide; it has no observed outputs): k_products
+        // in chunks of 8 bands, the plane sums with the first; the reduction and the component models take any B
+        for (int b0 = 0; p.main_pass && b0 < B; b0 += SC_BMAX) {
+            ProdArgs m = a;
+            m.B = std::min(SC_BMAX, B - b0); m.band0 = b0; m.model = o->model; m.model_C = B; m.model_b0 = b0;
+            if (b0 > 0) m.flux_part = nullptr;
+            if (!m.model && !m.flux_part) break;
+            auto k = vec4 ? (m.flux_part ? k_products<true, true> : k_products<true, false>)
+                          : (m.flux_part ? k_products<false, true> : k_products<false, false>);
+            hipLaunchKernelGGL(k, dim3(p.T, S), dim3(SC_BLOCK), 0, st, m);
+        }
+    } else if (p.main_pass && !p.stage) main_pass(0, S, o->model, 0);
     if (psf) {
         ProdObsArgs r = {};
         r.B = B; r.HW = HW; r.T = p.T;
@@ -2960,6 +3035,11 @@ extern "C" int64_t scarlet_products_scratch_bytes(const scarlet_batch *b, const 
     if (!b || !out || check_shape(b)) return 0;
     return products_plan_of(b, b->K, out, WS_PEEK, nullptr).total;
 }
+extern "C" int64_t scarlet_products_scratch_bytes_wide(const scarlet_batch *state, const scarlet_products *out)
+{
+    if (!state || !out || check_shape(state, SC_CMAX)) return 0;
+    return products_plan_of(state, state->K, out, WS_PEEK, nullptr).total;
+}
 
 extern "C" int scarlet_batch_products(const scarlet_batch *b, const scarlet_products *out, void *scratch, int64_t scratch_bytes,
                                       void *stream)
@@ -2981,7 +3061,7 @@ static LowresProductsPlan lowres_products_plan_of(const scarlet_batch *state, co
 }
 // host-side check of one such evaluation, before anything is launched (every refusal is SCARLET_E_ARG)
 static int check_lowres_products(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr, int band0,
-                                 const scarlet_products *o)
+                                 const scarlet_products *o, int bmax = SC_BMAX)
 {
     if (!state || !ob || !lr) return set_err(SCARLET_E_ARG, "null batch");
     if (!o) return set_err(SCARLET_E_ARG, "products: out is NULL");
@@ -2989,7 +3069,7 @@ static int check_lowres_products(const scarlet_batch *state, const scarlet_batch
     if (state->H > SCARLET_MAX_SIDE || state->W > SCARLET_MAX_SIDE || lr->h > SCARLET_MAX_SIDE || lr->w > SCARLET_MAX_SIDE ||
         lr->nfy > SCARLET_MAX_SIDE || lr->nfx > 2 * SCARLET_MAX_SIDE)
         return set_err(SCARLET_E_ARG, "products: sides above SCARLET_MAX_SIDE are not supported");
-    if (int rc = check_shape(state)) return rc;
+    if (int rc = check_shape(state, bmax)) return rc;
     if (ob->S != state->S || ob->K != state->K || ob->H != lr->h || ob->W != lr->w || ob->B < 1 || band0 < 0 ||
         band0 + ob->B > state->B)
         return set_err(SCARLET_E_ARG, "products: a low-resolution observation does not fit the model frame or its scarlet_lowres");
@@ -3063,11 +3143,19 @@ extern "C" int64_t scarlet_lowres_products_scratch_bytes(const scarlet_batch *st
     if (int rc = check_lowres_products(state, obs, lr, 0, out)) return rc;
     return lowres_products_plan_of(state, obs, lr, false).total;
 }
+extern "C" int64_t scarlet_lowres_products_scratch_bytes_wide(const scarlet_batch *state, const scarlet_batch *obs,
+                                                              const scarlet_lowres *lr, const scarlet_products *out)
+{
+    if (!out || !products_any(out)) return 0;
+    if (int rc = check_lowres_products(state, obs, lr, 0, out, SC_CMAX)) return rc;
+    return lowres_products_plan_of(state, obs, lr, false).total;
+}
 
 // the evaluations of scarlet_observations_products; lowres: NULL, or n_obs pointers (NULL = on the model's grid)
 static int observations_products_call(const scarlet_batch *state, scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
                                       const int32_t *band0, int n_obs, const scarlet_products *state_out,
-                                      const scarlet_products *out, void *scratch, int64_t scratch_bytes, void *stream)
+                                      const scarlet_products *out, void *scratch, int64_t scratch_bytes, void *stream,
+                                      int bmax = SC_BMAX)
 {
     if (!state) return set_err(SCARLET_E_ARG, "null batch");
     if (n_obs < 0 || n_obs > SCARLET_MAX_OBSERVATIONS || (n_obs > 0 && (!obs || !band0 || !out)))
@@ -3079,7 +3167,7 @@ static int observations_products_call(const scarlet_batch *state, scarlet_batch 
     if (state_out && products_any(state_out)) {
         if (state_out->rendered || state_out->residual || state_out->loss)
             return set_err(SCARLET_E_ARG, "products: rendered, residual and loss belong to an observation, not to the state");
-        if ((rc = check_products(state, state, 0, state_out)) ||
+        if ((rc = check_products(state, state, 0, state_out, bmax)) ||
             (rc = check_products_scratch(products_plan_of(state, state->K, state_out, WS_PEEK, nullptr), scratch, scratch_bytes)))
             return rc;
     }
@@ -3089,13 +3177,13 @@ static int observations_products_call(const scarlet_batch *state, scarlet_batch 
         if (out[i].model || out[i].flux || out[i].component_models || out[i].n_select)
             return set_err(SCARLET_E_ARG, "products: model, flux and component_models belong to the state, not to an observation");
         if (lowres && lowres[i]) {
-            if ((rc = check_lowres_products(state, obs[i], lowres[i], band0[i], &out[i]))) return rc;
+            if ((rc = check_lowres_products(state, obs[i], lowres[i], band0[i], &out[i], bmax))) return rc;
             const int64_t need = lowres_products_plan_of(state, obs[i], lowres[i], model != nullptr).total;
             if (need > 0 && (!scratch || scratch_bytes < need))
                 return set_err(SCARLET_E_ARG, "products: scratch is too small (scarlet_lowres_products_scratch_bytes)");
             continue;
         }
-        if ((rc = check_products(state, obs[i], band0[i], &out[i])) ||
+        if ((rc = check_products(state, obs[i], band0[i], &out[i], bmax)) ||
             (rc = check_products_scratch(products_plan_of(obs[i], state->K, &out[i], WS_PEEK, nullptr), scratch, scratch_bytes)))
             return rc;
     }
@@ -3126,4 +3214,24 @@ extern "C" int scarlet_observations_products_lowres(const scarlet_batch *state, 
 {
     if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
     return observations_products_call(state, obs, lowres, band0, n_obs, state_out, out, scratch, scratch_bytes, stream);
+}
+
+// scarlet_observations_products_lowres for a state of up to SCARLET_MAX_CHANNELS channels; `lowres` may be NULL
+extern "C" int scarlet_observations_products_wide(const scarlet_batch *state, scarlet_batch *const *obs,
+                                                  const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                                  const scarlet_products *state_out, const scarlet_products *out,
+                                                  void *scratch, int64_t scratch_bytes, void *stream)
+{
+    return observations_products_call(state, obs, lowres, band0, n_obs, state_out, out, scratch, scratch_bytes, stream, SC_CMAX);
+}
+
+// diagnostics: contract_plan (launch_plan.h) of a joint fit with K components over C model channels:
+// {kernel (ContractKernel), channel width, waves, threads, dynamic LDS bytes, LDS limit, prior, 0}
+extern "C" int scarlet_debug_contract_plan(int K, int C, int prior, int32_t *out8)
+{
+    if (!out8) return -1;
+    const ContractPlan p = contract_plan(K, C, prior != 0);
+    const int v[8] = {p.kernel, p.cw, p.nw, p.block, (int)p.lds, (int)LDS_LIMIT, p.prior ? 1 : 0, 0};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return p.kernel == CONTRACT_NONE ? -1 : 0;
 }
