@@ -316,7 +316,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
         }
         STAMP(9);
         int lstop = 1 << 30;            // last sweep level computed (early exit); pixels beyond are <= 0 -> 0
-        if (c_monotonic()) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
+        if (c_monotonic()) wave_monotonic<float, false>(t, cy, cx, 0.f, &lstop);       // (this kernel spills already: see there)
         STAMP(10);
         if (lane == 0) { a.centers[2 * c] = cy; a.centers[2 * c + 1] = cx; }
         // ---- sparsity, positivity (update.py:71-82, 27-32), normalisation (update.py:62-65),

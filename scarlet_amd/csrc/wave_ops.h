@@ -248,7 +248,11 @@ __device__ __forceinline__ Walker<T> make_compact_walker(int e, int H, int W, in
 // `level_cap` > SC_COMPACT_LAST (with quiet_out): the sweep continues through the two-trip levels up to
 // level_cap and reports there -- for a caller whose tile is a box around the peak that is complete only up to
 // that level (boxupdate.h).
-template <typename T>
+// `PAIRS` = false: the compact levels as they were before the pair loop (one trip for level 1, an exit behind every level).
+// Only for fused.h's k_iterate<4, 6 / 8>: at 256 VGPRs they spill already, and ANY other shape of this loop moves their
+// register allocation -- the pair loop takes their scratch from 232 / 280 / 224 / 280 to 272 / 328 / 236 / 276 bytes per lane.
+// The same levels, stores and outputs either way (tests/test_gpu_sweep_levels.py runs both on the same scenes).
+template <typename T, bool PAIRS = true>
 __device__ inline void wave_monotonic(const TileT<T> &t, int cy, int cx, T thresh, int *last_level = nullptr,
                                       int *quiet_out = nullptr, T floor = (T)0, int level_cap = 0)
 {
@@ -313,12 +317,13 @@ __device__ inline void wave_monotonic(const TileT<T> &t, int cy, int cx, T thres
         return v;
 #endif
     };
-    auto finish = [&](const Prep &q, const Vals &v, const Walker<T> &w) {
+    // `admit` (wave-uniform): false = the level does not run -- nothing is stored, the returned mask means nothing.
+    auto finish = [&](const Prep &q, const Vals &v, const Walker<T> &w, bool admit = true) {
         const T inv = fast_rcp(q.c1 + q.c2 + q.c3 + w.c4);
         // unused neighbours were read from a dummy address: mask them (0 * NaN != 0)
         const T t1 = mul_or_zero(v.x1, q.c1), t3 = mul_or_zero(v.x3, q.c3), t4 = mul_or_zero(v.x4, w.c4);
         const T cap = (fma_t(v.x2, q.c2, t1) + (t3 + t4)) * inv * one_minus;
-        const bool lower = q.act && cap < v.x0;
+        const bool lower = admit && q.act && cap < v.x0;
         if (lower) *(LdsT *)q.p = cap;
         // lanes whose pixel ends up positive, as a lane mask straight from the compare (idle lanes count as -1)
         return positive_lanes(q.act ? (lower ? cap : v.x0) - floor : (T)-1);
@@ -334,11 +339,12 @@ __device__ inline void wave_monotonic(const TileT<T> &t, int cy, int cx, T thres
     int done = 1 << 30;                          // 1 << 30: swept to the end
     int ell = 1;
     bool stop = false;
-    {   // ---- levels 1 .. 46: one trip per level
+    const int qstop = early ? 3 : 1 << 30;       // the exit test of every level: quiet >= qstop (never, without `early`)
+    const int Lc = min(Lall, SC_COMPACT_LAST);
+    if constexpr (!PAIRS) {   // ---- levels 1 .. 46: one trip per level, an exit behind every level
         const Walker<T> c0 = make_compact_walker<T>(0, H, W, LW, cy, cx, lane);
         const Walker<T> c1 = make_compact_walker<T>(1, H, W, LW, cy, cx, lane);
         WalkState<T> s0 = walk_from(c0, 2, mb), s1 = walk_from(c1, 1, mb);
-        const int Lc = min(Lall, SC_COMPACT_LAST);
         Prep pa = prepare(s1, c1);
         while (ell <= Lc) {
             Prep na;
@@ -363,6 +369,70 @@ __device__ inline void wave_monotonic(const TileT<T> &t, int cy, int cx, T thres
                 if (early && quiet >= 3) { stop = true; break; }
                 ++ell;
             }
+        }
+    } else if (Lc >= 1) {   // ---- levels 1 .. 46: one trip per level, in pairs
+        // Level 1 holds no pixel (2 a + b = 1 needs a >= 1; the odd walkers have b >= 1, so a = (1 - b) >> 1 <= 0 lies
+        // below amin): its trip stored nothing and left quiet = 1 and the odd walkers one step out.  Start from there.
+        // The loop runs level pairs (even, odd) from level 2 to the last odd level Lodd <= Lc; an even Lc leaves one
+        // even level behind it.  The loop has ONE exit, at its foot, where the bound is tested as well (once per pair);
+        // which of the two ended it is read off `quiet` behind it.  A sweep that ends on an even level passes the odd
+        // level without a store and without a count (`admit`): an exit between the two levels, in a loop that holds the
+        // lanes' conditional store, is compiled into flag arithmetic on every level (ten scalar instructions per pair).
+        // Measured (profiles/sweep_exit_notes.md): what a level costs is the instructions its wave issues, not the
+        // latency of its gathers.  Requesting a level's gathers ahead, directly behind the store of the level before (1 and
+        // 2 instructions in between instead of 12 and 29), was worth 0.5 % of a k_fit2x step, far below the bar set for
+        // keeping a part, and cost volatile reads, a scheduling barrier and pinned addresses: taken out again.
+        const Walker<T> c0 = make_compact_walker<T>(0, H, W, LW, cy, cx, lane);
+        const Walker<T> c1 = make_compact_walker<T>(1, H, W, LW, cy, cx, lane);
+        WalkState<T> s0 = walk_from(c0, 2, mb), s1 = walk_from(c1, 3, mb);
+        const int Lodd = (Lc - 1) | 1;
+        quiet = 1;
+        ell = 2;
+        // prepare + pin, the walker's running address made opaque first: one step and four offsets per level.  Left to
+        // itself the compiler keeps thirteen running offsets per pair and adds the tile's base to each before its gather
+        auto prepare_pinned = [&](WalkState<T> &st, const Walker<T> &w) {
+            asm volatile("" : "+v"(st.p));
+            const Prep q = prepare(st, w);
+            pin(q);
+            return q;
+        };
+        Prep pe = prepare_pinned(s0, c0);                       // level 2
+        if (Lodd >= 3) {
+            for (;;) {
+                int go;                                         // -1: the sweep goes on behind the even level, 0: it ends there
+                Prep po;
+                {   // even level
+                    const Vals va = load(pe, c0);
+                    po = prepare_pinned(s1, c1);                // (no active pixel beyond Lall)
+                    const unsigned long long pm = finish(pe, va, c0);
+                    wave_sync();
+                    quiet = pm != 0 ? 0 : quiet + 1;
+                    // (quiet - qstop) >> 31, on the scalar unit.  Written in C++, AMD clang 22.0.0git (ROCm 7.2.0) brings it
+                    // back as a lane compare, a select and v_readfirstlane; profiles/sweep_exit_notes.md has the loop's
+                    // instruction counts as that compiler gives them -- recount there when the compiler changes
+                    asm("s_sub_i32 %0, %1, %2\n\ts_ashr_i32 %0, %0, 31" : "=&s"(go) : "s"(quiet), "s"(qstop) : "scc");
+                    ell -= go;
+                }
+                {   // odd level
+                    const Vals va = load(po, c1);
+                    pe = prepare_pinned(s0, c0);
+                    const unsigned long long pm = finish(po, va, c1, go != 0);
+                    wave_sync();
+                    quiet += ((pm != 0 ? 0 : quiet + 1) - quiet) & go;
+                    if (((qstop - 1 - quiet) | (Lodd - 1 - ell)) < 0) break;       // quiet >= qstop or ell >= Lodd
+                    ++ell;
+                }
+            }
+            stop = quiet >= qstop;
+            if (!stop) ++ell;
+        }
+        if (!stop && ell == Lc) {                               // the even level behind the last pair
+            const Vals va = load(pe, c0);
+            const unsigned long long pm = finish(pe, va, c0);
+            wave_sync();
+            quiet = pm != 0 ? 0 : quiet + 1;
+            stop = quiet >= qstop;
+            if (!stop) ++ell;
         }
     }
     if (quiet_out) *quiet_out = quiet;
