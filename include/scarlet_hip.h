@@ -73,6 +73,8 @@ extern "C" {
                                                left untouched and inactive                 */
 #define SCARLET_STATUS_BAD_INIT          8  /* bad input of scarlet_init_sources in this scene:
                                                it is left untouched and inactive           */
+#define SCARLET_STATUS_BAD_FRAME        16  /* frame_hw[s] outside 1..H x 1..W: the scene is
+                                               left untouched and inactive                 */
 
 /* source types of scarlet_init_sources (scarlet_init_spec::kind) */
 #define SCARLET_INIT_EXTENDED 0   /* ExtendedSource (source.py:139-180, 443-492)                */
@@ -238,7 +240,8 @@ int scarlet_match_psfs(const float *psf1, int n, int P1y, int P1x, const float *
  * ---------------------------------------------------------------------------- */
 
 typedef struct scarlet_batch {
-    /* shapes: S scenes, K components per scene (at most: see n_components), B bands, H x W pixels */
+    /* shapes: S scenes, K components per scene (at most: see n_components), B bands, H x W pixels (scenes with frames
+       of their own inside H x W: struct scarlet_frames and the _frames entry points, below; this struct does not change) */
     int32_t S, K, B, H, W;
     /* data (read only) */
     const float *images;      /* [S][B][H][W]                                          */
@@ -429,6 +432,48 @@ int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_con
                                          const int32_t *band0, int n_obs, int max_iter, double e_rel,
                                          int approximate_L, int check_every, void *stream);
 
+/* Ragged frames: scenes of different frame sizes in one batch.  scarlet_batch does not change; the shapes travel in a
+ * struct of their own.  frame_hw: device [S][2] int32 (h, w), or NULL = every scene is H x W (the _frames entry points then
+ * ARE their plain counterparts, bit for bit).  Scene s has its own frame of 1 <= h <= H by 1 <= w <= W pixels in the
+ * top-left corner of its padded H x W planes (row stride W).  Its result is what the reference computes for the (B, h, w)
+ * scene alone:
+ *   - pixels outside the frame do not exist: they are no neighbour, partner or window pixel of any constraint (max_pixel,
+ *     centroid, symmetry window and monotonic sweep take the scene's bounds), and the convergence sums run over the
+ *     scene's pixels.  After every call they are exactly 0.0f in both morphology buffers (they must be when the first
+ *     call starts);
+ *   - the gradient kernels are the batch's: the caller passes `weights` that are zero outside each scene's frame, so that
+ *     outside pixels add nothing to the loss, the gradients or the Lipschitz constants (the model is zero there because
+ *     the morphologies are; what a PSF's adjoint writes there is zeroed by the constraint kernels), and `images` that are
+ *     zero there;
+ *   - centres are in the scene's own pixel coordinates (= the padded plane's); one outside (h, w) is treated like one
+ *     outside (H, W) of a uniform batch;
+ *   - every _frames entry point that iterates, updates or initialises checks the entries on the device first: a scene
+ *     whose entry lies outside 1..H x 1..W gets SCARLET_STATUS_BAD_FRAME and active = 0 and is not touched again; the
+ *     other scenes go on.  No entry beyond the padded plane is ever used as a loop bound;
+ *   - the workspace and the launch forms are those of the padded (H, W).  Such a batch takes the general path (no
+ *     one-launch kernels) and runs no box stage beyond 64 pixels;
+ *   - SCARLET_E_NOTIMPL, found on the host before any launch: frame_hw with b->group; scarlet_init_sources_frames with
+ *     spec->kind (extended sources only).  Priors, scarlet_fit_multi and the scarlet_fit_observations family have no
+ *     _frames form.  f == NULL is SCARLET_E_ARG. */
+typedef struct scarlet_frames {
+    const int32_t *frame_hw;    /* device [S][2] (h, w), or NULL = every scene is H x W */
+} scarlet_frames;               /* 8 bytes */
+
+/* scarlet_fit_constrained without a prior (c may be NULL: the batch's scalars) */
+int scarlet_fit_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */, int max_iter,
+                       double e_rel, int approximate_L, int check_every, void *stream);
+/* scarlet_source_update_constrained without a prior */
+int scarlet_source_update_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
+                                 int in_iteration, void *stream);
+/* the device check alone, for callers that run an iteration phase by phase: call it before scarlet_backward_step, whose
+ * kernels skip the scenes it made inactive */
+int scarlet_check_frames(scarlet_batch *b, const scarlet_frames *f, void *stream);
+/* scarlet_init_extended / scarlet_init_sources on each scene's own frame: the detection coadd, the sdss symmetry's window,
+ * the thresholded sweep and the centre-outside test use the scene's bounds; outside pixels are written as zero */
+int scarlet_init_extended_frames(scarlet_batch *b, const scarlet_frames *f, const float *bg_rms_host, float thresh,
+                                 const float *sed_scale_host, int init_symmetric, int init_monotonic, int run_update,
+                                 void *stream);
+
 /* A LOW-RESOLUTION observation of the model frame (reference LowResObservation, observation.py:242-599): a second data
  * set with coarser pixels and its own PSFs, fitted jointly with the others.  For frames that are not rotated against
  * each other the reference's resample-and-convolve operator, restricted to the frequencies its sinc cut keeps, is
@@ -591,6 +636,11 @@ typedef struct scarlet_products {
 int64_t scarlet_products_scratch_bytes(const scarlet_batch *b, const scarlet_products *out);
 int scarlet_batch_products(const scarlet_batch *b, const scarlet_products *out, void *scratch, int64_t scratch_bytes,
                            void *stream);
+/* scarlet_batch_products of a batch whose scenes have their own frames (scarlet_frames): model, rendered and residual are
+ * exactly zero outside each scene's frame -- where a difference kernel's convolution spills, the kernels mask it -- and
+ * those pixels add nothing to the loss.  The scratch is that of scarlet_batch_products. */
+int scarlet_batch_products_frames(const scarlet_batch *b, const scarlet_frames *f, const scarlet_products *out, void *scratch,
+                                  int64_t scratch_bytes, void *stream);
 /* The same for a batch fitted against several observations (scarlet_fit_observations): observation i sees the channels
  * band0[i] .. band0[i] + obs[i]->B - 1 of the state's model through its own difference kernel, images and weights, and
  * out[i] takes its rendered / residual / loss ([S][obs[i]->B]...; model, flux and component_models must be NULL there).
@@ -734,6 +784,8 @@ typedef struct scarlet_init_spec {
 } scarlet_init_spec;
 
 int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *spec, void *stream);
+/* ... on each scene's own frame (scarlet_frames): extended sources only, spec->kind must be NULL */
+int scarlet_init_sources_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_init_spec *spec, void *stream);
 
 /* Row a3b set-up: FFT the difference kernel into the workspace (K-hat at the reference's FFT
  * shape next_fast_len(N + P + 3), fft.py:68-106) and create the batched hipFFT plans (cached

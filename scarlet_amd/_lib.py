@@ -38,6 +38,7 @@ lib = ctypes.CDLL(LIB_PATH)
 OK, E_ARG, E_TOO_LARGE, E_HIP, E_NOTIMPL = 0, -1, -2, -3, -4
 FLAG_SED_NOT_CONVERGED, FLAG_MORPH_NOT_CONVERGED, FLAG_EDGE_PIXELS, FLAG_NO_VALID_PIXELS = 1, 2, 4, 8
 STATUS_CENTER_AT_EDGE, STATUS_NONFINITE, STATUS_BAD_COUNT, STATUS_BAD_INIT = 1, 2, 4, 8
+STATUS_BAD_FRAME = 16
 INIT_EXTENDED, INIT_POINT = 0, 1           # SCARLET_INIT_*
 MAX_LAYERS = 8                             # SCARLET_MAX_LAYERS
 SYM_KSPACE, SYM_SOFT, SYM_SDSS = 0, 1, 2
@@ -67,6 +68,11 @@ class ScarletBatch(Structure):
         ("group", c_void_p),
         ("n_components", c_void_p),
     ]
+
+
+class ScarletFrames(Structure):
+    """struct scarlet_frames of include/scarlet_hip.h."""
+    _fields_ = [("frame_hw", c_void_p)]
 
 
 class ScarletInitSpec(Structure):
@@ -198,6 +204,13 @@ _SIGNATURES = {
     "scarlet_profile_end_ex": (c_int, [_P, _P, _P]),
     "scarlet_init_extended": (c_int, [POINTER(ScarletBatch), _P, c_float, _P, c_int, c_int, c_int, _P]),
     "scarlet_init_sources": (c_int, [POINTER(ScarletBatch), POINTER(ScarletInitSpec), _P]),
+    "scarlet_fit_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints), c_int, c_double,
+                                   c_int, c_int, _P]),
+    "scarlet_source_update_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints), c_int, _P]),
+    "scarlet_check_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), _P]),
+    "scarlet_init_extended_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), _P, c_float, _P, c_int, c_int, c_int, _P]),
+    "scarlet_init_sources_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletInitSpec), _P]),
+    "scarlet_batch_products_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletProducts), _P, c_int64, _P]),
     "scarlet_convergence_sums": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_batch_prepare_psf": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_convolve_same": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P]),

@@ -45,6 +45,89 @@ def pad_centers(centers, K=None):
     return out, counts
 
 
+def pad_frames(images, fill=0):
+    """Scenes of different frame sizes -> one padded block and the shapes (no device needed).
+
+    images : list of S arrays of shape (B, h_s, w_s): every scene has its own height and width, all have B bands
+    fill : value of the padding (the batch never reads it as data: its weights are zero there)
+    Returns ((S, B, H, W) float32 with scene s in the top-left corner of its planes, where H = max h_s and W = max w_s
+    rounded up to a multiple of 4 (the 16-byte paths of the kernels), and the (S, 2) int32 shapes (h_s, w_s))."""
+    arrs = [np.asarray(a.detach().cpu() if hasattr(a, "detach") else a) for a in images]
+    if not arrs:
+        raise ValueError("pad_frames: no scenes")
+    for s, a in enumerate(arrs):
+        if a.ndim != 3 or min(a.shape) < 1:
+            raise ValueError("pad_frames: scene %d must be (B, h, w) with every side >= 1, not %s" % (s, a.shape))
+        if a.shape[0] != arrs[0].shape[0]:
+            raise ValueError("pad_frames: scene %d has %d bands, scene 0 has %d" % (s, a.shape[0], arrs[0].shape[0]))
+    shapes = np.array([a.shape[1:] for a in arrs], dtype=np.int32)
+    H, W = int(shapes[:, 0].max()), -(-int(shapes[:, 1].max()) // 4) * 4
+    out = np.full((len(arrs), arrs[0].shape[0], H, W), fill, dtype=np.float32)
+    for s, a in enumerate(arrs):
+        out[s, :, :a.shape[1], :a.shape[2]] = a
+    return out, shapes
+
+
+def _is_frame_list(images):
+    """True for a list of per-scene (B, h_s, w_s) arrays (not one (S, B, H, W) block, nested lists included)."""
+    return isinstance(images, (list, tuple)) and len(images) > 0 and all(np.ndim(a) == 3 for a in images)
+
+
+def ragged_frame_inputs(images, centers, frame_shapes, weights, group, n_components):
+    """The host-side checks and padding of a ragged-frame batch (no device needed): what BlendBatch does with `images`
+    given as a list, or as a padded block with `frame_shapes`.  Returns (images block, (S, 2) int32 shapes, weights as None /
+    scalar / (S, B, H, W) block, centres, n_components); ValueError for bad input, NotImplementedError for `group`."""
+    if group is not None:
+        raise NotImplementedError("a ragged-frame batch (frame_shapes / a list of images) does not take group=")
+    if images is None:
+        raise NotImplementedError("from_observations does not take frame_shapes")
+    if _is_frame_list(images):
+        if frame_shapes is not None:
+            raise ValueError("frame_shapes comes with a padded (S, B, H, W) block; a list of images carries its own shapes")
+        images, shapes = pad_frames(images)
+    else:
+        if isinstance(images, (list, tuple)):
+            images = np.asarray(images)
+        if np.ndim(images) != 4:
+            raise ValueError("images must be (S, B, H, W) or a list of (B, h, w) arrays")
+        shapes = np.asarray(frame_shapes.cpu() if hasattr(frame_shapes, "cpu") else frame_shapes)
+        if shapes.shape != (np.shape(images)[0], 2) or not np.issubdtype(shapes.dtype, np.integer):
+            raise ValueError("frame_shapes must be (S, 2) = (%d, 2) integers (h, w)" % np.shape(images)[0])
+        shapes = shapes.astype(np.int32)
+    S, B, H, W = (int(v) for v in np.shape(images))
+    bad = (shapes[:, 0] < 1) | (shapes[:, 0] > H) | (shapes[:, 1] < 1) | (shapes[:, 1] > W)
+    if bad.any():
+        s = int(np.argmax(bad))
+        raise ValueError("frame_shapes[%d] = %s lies outside 1..%d x 1..%d" % (s, tuple(int(v) for v in shapes[s]), H, W))
+    if isinstance(weights, (list, tuple)) and _is_frame_list(weights):
+        if len(weights) != S:
+            raise ValueError("weights: %d per-scene arrays for S = %d scenes" % (len(weights), S))
+        for s, w in enumerate(weights):
+            if tuple(np.shape(w)) != (B, int(shapes[s, 0]), int(shapes[s, 1])):
+                raise ValueError("weights[%d] must be %s, not %s" % (s, (B, int(shapes[s, 0]), int(shapes[s, 1])), tuple(np.shape(w))))
+        weights = pad_frames(weights)[0]
+    # the centres of the present components lie inside their scene's own frame
+    if isinstance(centers, (list, tuple)) and len(centers) and np.ndim(centers[0]) == 2 and \
+            len(set(np.shape(c)[0] for c in centers)) > 1:
+        centers, counts = pad_centers(centers)
+        if n_components is not None and not np.array_equal(np.asarray(n_components).reshape(-1), counts):
+            raise ValueError("n_components does not match the lengths of the centre lists")
+        n_components = counts
+    c = np.asarray(centers.cpu() if hasattr(centers, "cpu") else centers)
+    if c.ndim != 3 or c.shape[0] != S or c.shape[2] != 2:
+        raise ValueError("centers must be (S, K, 2) or a list of S (n_s, 2) arrays")
+    out = (c[..., 0] < 0) | (c[..., 0] >= shapes[:, None, 0]) | (c[..., 1] < 0) | (c[..., 1] >= shapes[:, None, 1])
+    if n_components is not None:
+        n = np.asarray(n_components.cpu() if hasattr(n_components, "cpu") else n_components).reshape(-1)
+        if n.shape == (S,):
+            out &= np.arange(c.shape[1])[None, :] < n[:, None]
+    if out.any():
+        s, k = [int(v[0]) for v in np.nonzero(out)]
+        raise ValueError("centre %s of scene %d, source %d lies outside the scene's %d x %d frame"
+                         % (tuple(int(v) for v in c[s, k]), s, k, shapes[s, 0], shapes[s, 1]))
+    return images, shapes, weights, centers, n_components
+
+
 _SWITCHES, _THRESHOLDS = ("symmetric", "monotonic"), ("l0_thresh", "l1_thresh")
 
 
@@ -246,10 +329,12 @@ class BlendBatch(object):
 
     Parameters
     ----------
-    images : (S, B, H, W) array or tensor
+    images : (S, B, H, W) array or tensor; or a list of S arrays (B, h_s, w_s) -- scenes with their own frame sizes,
+        padded by `pad_frames`; or the padded block together with `frame_shapes`
     centers : (S, K, 2) integer pixel centres (y, x) of the sources, or a list of S arrays (n_s, 2): the scenes then
         have different numbers of sources, padded to K = max n_s (`pad_centers`), and n_components is derived
-    weights : None (scalar 1, reference observation.py:148-151), a Python scalar, or (S, B, H, W)
+    weights : None (scalar 1, reference observation.py:148-151), a Python scalar, or (S, B, H, W); for a ragged-frame
+        batch also a list of per-scene (B, h_s, w_s) arrays
     symmetric, monotonic : constraint switches of PointSource/ExtendedSource.update
     l0_thresh, l1_thresh : None or sparsity thresholds (update.sparse_l0 / sparse_l1)
         Each of the four is one value for the batch, or one per component (`constraint_arrays`): a (K,) sequence, an
@@ -265,11 +350,20 @@ class BlendBatch(object):
         of a source (adjacent components) share one centre measured on their flux-weighted sum
     n_components : None (every scene has K components), or (S,) counts: scene s uses components 0 .. n[s] - 1, the
         others are absent -- zero in both buffers, flags 0, outside the model, the constraints and the convergence test
+    frame_shapes : None (every scene is H x W), or (S, 2) integers (h_s, w_s): scene s lies in the top-left corner of its
+        padded planes and is fitted as the reference fits the (B, h_s, w_s) scene alone -- pixels outside do not exist
+        for the constraints, stay exactly zero in the morphologies and carry zero weight (the batch materialises
+        (S, B, H, W) weights with the frame mask multiplied in).  Centres are in the scene's own coordinates.  Such a
+        batch takes no `group`, no prior and no `from_observations`; `init_sources` starts extended sources only.
     """
 
     def __init__(self, images, centers, weights=None, symmetric=True, monotonic=True,
                  l0_thresh=None, l1_thresh=None, centroid_weight=None, mse_capacity=256,
-                 device=None, group=None, n_components=None, _frame=None, _morph=True):
+                 device=None, group=None, n_components=None, _frame=None, _morph=True, frame_shapes=None):
+        frames = None
+        if frame_shapes is not None or _is_frame_list(images):      # host-side checks first: they need no device
+            images, frames, weights, centers, n_components = ragged_frame_inputs(images, centers, frame_shapes, weights, group,
+                                                                                  n_components)
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -295,6 +389,7 @@ class BlendBatch(object):
         assert self.centers.ndim == 3 and self.centers.shape[0] == S and self.centers.shape[2] == 2
         K = self.centers.shape[1]
         self.S, self.K, self.B, self.H, self.W = S, K, B, H, W
+        self.frame_shapes = None if frames is None else torch.as_tensor(frames).to(**i32).contiguous()
         self.n_components = None
         if n_components is not None:
             n = np.asarray(n_components.cpu() if torch.is_tensor(n_components) else n_components).reshape(-1)
@@ -310,6 +405,21 @@ class BlendBatch(object):
         if weights is not None and np.ndim(weights) == 0 and not torch.is_tensor(weights):
             self.weight_scalar, weights = float(weights), None
         self.weights = None if weights is None else torch.as_tensor(weights).to(**f32).contiguous()
+        self._frame_mask = None
+        self._frames = _lib.ScarletFrames()         # frame_hw NULL: the _frames entry points are their plain counterparts
+        if frames is not None:
+            # pixels outside a scene's frame do not exist: zero weight (and zero data, so that residuals vanish there)
+            self._frames.frame_hw = self.frame_shapes.data_ptr()
+            fh, fw = self.frame_shapes[:, 0].view(S, 1, 1, 1), self.frame_shapes[:, 1].view(S, 1, 1, 1)
+            self._frame_mask = (torch.arange(H, device=self.device).view(1, 1, H, 1) < fh) & \
+                               (torch.arange(W, device=self.device).view(1, 1, 1, W) < fw)            # (S, 1, H, W)
+            zero = torch.zeros((), **f32)
+            full = torch.full((S, B, H, W), self.weight_scalar, **f32) if self.weights is None else self.weights
+            if tuple(full.shape) != (S, B, H, W):
+                raise ValueError("weights must be a scalar, (S, B, H, W) = %s or per-scene arrays, not %s"
+                                 % ((S, B, H, W), tuple(full.shape)))
+            self.weights, self.weight_scalar = torch.where(self._frame_mask, full, zero).contiguous(), 1.0
+            self.images = torch.where(self._frame_mask, self.images, zero).contiguous()
         self.sed = [torch.zeros((S, K, B), **f32) for _ in range(2)]
         # (_morph=False: a gradient batch of from_observations, whose fit reads the state's morphologies instead)
         self.morph = [torch.zeros((S, K, H, W) if _morph else (1,), **f32) for _ in range(2)]
@@ -380,11 +490,18 @@ class BlendBatch(object):
     # Every call into the library's loops goes through these two and _fit_observations.  The *_constrained entry points
     # with a NULL member read that setting from the batch's scalars, and with prior = NULL step without one.
     def _lib_fit(self, ps, max_iter, e_rel, approximate_L, check_every):
+        if self.frame_shapes is not None:           # (never with a prior: _refuse_frames_prior)
+            return _lib.check(_lib.lib.scarlet_fit_frames(
+                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(max_iter), float(e_rel),
+                int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
         return _lib.check(_lib.lib.scarlet_fit_constrained(
             ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(max_iter),
             float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
 
     def _lib_update(self, ps, in_iteration):
+        if self.frame_shapes is not None:
+            return _lib.check(_lib.lib.scarlet_source_update_frames(
+                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(in_iteration), _lib.stream_ptr()))
         return _lib.check(_lib.lib.scarlet_source_update_constrained(
             ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(in_iteration),
             _lib.stream_ptr()))
@@ -408,6 +525,10 @@ class BlendBatch(object):
         IndexError for a source outside the image; here it is a ValueError before anything is launched.
         The centres of absent components are not read and not checked."""
         c = centers
+        if self.frame_shapes is not None:
+            hw = self.frame_shapes.view(self.S, 1, 2)
+            if bool(((c < 0) | (c >= hw))[self._present()].any().item()):
+                raise ValueError("a centre lies outside its scene's own frame (frame_shapes)")
         bad = (c[..., 0] < 0) | (c[..., 0] >= self.H) | (c[..., 1] < 0) | (c[..., 1] >= self.W)
         if self.n_components is not None:
             bad &= self._present()
@@ -464,6 +585,8 @@ class BlendBatch(object):
             sed = t.where(present.view(self.S, self.K, 1), sed.expand_as(self.sed[0]), t.zeros((), dtype=sed.dtype, device=self.device))
             morph = t.where(present.view(self.S, self.K, 1, 1), morph.expand_as(self.morph[0]),
                             t.zeros((), dtype=morph.dtype, device=self.device))
+        if self.frame_shapes is not None:                # pixels outside a scene's frame stay zero in both buffers
+            morph = t.where(self._frame_mask, morph.expand_as(self.morph[0]), t.zeros((), dtype=morph.dtype, device=self.device))
         for b in range(2):
             self.sed[b].copy_(sed)
             self.morph[b].copy_(morph)
@@ -501,9 +624,13 @@ class BlendBatch(object):
         return self._pick(self.morph)
 
     def scene(self, s):
-        """Current (sed, morph) of scene s: (n, B) and (n, H, W) tensors of its n = n_components[s] components."""
+        """Current (sed, morph) of scene s: (n, B) and (n, H, W) tensors of its n = n_components[s] components; of a
+        ragged-frame batch the morphologies on the scene's own frame, (n, h_s, w_s)."""
         n = self.K if self.n_components is None else int(self.n_components[s].item())
         c = int(self.cur[s].item())
+        if self.frame_shapes is not None:
+            h, w = (int(v) for v in self.frame_shapes[s].tolist())
+            return self.sed[c][s, :n], self.morph[c][s, :n, :h, :w]
         return self.sed[c][s, :n], self.morph[c][s, :n]
 
     def mse(self, s=0):
@@ -513,6 +640,10 @@ class BlendBatch(object):
 
     def raise_on_status(self):
         st = self.status.cpu().numpy()
+        if (st & _lib.STATUS_BAD_FRAME).any():
+            bad = np.nonzero(st & _lib.STATUS_BAD_FRAME)[0]
+            raise ValueError("frame_shapes of scenes {} lie outside 1..{} x 1..{}; they were left untouched and "
+                             "inactive".format(bad.tolist(), self.H, self.W))
         if (st & _lib.STATUS_CENTER_AT_EDGE).any():
             bad = np.nonzero(st & _lib.STATUS_CENTER_AT_EDGE)[0][:5]
             raise ValueError("max_pixel window left the image in scenes {} (the reference fails "
@@ -582,6 +713,10 @@ class BlendBatch(object):
                 setattr(ps, name, _lib.ptr(x))
             nbytes = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._c), ctypes.byref(ps))
             scratch = self._products_scratch(nbytes)
+            if self.frame_shapes is not None:       # nothing outside each scene's own frame
+                _lib.check(_lib.lib.scarlet_batch_products_frames(ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(ps),
+                                                                  _lib.ptr(scratch), int(nbytes), _lib.stream_ptr()))
+                return res
             _lib.check(_lib.lib.scarlet_batch_products(ctypes.byref(self._c), ctypes.byref(ps), _lib.ptr(scratch), int(nbytes),
                                                        _lib.stream_ptr()))
             return res
@@ -685,11 +820,14 @@ class BlendBatch(object):
         bg = np.ascontiguousarray(bg_rms, dtype=np.float32)
         assert bg.shape == (self.B,)
         sc = None if sed_scale is None else np.ascontiguousarray(sed_scale, dtype=np.float32)
-        rc = _lib.lib.scarlet_init_extended(
-            ctypes.byref(self._c), bg.ctypes.data_as(ctypes.c_void_p), float(thresh),
-            None if sc is None else sc.ctypes.data_as(ctypes.c_void_p), int(bool(init_symmetric)),
-            int(self.monotonic if init_monotonic is None else bool(init_monotonic)),
-            int(bool(run_update) and not self.constrained), _lib.stream_ptr())
+        args = (bg.ctypes.data_as(ctypes.c_void_p), float(thresh),
+                None if sc is None else sc.ctypes.data_as(ctypes.c_void_p), int(bool(init_symmetric)),
+                int(self.monotonic if init_monotonic is None else bool(init_monotonic)),
+                int(bool(run_update) and not self.constrained), _lib.stream_ptr())
+        if self.frame_shapes is not None:           # each scene's start on its own frame
+            rc = _lib.lib.scarlet_init_extended_frames(ctypes.byref(self._c), ctypes.byref(self._frames), *args)
+        else:
+            rc = _lib.lib.scarlet_init_extended(ctypes.byref(self._c), *args)
         _lib.check(rc)
         if run_update and self.constrained:       # the constructors' update() with each component's own settings
             self.update_sources()
@@ -714,8 +852,12 @@ class BlendBatch(object):
 
         Bad input of the whole call raises ValueError; bad input of single scenes (a bg_rms row with a value <= 0, a
         group of more than MAX_LAYERS members, percentiles not ascending inside (0, 100)) gives those scenes
-        STATUS_BAD_INIT and leaves them untouched and inactive (`raise_on_status` names them)."""
+        STATUS_BAD_INIT and leaves them untouched and inactive (`raise_on_status` names them).
+
+        A ragged-frame batch (`frame_shapes`) starts extended sources only: `kind` raises NotImplementedError."""
         self._refuse_single_init()
+        if self.frame_shapes is not None and kind is not None:
+            raise NotImplementedError("init_sources on a ragged-frame batch starts extended sources only (kind must be None)")
         t = self.torch
         S, K, B = self.S, self.K, self.B
         keep = []
@@ -786,7 +928,11 @@ class BlendBatch(object):
         spec.init_symmetric = int(bool(init_symmetric))
         spec.init_monotonic = int(self.monotonic if init_monotonic is None else bool(init_monotonic))
         spec.run_update = int(bool(run_update) and not self.constrained)
-        _lib.check(_lib.lib.scarlet_init_sources(ctypes.byref(self._c), ctypes.byref(spec), _lib.stream_ptr()))
+        if self.frame_shapes is not None:
+            _lib.check(_lib.lib.scarlet_init_sources_frames(ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(spec),
+                                                            _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.lib.scarlet_init_sources(ctypes.byref(self._c), ctypes.byref(spec), _lib.stream_ptr()))
         self._init_checked = True
         if run_update and self.constrained:
             # the constructors' update() with each component's own settings; scenes with STATUS_BAD_INIT stay untouched
@@ -809,6 +955,7 @@ class BlendBatch(object):
             current stream (the host looks at `active` only every `check_every` iterations), or a list of these.
             `L_components` then holds the constants each component stepped with.  Shapes are those of this batch: for
             one made by `from_observations` the SEDs are (S, K, C) over the model frame's C channels."""
+        self._refuse_frames_prior(prior)
         self._ensure_mse_capacity(max_iter)
         self.active.fill_(1)          # a new fit() call iterates again, like the reference
         if self._init_checked:        # ... except the scenes whose init_sources input was bad
@@ -823,6 +970,7 @@ class BlendBatch(object):
         """One iteration in three separately callable phases (used by tests and by the
         Python-level update() override path).  A batch made by `from_observations` runs one iteration
         of scarlet_fit_observations_constrained (scarlet_fit_observations_prior with one).  `prior`: as in `fit`."""
+        self._refuse_frames_prior(prior)
         self._ensure_mse_capacity(1)
         if self._observations is not None:
             if self._init_checked:
@@ -835,9 +983,15 @@ class BlendBatch(object):
             self._prior_iteration(self._prior_struct(quad), given, fns, float(e_rel), int(bool(approximate_L)))
             return
         s = _lib.stream_ptr()
+        if self.frame_shapes is not None:           # the device check first: the gradient kernels skip the scenes it refuses
+            _lib.check(_lib.lib.scarlet_check_frames(ctypes.byref(self._c), ctypes.byref(self._frames), s))
         _lib.check(_lib.lib.scarlet_backward_step(ctypes.byref(self._c), int(bool(approximate_L)), s))
         self._lib_update(None, 1)
         _lib.check(_lib.lib.scarlet_check_convergence(ctypes.byref(self._c), float(e_rel), s))
+
+    def _refuse_frames_prior(self, prior):
+        if prior is not None and self.frame_shapes is not None:
+            raise NotImplementedError("a ragged-frame batch (frame_shapes) does not take a prior")
 
     # ------------------------------------------------------------------ priors
     def _prior_struct(self, quad):
@@ -928,6 +1082,8 @@ class BlendBatch(object):
             observation's batch itself, so the state gets real (zero) images and the observations' batches keep their
             own morphology planes; the joint fit reads neither.
         _channels : the model frame's channel count where the observations need not reach its last channel (`Blend`)."""
+        if kwargs.get("frame_shapes") is not None:
+            raise NotImplementedError("from_observations does not take frame_shapes (ragged frames)")
         obs = list(observations)
         if not 1 <= len(obs) <= _lib.MAX_OBSERVATIONS:
             raise ValueError("from_observations: 1 to %d observations, not %d" % (_lib.MAX_OBSERVATIONS, len(obs)))
@@ -1064,6 +1220,8 @@ class BlendBatch(object):
         model_psf : None or (P, P), P odd
         The observations' channel slices must tile 0 .. C - 1 in order (the reference's concatenation).  A scene
         whose bg_rms row of observation obs_idx has a value <= 0 gets STATUS_BAD_INIT and stays inactive."""
+        if getattr(self, "frame_shapes", None) is not None:
+            raise NotImplementedError("init_combined on a ragged-frame batch (frame_shapes)")
         if self._observations is None:
             raise ValueError("init_combined needs a batch made by BlendBatch.from_observations")
         t, obs = self.torch, self._observations

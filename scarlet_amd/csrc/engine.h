@@ -496,6 +496,8 @@ struct UpdateArgs {
     const uint8_t *symmetric_c, *monotonic_c;
     const float *l0_c, *l1_c;
     int skip_status;                  // constructor call (force_it0): scenes with one of these status bits are left untouched
+    const int *frame_hw;              // [S][2] (h, w) or NULL: the scene's own frame in the top-left corner of its H x W planes.
+                                      // Read by the RAGGED instantiations only (frame_ok / k_check_frames guard the entries)
 };
 
 // The constraint switches of component c (scarlet_constraints, or the batch's scalars).  Every caller runs one component
@@ -506,6 +508,26 @@ __device__ __forceinline__ float comp_l0(const UpdateArgs &a, int c) { return a.
 __device__ __forceinline__ float comp_l1(const UpdateArgs &a, int c) { return a.l1_c ? a.l1_c[c] : a.l1_thresh; }
 // a scene the constructors' update leaves alone (SCARLET_STATUS_BAD_INIT / BAD_COUNT under scarlet_source_update_constrained)
 __device__ __forceinline__ bool update_skips_scene(const UpdateArgs &a, int s) { return a.skip_status && (a.status[s] & a.skip_status); }
+
+// Ragged frames: scene s's own frame (h, w) out of frame_hw, as uniform values (s is uniform: scalar loads).  False for an
+// entry outside 1..H x 1..W (k_check_frames gave the scene SCARLET_STATUS_BAD_FRAME): the caller returns before it reads
+// a plane, so an entry is never a loop bound unless it lies inside the padded plane.
+__device__ __forceinline__ bool frame_ok(const int *frame_hw, int s, int H, int W, int &h, int &w)
+{
+    h = frame_hw[2 * s]; w = frame_hw[2 * s + 1];
+    return h >= 1 && h <= H && w >= 1 && w <= W;
+}
+// zero the pixels of the stride-PW plane gm [PH][PW] that lie outside its h x w frame (whole workgroup or whole wave:
+// thread `tid` of `nthreads`)
+__device__ __forceinline__ void zero_outside_frame(float *gm, int PH, int PW, int h, int w, int tid, int nthreads)
+{
+    const int right = PW - w;                                      // columns w .. PW - 1 of the frame's rows
+    for (int i = tid; i < h * right; i += nthreads) {
+        const int y = i / right, x = w + (i - y * right);
+        gm[y * PW + x] = 0.f;
+    }
+    for (int i = h * PW + tid; i < PH * PW; i += nthreads) gm[i] = 0.f;        // rows h .. PH - 1
+}
 
 // the step that scales the sparse_l0 / sparse_l1 cut (update.py:71-82): 1 / L_morph of the scene, or of the component
 // itself when it stepped with a prior's constant added (component.py:177-187)
@@ -525,7 +547,10 @@ __device__ __forceinline__ float update_step_morph(const UpdateArgs &a, int s, i
 #define SC_BOX_R (SC_COMPACT_LAST / 2)           // levels <= 46 stay within 23 pixels of the peak
 #define SC_BOX_LW (2 * SC_BOX_R + 3)
 #define SC_BOX_FLOATS ((2 * SC_BOX_R + 1) * SC_BOX_LW)
-template <int MODE>
+// RAGGED: the component's scene has its own frame (UpdateArgs::frame_hw) in the top-left corner of the H x W plane.  The
+// tile is built with the scene's bounds (every operator takes its bounds from the tile), only the scene's pixels are
+// loaded from the stride-W plane, and the rest of the plane is written as zero.  LDS is laid out for the padded frame.
+template <int MODE, bool RAGGED = false>
 __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
 {
     constexpr bool GT = MODE == 2;
@@ -536,21 +561,25 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     if (a.only_flagged && !a.only_flagged[c]) return;
     if (update_skips_scene(a, s)) return;
     const bool symmetric = comp_symmetric(a, c), monotonic = comp_monotonic(a, c);
-    const int H = a.H, W = a.W, HW = H * W, B = a.B;
-    const int hp = round16(H), wp = round16(W);
+    // PH x PW: the plane in HBM (what LDS and the scratch are laid out for);  H x W: the frame the operators see
+    const int PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
+    int fh = PH, fw = PW;
+    if (RAGGED && !frame_ok(a.frame_hw, s, PH, PW, fh, fw)) return;
+    const int H = fh, W = fw, HW = H * W;
+    const int hp = round16(PH), wp = round16(PW);
     Tile t; t.H = H; t.W = W;
     float *scr, *av;
     if (GT) {
-        t.LW = W; t.m = nullptr;                    // set below: the plane itself
+        t.LW = PW; t.m = nullptr;                   // set below: the plane itself
         scr = a.gscratch + (size_t)c * hp * scratch_stride(wp);
         av = lds;
     } else if (MODE == 1) {
-        t.LW = tile_stride(W); t.m = lds;
+        t.LW = tile_stride(PW); t.m = lds;
         scr = a.gscratch + (size_t)c * hp * scratch_stride(wp);
-        av = lds + H * t.LW;
+        av = lds + PH * t.LW;
     } else {
-        t.LW = tile_stride(W); t.m = lds;
-        scr = lds + H * t.LW;
+        t.LW = tile_stride(PW); t.m = lds;
+        scr = lds + PH * t.LW;
         av = scr + hp * scratch_stride(wp);
     }
     // (sized by update_lds_bytes, tile_stage_lds_bytes, plane_lds_bytes for MODE 0, 1, 2: prox_ops.h)
@@ -566,24 +595,25 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
 
     const int c0 = a.cur[s];
     const int wbuf = a.in_iteration ? 1 - c0 : c0;
-    float *gm = a.morph[wbuf] + (size_t)c * HW;
-    // float4 groups walked without divisions: +256 groups per step
-    const bool vec4 = (W & 3) == 0;
-    const int gpr = W >> 2, ngroups = HW >> 2;
+    float *gm = a.morph[wbuf] + (size_t)c * PHW;
+    // float4 groups walked without divisions: +256 groups per step.  (RAGGED: a row of the scene ends at W, so both the
+    // frame's and the plane's width must be multiples of 4; group (y, xq) is float4 y * PW / 4 + xq of the plane)
+    const bool vec4 = (W & 3) == 0 && (!RAGGED || (PW & 3) == 0);
+    const int gpr = W >> 2, ngroups = HW >> 2, pgpr = PW >> 2;
     const int dyq = vec4 ? SC_BLOCK / gpr : 0, dxq = vec4 ? SC_BLOCK - dyq * gpr : 0;
     const int y0 = vec4 ? (int)threadIdx.x / gpr : 0, x0 = vec4 ? (int)threadIdx.x - y0 * gpr : 0;
     if (GT) t.m = gm;
     else if (vec4) {
         int y = y0, xq = x0;
         for (int g = threadIdx.x; g < ngroups; g += SC_BLOCK) {
-            lds_store4(t.m + y * t.LW + (xq << 2), reinterpret_cast<const float4 *>(gm)[g]);
+            lds_store4(t.m + y * t.LW + (xq << 2), reinterpret_cast<const float4 *>(gm)[RAGGED ? y * pgpr + xq : g]);
             y += dyq; xq += dxq;
             if (xq >= gpr) { xq -= gpr; ++y; }
         }
     } else
         for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
             const int y = i / W, x = i - y * W;
-            t.m[y * t.LW + x] = gm[i];
+            t.m[y * t.LW + x] = gm[RAGGED ? y * PW + x : i];
         }
     if (threadIdx.x == 0) stat = 0;
     __syncthreads();
@@ -658,7 +688,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     // sparse_l0 / sparse_l1 (update.py:71-82; config 5), positive (update.py:27-32),
     // normalized('morph_max') (update.py:62-65)
     const float step_morph = update_step_morph(a, s, c);
-    const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * HW : nullptr;
+    const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * PHW : nullptr;
     const float l0t = comp_l0(a, c), l1t = comp_l1(a, c);
     const float l0 = l0t >= 0.f ? l0t * step_morph : -1.f;
     const float l1 = l1t >= 0.f ? l1t * step_morph : -1.f;
@@ -693,9 +723,10 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
                 if (regular) { const float q = v[e] * rnorm; o[e] = fmaf(fmaf(-q, norm, v[e]), rnorm, q); }   // v / norm, see fused2.h
                 else o[e] = v[e] / norm;
             }
-            reinterpret_cast<float4 *>(gm)[g] = make_float4(o[0], o[1], o[2], o[3]);
+            const int gi = RAGGED ? y * pgpr + xq : g;
+            reinterpret_cast<float4 *>(gm)[gi] = make_float4(o[0], o[1], o[2], o[3]);
             if (gl) {
-                const float4 l = reinterpret_cast<const float4 *>(gl)[g];
+                const float4 l = reinterpret_cast<const float4 *>(gl)[gi];
                 const float e0 = l.x - o[0], e1 = l.y - o[1], e2 = l.z - o[2], e3 = l.w - o[3];
                 d2f += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
             }
@@ -709,6 +740,12 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
         if (n2 != n2 && norm == norm) {
             // a NaN pixel away from the peak: np.max is NaN and the reference's morph becomes NaN everywhere
             norm = __builtin_nanf("");
+            if (RAGGED) {
+                for (int g = threadIdx.x; g < ngroups; g += SC_BLOCK) {
+                    const int y = g / gpr;
+                    reinterpret_cast<float4 *>(gm)[y * pgpr + (g - y * gpr)] = make_float4(norm, norm, norm, norm);
+                }
+            } else
             for (int g = threadIdx.x; g < ngroups; g += SC_BLOCK) reinterpret_cast<float4 *>(gm)[g] = make_float4(norm, norm, norm, norm);
             d2 = norm;
         }
@@ -726,13 +763,15 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
         for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
             const int y = i / W, x = i - y * W;
             const float v = t.m[y * t.LW + x] / norm;
-            gm[i] = v;
-            if (gl) { const float d = gl[i] - v; d2 += (double)(d * d); }
+            const int gi = RAGGED ? y * PW + x : i;
+            gm[gi] = v;
+            if (gl) { const float d = gl[gi] - v; d2 += (double)(d * d); }
             n2 += (double)(v * v);
         }
         d2 = block_sum(d2, red);
         n2 = block_sum(n2, red);
     }
+    if (RAGGED) zero_outside_frame(gm, PH, PW, H, W, threadIdx.x, SC_BLOCK);       // whatever the gradient step wrote there
     if (threadIdx.x == 0 && (!(norm > 0.f) || isinf(norm))) stat |= SCARLET_STATUS_NONFINITE;
     if (threadIdx.x == 0) {
         float *gs = a.sed[wbuf] + (size_t)c * B;
@@ -846,29 +885,34 @@ __global__ void k_converge(int S, int K, const double *conv, int *flags, int *ac
 // ------------------------------------------------------------------------------------
 // k_source_update_w: the same pipeline with one WAVE per component (wave_ops.h), four
 // components per 256-thread workgroup, no workgroup barriers.  H, W <= 64.
+// RAGGED: as in k_source_update -- the tile has the scene's own bounds, the LDS layout is the padded frame's
+template <bool RAGGED = false>
 __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave)
 {
     const int s = c / a.K;
-    const int H = a.H, W = a.W, HW = H * W, B = a.B;
+    const int PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
+    int fh = PH, fw = PW;
+    if (RAGGED && !frame_ok(a.frame_hw, s, PH, PW, fh, fw)) return;
+    const int H = fh, W = fw, HW = H * W;
     const int lane = lane_id();
-    Tile t; t.H = H; t.W = W; t.LW = tile_stride(W); t.m = lds_wave;
-    float *vec = lds_wave + H * t.LW;
+    Tile t; t.H = H; t.W = W; t.LW = tile_stride(PW); t.m = lds_wave;
+    float *vec = lds_wave + PH * t.LW;
     const int c0 = a.cur[s];
     const int wbuf = a.in_iteration ? 1 - c0 : c0;
-    float *gm = a.morph[wbuf] + (size_t)c * HW;
-    const bool vec4 = (W & 3) == 0;                     // float4 groups, rows 8-byte aligned in LDS
-    const int gpr = W >> 2, ngroups = HW >> 2;
+    float *gm = a.morph[wbuf] + (size_t)c * PHW;
+    const bool vec4 = (W & 3) == 0 && (!RAGGED || (PW & 3) == 0);      // float4 groups, rows 8-byte aligned in LDS
+    const int gpr = W >> 2, ngroups = HW >> 2, pgpr = PW >> 2;
     const int dyq = vec4 ? SC_WAVE / gpr : 0, dxq = vec4 ? SC_WAVE - dyq * gpr : 0;    // +64 groups per step
     const int y0 = vec4 ? lane / gpr : 0, x0 = vec4 ? lane - y0 * gpr : 0;
     if (vec4) {
         int y = y0, xq = x0;
         for (int g = lane; g < ngroups; g += SC_WAVE) {
-            lds_store4(t.m + y * t.LW + (xq << 2), reinterpret_cast<const float4 *>(gm)[g]);
+            lds_store4(t.m + y * t.LW + (xq << 2), reinterpret_cast<const float4 *>(gm)[RAGGED ? y * pgpr + xq : g]);
             y += dyq; xq += dxq;
             if (xq >= gpr) { xq -= gpr; ++y; }
         }
     } else
-        for (int i = lane; i < HW; i += SC_WAVE) t.m[(i / W) * t.LW + (i % W)] = gm[i];
+        for (int i = lane; i < HW; i += SC_WAVE) t.m[(i / W) * t.LW + (i % W)] = gm[RAGGED ? (i / W) * PW + (i % W) : i];
     wave_sync();
     const int it = a.force_it0 ? 0 : a.it[s] + (a.in_iteration ? 1 : 0);
     int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
@@ -889,7 +933,7 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
     if (monotonic) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
     if (lane == 0) { a.centers[2 * c] = cy; a.centers[2 * c + 1] = cx; }
     const float step_morph = update_step_morph(a, s, c);
-    const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * HW : nullptr;
+    const float *gl = a.in_iteration ? a.morph[c0] + (size_t)c * PHW : nullptr;
     const float l0t = comp_l0(a, c), l1t = comp_l1(a, c);
     const float l0 = l0t >= 0.f ? l0t * step_morph : -1.f;
     const float l1 = l1t >= 0.f ? l1t * step_morph : -1.f;
@@ -922,9 +966,10 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
                 if (regular) { const float q = v[e] * rnorm; o[e] = fmaf(fmaf(-q, norm, v[e]), rnorm, q); }   // v / norm, see fused2.h
                 else o[e] = v[e] / norm;
             }
-            reinterpret_cast<float4 *>(gm)[g] = make_float4(o[0], o[1], o[2], o[3]);
+            const int gi = RAGGED ? y * pgpr + xq : g;
+            reinterpret_cast<float4 *>(gm)[gi] = make_float4(o[0], o[1], o[2], o[3]);
             if (gl) {
-                const float4 l = reinterpret_cast<const float4 *>(gl)[g];
+                const float4 l = reinterpret_cast<const float4 *>(gl)[gi];
                 const float e0 = l.x - o[0], e1 = l.y - o[1], e2 = l.z - o[2], e3 = l.w - o[3];
                 d2f += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
             }
@@ -935,6 +980,12 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
         if (__any(n2f != n2f) && norm == norm) {
             // a NaN pixel away from the peak: np.max is NaN and the reference's morph becomes NaN everywhere
             norm = __builtin_nanf("");
+            if (RAGGED) {
+                for (int g = lane; g < ngroups; g += SC_WAVE) {
+                    const int y = g / gpr;
+                    reinterpret_cast<float4 *>(gm)[y * pgpr + (g - y * gpr)] = make_float4(norm, norm, norm, norm);
+                }
+            } else
             for (int g = lane; g < ngroups; g += SC_WAVE) reinterpret_cast<float4 *>(gm)[g] = make_float4(norm, norm, norm, norm);
             d2f = norm; n2f = norm;
         }
@@ -953,11 +1004,13 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
         if (__any(anynan)) norm = __builtin_nanf("");
         for (int i = lane; i < HW; i += SC_WAVE) {
             const float v = t.m[(i / W) * t.LW + (i % W)] / norm;
-            gm[i] = v;
-            if (gl) { const float d = gl[i] - v; d2 += (double)(d * d); }
+            const int gi = RAGGED ? (i / W) * PW + (i % W) : i;
+            gm[gi] = v;
+            if (gl) { const float d = gl[gi] - v; d2 += (double)(d * d); }
             n2 += (double)(v * v);
         }
     }
+    if (RAGGED) zero_outside_frame(gm, PH, PW, H, W, lane, SC_WAVE);               // whatever the gradient step wrote there
     if (!(norm > 0.f) || isinf(norm)) stat |= SCARLET_STATUS_NONFINITE;
     d2 = wave_sum(d2); n2 = wave_sum(n2);
     // SED: positive, * norm (update.py:27-32,62-65) and its convergence sums
@@ -991,4 +1044,17 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w(UpdateArgs a)
     if (update_skips_scene(a, c / a.K)) return;
     const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;      // wave_tile_floats (wave_ops.h)
     wave_pipeline(a, c, lds + (size_t)wid * per_wave);
+}
+// ... for a batch whose scenes have their own frames (UpdateArgs::frame_hw)
+__global__ __launch_bounds__(SC_BLOCK) void k_source_update_w_ragged(UpdateArgs a)
+{
+    extern __shared__ __align__(16) float lds[];
+    const int wid = threadIdx.x / SC_WAVE;
+    const int c = uniform((int)(blockIdx.x * SC_NWAVES + wid));
+    if (c >= a.S * a.K) return;
+    if (!a.force_it0 && !a.active[c / a.K]) return;
+    if (c % a.K >= scene_ncomp(a.ncomp, c / a.K, a.K)) return;
+    if (update_skips_scene(a, c / a.K)) return;
+    const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;
+    wave_pipeline<true>(a, c, lds + (size_t)wid * per_wave);
 }

@@ -8,10 +8,12 @@
 // (source.py:165-167).  The tile holds the float64 coadd afterwards; returns the sweep level past which nothing is
 // kept (the sweep may stop once three levels hold nothing above the cutoff: the levels beyond cannot exceed it
 // either) and the noise cutoff in `cutoff`.
-template <bool GT>
+// RAGGED: the tile is a scene's own frame in the top-left corner of image planes of PHW pixels with row stride PW.
+template <bool GT, bool RAGGED = false>
 __device__ __forceinline__ int init_detect_tile(TileT<double> &t, const float *img, int B, int cy, int cx,
                                                 const float *sed_s, const double (&bg)[SC_BMAX], double thresh,
-                                                int do_symmetric, int do_monotonic, int no_hybrid, double &cutoff)
+                                                int do_symmetric, int do_monotonic, int no_hybrid, double &cutoff,
+                                                int PW = 0, int PHW = 0)
 {
     const int H = t.H, W = t.W, HW = H * W;
     double wb[SC_BMAX], jac = 0, var = 0;
@@ -30,7 +32,7 @@ __device__ __forceinline__ int init_detect_tile(TileT<double> &t, const float *i
         double acc = 0;
 #pragma unroll
         for (int b = 0; b < SC_BMAX; ++b)
-            if (b < B && wb[b] != 0) acc += wb[b] * (double)img[(size_t)b * HW + i];
+            if (b < B && wb[b] != 0) acc += wb[b] * (double)img[RAGGED ? (size_t)b * PHW + (i / W) * PW + (i % W) : (size_t)b * HW + i];
         t.m[(i / W) * t.LW + (i % W)] = acc / jac;
     }
     __syncthreads();
@@ -95,6 +97,7 @@ struct InitSrcArgs {
     const float *perc;                // [S][K] or NULL (25)
     double thresh;
     int do_symmetric, do_monotonic, group_symmetric, no_hybrid;
+    const int *frame_hw;              // scarlet_batch::frame_hw (NULL: every scene is H x W); read by the RAGGED instantiation
 };
 
 __device__ __forceinline__ int init_kind(const InitSrcArgs &a, int c)
@@ -179,35 +182,41 @@ __device__ __forceinline__ void init_scene_bg(const InitSrcArgs &a, int s, doubl
 __host__ __device__ inline size_t init_tile_bytes(int H, int W) { return sizeof(double) * (size_t)H * (W + 1); }
 
 // ---- ExtendedSource with the scene's own noise and PSF peaks: what k_init_extended does for one row of bg_rms
-template <bool GT>
+// RAGGED: the scene's own frame (frame_hw) bounds the coadd, the symmetry window, the sweep and the centre test; the
+// rest of the H x W plane is written as zero
+template <bool GT, bool RAGGED = false>
 __global__ __launch_bounds__(SC_BLOCK) void k_init_extended_rows(InitSrcArgs a, double *gtile)
 {
     extern __shared__ __align__(16) double ldsd[];
-    const int c = blockIdx.x, s = c / a.K, H = a.H, W = a.W, HW = H * W, B = a.B;
+    const int c = blockIdx.x, s = c / a.K, PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
     __shared__ double red[SC_NWAVES];
     __shared__ float redf[SC_NWAVES], sed_s[SC_BMAX], mmax_s;
     if (c - s * a.K >= a.ncomp[s] || init_kind(a, c) != SCARLET_INIT_EXTENDED) return;
+    int fh = PH, fw = PW;
+    if (RAGGED && !frame_ok(a.frame_hw, s, PH, PW, fh, fw)) return;
+    const int H = fh, W = fw, HW = H * W;
     const int wbuf = a.cur[s];
-    float *gm = a.morph[wbuf] + (size_t)c * HW, *gs = a.sed[wbuf] + (size_t)c * B;
+    float *gm = a.morph[wbuf] + (size_t)c * PHW, *gs = a.sed[wbuf] + (size_t)c * B;
     const int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
-    if (cy < 0 || cy >= H || cx < 0 || cx >= W) { init_empty_outside(gm, gs, HW, B, &a.flags[c], &a.status[s]); return; }
+    if (cy < 0 || cy >= H || cx < 0 || cx >= W) { init_empty_outside(gm, gs, PHW, B, &a.flags[c], &a.status[s]); return; }
     const float mmax = init_model_psf_max(a, redf);
     if (threadIdx.x == 0) mmax_s = mmax;
     __syncthreads();
     init_pixel_sed(a, s, cy, cx, a.model_psf ? &mmax_s : nullptr, sed_s);
-    TileT<double> t; t.H = H; t.W = W; t.LW = W + 1;
-    t.m = GT ? gtile + (size_t)c * H * (W + 1) : ldsd;
+    TileT<double> t; t.H = H; t.W = W; t.LW = PW + 1;
+    t.m = GT ? gtile + (size_t)c * PH * (PW + 1) : ldsd;
     double bg[SC_BMAX], cutoff;
     init_scene_bg(a, s, bg);
-    const int lstop = init_detect_tile<GT>(t, a.images + (size_t)s * B * HW, B, cy, cx, sed_s, bg, a.thresh,
-                                           a.do_symmetric, a.do_monotonic, a.no_hybrid, cutoff);
+    const int lstop = init_detect_tile<GT, RAGGED>(t, a.images + (size_t)s * B * PHW, B, cy, cx, sed_s, bg, a.thresh,
+                                                   a.do_symmetric, a.do_monotonic, a.no_hybrid, cutoff, PW, PHW);
     double cnt = 0;
     for (int i = threadIdx.x; i < HW; i += SC_BLOCK)
         if (init_kept(t, i, cy, cx, cutoff, lstop)) cnt += 1;
     cnt = block_sum(cnt, red);
     const double centre = t.m[cy * t.LW + cx] > cutoff ? t.m[cy * t.LW + cx] : 0.0;
     for (int i = threadIdx.x; i < HW; i += SC_BLOCK)
-        gm[i] = (float)(init_kept(t, i, cy, cx, cutoff, lstop) ? t.m[(i / W) * t.LW + (i % W)] / centre : 0.0);
+        gm[RAGGED ? (i / W) * PW + (i % W) : i] = (float)(init_kept(t, i, cy, cx, cutoff, lstop) ? t.m[(i / W) * t.LW + (i % W)] / centre : 0.0);
+    if (RAGGED) zero_outside_frame(gm, PH, PW, H, W, threadIdx.x, SC_BLOCK);
     if (threadIdx.x < B) gs[threadIdx.x] = sed_s[threadIdx.x];
     if (threadIdx.x == 0)
         a.flags[c] = SCARLET_FLAG_SED_NOT_CONVERGED | SCARLET_FLAG_MORPH_NOT_CONVERGED |

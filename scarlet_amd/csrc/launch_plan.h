@@ -23,7 +23,7 @@ enum BoxInstance { BOX_NONE, BOX_STREAMED, BOX_8_128, BOX_16_256, BOX_8, BOX_16 
 struct UpdateWants {
     bool wave;              // the wave form is allowed (an operator without one, FORCE_BLOCK_UPDATE: false)
     bool gscratch;          // a workspace with `gscratch` stands behind the launch (the operators have none)
-    bool box, box2, exact;  // the box stage (monotonic batches), its second box, the exact-shape instances
+    bool box, box2, exact;  // the box stage (monotonic batches with uniform frames), its second box, the exact-shape instances
 };
 struct UpdatePlan {
     int form;
@@ -75,12 +75,15 @@ struct FusedPlan {
 };
 // per_component: the components carry their own switches (scarlet_constraints); n_iter: the iterations wanted of
 // one launch (only k_fit2x covers more than one)
-inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_component, int n_iter, const FusedSwitches &sw)
+// ragged_frames: the scenes have their own frames (scarlet_frames::frame_hw): no fused kernel takes them
+inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_component, int n_iter, const FusedSwitches &sw,
+                            bool ragged_frames = false)
 {
     FusedPlan p = {FUSED_NONE, SC_BLOCK, 0, true};
     // K > 4: eight tiles leave one workgroup per CU and the general path is faster (measured at K = 6, 8:
     // 2.44 vs 2.58 ms and 3.25 vs 3.90 ms per iteration of 4000 scenes)
     if (approximate_L || b->diff_kernel || b->K > 4 || b->group || sw.no_fused) return p;
+    if (ragged_frames) return p;        // the general path (the constraint kernels' RAGGED forms)
     if (b->H > 64 || b->W > 64 || (b->W & 3) || b->H < 3 || b->W < 3) return p;
     // admission by the four-wave kernel's size; the eight-wave kernel's K <= 4 sets of vectors ask for at most 1 KB
     // more and its exact shape for 76 KB, so without PAD_LDS every admitted launch fits

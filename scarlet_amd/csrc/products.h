@@ -205,7 +205,19 @@ struct ProdObsArgs {
     float *rendered, *residual;      // [S][B][HW] or NULL
     double *loss;                    // k_products_conv: [S][B] or NULL
     double *loss_part;               // k_products_finish: [S][T][B] or NULL
+    const int *frame_hw;             // scarlet_batch::frame_hw; read by the RAGGED instantiations only
 };
+// Ragged frames: pixel (y, x) of plane `plane` lies outside its scene's own frame, where the convolution spills: rendered
+// and residual are written as zero there and the pixel adds nothing to the loss.  (The entries are only compared with.)
+__device__ __forceinline__ bool pr_outside(const ProdObsArgs &a, size_t plane, int pix, int y, int x)
+{
+    const size_t s = plane / a.B;
+    if (y < a.frame_hw[2 * s] && x < a.frame_hw[2 * s + 1]) return false;
+    const size_t i = plane * a.HW + pix;
+    if (a.rendered) a.rendered[i] = 0.f;
+    if (a.residual) a.residual[i] = 0.f;
+    return true;
+}
 // rendered value r of pixel `pix` of plane `plane`: the outputs it feeds; returns its squared weighted residual
 __device__ __forceinline__ double pr_observe(const ProdObsArgs &a, size_t plane, int pix, float r)
 {
@@ -219,6 +231,7 @@ __device__ __forceinline__ double pr_observe(const ProdObsArgs &a, size_t plane,
 
 // The LDS-resident transform (fftconv.h) on compact planes in [n][H][W]: one workgroup per plane renders it with the
 // batch's prepared K-hat (khat [B] or [S * B] planes of Fy x (M + 1)) and feeds rendered / residual / loss from LDS.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(SC_FFT_NT) void k_products_conv(ProdObsArgs a, const float *in, FftPlan p, const float2 *khat,
                                                              int khat_per_scene)
 {
@@ -245,6 +258,7 @@ __global__ __launch_bounds__(SC_FFT_NT) void k_products_conv(ProdObsArgs a, cons
     for (int u = threadIdx.x; u < H * W; u += SC_FFT_NT) {
         const int y = u / W, x = u - y * W;
         const cf v = l.A[y * p.RS + (x >> 1)];
+        if (RAGGED && pr_outside(a, plane, u, y, x)) continue;
         loss += pr_observe(a, plane, u, (x & 1) ? v.y : v.x);
     }
     if (!a.loss) return;
@@ -259,6 +273,7 @@ __global__ __launch_bounds__(SC_FFT_NT) void k_products_conv(ProdObsArgs a, cons
 }
 
 // After the hipFFT chain: the rendered planes lie padded in real [n][g.Fy][g.Fx].  grid (planes of the launch, T)
+template <bool RAGGED = false>
 __global__ __launch_bounds__(SC_BLOCK) void k_products_finish(ProdObsArgs a, const float *real, PsfGeom g)
 {
     __shared__ double red[SC_NWAVES];
@@ -269,6 +284,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_products_finish(ProdObsArgs a, con
     double loss = 0;
     for (int pix = tile * PR_TILE_PIX + threadIdx.x; pix < p_end; pix += SC_BLOCK) {
         const int y = pix / g.W, x = pix - y * g.W;
+        if (RAGGED && pr_outside(a, plane, pix, y, x)) continue;
         loss += pr_observe(a, plane, pix, rp[(size_t)pos_mod(y + g.oy, g.Fy) * g.Fx + pos_mod(x + g.ox, g.Fx)]);
     }
     if (!a.loss_part) return;

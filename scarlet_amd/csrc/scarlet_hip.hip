@@ -849,6 +849,33 @@ static int check_counts(const scarlet_batch *b, void *stream)
     return SCARLET_OK;
 }
 
+// Ragged frames: the same for frame_hw, before any kernel reads a plane.  A scene whose entry lies outside 1..H x 1..W
+// gets SCARLET_STATUS_BAD_FRAME and active = 0.  The kernels that read frame_hw test the entry again themselves
+// (frame_ok, engine.h) and return before they touch a plane, so no entry beyond the padded plane is ever a loop bound --
+// also in the constructors' update, which ignores `active`.
+__global__ void k_check_frames(const int *frame_hw, int S, int H, int W, int *status, int *active)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const int h = frame_hw[2 * s], w = frame_hw[2 * s + 1];
+    if (h < 1 || h > H || w < 1 || w > W) { status[s] |= SCARLET_STATUS_BAD_FRAME; active[s] = 0; }
+}
+static int check_frames(const scarlet_batch *b, const int32_t *frame_hw, void *stream)
+{
+    if (!frame_hw) return SCARLET_OK;
+    hipLaunchKernelGGL(k_check_frames, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
+                       (const int *)frame_hw, b->S, b->H, b->W, b->status, b->active);
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+// the host-side check of the _frames entry points, after check_call: the struct, and what a ragged-frame batch does not take
+static int check_frames_call(const scarlet_batch *b, const scarlet_frames *f)
+{
+    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+    if (f->frame_hw && b->group) return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames) with group: not implemented");
+    return SCARLET_OK;
+}
+
 static int n_tiles(const scarlet_batch *b) { return (b->H * b->W + SC_TILE_PIX - 1) / SC_TILE_PIX; }
 
 // ---- PSF path geometry (fft.py:68-106: next_fast_len(N + P + 3) per axis, last axis even)
@@ -1729,7 +1756,8 @@ __global__ void k_zero_int(int *p) { *p = 0; }
 
 // L_comp: the constants each component stepped with (scarlet_prior::L_comp), or NULL: the scene's
 // cons: the components' own switches, or NULL: the batch's.  skip_status: status bits of the scenes a constructor call leaves alone
-struct UpdateOpts { const double *L_comp; const scarlet_constraints *cons; int skip_status; };
+// frame_hw: scarlet_frames::frame_hw of the batch (or of the view: advanced to its first scene), or NULL
+struct UpdateOpts { const double *L_comp; const scarlet_constraints *cons; int skip_status; const int32_t *frame_hw; };
 // in_iteration = 0: the constructors' call (UpdateArgs::force_it0)
 static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, void *stream, const UpdateOpts &o)
 {
@@ -1751,8 +1779,12 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.symmetric_c = o.cons ? o.cons->symmetric : nullptr; u.monotonic_c = o.cons ? o.cons->monotonic : nullptr;
     u.l0_c = o.cons ? o.cons->l0_thresh : nullptr; u.l1_c = o.cons ? o.cons->l1_thresh : nullptr;
     u.skip_status = o.skip_status;
+    u.frame_hw = (const int *)o.frame_hw;
+    const bool ragged = o.frame_hw != nullptr;
+    if (ragged && b->group) return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames) with group: not implemented");
     u.hybrid_sweep = opt(OPT_NO_HYBRID_SWEEP) ? 0 : 1;
-    const UpdatePlan p = update_plan(b->H, b->W, {!opt(OPT_FORCE_BLOCK_UPDATE), true, b->monotonic && !opt(OPT_NO_BOX),
+    // (a ragged-frame batch runs no box stage: the box kernels take their bounds from the batch's frame)
+    const UpdatePlan p = update_plan(b->H, b->W, {!opt(OPT_FORCE_BLOCK_UPDATE), true, b->monotonic && !opt(OPT_NO_BOX) && !ragged,
                                                   !opt(OPT_NO_BOX2), !opt(OPT_NO_EXACT)});
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(b->S * b->K), block(SC_BLOCK);
@@ -1787,6 +1819,19 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     if (p.form == FORM_TILE_GSCRATCH || p.form == FORM_PLANE) {
         if (!l.has_gscratch) return set_err(SCARLET_E_ARG, "the workspace layout holds no symmetry scratch for this frame");
         u.gscratch = ws_at<float>(b, l.gscratch);
+    }
+    if (ragged) {               // the same forms on each scene's own frame (engine.h RAGGED)
+        switch (p.form) {
+        case FORM_WAVE:
+            rc = launch_lds(k_source_update_w_ragged, dim3((b->S * b->K + SC_NWAVES - 1) / SC_NWAVES), block, p.lds, st, u);
+            break;
+        case FORM_TILE_GSCRATCH: rc = launch_lds(k_source_update<1, true>, grid, block, p.lds, st, u); break;
+        case FORM_TILE: rc = launch_lds(k_source_update<0, true>, grid, block, p.lds, st, u); break;
+        default: rc = launch_lds(k_source_update<2, true>, grid, block, p.lds, st, u);
+        }
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+        return SCARLET_OK;
     }
     switch (p.form) {
     case FORM_WAVE:             // one wave per component, four components per workgroup (wave_ops.h)
@@ -1845,9 +1890,9 @@ static FusedSwitches fused_switches(void)
     return {opt(OPT_NO_EXACT) != 0, opt(OPT_FUSED_V1) != 0, opt(OPT_NO_FUSED) != 0, opt(OPT_NO_PERSIST) != 0, opt(OPT_PERSIST_DBG),
             (size_t)opt(OPT_PAD_LDS)};
 }
-static bool fused_ok(const scarlet_batch *b, int approximate_L)
+static bool fused_ok(const scarlet_batch *b, int approximate_L, bool ragged_frames = false)
 {
-    return fused_plan(b, approximate_L, false, 1, fused_switches()).kernel != FUSED_NONE;
+    return fused_plan(b, approximate_L, false, 1, fused_switches(), ragged_frames).kernel != FUSED_NONE;
 }
 // n_iter > 1: that many iterations in ONE launch where the persistent form exists (k_fit2: the headline shape's
 // exact instance); *done receives the number of iterations the launch covers
@@ -2012,15 +2057,18 @@ extern "C" int scarlet_backward_step_prior(scarlet_batch *b, const scarlet_prior
     return rc ? rc : backward_call(b, p, approximate_L, 1, stream);
 }
 
-static int update_call(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int in_iteration, void *stream)
+static int update_call(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int in_iteration, void *stream,
+                       const int32_t *frame_hw = nullptr)
 {
-    const int rc = check_counts(b, stream);
+    int rc = check_counts(b, stream);
+    if (!rc) rc = check_frames(b, frame_hw, stream);
     if (rc) return rc;
     // the constructors' call (in_iteration = 0) ignores `active`: a scene the initialisation refused stays untouched
     // (BAD_COUNT scenes have no present component, scene_ncomp)
     const bool any = cons_any(c);
     const int skip = (any && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
-    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, stream, {p ? p->L_comp : nullptr, any ? c : nullptr, skip});
+    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, stream,
+                         {p ? p->L_comp : nullptr, any ? c : nullptr, skip, frame_hw});
 }
 extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *stream)
 {
@@ -2041,22 +2089,23 @@ extern "C" int scarlet_source_update_constrained(scarlet_batch *b, const scarlet
 
 // One observation: the fused launch where it applies (never with a prior), two half-batches on two streams where the
 // layout splits the batch (see split_views; never with a prior), the general step otherwise.
+// frame_hw: the scenes' own frames (scarlet_fit_frames; never with a prior), or NULL
 static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const scarlet_prior *p, int max_iter, double e_rel,
-                    int approximate_L, int check_every, void *stream)
+                    int approximate_L, int check_every, void *stream, const int32_t *frame_hw = nullptr)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
-    if ((rc = check_counts(b, stream))) return rc;
+    if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const WsLayout l = ws_layout(b, WS_FIX);
-    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0};
+    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw};
     if (p)       // gradients, prior step, constraints, convergence test
         return fit_loop(b, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
             int r = backward_impl(b, l, approximate_L, 1, stream);
             if (!r) r = launch_prior_step(b, p, stream);
             return r ? r : iteration_tail(b, l, e_rel, stream, uo);
         });
-    if (fused_ok(b, approximate_L))      // up to the next host look in one launch where the persistent kernel applies
+    if (fused_ok(b, approximate_L, frame_hw != nullptr))      // up to the next host look in one launch where the persistent kernel applies
         return fit_loop(b, l, max_iter, check_every, st,
                         [&](int want, bool, int *did) { return launch_fused(b, l, e_rel, stream, want, did, cons); });
     SideStream *side = nullptr;
@@ -2087,7 +2136,8 @@ static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const sca
             forked = true;          // (from here on an error joins)
         }
         for (int h = 0; h < 2; ++h) {
-            const UpdateOpts uh = {nullptr, cons ? &cv[h] : nullptr, 0};
+            // (a view's frames: advanced to its first scene, where batch_view advances n_components)
+            const UpdateOpts uh = {nullptr, cons ? &cv[h] : nullptr, 0, frame_hw ? frame_hw + 2 * (size_t)(h ? l.n0 : 0) : nullptr};
             if ((r = backward_impl(&v[h], lv[h], approximate_L, 0, sv[h])) || (r = iteration_tail(&v[h], lv[h], e_rel, sv[h], uh)))
                 return bail(r);
         }
@@ -2112,6 +2162,29 @@ extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constrain
 {
     const int rc = check_call(b, true, c, false, p, max_iter);
     return rc ? rc : fit_call(b, c, p, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+// ---- scenes with their own frames (scarlet_frames): scarlet_fit_constrained / scarlet_source_update_constrained without
+// a prior and with frame_hw; the device check of the entries, alone, for callers that step phase by phase
+extern "C" int scarlet_fit_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c, int max_iter,
+                                  double e_rel, int approximate_L, int check_every, void *stream)
+{
+    int rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
+    if (!rc) rc = check_frames_call(b, f);
+    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, f->frame_hw);
+}
+extern "C" int scarlet_source_update_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
+                                            int in_iteration, void *stream)
+{
+    int rc = check_call(b, c != nullptr, c, false, nullptr);
+    if (!rc) rc = check_frames_call(b, f);
+    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw);
+}
+extern "C" int scarlet_check_frames(scarlet_batch *b, const scarlet_frames *f, void *stream)
+{
+    int rc = check_call(b, false, nullptr, false, nullptr);
+    if (!rc) rc = check_frames_call(b, f);
+    return rc ? rc : check_frames(b, f->frame_hw, stream);
 }
 
 // ---- a low-resolution observation (lowres.h): the shapes, the workspace and the host checks
@@ -2688,16 +2761,22 @@ struct InitArgs {
     int do_symmetric, do_monotonic;
     double thresh;
     int no_hybrid;                    // diagnostics: SCARLET_NO_HYBRID_SWEEP
+    const int *frame_hw;              // scarlet_batch::frame_hw (NULL: every scene is H x W); read by the RAGGED instantiation
 };
 
 // GT: frames whose float64 tile does not fit LDS work on a tile in a temporary HBM buffer
-template <bool GT>
+// RAGGED: the scene's own frame (frame_hw) bounds the coadd, the symmetry window, the sweep and the centre test; the
+// rest of the H x W plane is written as zero
+template <bool GT, bool RAGGED = false>
 __global__ __launch_bounds__(SC_BLOCK) void k_init_extended(InitArgs a, double *gtile)
 {
     extern __shared__ __align__(16) double ldsd[];
-    const int c = blockIdx.x, s = c / a.K, H = a.H, W = a.W, HW = H * W, B = a.B;
-    TileT<double> t; t.H = H; t.W = W; t.LW = W + 1;
-    t.m = GT ? gtile + (size_t)c * H * (W + 1) : ldsd;
+    const int c = blockIdx.x, s = c / a.K, PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
+    int fh = PH, fw = PW;
+    if (RAGGED && !frame_ok(a.frame_hw, s, PH, PW, fh, fw)) return;
+    const int H = fh, W = fw, HW = H * W;
+    TileT<double> t; t.H = H; t.W = W; t.LW = PW + 1;
+    t.m = GT ? gtile + (size_t)c * PH * (PW + 1) : ldsd;
     __shared__ double red[SC_NWAVES];
     __shared__ float sed_s[SC_BMAX];
     if (c - s * a.K >= scene_ncomp(a.ncomp, s, a.K)) return;        // absent component
@@ -2705,8 +2784,8 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_extended(InitArgs a, double *
     if (cy < 0 || cy >= H || cx < 0 || cx >= W) {
         // a source outside the frame (IndexError in the reference, ValueError in BlendBatch): empty component
         const int wb = a.cur[s];
-        float *gm0 = a.morph[wb] + (size_t)c * HW;
-        for (int i = threadIdx.x; i < HW; i += SC_BLOCK) gm0[i] = 0.f;
+        float *gm0 = a.morph[wb] + (size_t)c * PHW;
+        for (int i = threadIdx.x; i < PHW; i += SC_BLOCK) gm0[i] = 0.f;
         if (threadIdx.x < B) a.sed[wb][(size_t)c * B + threadIdx.x] = 0.f;
         if (threadIdx.x == 0) {
             a.flags[c] = SCARLET_FLAG_SED_NOT_CONVERGED | SCARLET_FLAG_MORPH_NOT_CONVERGED | SCARLET_FLAG_NO_VALID_PIXELS;
@@ -2714,18 +2793,18 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_extended(InitArgs a, double *
         }
         return;
     }
-    const float *img = a.images + (size_t)s * B * HW;
+    const float *img = a.images + (size_t)s * B * PHW;
     // get_psf_sed (source.py:41-71): float32 like the reference (images.dtype)
     if (threadIdx.x < B) {
-        float v = img[(size_t)threadIdx.x * HW + cy * W + cx];
+        float v = img[(size_t)threadIdx.x * PHW + cy * PW + cx];
         if (a.has_scale) v = v * (float)a.sed_scale[threadIdx.x];
         sed_s[threadIdx.x] = v;
     }
     __syncthreads();
     // detection coadd, sdss symmetry, thresh=.1 monotone sweep (initsrc.h)
     double cutoff;
-    const int lstop = init_detect_tile<GT>(t, img, B, cy, cx, sed_s, a.bg_rms, a.thresh, a.do_symmetric,
-                                           a.do_monotonic, a.no_hybrid, cutoff);
+    const int lstop = init_detect_tile<GT, RAGGED>(t, img, B, cy, cx, sed_s, a.bg_rms, a.thresh, a.do_symmetric,
+                                                   a.do_monotonic, a.no_hybrid, cutoff, PW, PHW);
     double cnt = 0;
     for (int i = threadIdx.x; i < HW; i += SC_BLOCK)
         if (t.m[(i / W) * t.LW + (i % W)] > cutoff && sweep_level(i / W, i % W, cy, cx) <= lstop) cnt += 1;
@@ -2733,11 +2812,12 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_extended(InitArgs a, double *
     // morph[~mask] = 0 happens BEFORE the centre pixel is read (source.py:174-178)
     const double centre = t.m[cy * t.LW + cx] > cutoff ? t.m[cy * t.LW + cx] : 0.0;
     const int wbuf = a.cur[s];
-    float *gm = a.morph[wbuf] + (size_t)c * HW;
+    float *gm = a.morph[wbuf] + (size_t)c * PHW;
     for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
         const double v = t.m[(i / W) * t.LW + (i % W)];
-        gm[i] = (float)((v > cutoff && sweep_level(i / W, i % W, cy, cx) <= lstop) ? v / centre : 0.0);
+        gm[RAGGED ? (i / W) * PW + (i % W) : i] = (float)((v > cutoff && sweep_level(i / W, i % W, cy, cx) <= lstop) ? v / centre : 0.0);
     }
+    if (RAGGED) zero_outside_frame(gm, PH, PW, H, W, threadIdx.x, SC_BLOCK);
     if (threadIdx.x < B) a.sed[wbuf][(size_t)c * B + threadIdx.x] = sed_s[threadIdx.x];
     if (threadIdx.x == 0) {
         int f = SCARLET_FLAG_SED_NOT_CONVERGED | SCARLET_FLAG_MORPH_NOT_CONVERGED;
@@ -2746,18 +2826,17 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_extended(InitArgs a, double *
     }
 }
 
-extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host, float thresh,
-                                     const float *sed_scale_host, int init_symmetric, int init_monotonic,
-                                     int run_update, void *stream)
+static int init_extended_call(scarlet_batch *b, const float *bg_rms_host, float thresh,
+                              const float *sed_scale_host, int init_symmetric, int init_monotonic,
+                              int run_update, void *stream, const int32_t *frame_hw)
 {
-    int rc = check_batch(b);
-    if (rc) return rc;
+    int rc;
     if (!bg_rms_host) return set_err(SCARLET_E_ARG, "bg_rms is required");
     InitArgs a;
     a.S = b->S; a.K = b->K; a.B = b->B; a.H = b->H; a.W = b->W;
     a.images = b->images; a.sed[0] = b->sed[0]; a.sed[1] = b->sed[1];
     a.morph[0] = b->morph[0]; a.morph[1] = b->morph[1]; a.cur = b->cur; a.centers = b->centers; a.flags = b->flags;
-    a.status = b->status; a.ncomp = b->n_components;
+    a.status = b->status; a.ncomp = b->n_components; a.frame_hw = (const int *)frame_hw;
     a.has_scale = sed_scale_host != nullptr; a.thresh = thresh;
     a.do_symmetric = init_symmetric; a.do_monotonic = init_monotonic;
     a.no_hybrid = opt(OPT_NO_HYBRID_SWEEP) ? 1 : 0;
@@ -2767,27 +2846,47 @@ extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host,
         if (i < b->B && !(a.bg_rms[i] > 0))
             return set_err(SCARLET_E_ARG, "bg_rms must be greater than zero in all channels");
     }
-    if ((rc = check_counts(b, stream))) return rc;
+    if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream))) return rc;
     const InitTilePlan t = init_tile_plan(b->H, b->W, (size_t)b->S * b->K);
+    const bool ragged = frame_hw != nullptr;
     if (t.in_lds) {
-        if ((rc = launch_lds(k_init_extended<false>, dim3(b->S * b->K), dim3(SC_BLOCK), t.lds, (hipStream_t)stream, a, (double *)nullptr)))
+        if ((rc = ragged ? launch_lds(k_init_extended<false, true>, dim3(b->S * b->K), dim3(SC_BLOCK), t.lds, (hipStream_t)stream, a, (double *)nullptr)
+                         : launch_lds(k_init_extended<false>, dim3(b->S * b->K), dim3(SC_BLOCK), t.lds, (hipStream_t)stream, a, (double *)nullptr)))
             return rc;
     } else {
         DevBuf gtile;                                  // one-time setup: a temporary float64 tile per component
         DEV_ALLOC(gtile, t.hbm);
+        if (ragged) hipLaunchKernelGGL((k_init_extended<true, true>), dim3(b->S * b->K), dim3(SC_BLOCK), 0, (hipStream_t)stream, a, gtile.as<double>());
+        else
         hipLaunchKernelGGL(k_init_extended<true>, dim3(b->S * b->K), dim3(SC_BLOCK), 0, (hipStream_t)stream, a, gtile.as<double>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     }
     HIP_TRY(hipGetLastError());
-    return run_update ? launch_update(b, ws_layout(b, WS_PEEK), 0, stream, {}) : SCARLET_OK;   // constructor's self.update()
+    // constructor's self.update()
+    return run_update ? launch_update(b, ws_layout(b, WS_PEEK), 0, stream, {nullptr, nullptr, 0, frame_hw}) : SCARLET_OK;
+}
+extern "C" int scarlet_init_extended(scarlet_batch *b, const float *bg_rms_host, float thresh,
+                                     const float *sed_scale_host, int init_symmetric, int init_monotonic,
+                                     int run_update, void *stream)
+{
+    const int rc = check_batch(b);
+    return rc ? rc : init_extended_call(b, bg_rms_host, thresh, sed_scale_host, init_symmetric, init_monotonic, run_update, stream, nullptr);
+}
+extern "C" int scarlet_init_extended_frames(scarlet_batch *b, const scarlet_frames *f, const float *bg_rms_host, float thresh,
+                                            const float *sed_scale_host, int init_symmetric, int init_monotonic,
+                                            int run_update, void *stream)
+{
+    int rc = check_batch(b);
+    if (!rc) rc = check_frames_call(b, f);
+    return rc ? rc : init_extended_call(b, bg_rms_host, thresh, sed_scale_host, init_symmetric, init_monotonic, run_update, stream,
+                                        f->frame_hw);
 }
 
 // ---- scarlet_init_sources (initsrc.h): every stock source type, per-scene noise and PSF peaks
-extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *spec, void *stream)
+static int init_sources_call(scarlet_batch *b, const scarlet_init_spec *spec, void *stream, const int32_t *frame_hw)
 {
-    int rc = check_batch(b);
-    if (rc) return rc;
+    int rc;
     if (!spec) return set_err(SCARLET_E_ARG, "null init spec");
     if (!spec->bg_rms) return set_err(SCARLET_E_ARG, "bg_rms is required");
     if (spec->model_psf && (spec->model_psf_P <= 0 || !(spec->model_psf_P & 1) || spec->model_psf_P > 2 * SCARLET_MAX_SIDE + 1))
@@ -2804,10 +2903,17 @@ extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *s
     a.perc = spec->flux_percentiles; a.thresh = spec->thresh;
     a.do_symmetric = spec->init_symmetric; a.do_monotonic = spec->init_monotonic; a.group_symmetric = b->symmetric;
     a.no_hybrid = opt(OPT_NO_HYBRID_SWEEP) ? 1 : 0;
+    a.frame_hw = (const int *)frame_hw;
+    const bool ragged = frame_hw != nullptr;
+    // ragged frames: extended sources only -- `kind` must be NULL (it lives on the device: its values cannot be looked at
+    // before the launch); check_frames_call refused groups
+    if (ragged && spec->kind)
+        return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames): scarlet_init_sources_frames starts extended sources only (kind must be NULL)");
     const InitTilePlan t = init_tile_plan(b->H, b->W, (size_t)b->S * b->K);
-    if (t.in_lds && ((rc = allow_lds(k_init_extended_rows<false>, t.lds)) || (rc = allow_lds(k_init_layers<false>, t.lds))))
+    if (t.in_lds && ((rc = allow_lds(k_init_extended_rows<false>, t.lds)) || (rc = allow_lds(k_init_layers<false>, t.lds)) ||
+                     (ragged && (rc = allow_lds(k_init_extended_rows<false, true>, t.lds)))))
         return rc;
-    if ((rc = check_counts(b, stream))) return rc;
+    if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
     // the counts this call works with: a scene with bad input keeps none (one-time set-up: a temporary buffer)
     DevBuf ncomp, gtile;
@@ -2815,7 +2921,13 @@ extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *s
     a.ncomp = ncomp.as<int>();
     hipLaunchKernelGGL(k_init_check, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a);
     const dim3 grid(b->S * b->K);
-    if (t.in_lds) {
+    if (ragged) {
+        if (t.in_lds) hipLaunchKernelGGL((k_init_extended_rows<false, true>), grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
+        else {
+            DEV_ALLOC(gtile, t.hbm);
+            hipLaunchKernelGGL((k_init_extended_rows<true, true>), grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
+        }
+    } else if (t.in_lds) {
         hipLaunchKernelGGL(k_init_extended_rows<false>, grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
         if (b->group) hipLaunchKernelGGL(k_init_layers<false>, grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
     } else {
@@ -2823,18 +2935,30 @@ extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *s
         hipLaunchKernelGGL(k_init_extended_rows<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
         if (b->group) hipLaunchKernelGGL(k_init_layers<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
     }
-    hipLaunchKernelGGL(k_init_point, grid, dim3(SC_BLOCK), 0, st, a);
+    if (!ragged) hipLaunchKernelGGL(k_init_point, grid, dim3(SC_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (spec->run_update) {                          // the constructors' self.update(), on the scenes initialised here
         scarlet_batch c = *b;
         c.n_components = a.ncomp;
-        if ((rc = launch_update(&c, ws_layout(b, WS_PEEK), 0, stream, {}))) {
+        if ((rc = launch_update(&c, ws_layout(b, WS_PEEK), 0, stream, {nullptr, nullptr, 0, frame_hw}))) {
             (void)hipStreamSynchronize(st);
             return rc;
         }
     }
     HIP_TRY(hipStreamSynchronize(st));               // before the temporary buffers go
     return SCARLET_OK;
+}
+
+extern "C" int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *spec, void *stream)
+{
+    const int rc = check_batch(b);
+    return rc ? rc : init_sources_call(b, spec, stream, nullptr);
+}
+extern "C" int scarlet_init_sources_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_init_spec *spec, void *stream)
+{
+    int rc = check_batch(b);
+    if (!rc) rc = check_frames_call(b, f);
+    return rc ? rc : init_sources_call(b, spec, stream, f->frame_hw);
 }
 
 // ---- convergence sums for the Python-override path (the built-in pipeline computes them itself)
@@ -2937,8 +3061,9 @@ static int check_products_scratch(const ProductsPlan &p, const void *scratch, in
 
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 // one evaluation, checked before: every launch of it on `st`
+// frame_hw: the scenes' own frames (scarlet_batch_products_frames), or NULL
 static int launch_products(const scarlet_batch *state, const scarlet_batch *ob, int band0, const scarlet_products *o,
-                           void *scratch, hipStream_t st)
+                           void *scratch, hipStream_t st, const int32_t *frame_hw = nullptr)
 {
     WsLayout l;
     const ProductsPlan p = products_plan_of(ob, state->K, o, WS_FIX, &l);
@@ -2986,6 +3111,7 @@ static int launch_products(const scarlet_batch *state, const scarlet_batch *ob, 
         r.B = B; r.HW = HW; r.T = p.T;
         r.images = a.images; r.weights = ob->weights; r.weight_scalar = ob->weight_scalar;
         r.rendered = o->rendered; r.residual = o->residual;
+        r.frame_hw = (const int *)frame_hw;      // scenes with their own frames: nothing outside them (the RAGGED instantiations)
         const int64_t kplane = p.psf == PRODUCTS_PSF_LDS ? (int64_t)l.plan.Fy * (l.plan.M + 1) : (int64_t)l.geom.Fy * l.geom.Fxh;
         const float2 *khat = ws_at<const float2>(ob, p.psf == PRODUCTS_PSF_LDS ? l.lds_khat : l.khat);
         for (int s0 = 0; s0 < S; s0 += p.chunk) {
@@ -2997,8 +3123,10 @@ static int launch_products(const scarlet_batch *state, const scarlet_batch *ob, 
                 FftPlan fp = l.plan;
                 fp.tables = ws_at<const float2>(ob, l.lds_tables);
                 r.loss = o->loss;
-                if ((rc = launch_lds(k_products_conv, dim3(planes), dim3(SC_FFT_NT), p.conv_lds, st, r, in, fp, khat,
-                                     (int)ob->diff_kernel_per_scene)))
+                if ((rc = r.frame_hw ? launch_lds(k_products_conv<true>, dim3(planes), dim3(SC_FFT_NT), p.conv_lds, st, r, in, fp, khat,
+                                                  (int)ob->diff_kernel_per_scene)
+                                     : launch_lds(k_products_conv<false>, dim3(planes), dim3(SC_FFT_NT), p.conv_lds, st, r, in, fp, khat,
+                                                  (int)ob->diff_kernel_per_scene)))
                     return rc;
             } else {
                 const PsfGeom &g = l.geom;
@@ -3012,7 +3140,8 @@ static int launch_products(const scarlet_batch *state, const scarlet_batch *ob, 
                                           per_scene ? planes : B, planes, (int)kplane, 0, 1.0f / ((float)g.Fy * (float)g.Fx), st)))
                     return rc;
                 r.loss_part = a.loss_part;
-                hipLaunchKernelGGL(k_products_finish, dim3(planes, p.T), dim3(SC_BLOCK), 0, st, r, (const float *)real, g);
+                if (r.frame_hw) hipLaunchKernelGGL(k_products_finish<true>, dim3(planes, p.T), dim3(SC_BLOCK), 0, st, r, (const float *)real, g);
+                else hipLaunchKernelGGL(k_products_finish<false>, dim3(planes, p.T), dim3(SC_BLOCK), 0, st, r, (const float *)real, g);
             }
         }
     }
@@ -3049,6 +3178,18 @@ extern "C" int scarlet_batch_products(const scarlet_batch *b, const scarlet_prod
     if (rc) return rc;
     (void)hipGetLastError();              // (what is reported at the end is ours: see check_batch)
     return launch_products(b, b, 0, out, scratch, (hipStream_t)stream);
+}
+// ... of a batch whose scenes have their own frames: rendered and residual are zero outside them (the spill of a
+// difference kernel is masked in the kernels; without one they are zero there because the morphologies and the images are)
+extern "C" int scarlet_batch_products_frames(const scarlet_batch *b, const scarlet_frames *f, const scarlet_products *out,
+                                             void *scratch, int64_t scratch_bytes, void *stream)
+{
+    int rc = check_products(b, b, 0, out);
+    if (!rc && !f) rc = set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+    if (!rc) rc = check_products_scratch(products_plan_of(b, b->K, out, WS_PEEK, nullptr), scratch, scratch_bytes);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    return launch_products(b, b, 0, out, scratch, (hipStream_t)stream, f->frame_hw);
 }
 
 // ---- rendered / residual / loss of a LOW-RESOLUTION observation (lowres.h k_lowres_products, lowres_stream.h; the form,
