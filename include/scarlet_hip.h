@@ -411,7 +411,7 @@ int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, do
  * A component without `symmetric` runs no centroid and its `shifts` are not touched; one without `monotonic` is
  * normalised by the maximum over its whole plane.  Batches that take the one-launch iteration (K <= 4, frames up to
  * 64 x 64 with W % 4 == 0, no PSF, exact L, no prior, no group) keep it: the four-wave kernel reads each wave's own
- * component's settings (profile class 4). */
+ * component's settings (profile class 4).  So do ragged-frame batches (scarlet_fit_frames, below) of that size class. */
 typedef struct scarlet_constraints {
     const uint8_t *symmetric;   /* device [S][K], or NULL = b->symmetric for every component */
     const uint8_t *monotonic;   /* device [S][K], or NULL = b->monotonic                     */
@@ -450,8 +450,11 @@ int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_con
  *   - every _frames entry point that iterates, updates or initialises checks the entries on the device first: a scene
  *     whose entry lies outside 1..H x 1..W gets SCARLET_STATUS_BAD_FRAME and active = 0 and is not touched again; the
  *     other scenes go on.  No entry beyond the padded plane is ever used as a loop bound;
- *   - the workspace and the launch forms are those of the padded (H, W).  Such a batch takes the general path (no
- *     one-launch kernels) and runs no box stage beyond 64 pixels;
+ *   - the workspace and the launch forms are those of the padded (H, W).  scarlet_fit_frames takes the one-launch
+ *     iteration where the padded frame meets the four-wave kernel's conditions (K <= 4, H, W <= 64 with W % 4 == 0,
+ *     H >= 3, no PSF, exact L; profile class 4): its ragged-frames instance walks each scene's own pixels only, for
+ *     every B and with or without per-component switches.  No eight-wave or persistent kernel takes such a batch; every
+ *     other one takes the general path, and none runs a box stage beyond 64 pixels;
  *   - SCARLET_E_NOTIMPL, found on the host before any launch: frame_hw with b->group; scarlet_init_sources_frames with
  *     spec->kind (extended sources only).  Priors, scarlet_fit_multi and the scarlet_fit_observations family have no
  *     _frames form.  f == NULL is SCARLET_E_ARG. */
@@ -588,6 +591,16 @@ int64_t scarlet_lowres_large_workspace_bytes_wide(const scarlet_batch *state, co
  * channels the instance is built for; waves; threads per workgroup; dynamic LDS bytes; the LDS limit of the plans;
  * prior; 0}.  Returns 0, or -1 where there is no form (C > SCARLET_MAX_CHANNELS, K > SCARLET_MAX_COMPONENTS). */
 int scarlet_debug_contract_plan(int K, int C, int prior, int32_t *out8);
+/* diagnostics, host-only: the one-launch iteration a fit of `b` takes (launch_plan.h fused_plan) with the frames and the
+ * constraints scarlet_fit_frames / scarlet_fit_constrained would be given (either may be NULL), under the options in
+ * force: {kernel; threads per workgroup; dynamic LDS bytes; 1 = that fits the LDS limit; the LDS limit of the plans;
+ * 1 = ragged frames (f->frame_hw given); 0; 0}.  kernel: 0 = none, the general path; 1, 2 = the four-wave kernel's
+ * per-component instance for B <= 6, B <= 8; 3 = the persistent eight-wave kernel; 4, 5 = the eight-wave kernel's exact
+ * and general instance; 6, 7 = the four-wave kernel for B <= 6, B <= 8; 8, 9 = its ragged-frames instance for B <= 6,
+ * B <= 8.  Reads the structs' own fields only: no device call, no device pointer is dereferenced.  Returns 0, or -1 for
+ * a NULL b or out8. */
+int scarlet_debug_fused_plan(const scarlet_batch *b, const scarlet_frames *f /* or NULL */,
+                             const scarlet_constraints *c /* or NULL */, int approximate_L, int n_iter, int32_t *out8);
 /* bytes of device scratch scarlet_lowres_render_large / _adjoint_large need for n planes: 0 where the LDS form runs;
  * < 0: an error code */
 int64_t scarlet_lowres_op_scratch_bytes(int n, int H, int W, const scarlet_lowres *lr);

@@ -194,6 +194,7 @@ _SIGNATURES = {
     "scarlet_lowres_products_scratch_bytes_wide": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres),
                                                              POINTER(ScarletProducts)]),
     "scarlet_debug_contract_plan": (c_int, [c_int, c_int, c_int, _P]),
+    "scarlet_debug_fused_plan": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints), c_int, c_int, _P]),
     "scarlet_backward_gradients": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_source_update": (c_int, [POINTER(ScarletBatch), c_int, _P]),
     "scarlet_check_convergence": (c_int, [POINTER(ScarletBatch), c_double, _P]),

@@ -53,6 +53,12 @@ struct FusedArgsPC : FusedArgs {
     const uint8_t *symmetric_c, *monotonic_c;
     const float *l0_c, *l1_c;
 };
+// ... for a batch whose scenes have their own frames (scarlet_frames): [S][2] (h, w) in the top-left corner of the padded
+// H x W planes.  k_iterate<KM, BM, FusedArgsFrames> walks the scene's own pixels only and hands the wave operators a Tile
+// with the scene's bounds; the per-component pointers may all be NULL (the batch's scalars).
+struct FusedArgsFrames : FusedArgsPC {
+    const int *frame_hw;
+};
 // Per component and wave of its pair: 64 entries of av, bv, cv (this wave's half), then the header
 // {H W cy cx, magic, dy (2 words), dx (2 words), s} the vectors were made for
 #define SC_KSC_FLOATS 200
@@ -66,11 +72,17 @@ __host__ __device__ inline size_t fused_lds_bytes(int K, int H, int W)
 template <int KM, int BM, class A = FusedArgs>
 __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
 {
-    constexpr bool PC = std::is_same<A, FusedArgsPC>::value;      // per-component constraint switches
+    constexpr bool RAGGED = std::is_same<A, FusedArgsFrames>::value;          // the scenes have their own frames
+    constexpr bool PC = std::is_same<A, FusedArgsPC>::value || RAGGED;        // per-component constraint switches
     extern __shared__ __align__(16) float lds[];
     const int s = blockIdx.x;
     if (!a.active[s]) return;
+    // RAGGED: the scene's frame fh x fw (uniform values) in the top-left corner of the H x W planes; an entry outside
+    // 1..H x 1..W (k_check_frames made the scene inactive) returns here, before any plane or bookkeeping is touched
+    int frame_h = 0, frame_w = 0;
+    if constexpr (RAGGED) { if (!frame_ok(a.frame_hw, s, a.H, a.W, frame_h, frame_w)) return; }
     const int K = a.K, B = a.B, H = a.H, W = a.W, HW = H * W, LW = tile_stride(W);
+    const int fh = RAGGED ? frame_h : H, fw = RAGGED ? frame_w : W;
     const int tile_floats = H * LW;
     float *tiles = lds;
     float *vecs = lds + (size_t)K * tile_floats;             // (fused_lds_bytes)
@@ -92,7 +104,12 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
     const float *sed_in = a.sed[c0] + (size_t)s * K * B;
     float *sed_out = a.sed[1 - c0] + (size_t)s * K * B;
     const int it_new = a.it[s] + 1;
-    const int ngroups = HW >> 2, gpr = W >> 2;           // float4 groups, groups per row
+    // float4 groups, groups per row.  RAGGED: those of the scene's own rows (the last group of a row straddles the
+    // frame's edge when fw % 4 != 0; its columns >= fw are zero in every input and masked wherever a pass writes or
+    // sums them); group (y, xq) is float4 y * (W >> 2) + xq of a padded plane
+    const int ngroups = RAGGED ? fh * ((fw + 3) >> 2) : HW >> 2, gpr = RAGGED ? (fw + 3) >> 2 : W >> 2;
+#define GIDX(g, y, xq) (RAGGED ? (y) * (W >> 2) + (xq) : (g))              /* of a group whose (row, group of the row) is known */
+#define GIDX_OF(g) (RAGGED ? ((g) / gpr) * (W >> 2) + (g) % gpr : (g))     /* of group g of the walk */
     const float *img = a.images + (size_t)s * B * HW;
     const float *wgt = a.weights ? a.weights + (size_t)s * B * HW : nullptr;
     // optional diagnostics: shader-clock stamps at the phase boundaries (never read back here)
@@ -106,7 +123,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
         const int g = tid + j * SC_BLOCK;
 #pragma unroll
         for (int k = 0; k < KM; ++k)
-            mreg[j][k] = (g < ngroups && k < K) ? reinterpret_cast<const float4 *>(min_g + (size_t)k * HW)[g]
+            mreg[j][k] = (g < ngroups && k < K) ? reinterpret_cast<const float4 *>(min_g + (size_t)k * HW)[GIDX_OF(g)]
                                                : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     float4 ireg[PREFETCH ? GPT : 1][PREFETCH ? BM : 1];
@@ -117,7 +134,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
 #pragma unroll
             for (int b = 0; b < BM; ++b)
                 ireg[PREFETCH ? j : 0][PREFETCH ? b : 0] =
-                    (g < ngroups && b < B) ? reinterpret_cast<const float4 *>(img + (size_t)b * HW)[g]
+                    (g < ngroups && b < B) ? reinterpret_cast<const float4 *>(img + (size_t)b * HW)[GIDX_OF(g)]
                                            : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
@@ -230,9 +247,9 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
             for (int b = 0; b < BM; ++b) {
                 if (b < B) {
                     const float4 iv = PREFETCH ? ireg[PREFETCH ? j : 0][PREFETCH ? b : 0]
-                                               : reinterpret_cast<const float4 *>(img + (size_t)b * HW)[g];
+                                               : reinterpret_cast<const float4 *>(img + (size_t)b * HW)[GIDX(g, y, x >> 2)];
                     float4 wv = make_float4(a.weight_scalar, a.weight_scalar, a.weight_scalar, a.weight_scalar);
-                    if (wgt) wv = reinterpret_cast<const float4 *>(wgt + (size_t)b * HW)[g];
+                    if (wgt) wv = reinterpret_cast<const float4 *>(wgt + (size_t)b * HW)[GIDX(g, y, x >> 2)];
                     const float im[4] = {iv.x, iv.y, iv.z, iv.w}, ww[4] = {wv.x, wv.y, wv.z, wv.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -290,7 +307,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
     const int n_present = scene_ncomp(a.ncomp, s, K);
     for (int k = wid; k < n_present; k += SC_NWAVES) {
         const int c = s * K + k;
-        Tile t; t.H = H; t.W = W; t.LW = LW; t.m = tiles + k * tile_floats;
+        Tile t; t.H = fh; t.W = fw; t.LW = LW; t.m = tiles + k * tile_floats;      // (RAGGED: the scene's bounds, the padded frame's stride)
         float *vec = vecs + wid * SC_WAVE_VEC_FLOATS;
         int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
         int stat = 0;
@@ -325,10 +342,24 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
         // flight together: loads queued behind this pass's own stores would wait for them.
         const float4 *last4 = reinterpret_cast<const float4 *>(min_g + (size_t)k * HW);
         float4 lastv[GPW];
+        int walk_dy = 0, walk_dx = 0, walk_y0 = 0, walk_x0 = 0;      // RAGGED: the walk of the passes below, needed here already
+        if constexpr (RAGGED) {
+            walk_dy = SC_WAVE / gpr; walk_dx = SC_WAVE - walk_dy * gpr;
+            walk_y0 = lane / gpr; walk_x0 = lane - walk_y0 * gpr;
+            int y = walk_y0, xq = walk_x0;
+#pragma unroll
+            for (int j = 0; j < GPW; ++j) {
+                const int g = lane + j * SC_WAVE;
+                lastv[j] = g < ngroups ? last4[GIDX(g, y, xq)] : make_float4(0.f, 0.f, 0.f, 0.f);
+                y += walk_dy; xq += walk_dx;
+                if (xq >= gpr) { xq -= gpr; ++y; }
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < GPW; ++j) {
             const int g = lane + j * SC_WAVE;
             lastv[j] = g < ngroups ? last4[g] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         }
         const bool cut = lstop < (1 << 30);
         float l0 = c_l0() >= 0.f ? c_l0() * step_morph : -1.f;
@@ -342,8 +373,8 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
             return v;
         };
         // lane -> (row, float4 group) walk without divisions: +64 groups per step
-        const int dyq = SC_WAVE / gpr, dxq = SC_WAVE - dyq * gpr;
-        const int y0 = lane / gpr, x0 = lane - y0 * gpr;
+        const int dyq = RAGGED ? walk_dy : SC_WAVE / gpr, dxq = RAGGED ? walk_dx : SC_WAVE - dyq * gpr;
+        const int y0 = RAGGED ? walk_y0 : lane / gpr, x0 = RAGGED ? walk_x0 : lane - y0 * gpr;
         float norm;
         if (c_monotonic()) {
             // after the sweep no pixel exceeds the peak pixel (each is capped by a convex
@@ -361,6 +392,12 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
                 v.x = sparse(v.x); v.y = sparse(v.y); v.z = sparse(v.z); v.w = sparse(v.w);
                 v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y;
                 v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w;
+                if constexpr (RAGGED) {             // columns beyond the frame: no pixel of the maximum (nor a NaN of it)
+                    const int x = xq << 2;
+                    if (x + 1 >= fw) v.y = 0.f;
+                    if (x + 2 >= fw) v.z = 0.f;
+                    if (x + 3 >= fw) v.w = 0.f;
+                }
                 anynan |= (v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w);
                 vmax = fmaxf(fmaxf(vmax, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
                 lds_store4(p, v);
@@ -403,8 +440,10 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
                             const float q = v[e] * rnorm;
                             o[e] = fmaf(fmaf(-q, norm, v[e]), rnorm, q);
                         }
+                        // columns beyond the frame: exact zeros in the result, nothing in the sums
+                        if constexpr (RAGGED) { if (e && (xq << 2) + e >= fw) o[e] = 0.f; }
                     }
-                    out4[g] = make_float4(o[0], o[1], o[2], o[3]);
+                    out4[GIDX(g, y, xq)] = make_float4(o[0], o[1], o[2], o[3]);
                     const float e0 = l.x - o[0], e1 = l.y - o[1], e2 = l.z - o[2], e3 = l.w - o[3];
                     d2f += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
                     n2f += (o[0] * o[0] + o[1] * o[1]) + (o[2] * o[2] + o[3] * o[3]);
@@ -424,6 +463,15 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
             // a NaN pixel away from the peak: np.max is NaN and the reference's morph becomes NaN everywhere
             norm = __builtin_nanf("");
             const float4 nan4 = make_float4(norm, norm, norm, norm);
+            if constexpr (RAGGED) {
+                int y = y0, xq = x0;
+                for (int g = lane; g < ngroups; g += SC_WAVE) {
+                    const int x = xq << 2;
+                    out4[GIDX(g, y, xq)] = make_float4(norm, x + 1 < fw ? norm : 0.f, x + 2 < fw ? norm : 0.f, x + 3 < fw ? norm : 0.f);
+                    y += dyq; xq += dxq;
+                    if (xq >= gpr) { xq -= gpr; ++y; }
+                }
+            } else
             for (int g = lane; g < ngroups; g += SC_WAVE) out4[g] = nan4;
             d2f = norm; n2f = norm;
         }
@@ -469,4 +517,6 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void k_iterate(A a)
     }
     STAMP(6);
 #undef STAMP
+#undef GIDX
+#undef GIDX_OF
 }

@@ -67,7 +67,8 @@ struct FusedSwitches {      // (scarlet_hip.hip fused_switches() reads them from
 };
 enum FusedKernel { FUSED_NONE, FUSED_PC_B6, FUSED_PC_B8,        // k_iterate<4, 6 / SC_BMAX, FusedArgsPC>
                    FUSED_FIT2X, FUSED_ITERATE2_EXACT, FUSED_ITERATE2, // k_fit2x, k_iterate2<4, 5, 64>, k_iterate2<4, 5>
-                   FUSED_B6, FUSED_B8 };                        // k_iterate<4, 6 / SC_BMAX>
+                   FUSED_B6, FUSED_B8,                          // k_iterate<4, 6 / SC_BMAX>
+                   FUSED_FRAMES_B6, FUSED_FRAMES_B8 };          // k_iterate<4, 6 / SC_BMAX, FusedArgsFrames>
 struct FusedPlan {
     int kernel, block;
     size_t lds;             // what the launch asks for, PAD_LDS included
@@ -75,7 +76,9 @@ struct FusedPlan {
 };
 // per_component: the components carry their own switches (scarlet_constraints); n_iter: the iterations wanted of
 // one launch (only k_fit2x covers more than one)
-// ragged_frames: the scenes have their own frames (scarlet_frames::frame_hw): no fused kernel takes them
+// ragged_frames: the scenes have their own frames (scarlet_frames::frame_hw).  The four-wave kernel's frames instance
+// takes them for every B, under its own conditions read off the padded frame (it reads the per-component switches where
+// there are any); no eight-wave kernel does.  Every other ragged-frame batch takes the general path.
 inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_component, int n_iter, const FusedSwitches &sw,
                             bool ragged_frames = false)
 {
@@ -83,7 +86,6 @@ inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_
     // K > 4: eight tiles leave one workgroup per CU and the general path is faster (measured at K = 6, 8:
     // 2.44 vs 2.58 ms and 3.25 vs 3.90 ms per iteration of 4000 scenes)
     if (approximate_L || b->diff_kernel || b->K > 4 || b->group || sw.no_fused) return p;
-    if (ragged_frames) return p;        // the general path (the constraint kernels' RAGGED forms)
     if (b->H > 64 || b->W > 64 || (b->W & 3) || b->H < 3 || b->W < 3) return p;
     // admission by the four-wave kernel's size; the eight-wave kernel's K <= 4 sets of vectors ask for at most 1 KB
     // more and its exact shape for 76 KB, so without PAD_LDS every admitted launch fits
@@ -92,7 +94,9 @@ inline FusedPlan fused_plan(const scarlet_batch *b, int approximate_L, bool per_
     // with every shape and switch folded at compile time
     const bool exact64 = b->K == 4 && b->B == 5 && b->H == 64 && b->W == 64 && !b->weights && b->weight_scalar == 1.0f && b->symmetric &&
                          b->monotonic && b->l0_thresh < 0.f && b->l1_thresh < 0.f && !sw.no_exact;
-    if (per_component) {
+    if (ragged_frames) {
+        p.kernel = b->B <= 6 ? FUSED_FRAMES_B6 : FUSED_FRAMES_B8; p.lds = fused_lds_bytes(b->K, b->H, b->W);
+    } else if (per_component) {
         // the four-wave kernel's per-component instance for every B (wave k reads component k's four settings in
         // phase 2), never k_iterate2 / k_fit2x
         p.kernel = b->B <= 6 ? FUSED_PC_B6 : FUSED_PC_B8; p.lds = fused_lds_bytes(b->K, b->H, b->W);

@@ -1896,8 +1896,9 @@ static bool fused_ok(const scarlet_batch *b, int approximate_L, bool ragged_fram
 }
 // n_iter > 1: that many iterations in ONE launch where the persistent form exists (k_fit2: the headline shape's
 // exact instance); *done receives the number of iterations the launch covers
+// frame_hw: the scenes' own frames (the frames instance of the four-wave kernel; per batch: no half-batch views here), or NULL
 static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void *stream, int n_iter, int *done,
-                        const scarlet_constraints *cons)
+                        const scarlet_constraints *cons, const int32_t *frame_hw = nullptr)
 {
     if (done) *done = 1;
     int rc = ensure_tables();
@@ -1919,7 +1920,7 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
     f.stamps = (opt(OPT_STAMPS) && n_partials(b->K, b->B) >= 16) ? ws_at<long long>(b, l.partials) : nullptr;
     if (n_iter > 0xffffff) n_iter = 0xffffff;
     const FusedSwitches sw = fused_switches();
-    const FusedPlan p = fused_plan(b, 0, cons_any(cons), n_iter, sw);
+    const FusedPlan p = fused_plan(b, 0, cons_any(cons), n_iter, sw, frame_hw != nullptr);
     if (p.kernel == FUSED_NONE) return set_err(SCARLET_E_ARG, "no fused kernel for this batch");
     if (!p.fits) return set_err(SCARLET_E_TOO_LARGE, "image tile does not fit in LDS");
     hipStream_t st = (hipStream_t)stream;
@@ -1940,6 +1941,15 @@ static int launch_fused(scarlet_batch *b, const WsLayout &l, double e_rel, void 
         static_cast<FusedArgs &>(fp) = f;
         fp.symmetric_c = cons->symmetric; fp.monotonic_c = cons->monotonic; fp.l0_c = cons->l0_thresh; fp.l1_c = cons->l1_thresh;
         return run(p.kernel == FUSED_PC_B6 ? k_iterate<4, 6, FusedArgsPC> : k_iterate<4, SC_BMAX, FusedArgsPC>, b->S, 1, fp);
+    }
+    case FUSED_FRAMES_B6:
+    case FUSED_FRAMES_B8: {
+        FusedArgsFrames ff;
+        static_cast<FusedArgs &>(ff) = f;
+        ff.symmetric_c = cons ? cons->symmetric : nullptr; ff.monotonic_c = cons ? cons->monotonic : nullptr;
+        ff.l0_c = cons ? cons->l0_thresh : nullptr; ff.l1_c = cons ? cons->l1_thresh : nullptr;
+        ff.frame_hw = (const int *)frame_hw;
+        return run(p.kernel == FUSED_FRAMES_B6 ? k_iterate<4, 6, FusedArgsFrames> : k_iterate<4, SC_BMAX, FusedArgsFrames>, b->S, 1, ff);
     }
     case FUSED_FIT2X: {
         // as many workgroups as the chip keeps resident; the scenes beyond them come from the launch's queue
@@ -2107,7 +2117,7 @@ static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const sca
         });
     if (fused_ok(b, approximate_L, frame_hw != nullptr))      // up to the next host look in one launch where the persistent kernel applies
         return fit_loop(b, l, max_iter, check_every, st,
-                        [&](int want, bool, int *did) { return launch_fused(b, l, e_rel, stream, want, did, cons); });
+                        [&](int want, bool, int *did) { return launch_fused(b, l, e_rel, stream, want, did, cons, frame_hw); });
     SideStream *side = nullptr;
     if (two_pipelines(l) && (rc = side_stream(&side))) return rc;
     if (!side)
@@ -3375,4 +3385,18 @@ extern "C" int scarlet_debug_contract_plan(int K, int C, int prior, int32_t *out
     const int v[8] = {p.kernel, p.cw, p.nw, p.block, (int)p.lds, (int)LDS_LIMIT, p.prior ? 1 : 0, 0};
     for (int i = 0; i < 8; ++i) out8[i] = v[i];
     return p.kernel == CONTRACT_NONE ? -1 : 0;
+}
+
+// diagnostics: fused_plan (launch_plan.h) of a fit of batch b -- with the frames and constraints scarlet_fit_frames /
+// scarlet_fit_constrained would get -- under the options in force: {kernel (FusedKernel), threads, dynamic LDS bytes,
+// fits, LDS limit, ragged, 0, 0}.  Reads the structs' host fields only; no device pointer is dereferenced.
+extern "C" int scarlet_debug_fused_plan(const scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
+                                        int approximate_L, int n_iter, int32_t *out8)
+{
+    if (!b || !out8) return -1;
+    const bool ragged = f && f->frame_hw;
+    const FusedPlan p = fused_plan(b, approximate_L, cons_any(c), n_iter, fused_switches(), ragged);
+    const int v[8] = {p.kernel, p.block, (int)p.lds, p.fits ? 1 : 0, (int)LDS_LIMIT, ragged ? 1 : 0, 0, 0};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return 0;
 }

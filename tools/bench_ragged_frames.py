@@ -2,18 +2,23 @@
 the BASELINE configs and is left alone.
 
 A seeded population of S = 4096 scenes, B = 5, K = 4, heights and widths drawn independently and uniformly from 24..64
-(survey cut-outs: every blend has its own footprint).  `--steps` iterations at e_rel = 0 are timed three ways:
-  (a) ragged   one ragged-frame batch, every scene padded to 64 x 64;
+(survey cut-outs: every blend has its own footprint).  `--steps` iterations at e_rel = 0 are timed four ways:
+  (a) ragged   one ragged-frame batch, every scene padded to 64 x 64: the one-launch iteration of the four-wave
+               kernel's ragged-frames instance (profile class 4);
   (b) buckets  the same scenes grouped into one uniform batch per distinct shape, fitted one after the other -- the only
                way to get the same results without frame_shapes.  Every bucket is built, initialised and warmed up
                before the clock starts; the time is that of the fit calls alone;
-  (c) ceiling  a uniform 64 x 64 batch of S scenes on the general path (the NO_FUSED switch: the path a ragged-frame
-               batch takes), the cost ceiling of (a).
+  (c) ceiling  a uniform 64 x 64 batch of S scenes on the general path (the NO_FUSED switch), the cost ceiling of (d);
+  (d) general  the batch of (a) under the NO_FUSED switch: the general path, which every ragged-frame batch took before
+               the one-launch instance existed and which larger ones still take -- in the same process as (a).
 Each figure: `--warmup` iterations, then `--steps` iterations between two CUDA events, `--repeats` repeats on fresh
-batches, the median.  A fourth run of (a) under scarlet_profile_begin / _end gives the share of the gradient kernels,
-which stream the padded planes: the padding's share of their pixels is 1 - mean(h w) / (H W).
+batches, the median.  One more run of (a) and of (d) under scarlet_profile_begin / _end gives the time per kernel class
+(0 k_grad, 1 k_step, 2 the constraint update, 3 k_converge, 4 the one-launch kernels) and, for (d), the share of the
+gradient kernels, which stream the padded planes: the padding's share of their pixels is 1 - mean(h w) / (H W).
 
-    python tools/bench_ragged_frames.py --out profiles/ragged_frames_bench.json
+    python tools/bench_ragged_frames.py --out ragged_frames_fused_run.json
+
+(profiles/ragged_frames_bench.json is the record of the general path alone, made before leg (d) existed.)
 """
 import argparse
 import ctypes
@@ -63,7 +68,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--scenes", type=int, default=S)
-    ap.add_argument("--out", default=None)
+    ap.add_argument("--out", default="ragged_frames_fused_run.json")
     args = ap.parse_args()
     import torch
     from scarlet_amd import _lib
@@ -117,21 +122,38 @@ def main():
     finally:
         _lib.set_option("NO_FUSED", prev)
     res["ceiling"] = dict(ms=ms, repeats=rep, scene_iterations_per_s=n_scenes * args.steps / ms * 1e3)
+    # (d) the ragged-frame batch on the general path
+    prev = _lib.set_option("NO_FUSED", 1)
+    try:
+        ms, rep = median_of(lambda: [make(block, centers, frame_shapes=shapes)])
+    finally:
+        _lib.set_option("NO_FUSED", prev)
+    res["general"] = dict(ms=ms, repeats=rep, scene_iterations_per_s=n_scenes * args.steps / ms * 1e3)
+    res["general_ms_over_ragged_ms"] = res["general"]["ms"] / res["ragged"]["ms"]
     res["buckets_ms_over_ragged_ms"] = res["buckets"]["ms"] / res["ragged"]["ms"]
     res["ceiling_ms_over_ragged_ms"] = res["ceiling"]["ms"] / res["ragged"]["ms"]
-    # the kernel classes of (a): 0 k_grad, 1 k_step, 2 the constraint update, 3 k_converge
-    b = make(block, centers, frame_shapes=shapes)
-    b.fit(args.warmup, e_rel=0, check_every=0)
-    torch.cuda.synchronize()
-    _lib.check(_lib.lib.scarlet_profile_begin(args.steps))
-    b.fit(args.steps, e_rel=0, check_every=0)
-    tot, cnt = (ctypes.c_double * 8)(), (ctypes.c_int64 * 8)()
-    _lib.check(_lib.lib.scarlet_profile_end(tot, cnt))
-    cls = dict(k_grad=tot[0], k_step=tot[1], update=tot[2], k_converge=tot[3])
-    res["ragged_kernel_ms"] = cls
-    share = (tot[0] + tot[1]) / max(sum(cls.values()), 1e-30)
-    res["gradient_share_of_ragged"] = share
-    res["padding_share_of_ragged"] = share * res["padding_share_of_gradient_pixels"]
+    # the kernel classes of (a) and (d): 0 k_grad, 1 k_step, 2 the constraint update, 3 k_converge, 4 the one-launch kernels
+    def classes(no_fused):
+        prev = _lib.set_option("NO_FUSED", no_fused)
+        try:
+            b = make(block, centers, frame_shapes=shapes)
+            b.fit(args.warmup, e_rel=0, check_every=0)
+            torch.cuda.synchronize()
+            _lib.check(_lib.lib.scarlet_profile_begin(args.steps))
+            b.fit(args.steps, e_rel=0, check_every=0)
+            tot, cnt = (ctypes.c_double * 8)(), (ctypes.c_int64 * 8)()
+            _lib.check(_lib.lib.scarlet_profile_end(tot, cnt))
+        finally:
+            _lib.set_option("NO_FUSED", prev)
+        return dict(k_grad=tot[0], k_step=tot[1], update=tot[2], k_converge=tot[3], fused=tot[4]), [int(v) for v in cnt][:5]
+    cls, cnt = classes(0)
+    res["ragged_kernel_ms"], res["ragged_launches"] = cls, cnt
+    res["fused_share_of_ragged"] = cls["fused"] / max(sum(cls.values()), 1e-30)
+    cls, cnt = classes(1)
+    res["general_kernel_ms"], res["general_launches"] = cls, cnt
+    share = (cls["k_grad"] + cls["k_step"]) / max(sum(cls.values()), 1e-30)
+    res["gradient_share_of_general"] = share
+    res["padding_share_of_general"] = share * res["padding_share_of_gradient_pixels"]
     print(json.dumps(res), flush=True)
     if args.out:
         with open(args.out, "w") as f:
