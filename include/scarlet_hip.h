@@ -456,8 +456,9 @@ int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_con
  *     every B and with or without per-component switches.  No eight-wave or persistent kernel takes such a batch; every
  *     other one takes the general path, and none runs a box stage beyond 64 pixels;
  *   - SCARLET_E_NOTIMPL, found on the host before any launch: frame_hw with b->group; scarlet_init_sources_frames with
- *     spec->kind (extended sources only).  Priors, scarlet_fit_multi and the scarlet_fit_observations family have no
- *     _frames form.  f == NULL is SCARLET_E_ARG. */
+ *     spec->kind (extended sources only).  Priors, scarlet_fit_multi and low-resolution observations have no _frames
+ *     form; the joint fit against same-grid observations has one (scarlet_fit_observations_frames, below).
+ *     f == NULL is SCARLET_E_ARG. */
 typedef struct scarlet_frames {
     const int32_t *frame_hw;    /* device [S][2] (h, w), or NULL = every scene is H x W */
 } scarlet_frames;               /* 8 bytes */
@@ -476,6 +477,21 @@ int scarlet_check_frames(scarlet_batch *b, const scarlet_frames *f, void *stream
 int scarlet_init_extended_frames(scarlet_batch *b, const scarlet_frames *f, const float *bg_rms_host, float thresh,
                                  const float *sed_scale_host, int init_symmetric, int init_monotonic, int run_update,
                                  void *stream);
+
+/* scarlet_fit_observations_constrained for scenes with their own frames (c may be NULL: the state's scalars).  The state
+ * may span up to SCARLET_MAX_CHANNELS channels: with state->B > 8 the call is scarlet_fit_observations_wide without a prior
+ * and without low-resolution observations; an observation keeps B <= 8.  With f->frame_hw == NULL it IS
+ * scarlet_fit_observations_constrained / _wide, bit for bit.  Otherwise the contract is that of scarlet_fit_frames, for
+ * every observation: the caller passes `weights` and `images` in every obs[i] that are zero outside each scene's frame, and
+ * state morphologies that are zero there.  The observations' kernels -- PSF planes, the contraction, the Gram and Lipschitz
+ * passes -- are those of the padded frame and sum nothing outside; what a PSF's adjoint and the step write outside is zeroed
+ * by the constraint kernels, which run on each scene's own frame (no box stage).  The entries are checked on the device
+ * first (SCARLET_STATUS_BAD_FRAME, active = 0, the scene is left untouched).  Errors before any launch: those of
+ * scarlet_fit_observations_constrained; f == NULL is SCARLET_E_ARG; frame_hw with state->group is SCARLET_E_NOTIMPL.  There
+ * is no `lowres` array and no prior: neither has a ragged-frames form. */
+int scarlet_fit_observations_frames(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
+                                    scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                    int approximate_L, int check_every, void *stream);
 
 /* A LOW-RESOLUTION observation of the model frame (reference LowResObservation, observation.py:242-599): a second data
  * set with coarser pixels and its own PSFs, fitted jointly with the others.  For frames that are not rotated against
@@ -710,6 +726,15 @@ int scarlet_observations_products_wide(const scarlet_batch *state, scarlet_batch
 int64_t scarlet_products_scratch_bytes_wide(const scarlet_batch *state, const scarlet_products *out);
 int64_t scarlet_lowres_products_scratch_bytes_wide(const scarlet_batch *state, const scarlet_batch *obs,
                                                    const scarlet_lowres *lr, const scarlet_products *out);
+/* scarlet_observations_products / _wide (state->B > 8) of a batch fitted by scarlet_fit_observations_frames: every
+ * observation's rendered and residual are exactly zero outside each scene's frame (a difference kernel's spill is masked
+ * in the kernels) and those pixels add nothing to its loss, as for scarlet_batch_products_frames; the state's model and
+ * component_models are zero there because the morphologies are.  With f->frame_hw == NULL the call IS
+ * scarlet_observations_products / _wide.  The scratch is theirs (scarlet_products_scratch_bytes / _wide).  f == NULL is
+ * SCARLET_E_ARG, frame_hw with state->group SCARLET_E_NOTIMPL; there is no `lowres` array. */
+int scarlet_observations_products_frames(const scarlet_batch *state, const scarlet_frames *f, scarlet_batch *const *obs,
+                                         const int32_t *band0, int n_obs, const scarlet_products *state_out,
+                                         const scarlet_products *out, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

@@ -212,6 +212,11 @@ _SIGNATURES = {
     "scarlet_init_extended_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), _P, c_float, _P, c_int, c_int, c_int, _P]),
     "scarlet_init_sources_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletInitSpec), _P]),
     "scarlet_batch_products_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletProducts), _P, c_int64, _P]),
+    "scarlet_fit_observations_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),
+                                                POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
+    "scarlet_observations_products_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(POINTER(ScarletBatch)),
+                                                     _P, c_int, POINTER(ScarletProducts), POINTER(ScarletProducts), _P, c_int64,
+                                                     _P]),
     "scarlet_convergence_sums": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_batch_prepare_psf": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_convolve_same": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P]),

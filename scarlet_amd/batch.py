@@ -81,6 +81,14 @@ def ragged_frame_inputs(images, centers, frame_shapes, weights, group, n_compone
         raise NotImplementedError("a ragged-frame batch (frame_shapes / a list of images) does not take group=")
     if images is None:
         raise NotImplementedError("from_observations does not take frame_shapes")
+    images, shapes, weights = ragged_frame_block(images, frame_shapes, weights)
+    centers, n_components = ragged_frame_centers(centers, shapes, n_components)
+    return images, shapes, weights, centers, n_components
+
+
+def ragged_frame_block(images, frame_shapes, weights):
+    """The image side of `ragged_frame_inputs`, which an `ObservationBatch` with frame shapes shares (no device needed):
+    (images block, (S, 2) int32 shapes, weights as None / scalar / (S, B, H, W) block); ValueError for bad input."""
     if _is_frame_list(images):
         if frame_shapes is not None:
             raise ValueError("frame_shapes comes with a padded (S, B, H, W) block; a list of images carries its own shapes")
@@ -106,7 +114,13 @@ def ragged_frame_inputs(images, centers, frame_shapes, weights, group, n_compone
             if tuple(np.shape(w)) != (B, int(shapes[s, 0]), int(shapes[s, 1])):
                 raise ValueError("weights[%d] must be %s, not %s" % (s, (B, int(shapes[s, 0]), int(shapes[s, 1])), tuple(np.shape(w))))
         weights = pad_frames(weights)[0]
-    # the centres of the present components lie inside their scene's own frame
+    return images, shapes, weights
+
+
+def ragged_frame_centers(centers, shapes, n_components):
+    """The centre side of `ragged_frame_inputs`: the centres of the present components lie inside their scene's own frame
+    (ValueError otherwise).  Returns (centres, n_components), padded from ragged lists where they were given."""
+    S = len(shapes)
     if isinstance(centers, (list, tuple)) and len(centers) and np.ndim(centers[0]) == 2 and \
             len(set(np.shape(c)[0] for c in centers)) > 1:
         centers, counts = pad_centers(centers)
@@ -125,7 +139,7 @@ def ragged_frame_inputs(images, centers, frame_shapes, weights, group, n_compone
         s, k = [int(v[0]) for v in np.nonzero(out)]
         raise ValueError("centre %s of scene %d, source %d lies outside the scene's %d x %d frame"
                          % (tuple(int(v) for v in c[s, k]), s, k, shapes[s, 0], shapes[s, 1]))
-    return images, shapes, weights, centers, n_components
+    return centers, n_components
 
 
 _SWITCHES, _THRESHOLDS = ("symmetric", "monotonic"), ("l0_thresh", "l1_thresh")
@@ -223,9 +237,19 @@ class ObservationBatch(object):
     band0 : first model channel of the observation; observations may overlap in channels (several epochs of the same
         bands)
     weights : None (scalar 1), a Python scalar, or (S, B, H, W)
+    frame_shapes : None (every scene is H x W), or (S, 2) integers (h_s, w_s): the images are the padded block of scenes
+        with their own frame sizes, as `BlendBatch(frame_shapes=...)` takes them (`from_frames` pads a list).  The joint
+        fit then runs every scene on its own frame; every same-grid observation of a batch must carry the same shapes.
+        `weights` may then also be a list of per-scene (B, h_s, w_s) arrays.  Checked on the host (ValueError).
     """
 
-    def __init__(self, images, band0=0, weights=None):
+    def __init__(self, images, band0=0, weights=None, frame_shapes=None):
+        self.frame_shapes = None
+        if frame_shapes is not None:
+            if _is_frame_list(images):
+                raise ValueError("ObservationBatch: frame_shapes comes with a padded (S, B, H, W) block; "
+                                 "ObservationBatch.from_frames takes a list of images")
+            images, self.frame_shapes, weights = ragged_frame_block(images, frame_shapes, weights)
         if np.ndim(images) != 4:
             raise ValueError("ObservationBatch: images must be (S, B, H, W), not %s" % (tuple(np.shape(images)),))
         self.images = images
@@ -237,6 +261,19 @@ class ObservationBatch(object):
             raise ValueError("ObservationBatch: weights must be a scalar or %s, not %s" % (self.shape, tuple(np.shape(weights))))
         self.weights = weights
         self.diff_kernel = None
+
+    @classmethod
+    def from_frames(cls, images, band0=0, weights=None):
+        """The observation of S scenes with their own frame sizes: `images` is a list of (B, h_s, w_s) arrays, padded by
+        `pad_frames` (H = max h_s, W = max w_s rounded up to a multiple of 4); `weights` a scalar or a list of per-scene
+        (B, h_s, w_s) arrays.  Two observations of one batch need one block size: lists of different maximum sizes are
+        padded by the caller (`ObservationBatch(block, frame_shapes=...)`)."""
+        if cls is not ObservationBatch:
+            raise NotImplementedError("%s.from_frames: only same-grid observations take ragged frames" % cls.__name__)
+        if not _is_frame_list(images):
+            raise ValueError("ObservationBatch.from_frames: images must be a list of (B, h, w) arrays")
+        block, shapes = pad_frames(images)
+        return cls(block, band0=band0, weights=weights, frame_shapes=shapes)
 
     @property
     def B(self):
@@ -354,13 +391,15 @@ class BlendBatch(object):
         padded planes and is fitted as the reference fits the (B, h_s, w_s) scene alone -- pixels outside do not exist
         for the constraints, stay exactly zero in the morphologies and carry zero weight (the batch materialises
         (S, B, H, W) weights with the frame mask multiplied in).  Centres are in the scene's own coordinates.  Such a
-        batch takes no `group`, no prior and no `from_observations`; `init_sources` starts extended sources only.
+        batch takes no `group` and no prior; `init_sources` starts extended sources only.  A joint fit gets its frames
+        from its observations (`ObservationBatch(frame_shapes=...)`), not from this keyword.
     """
 
     def __init__(self, images, centers, weights=None, symmetric=True, monotonic=True,
                  l0_thresh=None, l1_thresh=None, centroid_weight=None, mse_capacity=256,
-                 device=None, group=None, n_components=None, _frame=None, _morph=True, frame_shapes=None):
-        frames = None
+                 device=None, group=None, n_components=None, _frame=None, _morph=True, frame_shapes=None,
+                 _frames=None):
+        frames = _frames             # (from_observations: the checked shapes of its observations, for the state)
         if frame_shapes is not None or _is_frame_list(images):      # host-side checks first: they need no device
             images, frames, weights, centers, n_components = ragged_frame_inputs(images, centers, frame_shapes, weights, group,
                                                                                   n_components)
@@ -413,6 +452,7 @@ class BlendBatch(object):
             fh, fw = self.frame_shapes[:, 0].view(S, 1, 1, 1), self.frame_shapes[:, 1].view(S, 1, 1, 1)
             self._frame_mask = (torch.arange(H, device=self.device).view(1, 1, H, 1) < fh) & \
                                (torch.arange(W, device=self.device).view(1, 1, 1, W) < fw)            # (S, 1, H, W)
+        if frames is not None and images is not None:       # (the state of a joint fit has no data to mask)
             zero = torch.zeros((), **f32)
             full = torch.full((S, B, H, W), self.weight_scalar, **f32) if self.weights is None else self.weights
             if tuple(full.shape) != (S, B, H, W):
@@ -658,7 +698,8 @@ class BlendBatch(object):
     def products(self, model=True, rendered=True, residual=True, loss=True, flux=True, components=None, out=None, obs=None):
         """What the reference reads off a fitted Blend, for every scene, from the current factors (read-only: the state,
         the fit's bookkeeping and the workspace stay as they are; scarlet_batch_products, or scarlet_observations_products
-        / scarlet_observations_products_lowres for a batch made by `from_observations`).  One call into the library on
+        / scarlet_observations_products_lowres / scarlet_observations_products_frames for a batch made by
+        `from_observations`).  One call into the library on
         the current stream, no host synchronisation.  Returns a `BatchProducts` of device tensors (None for what was not
         asked for):
 
@@ -764,7 +805,9 @@ class BlendBatch(object):
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
-        if self._wide:
+        if self.frame_shapes is not None:           # nothing outside each scene's own frame, in every observation
+            _lib.check(_lib.lib.scarlet_observations_products_frames(ctypes.byref(self._c), ctypes.byref(self._frames), ptrs, *tail))
+        elif self._wide:
             _lib.check(_lib.lib.scarlet_observations_products_wide(ctypes.byref(self._c), ptrs, lows, *tail))
         elif lows is not None:
             _lib.check(_lib.lib.scarlet_observations_products_lowres(ctypes.byref(self._c), ptrs, lows, *tail))
@@ -1070,6 +1113,11 @@ class BlendBatch(object):
         (C <= 8, with `wide=True` C <= 32); `centers` and the other keyword arguments are those of BlendBatch (ragged
         centre lists give n_components).  Start the sources with `init_combined` (or `set_state`), then `fit` / `step`.
 
+        Observations that carry `frame_shapes` (all of them, with equal shapes) make the batch a ragged-frame one: every
+        scene is fitted on its own (C, h_s, w_s) frame, as the reference fits it alone (scarlet_fit_observations_frames;
+        see `BlendBatch`'s frame_shapes).  Centres are then in each scene's own coordinates.  Such a batch takes no
+        low-resolution observation, no `group` and no prior (NotImplementedError).
+
         wide : the model frame may span up to 32 channels (scarlet_fit_observations_wide and its siblings): instruments
             whose bands do not coincide, each still with at most 8 bands of its own.  SEDs, `flux` and `model` then
             have C channels.  With C <= 8 the batch is the one made without the keyword, bit for bit; without the
@@ -1083,7 +1131,8 @@ class BlendBatch(object):
             own morphology planes; the joint fit reads neither.
         _channels : the model frame's channel count where the observations need not reach its last channel (`Blend`)."""
         if kwargs.get("frame_shapes") is not None:
-            raise NotImplementedError("from_observations does not take frame_shapes (ragged frames)")
+            raise NotImplementedError("from_observations does not take frame_shapes (ragged frames): they belong to the "
+                                      "observations, ObservationBatch(..., frame_shapes=...) or ObservationBatch.from_frames")
         obs = list(observations)
         if not 1 <= len(obs) <= _lib.MAX_OBSERVATIONS:
             raise ValueError("from_observations: 1 to %d observations, not %d" % (_lib.MAX_OBSERVATIONS, len(obs)))
@@ -1092,6 +1141,18 @@ class BlendBatch(object):
         same_grid = [o for o in obs if not isinstance(o, LowResObservationBatch)]
         S = obs[0].shape[0]
         H, W = same_grid[0].shape[2:] if same_grid else obs[0].model_shape
+        # scenes with their own frames: the shapes travel with the same-grid observations, which must agree on them
+        ragged = any(o.frame_shapes is not None for o in same_grid)
+        if ragged:
+            if len(same_grid) != len(obs):
+                raise NotImplementedError("from_observations: a low-resolution observation (observation %d) in a batch whose "
+                                          "observations carry frame_shapes (ragged frames)"
+                                          % next(i for i, o in enumerate(obs) if isinstance(o, LowResObservationBatch)))
+            if kwargs.get("group") is not None:
+                raise NotImplementedError("from_observations: observations with frame_shapes (ragged frames) do not take group=")
+            if _host_gradients:
+                raise NotImplementedError("from_observations: observations with frame_shapes (ragged frames) have no "
+                                          "host-gradient form")
         for i, o in enumerate(obs):
             if isinstance(o, LowResObservationBatch):
                 if o.shape[0] != S or o.model_shape != (H, W):
@@ -1100,8 +1161,10 @@ class BlendBatch(object):
                                      % ((i, o.shape[0]) + o.model_shape + (S, H, W)))
                 continue
             if (o.shape[0], o.shape[2], o.shape[3]) != (S, H, W):
-                raise ValueError("from_observations: observation %d has %d scenes of %d x %d, observation 0 %d of %d x %d"
-                                 % (i, o.shape[0], o.shape[2], o.shape[3], S, H, W))
+                raise ValueError("from_observations: observation %d has %d scenes of %d x %d, observation 0 %d of %d x %d%s"
+                                 % (i, o.shape[0], o.shape[2], o.shape[3], S, H, W,
+                                    " (observations with frame_shapes share one padded block size: pad lists of different "
+                                    "maximum sizes to one (S, B, H, W) block and pass frame_shapes)" if ragged else ""))
         C = max(o.band0 + o.B for o in obs)
         if _channels is not None:
             if int(_channels) < C:
@@ -1120,7 +1183,23 @@ class BlendBatch(object):
         for k in ("weights", "images"):
             if k in kwargs:
                 raise ValueError("from_observations: %s belong to the observations" % k)
-        state = cls(None, centers, _frame=(S, C, H, W), **kwargs)
+        frames = None
+        if ragged:
+            first = next(i for i, o in enumerate(obs) if o.frame_shapes is not None)
+            frames = obs[first].frame_shapes
+            for i, o in enumerate(obs):
+                if o.frame_shapes is None:
+                    raise ValueError("from_observations: observation %d carries no frame_shapes, observation %d does "
+                                     "(scene 0 there is %d x %d): every observation of a ragged-frame batch needs them"
+                                     % (i, first, frames[0, 0], frames[0, 1]))
+                if not np.array_equal(o.frame_shapes, frames):
+                    s = int(np.argmax((o.frame_shapes != frames).any(axis=1)))
+                    raise ValueError("from_observations: observation %d has scene %d at %d x %d, observation %d at %d x %d: "
+                                     "the observations must agree on every scene's frame"
+                                     % (i, s, o.frame_shapes[s, 0], o.frame_shapes[s, 1], first, frames[s, 0], frames[s, 1]))
+            # centres are in each scene's own coordinates (host check, as for BlendBatch; ragged lists are padded here)
+            centers, kwargs["n_components"] = ragged_frame_centers(centers, frames, kwargs.get("n_components"))
+        state = cls(None, centers, _frame=(S, C, H, W), _frames=frames, **kwargs)
         state._wide = bool(wide)
         torch, f32 = state.torch, dict(dtype=state.torch.float32, device=state.device)
         if _host_gradients:
@@ -1134,7 +1213,7 @@ class BlendBatch(object):
             # (a low-resolution batch lives on its own pixel grid: the model-frame centres mean nothing there)
             ob = cls(o.images, torch.zeros_like(state.centers) if low else state.centers, weights=o.weights, symmetric=False,
                      monotonic=False, mse_capacity=1, centroid_weight=state.centroid_weight.cpu().numpy(), device=state.device,
-                     _morph=_host_gradients)
+                     _morph=_host_gradients, frame_shapes=None if low else o.frame_shapes)
             if low:
                 state._lowres[i] = state._attach_lowres(o, ob)
             elif o.diff_kernel is not None:
@@ -1186,7 +1265,8 @@ class BlendBatch(object):
     def _fit_observations(self, max_iter, e_rel, approximate_L, check_every, ps=None):
         """The joint fit against `_observations` (scarlet_fit_observations_lowres_large when one of them is
         low-resolution: the LDS-resident kernels where the model frame lets them, the streamed form beyond;
-        scarlet_fit_observations_prior, which takes both kinds, with the prior's struct `ps`).  The
+        scarlet_fit_observations_prior, which takes both kinds, with the prior's struct `ps`;
+        scarlet_fit_observations_frames when the observations carry frame shapes).  The
         library copies the pointer arrays into its argument structs before it launches anything."""
         n = len(self._observations)
         ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
@@ -1197,6 +1277,9 @@ class BlendBatch(object):
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+        if self.frame_shapes is not None:           # (never with a prior or a low-resolution observation; any channel count)
+            return _lib.check(_lib.lib.scarlet_fit_observations_frames(
+                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ptrs, band0, *tail))
         if self._wide:
             return _lib.check(_lib.lib.scarlet_fit_observations_wide(
                 ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), ptrs, lows, band0, *tail))
@@ -1219,9 +1302,10 @@ class BlendBatch(object):
         obs_psfs : None, or one entry per observation: None, (B_o, P, P) or (S, B_o, P, P)
         model_psf : None or (P, P), P odd
         The observations' channel slices must tile 0 .. C - 1 in order (the reference's concatenation).  A scene
-        whose bg_rms row of observation obs_idx has a value <= 0 gets STATUS_BAD_INIT and stays inactive."""
-        if getattr(self, "frame_shapes", None) is not None:
-            raise NotImplementedError("init_combined on a ragged-frame batch (frame_shapes)")
+        whose bg_rms row of observation obs_idx has a value <= 0 gets STATUS_BAD_INIT and stays inactive.
+        Where the observations carry frame shapes, every scene starts on its own frame (scarlet_init_sources_frames)."""
+        if getattr(self, "frame_shapes", None) is not None and self._observations is None:
+            raise NotImplementedError("init_combined on a ragged-frame batch (frame_shapes) that was not made by from_observations")
         if self._observations is None:
             raise ValueError("init_combined needs a batch made by BlendBatch.from_observations")
         t, obs = self.torch, self._observations

@@ -2494,15 +2494,19 @@ static ObsKernel wide_contract_kernel(const ContractPlan &cp, bool prior)
 // Several observations: one pipeline, every iteration the observation step (the observations' G planes, the contraction
 // over them, L x n_obs, the step) and the tail.  `p` NULL: no prior; given: the passes that write a step are the PRIOR
 // instances (multiobs.h), which read the prior in the pass that already holds the factors and their gradients
+// frame_hw: the scenes' own frames (scarlet_fit_observations_frames; no prior, no low-resolution observation), or NULL.
+// Only the tail reads them: the morphologies and the observations' weights are zero outside a scene's frame, so the
+// planes, the contraction and the Lipschitz constants sum nothing there, and what a PSF's adjoint and the step write
+// outside is zeroed by the RAGGED constraint kernels before anything reads it
 static int fit_observations_call(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
                                  const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
                                  int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr,
-                                 bool large = false, const scarlet_prior *p = nullptr)
+                                 bool large = false, const scarlet_prior *p = nullptr, const int32_t *frame_hw = nullptr)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = check_counts(state, stream))) return rc;
+    if ((rc = check_counts(state, stream)) || (rc = check_frames(state, frame_hw, stream))) return rc;
     const WsLayout l = ws_layout(state, WS_FIX);
     WsLayout lo[SC_MAX_OBS];
     ObsArgs m = {};
@@ -2577,7 +2581,7 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         else hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
     };
     // with a prior the sparse_l0 / sparse_l1 cut uses each component's own step (update.py:71-82)
-    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0};
+    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw};
     return fit_loop(state, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
         prof_start(0, st);
         for (int o = 0; o < n_obs; ++o) {
@@ -2704,6 +2708,20 @@ extern "C" int scarlet_fit_observations_wide(scarlet_batch *state, const scarlet
     if (!rc && p) rc = check_prior(p);
     return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
                                            lowres, true, p);
+}
+
+// scarlet_fit_observations_constrained / _wide (the state's channel count decides, as it does between those two) for
+// scenes with their own frames; `c` may be NULL.  With frame_hw = NULL it is one of those two calls.
+extern "C" int scarlet_fit_observations_frames(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c,
+                                               scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter,
+                                               double e_rel, int approximate_L, int check_every, void *stream)
+{
+    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+    const int bmax = state && state->B > SC_BMAX ? SC_CMAX : SC_BMAX;
+    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, nullptr, false, bmax);
+    if (!rc) rc = check_frames_call(state, f);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
+                                           nullptr, false, nullptr, f->frame_hw);
 }
 
 // scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused
@@ -3303,10 +3321,11 @@ extern "C" int64_t scarlet_lowres_products_scratch_bytes_wide(const scarlet_batc
 }
 
 // the evaluations of scarlet_observations_products; lowres: NULL, or n_obs pointers (NULL = on the model's grid)
+// frame_hw: the scenes' own frames (scarlet_observations_products_frames; never with `lowres`), or NULL
 static int observations_products_call(const scarlet_batch *state, scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
                                       const int32_t *band0, int n_obs, const scarlet_products *state_out,
                                       const scarlet_products *out, void *scratch, int64_t scratch_bytes, void *stream,
-                                      int bmax = SC_BMAX)
+                                      int bmax = SC_BMAX, const int32_t *frame_hw = nullptr)
 {
     if (!state) return set_err(SCARLET_E_ARG, "null batch");
     if (n_obs < 0 || n_obs > SCARLET_MAX_OBSERVATIONS || (n_obs > 0 && (!obs || !band0 || !out)))
@@ -3339,13 +3358,14 @@ static int observations_products_call(const scarlet_batch *state, scarlet_batch 
             return rc;
     }
     (void)hipGetLastError();
-    if (state_out && products_any(state_out) && (rc = launch_products(state, state, 0, state_out, scratch, (hipStream_t)stream)))
+    if (state_out && products_any(state_out) &&
+        (rc = launch_products(state, state, 0, state_out, scratch, (hipStream_t)stream, frame_hw)))
         return rc;
     for (int i = 0; i < n_obs; ++i) {
         if (!products_any(&out[i])) continue;
         if (lowres && lowres[i])
             rc = launch_lowres_products(state, obs[i], lowres[i], band0[i], &out[i], model, scratch, (hipStream_t)stream);
-        else rc = launch_products(state, obs[i], band0[i], &out[i], scratch, (hipStream_t)stream);
+        else rc = launch_products(state, obs[i], band0[i], &out[i], scratch, (hipStream_t)stream, frame_hw);
         if (rc) return rc;
     }
     return SCARLET_OK;
@@ -3374,6 +3394,20 @@ extern "C" int scarlet_observations_products_wide(const scarlet_batch *state, sc
                                                   void *scratch, int64_t scratch_bytes, void *stream)
 {
     return observations_products_call(state, obs, lowres, band0, n_obs, state_out, out, scratch, scratch_bytes, stream, SC_CMAX);
+}
+
+// scarlet_observations_products / _wide (the state's channel count decides) of scenes with their own frames: rendered
+// and residual are zero outside them, as scarlet_batch_products_frames leaves them
+extern "C" int scarlet_observations_products_frames(const scarlet_batch *state, const scarlet_frames *f, scarlet_batch *const *obs,
+                                                    const int32_t *band0, int n_obs, const scarlet_products *state_out,
+                                                    const scarlet_products *out, void *scratch, int64_t scratch_bytes,
+                                                    void *stream)
+{
+    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+    if (!state) return set_err(SCARLET_E_ARG, "null batch");
+    if (int rc = check_frames_call(state, f)) return rc;
+    return observations_products_call(state, obs, nullptr, band0, n_obs, state_out, out, scratch, scratch_bytes, stream,
+                                      state->B > SC_BMAX ? SC_CMAX : SC_BMAX, f->frame_hw);
 }
 
 // diagnostics: contract_plan (launch_plan.h) of a joint fit with K components over C model channels:
