@@ -456,9 +456,10 @@ int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_con
  *     every B and with or without per-component switches.  No eight-wave or persistent kernel takes such a batch; every
  *     other one takes the general path, and none runs a box stage beyond 64 pixels;
  *   - SCARLET_E_NOTIMPL, found on the host before any launch: frame_hw with b->group; scarlet_init_sources_frames with
- *     spec->kind (extended sources only).  Priors, scarlet_fit_multi and low-resolution observations have no _frames
- *     form; the joint fit against same-grid observations has one (scarlet_fit_observations_frames, below).
- *     f == NULL is SCARLET_E_ARG. */
+ *     spec->kind (extended sources only).  Priors and scarlet_fit_multi have no _frames form; the joint fit against
+ *     same-grid observations has one (scarlet_fit_observations_frames, below), and so has the joint fit against
+ *     low-resolution observations, each scene with its own operator (struct scarlet_lowres_frames,
+ *     scarlet_fit_observations_frames_lowres, further below).  f == NULL is SCARLET_E_ARG. */
 typedef struct scarlet_frames {
     const int32_t *frame_hw;    /* device [S][2] (h, w), or NULL = every scene is H x W */
 } scarlet_frames;               /* 8 bytes */
@@ -488,7 +489,7 @@ int scarlet_init_extended_frames(scarlet_batch *b, const scarlet_frames *f, cons
  * by the constraint kernels, which run on each scene's own frame (no box stage).  The entries are checked on the device
  * first (SCARLET_STATUS_BAD_FRAME, active = 0, the scene is left untouched).  Errors before any launch: those of
  * scarlet_fit_observations_constrained; f == NULL is SCARLET_E_ARG; frame_hw with state->group is SCARLET_E_NOTIMPL.  There
- * is no `lowres` array and no prior: neither has a ragged-frames form. */
+ * is no prior (it has no ragged-frames form) and no `lowres` array: scarlet_fit_observations_frames_lowres takes one. */
 int scarlet_fit_observations_frames(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
                                     scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter, double e_rel,
                                     int approximate_L, int check_every, void *stream);
@@ -735,6 +736,57 @@ int64_t scarlet_lowres_products_scratch_bytes_wide(const scarlet_batch *state, c
 int scarlet_observations_products_frames(const scarlet_batch *state, const scarlet_frames *f, scarlet_batch *const *obs,
                                          const int32_t *band0, int n_obs, const scarlet_products *state_out,
                                          const scarlet_products *out, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* LOW-RESOLUTION observations of scenes with their own frames.  The reference builds the operator from the scene's own
+ * frame -- the periodic plane is fast_shape(max(frame, PSF) + 3), the frame sits at pad_start inside it, the shifts are
+ * relative to the extent the observation's pixels span -- so a scene fitted on a padded frame is not the scene the
+ * reference fits: every scene brings its own H_s, W_s, h_s, w_s, nfy_s, nfx_s and its own five factor matrices.  The
+ * caller computes them per scene (scarlet_amd/resampling.py, float64) and ZERO-PADS every table to the per-dimension
+ * maxima, which is exact: the padded rows and columns only add products with 0.  This struct travels beside the
+ * observation's scarlet_lowres, which then holds the maxima in h, w, nfy, nfx (H, W are the state's), needs
+ * v_per_scene = dhat_per_scene = 1 with vy [S][h][nfy][2], vx [S][w][nfx][2] and dhat [S][B][nfy][nfx][2] zero-padded
+ * the same way, and whose own uy / ux are not read (they must not be NULL).  Images and weights are the padded
+ * [S][B][h][w] blocks, zero outside each scene's own h_s x w_s. */
+typedef struct scarlet_lowres_frames {
+    const int32_t *dims;   /* device [S][6]: H_s, W_s, h_s, w_s, nfy_s, nfx_s                                  */
+    const float *uy, *ux;  /* [S][nfy][H][2], [S][nfx][W][2]: each scene's own matrices, zero-padded to the     */
+} scarlet_lowres_frames;   /* maxima that the accompanying scarlet_lowres holds in h, w, nfy, nfx (24 bytes)    */
+
+/* scarlet_fit_observations_lowres_large / scarlet_fit_observations_wide without a prior (the state's channel count
+ * decides; c may be NULL) for such scenes: `lowres` and `lowres_frames` are arrays of n_obs pointers, NULL = that
+ * observation is on the model's grid / brings no tables of its own.  With every lowres_frames[i] NULL and f->frame_hw NULL
+ * the call IS scarlet_fit_observations_lowres_large (or _wide), bit for bit.  Otherwise the contract is that of
+ * scarlet_fit_observations_frames, and for a low-resolution observation:
+ *   - the call is of the `large` kind: where the maxima fit LDS (the limit at scarlet_lowres, evaluated for the maxima,
+ *     which may come from different scenes) one workgroup per scene (k_lowres_planes_frames) reads its row of `dims` and
+ *     its own tables and runs every loop and GEMM over the scene's own sizes; it writes the gradient planes over the
+ *     whole padded H x W, 0.0f outside the scene's frame, and sums the loss over the scene's own pixels.  Beyond, and
+ *     under LOWRES_STREAMED, the streamed form runs on the padded extents of every scene (it streams the padding: the
+ *     same sums plus products with 0);
+ *   - workspace: scarlet_lowres_large_workspace_bytes() / _wide of the scarlet_lowres that holds the maxima;
+ *   - the device check of scarlet_frames extends to `dims`: a row outside 1..max in any column, or whose H_s, W_s
+ *     differ from frame_hw[s], gives the scene SCARLET_STATUS_BAD_FRAME and active = 0; it is not touched again, the
+ *     others go on.  No entry is a loop bound before it has been tested against the padded blocks.
+ * Errors before any launch: those of scarlet_fit_observations_lowres_large / _frames; SCARLET_E_ARG for f, `lowres` or
+ * `lowres_frames` NULL, lowres_frames[i] without lowres[i] or without f->frame_hw, a null table, v_per_scene or
+ * dhat_per_scene not set; SCARLET_E_NOTIMPL for f->frame_hw with a lowres[i] that has no lowres_frames[i], and for
+ * frame_hw with state->group.  There is no prior argument.  Not covered: frames rotated against each other, and batches
+ * whose observations are all low-resolution (nothing would carry the model frames). */
+int scarlet_fit_observations_frames_lowres(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
+                                           scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                           const scarlet_lowres_frames *const *lowres_frames, const int32_t *band0, int n_obs,
+                                           int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+/* scarlet_observations_products_lowres / _wide for such a batch: rendered and residual of a low-resolution observation
+ * are written over the whole padded [S][B][h][w] block, 0.0f outside each scene's own h_s x w_s, and its loss runs over
+ * the scene's own pixels; a scene whose `dims` row fails the test above gets zeros in all three (the call is read-only:
+ * it marks nothing).  The same-grid observations and the state are evaluated as scarlet_observations_products_frames
+ * does.  Scratch: scarlet_lowres_products_scratch_bytes() / _wide of the scarlet_lowres that holds the maxima, and the
+ * others' as there.  Errors: those of scarlet_observations_products_lowres and the ones listed above. */
+int scarlet_observations_products_frames_lowres(const scarlet_batch *state, const scarlet_frames *f, scarlet_batch *const *obs,
+                                                const scarlet_lowres *const *lowres,
+                                                const scarlet_lowres_frames *const *lowres_frames, const int32_t *band0,
+                                                int n_obs, const scarlet_products *state_out, const scarlet_products *out,
+                                                void *scratch, int64_t scratch_bytes, void *stream);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

@@ -110,6 +110,11 @@ class ScarletLowres(Structure):
                 ("v_per_scene", c_int32), ("dhat_per_scene", c_int32), ("workspace", c_void_p)]
 
 
+class ScarletLowresFrames(Structure):
+    """struct scarlet_lowres_frames of include/scarlet_hip.h (field order must match)."""
+    _fields_ = [("dims", c_void_p), ("uy", c_void_p), ("ux", c_void_p)]
+
+
 class ScarletProducts(Structure):
     """struct scarlet_products of include/scarlet_hip.h (field order must match); `components` is a HOST pointer."""
     _fields_ = [("model", c_void_p), ("rendered", c_void_p), ("residual", c_void_p), ("loss", c_void_p), ("flux", c_void_p),
@@ -217,6 +222,14 @@ _SIGNATURES = {
     "scarlet_observations_products_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(POINTER(ScarletBatch)),
                                                      _P, c_int, POINTER(ScarletProducts), POINTER(ScarletProducts), _P, c_int64,
                                                      _P]),
+    "scarlet_fit_observations_frames_lowres": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),
+                                                       POINTER(POINTER(ScarletBatch)), POINTER(POINTER(ScarletLowres)),
+                                                       POINTER(POINTER(ScarletLowresFrames)), _P, c_int, c_int, c_double, c_int,
+                                                       c_int, _P]),
+    "scarlet_observations_products_frames_lowres": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames),
+                                                            POINTER(POINTER(ScarletBatch)), POINTER(POINTER(ScarletLowres)),
+                                                            POINTER(POINTER(ScarletLowresFrames)), _P, c_int,
+                                                            POINTER(ScarletProducts), POINTER(ScarletProducts), _P, c_int64, _P]),
     "scarlet_convergence_sums": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_batch_prepare_psf": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_convolve_same": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P]),

@@ -301,15 +301,30 @@ class LowResObservationBatch(ObservationBatch):
         the observation's shape).  Only its geometry is read (factor matrices, band count), not its images.
     weights : None (scalar 1), a Python scalar, or (S, B, h, w)
 
+    frame_shapes : None, or (S, 2) integers (h_s, w_s): the images are the padded block of scenes whose observations have
+        their own sizes (`from_frames(images, geometry=[...])` pads a list), beside same-grid observations that carry the
+        scenes' model frames.  `geometry` is then a list of S `LowResObservation`s, each matched to its own scene's model
+        frame (C, H_s, W_s) -- the reference builds the operator from the scene's own frame, so a geometry matched to the
+        padded frame would fit another scene.  The batch keeps `model_shapes` (S, 2) = (H_s, W_s) read from the
+        geometries, `dims` (S, 6) = (H_s, W_s, h_s, w_s, nfy_s, nfx_s), and every scene's five factor matrices
+        zero-padded to the per-dimension maxima (exact: the padding only adds products with 0).  `weights` may also be a
+        list of per-scene (B, h_s, w_s) arrays.  The geometries must share the model PSF and the band count.
+
     Every pixel of the observation must lie inside the model frame (ValueError otherwise); a geometry that was not
     matched raises ValueError too."""
 
-    def __init__(self, images, band0=0, geometry=None, weights=None):
-        ObservationBatch.__init__(self, images, band0=band0, weights=weights)
+    def __init__(self, images, band0=0, geometry=None, weights=None, frame_shapes=None):
+        if frame_shapes is not None and _is_frame_list(images):
+            raise ValueError("LowResObservationBatch: frame_shapes comes with a padded (S, B, h, w) block; "
+                             "LowResObservationBatch.from_frames takes a list of images")
+        ObservationBatch.__init__(self, images, band0=band0, weights=weights, frame_shapes=frame_shapes)
         S, B, h, w = self.shape
         geoms = list(geometry) if isinstance(geometry, (list, tuple)) else [geometry]
         if isinstance(geometry, (list, tuple)) and len(geoms) != S:
             raise ValueError("LowResObservationBatch: %d geometries for S = %d scenes" % (len(geoms), S))
+        if frame_shapes is not None and not isinstance(geometry, (list, tuple)):
+            raise ValueError("LowResObservationBatch: frame_shapes needs a list of S geometries, each matched to its own "
+                             "scene's model frame")
         for g in geoms:
             if not hasattr(g, "factors_f32") or getattr(g, "model_shape", None) is None:
                 raise ValueError("LowResObservationBatch: geometry must be a LowResObservation after match(model_frame)")
@@ -319,6 +334,10 @@ class LowResObservationBatch(ObservationBatch):
         self.per_scene = isinstance(geometry, (list, tuple))
         self.geometries = geoms
         self.model_shape = tuple(geoms[0].model_shape)
+        self.model_shapes = self.dims = None
+        if frame_shapes is not None:
+            self._pack_frames()
+            return
         f0 = geoms[0].factors_f32()
         if f0["dhat"].shape[0] != B or (f0["vy"].shape[0], f0["vx"].shape[0]) != (h, w):
             raise ValueError("LowResObservationBatch: images are %s, the geometry describes %s"
@@ -333,6 +352,49 @@ class LowResObservationBatch(ObservationBatch):
         for k in ("vy", "vx", "dhat"):
             self.host_factors[k] = np.stack([f[k] for f in fs]) if self.per_scene else f0[k]
 
+    def _pack_frames(self):
+        """The per-scene tables of scenes with their own frames: `model_shapes`, `dims` and the zero-padded factors."""
+        S, B, h, w = self.shape
+        fs = [g.factors_f32() for g in self.geometries]
+        for s, (g, f) in enumerate(zip(self.geometries, fs)):
+            own = (f["dhat"].shape[0], f["vy"].shape[0], f["vx"].shape[0])
+            want = (B, int(self.frame_shapes[s, 0]), int(self.frame_shapes[s, 1]))
+            if own != want:
+                raise ValueError("LowResObservationBatch: scene %d's images are %s, its geometry describes %s" % (s, want, own))
+            if own[0] != fs[0]["dhat"].shape[0]:
+                raise ValueError("LowResObservationBatch: the scenes' geometries must share the band count")
+            if not np.array_equal(g.model_psf, self.geometries[0].model_psf):
+                raise ValueError("LowResObservationBatch: scene %d's geometry was matched with another model PSF than scene "
+                                 "0's; the scenes' geometries must share the model PSF" % s)
+        self.model_shapes = np.array([g.model_shape for g in self.geometries], dtype=np.int32)
+        self.dims = np.array([tuple(g.model_shape) + (f["vy"].shape[0], f["vx"].shape[0], f["uy"].shape[0], f["ux"].shape[0])
+                              for g, f in zip(self.geometries, fs)], dtype=np.int32)
+        self.model_shape = (int(self.dims[:, 0].max()), int(self.dims[:, 1].max()))
+        H, W = self.model_shape
+        nfy, nfx = int(self.dims[:, 4].max()), int(self.dims[:, 5].max())
+        shapes = dict(uy=(nfy, H), ux=(nfx, W), vy=(h, nfy), vx=(w, nfx), dhat=(B, nfy, nfx))
+        self.host_factors = {}
+        for k, shape in shapes.items():
+            out = np.zeros((S,) + shape + (2,), np.float32)
+            for s, f in enumerate(fs):
+                out[(s,) + tuple(slice(0, n) for n in f[k].shape)] = f[k]
+            self.host_factors[k] = out
+
+    @classmethod
+    def from_frames(cls, images, band0=0, weights=None, geometry=None):
+        """The low-resolution observation of S scenes with their own sizes: `images` is a list of (B, h_s, w_s) arrays,
+        padded by `pad_frames`; `geometry` a list of S `LowResObservation`s, each matched to its own scene's model frame
+        (C, H_s, W_s); `weights` a scalar or a list of per-scene (B, h_s, w_s) arrays.  The padded-block spelling is
+        `LowResObservationBatch(block, band0, geometry=[...], weights=..., frame_shapes=...)`.  Without `geometry` there
+        is nothing to build the scenes' operators from: NotImplementedError."""
+        if geometry is None:
+            raise NotImplementedError("%s.from_frames: only same-grid observations take ragged frames without geometry= "
+                                      "(a list of per-scene LowResObservations)" % cls.__name__)
+        if not _is_frame_list(images):
+            raise ValueError("LowResObservationBatch.from_frames: images must be a list of (B, h, w) arrays")
+        block, shapes = pad_frames(images)
+        return cls(block, band0=band0, geometry=geometry, weights=weights, frame_shapes=shapes)
+
     def pixels_of(self, centers):
         """(..., 2) model-frame centres (torch, integer) -> the observation's pixels under them, truncated as
         Frame.get_pixel does; scene s uses its own geometry."""
@@ -344,10 +406,27 @@ class LowResObservationBatch(ObservationBatch):
         stp = t.new_tensor([g.step for g in geoms]).view(S, 1, 2)
         return ((t - org) / stp).trunc().to(dtype=centers.dtype)
 
-    def lowres_struct(self, device):
-        """(struct scarlet_lowres without a workspace, the device tensors it points to)"""
+    def lowres_struct(self, device, model_block=None):
+        """(struct scarlet_lowres without a workspace, the device tensors it points to).  With frame shapes: the struct
+        holds the maxima, uy / ux are the per-scene tables padded on to the (H, W) of `model_block` -- the state's padded
+        planes -- and the tensors include `dims` and the struct scarlet_lowres_frames ("frames") that points to them."""
         from .observation import lowres_struct
-        return lowres_struct(self.host_factors, self.shape[2], self.shape[3], self.shape[1], self.per_scene, device)
+        if self.dims is None:
+            return lowres_struct(self.host_factors, self.shape[2], self.shape[3], self.shape[1], self.per_scene, device)
+        f = dict(self.host_factors)
+        H, W = self.model_shape if model_block is None else (int(v) for v in model_block)
+        for k, n in (("uy", H), ("ux", W)):
+            if f[k].shape[2] != n:
+                out = np.zeros(f[k].shape[:2] + (n, 2), np.float32)
+                out[:, :, :f[k].shape[2]] = f[k]
+                f[k] = out
+        lr, keep = lowres_struct(f, self.shape[2], self.shape[3], self.shape[1], True, device)
+        lr.nfy, lr.nfx = f["uy"].shape[1], f["ux"].shape[1]
+        keep["dims"] = _lib.require_gpu().as_tensor(self.dims).to(device).contiguous()
+        lf = _lib.ScarletLowresFrames()
+        lf.dims, lf.uy, lf.ux = keep["dims"].data_ptr(), keep["uy"].data_ptr(), keep["ux"].data_ptr()
+        keep["frames"] = lf
+        return lr, keep
 
 
 class BatchProducts(object):
@@ -805,7 +884,10 @@ class BlendBatch(object):
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
-        if self.frame_shapes is not None:           # nothing outside each scene's own frame, in every observation
+        if self.frame_shapes is not None and lows is not None:
+            _lib.check(_lib.lib.scarlet_observations_products_frames_lowres(
+                ctypes.byref(self._c), ctypes.byref(self._frames), ptrs, lows, self._lowres_frames(), *tail))
+        elif self.frame_shapes is not None:         # nothing outside each scene's own frame, in every observation
             _lib.check(_lib.lib.scarlet_observations_products_frames(ctypes.byref(self._c), ctypes.byref(self._frames), ptrs, *tail))
         elif self._wide:
             _lib.check(_lib.lib.scarlet_observations_products_wide(ctypes.byref(self._c), ptrs, lows, *tail))
@@ -1115,8 +1197,11 @@ class BlendBatch(object):
 
         Observations that carry `frame_shapes` (all of them, with equal shapes) make the batch a ragged-frame one: every
         scene is fitted on its own (C, h_s, w_s) frame, as the reference fits it alone (scarlet_fit_observations_frames;
-        see `BlendBatch`'s frame_shapes).  Centres are then in each scene's own coordinates.  Such a batch takes no
-        low-resolution observation, no `group` and no prior (NotImplementedError).
+        see `BlendBatch`'s frame_shapes).  Centres are then in each scene's own coordinates.  A low-resolution
+        observation joins such a batch with one geometry per scene, each matched to its own scene's model frame
+        (`LowResObservationBatch.from_frames(images, geometry=[...])`; its `model_shapes` must be the same-grid
+        observations' shapes: scarlet_fit_observations_frames_lowres); one without frame shapes of its own, a batch of
+        low-resolution observations only, `group` and a prior raise NotImplementedError.
 
         wide : the model frame may span up to 32 channels (scarlet_fit_observations_wide and its siblings): instruments
             whose bands do not coincide, each still with at most 8 bands of its own.  SEDs, `flux` and `model` then
@@ -1143,17 +1228,32 @@ class BlendBatch(object):
         H, W = same_grid[0].shape[2:] if same_grid else obs[0].model_shape
         # scenes with their own frames: the shapes travel with the same-grid observations, which must agree on them
         ragged = any(o.frame_shapes is not None for o in same_grid)
+        low_frames = [i for i, o in enumerate(obs) if isinstance(o, LowResObservationBatch) and o.frame_shapes is not None]
+        if low_frames and not same_grid:
+            raise NotImplementedError("from_observations: a ragged-frame batch of low-resolution observations only (observation "
+                                      "%d carries frame shapes): a same-grid observation must carry the model frames" % low_frames[0])
+        if low_frames and not ragged:
+            raise ValueError("from_observations: low-resolution observation %d carries frame shapes, the same-grid "
+                             "observations carry none: every observation of a ragged-frame batch needs them" % low_frames[0])
         if ragged:
-            if len(same_grid) != len(obs):
-                raise NotImplementedError("from_observations: a low-resolution observation (observation %d) in a batch whose "
-                                          "observations carry frame_shapes (ragged frames)"
-                                          % next(i for i, o in enumerate(obs) if isinstance(o, LowResObservationBatch)))
+            for i, o in enumerate(obs):
+                # (one geometry, or a list matched to one frame: its operator would be that of the padded frame)
+                if isinstance(o, LowResObservationBatch) and o.frame_shapes is None:
+                    raise NotImplementedError("from_observations: a low-resolution observation (observation %d) without frame "
+                                              "shapes of its own in a batch whose observations carry frame_shapes (ragged "
+                                              "frames): make it with LowResObservationBatch.from_frames(images, geometry=[...])"
+                                              % i)
             if kwargs.get("group") is not None:
                 raise NotImplementedError("from_observations: observations with frame_shapes (ragged frames) do not take group=")
             if _host_gradients:
                 raise NotImplementedError("from_observations: observations with frame_shapes (ragged frames) have no "
                                           "host-gradient form")
         for i, o in enumerate(obs):
+            if isinstance(o, LowResObservationBatch) and o.frame_shapes is not None:
+                if o.shape[0] != S:
+                    raise ValueError("from_observations: low-resolution observation %d has %d scenes, the batch has %d"
+                                     % (i, o.shape[0], S))
+                continue                    # (its model frames are checked against the same-grid observations' below)
             if isinstance(o, LowResObservationBatch):
                 if o.shape[0] != S or o.model_shape != (H, W):
                     raise ValueError("from_observations: low-resolution observation %d has %d scenes and was matched to a "
@@ -1185,9 +1285,17 @@ class BlendBatch(object):
                 raise ValueError("from_observations: %s belong to the observations" % k)
         frames = None
         if ragged:
-            first = next(i for i, o in enumerate(obs) if o.frame_shapes is not None)
+            first = next(i for i, o in enumerate(obs) if o.frame_shapes is not None and not isinstance(o, LowResObservationBatch))
             frames = obs[first].frame_shapes
             for i, o in enumerate(obs):
+                if isinstance(o, LowResObservationBatch):
+                    if not np.array_equal(o.model_shapes, frames):
+                        s = int(np.argmax((o.model_shapes != frames).any(axis=1)))
+                        raise ValueError("from_observations: low-resolution observation %d was matched to a %d x %d model frame "
+                                         "in scene %d, observation %d has that scene at %d x %d: the geometries must be "
+                                         "matched to the scenes' own frames"
+                                         % (i, o.model_shapes[s, 0], o.model_shapes[s, 1], s, first, frames[s, 0], frames[s, 1]))
+                    continue
                 if o.frame_shapes is None:
                     raise ValueError("from_observations: observation %d carries no frame_shapes, observation %d does "
                                      "(scene 0 there is %d x %d): every observation of a ragged-frame batch needs them"
@@ -1213,7 +1321,7 @@ class BlendBatch(object):
             # (a low-resolution batch lives on its own pixel grid: the model-frame centres mean nothing there)
             ob = cls(o.images, torch.zeros_like(state.centers) if low else state.centers, weights=o.weights, symmetric=False,
                      monotonic=False, mse_capacity=1, centroid_weight=state.centroid_weight.cpu().numpy(), device=state.device,
-                     _morph=_host_gradients, frame_shapes=None if low else o.frame_shapes)
+                     _morph=_host_gradients, frame_shapes=o.frame_shapes)
             if low:
                 state._lowres[i] = state._attach_lowres(o, ob)
             elif o.diff_kernel is not None:
@@ -1231,7 +1339,11 @@ class BlendBatch(object):
         pix = o.pixels_of(self.centers).long()
         h, w = o.shape[2:]
         present = self._present() & ((self.status & _lib.STATUS_BAD_INIT) == 0).view(-1, 1)
-        bad = present & ((pix[..., 0] < 0) | (pix[..., 0] >= h) | (pix[..., 1] < 0) | (pix[..., 1] >= w))
+        hs, ws = h, w
+        if o.frame_shapes is not None:             # the scene's own pixels
+            own = t.as_tensor(o.frame_shapes).to(device=self.device, dtype=pix.dtype)
+            hs, ws = own[:, 0].view(-1, 1), own[:, 1].view(-1, 1)
+        bad = present & ((pix[..., 0] < 0) | (pix[..., 0] >= hs) | (pix[..., 1] < 0) | (pix[..., 1] >= ws))
         if bool(bad.any().item()):
             s, k = [int(v[0]) for v in t.nonzero(bad, as_tuple=True)]
             raise ValueError("init_combined: source %d of scene %d lies outside the low-resolution observation" % (k, s))
@@ -1255,18 +1367,25 @@ class BlendBatch(object):
     def _attach_lowres(self, o, ob):
         """(scarlet_lowres with its workspace, what it points to) of the low-resolution observation `o` with gradient
         batch `ob`, sized for this state batch"""
-        lr, keep = o.lowres_struct(self.device)
+        lr, keep = o.lowres_struct(self.device) if o.dims is None else o.lowres_struct(self.device, (self.H, self.W))
         sizer = _lib.lib.scarlet_lowres_large_workspace_bytes_wide if self._wide else _lib.lib.scarlet_lowres_large_workspace_bytes
         nbytes = _lib.check(sizer(ctypes.byref(self._c), ctypes.byref(ob._c), ctypes.byref(lr)))
         keep["workspace"] = self.torch.empty((int(nbytes),), dtype=self.torch.uint8, device=self.device)
         lr.workspace = keep["workspace"].data_ptr()
         return lr, keep
 
+    def _lowres_frames(self):
+        """the array of scarlet_lowres_frames pointers beside `_lowres` (NULL for the same-grid observations)"""
+        none = ctypes.POINTER(_lib.ScarletLowresFrames)()
+        return (ctypes.POINTER(_lib.ScarletLowresFrames) * len(self._lowres))(
+            *[none if x is None or "frames" not in x[1] else ctypes.pointer(x[1]["frames"]) for x in self._lowres])
+
     def _fit_observations(self, max_iter, e_rel, approximate_L, check_every, ps=None):
         """The joint fit against `_observations` (scarlet_fit_observations_lowres_large when one of them is
         low-resolution: the LDS-resident kernels where the model frame lets them, the streamed form beyond;
         scarlet_fit_observations_prior, which takes both kinds, with the prior's struct `ps`;
-        scarlet_fit_observations_frames when the observations carry frame shapes).  The
+        scarlet_fit_observations_frames when the observations carry frame shapes, scarlet_fit_observations_frames_lowres
+        when one of those is low-resolution).  The
         library copies the pointer arrays into its argument structs before it launches anything."""
         n = len(self._observations)
         ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
@@ -1277,7 +1396,11 @@ class BlendBatch(object):
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
-        if self.frame_shapes is not None:           # (never with a prior or a low-resolution observation; any channel count)
+        if self.frame_shapes is not None and lows is not None:      # (each low-resolution observation with its own tables)
+            return _lib.check(_lib.lib.scarlet_fit_observations_frames_lowres(
+                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ptrs, lows, self._lowres_frames(),
+                band0, *tail))
+        if self.frame_shapes is not None:           # (never with a prior; any channel count)
             return _lib.check(_lib.lib.scarlet_fit_observations_frames(
                 ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ptrs, band0, *tail))
         if self._wide:

@@ -195,6 +195,24 @@ inline ProductsPlan products_plan(int S, int K, int B, int H, int W, int psf, co
     return p;
 }
 
+// ---- the gradient planes of a LOW-RESOLUTION observation in a fit of the *_large kind (fit_observations_call):
+// k_lowres_planes, one workgroup per scene with the factor matrices in LDS, wherever they fit; beyond, and everywhere
+// under LOWRES_STREAMED, the streamed chain of lowres_stream.h.  For scenes with their own frames
+// (scarlet_lowres_frames, k_lowres_planes_frames) `d` holds the per-dimension MAXIMA over the scenes -- the shape of the
+// padded blocks -- and never one scene's row of `dims`: the largest h, w and the largest H, W may belong to different
+// scenes, and every workgroup lays its LDS out the same way.  lowres_products_plan below takes the same `d`.
+enum LowresPlanesForm { LOWRES_PLANES_LDS, LOWRES_PLANES_STREAMED };
+struct LowresPlanesPlan {
+    int form;
+    size_t lds;             // dynamic LDS of k_lowres_planes / k_lowres_planes_frames (0 streamed)
+};
+inline LowresPlanesPlan lowres_planes_plan(const LowresDims &d, bool streamed)
+{
+    LowresPlanesPlan p = {LOWRES_PLANES_LDS, lowres_lds_bytes(d)};
+    if (streamed || p.lds > LDS_LIMIT) { p.form = LOWRES_PLANES_STREAMED; p.lds = 0; }
+    return p;
+}
+
 // ---- the read-only products of a LOW-RESOLUTION observation (launch_lowres_products): k_lowres_products, one workgroup
 // per scene with the factor matrices in LDS, wherever they fit; beyond, and everywhere under LOWRES_STREAMED, the
 // streamed chain of lowres_stream.h on the S B band planes, taken in chunks that keep the caller's scratch within

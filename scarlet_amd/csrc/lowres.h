@@ -25,6 +25,7 @@
 // the *_large entry points run the STREAMED form of lowres_stream.h: the same sums as batched GEMMs through HBM scratch.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 struct LowresDims {
     int H, W, h, w, nfy, nfx, B;
@@ -109,29 +110,34 @@ __device__ __forceinline__ void lr_gemm(const float *A, int a_rs, int a_cs, cons
 }
 
 // the four factor matrices into LDS as stacked real matrices: uy [2 nfy][ldH] and ux [2 nfx][ldW] (rows: Re, then Im),
-// vy [h][ldVy] and vx [w][ldVx] (columns: Re, then Im)
-__device__ inline void lr_load_factors(float *lds, const LowresLds &l, const LowresDims &d, const LowresFactors &f, int scene)
+// vy [h][ldVy] and vx [w][ldVx] (columns: Re, then Im).  `p` holds the shape of the global tables: d itself, or (RAGGED,
+// below) the maxima that every scene's own tables are zero-padded to, with uy and ux per scene like vy and vx.
+template <bool RAGGED = false>
+__device__ inline void lr_load_factors(float *lds, const LowresLds &l, const LowresDims &d, const LowresDims &p,
+                                       const LowresFactors &f, int scene)
 {
-    const float2 *vy = f.vy + (f.v_per_scene ? (size_t)scene * d.h * d.nfy : 0);
-    const float2 *vx = f.vx + (f.v_per_scene ? (size_t)scene * d.w * d.nfx : 0);
+    const float2 *uy = RAGGED ? f.uy + (size_t)scene * p.nfy * p.H : f.uy;
+    const float2 *ux = RAGGED ? f.ux + (size_t)scene * p.nfx * p.W : f.ux;
+    const float2 *vy = f.vy + (f.v_per_scene ? (size_t)scene * p.h * p.nfy : 0);
+    const float2 *vx = f.vx + (f.v_per_scene ? (size_t)scene * p.w * p.nfx : 0);
     for (int e = threadIdx.x; e < d.nfy * d.H; e += SC_BLOCK) {
         const int r = e / d.H, c = e - r * d.H;
-        const float2 v = f.uy[e];
+        const float2 v = uy[RAGGED ? r * p.H + c : e];
         lds[l.uy + r * l.ldH + c] = v.x; lds[l.uy + (d.nfy + r) * l.ldH + c] = v.y;
     }
     for (int e = threadIdx.x; e < d.nfx * d.W; e += SC_BLOCK) {
         const int r = e / d.W, c = e - r * d.W;
-        const float2 v = f.ux[e];
+        const float2 v = ux[RAGGED ? r * p.W + c : e];
         lds[l.ux + r * l.ldW + c] = v.x; lds[l.ux + (d.nfx + r) * l.ldW + c] = v.y;
     }
     for (int e = threadIdx.x; e < d.h * d.nfy; e += SC_BLOCK) {
         const int r = e / d.nfy, c = e - r * d.nfy;
-        const float2 v = vy[e];
+        const float2 v = vy[RAGGED ? r * p.nfy + c : e];
         lds[l.vy + r * l.ldVy + c] = v.x; lds[l.vy + r * l.ldVy + d.nfy + c] = v.y;
     }
     for (int e = threadIdx.x; e < d.w * d.nfx; e += SC_BLOCK) {
         const int r = e / d.nfx, c = e - r * d.nfx;
-        const float2 v = vx[e];
+        const float2 v = vx[RAGGED ? r * p.nfx + c : e];
         lds[l.vx + r * l.ldVx + c] = v.x; lds[l.vx + r * l.ldVx + d.nfx + c] = v.y;
     }
 }
@@ -139,17 +145,22 @@ __device__ inline void lr_load_factors(float *lds, const LowresLds &l, const Low
 // one H x W plane (global, row stride W) -> the tile of the p region, then its projection Uy m Ux^T as the four real
 // blocks C = [[Re Uy . Re T, Re Uy . Im T], [Im Uy . Re T, Im Uy . Im T]] (T = m Ux^T) in buffer X, [2 nfy][ld2x].
 // Ends with the workgroup synchronised.
+// (RAGGED changes nothing in the helpers that only take it along: the ragged-frames kernels get instances of their own,
+// so that the compiler's inlining of the uniform kernels' instances does not depend on them)
+template <bool RAGGED = false>
 __device__ inline void lr_project_tile(float *lds, const LowresLds &l, const LowresDims &d, bool mfma);
-__device__ inline void lr_project(float *lds, const LowresLds &l, const LowresDims &d, const float *plane, bool mfma)
+template <bool RAGGED = false>
+__device__ inline void lr_project(float *lds, const LowresLds &l, const LowresDims &d, const float *plane, bool mfma, int stride = 0)
 {
     float *tile = lds + l.p;
     for (int e = threadIdx.x; e < d.H * d.W; e += SC_BLOCK) {
         const int y = e / d.W, x = e - y * d.W;
-        tile[y * l.ldW + x] = plane[e];
+        tile[y * l.ldW + x] = plane[RAGGED ? y * stride + x : e];      // (RAGGED: the plane's rows are `stride` apart)
     }
-    lr_project_tile(lds, l, d, mfma);
+    lr_project_tile<RAGGED>(lds, l, d, mfma);
 }
 // ... of the plane that the workgroup has written into the tile [H][ldW] of the p region itself (no barrier needed before)
+template <bool RAGGED>
 __device__ inline void lr_project_tile(float *lds, const LowresLds &l, const LowresDims &d, bool mfma)
 {
     float *tile = lds + l.p, *tp = lds + l.p + l.tp, *C = lds + l.x;
@@ -170,12 +181,13 @@ __device__ __forceinline__ float2 lr_projected(const float *C, int ld2x, int nfy
 }
 
 // A complex spectrum z(f, g) times Dhat, written into `dst` [2 nfy][ld2x] as [[Re, -Im], [-Im, -Re]]
-template <typename Z>
-__device__ __forceinline__ void lr_expand(float *dst, int ld2x, int nfy, int nfx, const float2 *dhat, Z z)
+// (RAGGED: the rows of dhat are `dld` apart, the nfx of the padded table)
+template <bool RAGGED = false, typename Z>
+__device__ __forceinline__ void lr_expand(float *dst, int ld2x, int nfy, int nfx, const float2 *dhat, Z z, int dld = 0)
 {
     for (int e = threadIdx.x; e < nfy * nfx; e += SC_BLOCK) {
         const int f = e / nfx, g = e - f * nfx;
-        const float2 a = z(f, g), b = dhat[e];
+        const float2 a = z(f, g), b = dhat[RAGGED ? f * dld + g : e];
         const float re = a.x * b.x - a.y * b.y, im = a.x * b.y + a.y * b.x;
         dst[f * ld2x + g] = re; dst[f * ld2x + nfx + g] = -im;
         dst[(nfy + f) * ld2x + g] = -im; dst[(nfy + f) * ld2x + nfx + g] = -re;
@@ -183,6 +195,7 @@ __device__ __forceinline__ void lr_expand(float *dst, int ld2x, int nfy, int nfx
 }
 
 // forward of one band: the expanded spectrum in buffer X -> out [h][ldw] in buffer X (through buffer Y).  Ends synchronised.
+template <bool RAGGED = false>
 __device__ inline void lr_forward(float *lds, const LowresLds &l, const LowresDims &d, bool mfma)
 {
     float *X = lds + l.x, *Y = lds + l.p;
@@ -196,8 +209,9 @@ __device__ inline void lr_forward(float *lds, const LowresLds &l, const LowresDi
 }
 
 // adjoint of one band: E [h][ldw] in buffer X -> store(y, x, value) for the H x W plane.  Starts and ends synchronised.
-template <typename Store>
-__device__ inline void lr_adjoint(float *lds, const LowresLds &l, const LowresDims &d, const float2 *dhat, bool mfma, Store store)
+template <bool RAGGED = false, typename Store>
+__device__ inline void lr_adjoint(float *lds, const LowresLds &l, const LowresDims &d, const float2 *dhat, bool mfma, Store store,
+                                  int dld = 0)
 {
     float *X = lds + l.x, *Y = lds + l.p;
     const int ldw = l.ldw, ld2x = l.ld2x, ldW = l.ldW, nfy = d.nfy, nfx = d.nfx;
@@ -207,7 +221,7 @@ __device__ inline void lr_adjoint(float *lds, const LowresLds &l, const LowresDi
     // C2 [2 nfy][2 nfx] = A1 . (Re Vx | Im Vx): the four real blocks of A1 Vx
     lr_gemm(Y, ldw, 1, lds + l.vx, l.ldVx, 1, 2 * nfy, 2 * nfx, d.w, mfma, [=](int i, int j, float v) { X[i * ld2x + j] = v; });
     __syncthreads();
-    lr_expand(Y, ld2x, nfy, nfx, dhat, [=](int f, int g) { return lr_projected(X, ld2x, nfy, nfx, f, g); });
+    lr_expand<RAGGED>(Y, ld2x, nfy, nfx, dhat, [=](int f, int g) { return lr_projected(X, ld2x, nfy, nfx, f, g); }, dld);
     __syncthreads();
     // G1 [2 nfy][W] = Z [2 nfy][2 nfx] . (Re Ux; Im Ux) = [Re G1; -Im G1]
     lr_gemm(Y, ld2x, 1, lds + l.ux, l.ldW, 1, 2 * nfy, d.W, 2 * nfx, mfma, [=](int i, int j, float v) { X[i * ldW + j] = v; });
@@ -230,57 +244,94 @@ struct LowresArgs {
     int mfma;
 };
 
-__global__ __launch_bounds__(SC_BLOCK) void k_lowres_planes(LowresArgs a)
+// RAGGED FRAMES (scarlet_lowres_frames): every scene has its own H_s, W_s, h_s, w_s, nfy_s, nfx_s in its row of `dims`
+// and its own five factor matrices, each zero-padded to the shape `d` of the arguments, which holds the per-dimension
+// maxima over the scenes: the strides of every global array and the LDS layout are those of the maxima, the loops and
+// the GEMM extents the scene's own.  frame_hw: the frames the constraint side runs on (scarlet_frames).
+struct LowresFrames {
+    const int *dims;                          // [S][6]
+    const int *frame_hw;                      // [S][2]
+};
+// the scene's own shape inside the padded shape p.  False -- the caller touches nothing -- for a row outside 1..max in
+// any column or one that disagrees with frame_hw (k_check_lowres_frames has marked that scene; the products run without
+// `active`): no entry becomes a loop bound before this test.
+__device__ __forceinline__ bool lr_scene_dims(const LowresFrames &r, int s, const LowresDims &p, LowresDims &d)
 {
+    const int *q = r.dims + 6 * (size_t)s;
+    d.H = q[0]; d.W = q[1]; d.h = q[2]; d.w = q[3]; d.nfy = q[4]; d.nfx = q[5]; d.B = p.B;
+    return d.H >= 1 && d.H <= p.H && d.W >= 1 && d.W <= p.W && d.h >= 1 && d.h <= p.h && d.w >= 1 && d.w <= p.w &&
+           d.nfy >= 1 && d.nfy <= p.nfy && d.nfx >= 1 && d.nfx <= p.nfx &&
+           r.frame_hw[2 * (size_t)s] == d.H && r.frame_hw[2 * (size_t)s + 1] == d.W;
+}
+
+// the arguments of the ragged-frames instance: a.d holds the maxima, a.f.uy / ux one table per scene, v and dhat are per scene
+struct LowresFramesArgs : LowresArgs {
+    LowresFrames fr;
+};
+// Args = LowresArgs: every scene has the shape a.d (k_lowres_planes); LowresFramesArgs: RAGGED (k_lowres_planes_frames)
+template <typename Args>
+__global__ __launch_bounds__(SC_BLOCK) void k_lowres_planes_t(Args a)
+{
+    constexpr bool RAGGED = std::is_same<Args, LowresFramesArgs>::value;
     const int s = blockIdx.x;
     if (!a.active[s]) return;
     extern __shared__ __align__(16) float lr_lds[];
     __shared__ double lred[SC_NWAVES];
-    const LowresDims d = a.d;
-    const LowresLds l = lowres_lds(d);
+    const LowresDims p = a.d;                  // the shape of the global arrays and of the LDS layout
+    LowresDims d = a.d;                        // the shape the scene runs on
+    if constexpr (RAGGED)
+        if (!lr_scene_dims(a.fr, s, p, d)) return;
+    const LowresLds l = lowres_lds(p);
     const bool mfma = a.mfma != 0;
-    const int n = scene_ncomp(a.ncomp, s, a.K), c0 = a.cur[s], nf = d.nfy * d.nfx, HW = d.H * d.W, hw = d.h * d.w;
+    const int n = scene_ncomp(a.ncomp, s, a.K), c0 = a.cur[s], nf = d.nfy * d.nfx, HW = p.H * p.W, hw = p.h * p.w;
+    const int nfp = p.nfy * p.nfx;
     float *spec = lr_lds + l.spec, *X = lr_lds + l.x;
-    lr_load_factors(lr_lds, l, d, a.f, s);
+    lr_load_factors<RAGGED>(lr_lds, l, d, p, a.f, s);
     for (int e = threadIdx.x; e < d.B * 2 * nf; e += SC_BLOCK) spec[e] = 0.f;
     const float *sed = a.sed[c0] + (size_t)s * a.K * a.C + a.band0;
     for (int k = 0; k < n; ++k) {
-        lr_project(lr_lds, l, d, a.morph[c0] + ((size_t)s * a.K + k) * HW, mfma);       // (its first barrier also covers the loads above)
+        lr_project<RAGGED>(lr_lds, l, d, a.morph[c0] + ((size_t)s * a.K + k) * HW, mfma, p.W);   // (its first barrier also covers the loads above)
         for (int e = threadIdx.x; e < nf; e += SC_BLOCK) {
-            const float2 p = lr_projected(X, l.ld2x, d.nfy, d.nfx, e / d.nfx, e % d.nfx);
+            const float2 z = lr_projected(X, l.ld2x, d.nfy, d.nfx, e / d.nfx, e % d.nfx);
             for (int c = 0; c < d.B; ++c) {
                 const float sc = sed[(size_t)k * a.C + c];
-                spec[(c * 2) * nf + e] += sc * p.x;
-                spec[(c * 2 + 1) * nf + e] += sc * p.y;
+                spec[(c * 2) * nf + e] += sc * z.x;
+                spec[(c * 2 + 1) * nf + e] += sc * z.y;
             }
         }
         __syncthreads();
     }
     if (n == 0) __syncthreads();
     for (int c = 0; c < d.B; ++c) {
-        const float2 *dhat = a.f.dhat + ((size_t)(a.f.dhat_per_scene ? s * d.B : 0) + c) * nf;
+        const float2 *dhat = a.f.dhat + ((size_t)(a.f.dhat_per_scene ? s * d.B : 0) + c) * nfp;
         const float *sre = spec + (c * 2) * nf, *sim = sre + nf;
         const int nfx = d.nfx;
-        lr_expand(X, l.ld2x, d.nfy, d.nfx, dhat, [=](int f, int g) { return make_float2(sre[f * nfx + g], sim[f * nfx + g]); });
+        lr_expand<RAGGED>(X, l.ld2x, d.nfy, d.nfx, dhat, [=](int f, int g) { return make_float2(sre[f * nfx + g], sim[f * nfx + g]); },
+                          p.nfx);
         __syncthreads();
-        lr_forward(lr_lds, l, d, mfma);
+        lr_forward<RAGGED>(lr_lds, l, d, mfma);
         const float *img = a.images + ((size_t)s * d.B + c) * hw;
         const float *wgt = a.weights ? a.weights + ((size_t)s * d.B + c) * hw : nullptr;
         double loss = 0;
-        for (int e = threadIdx.x; e < hw; e += SC_BLOCK) {
-            const int i = e / d.w, j = e - i * d.w;
-            const float w = wgt ? wgt[e] : a.weight_scalar;
-            const float r = w * (X[i * l.ldw + j] - img[e]);
+        for (int e = threadIdx.x; e < d.h * d.w; e += SC_BLOCK) {
+            const int i = e / d.w, j = e - i * d.w, ge = RAGGED ? i * p.w + j : e;
+            const float w = wgt ? wgt[ge] : a.weight_scalar;
+            const float r = w * (X[i * l.ldw + j] - img[ge]);
             loss += (double)r * (double)r;
             X[i * l.ldw + j] = w * r;
         }
         loss = block_sum(0.5 * loss, lred);                      // (its barriers also complete E)
         if (threadIdx.x == 0) a.loss_part[(size_t)s * d.B + c] = loss;
         float *G = a.G + ((size_t)s * d.B + c) * HW;
-        const int W = d.W;
-        lr_adjoint(lr_lds, l, d, dhat, mfma, [=](int y, int x, float v) { G[y * W + x] = v; });
+        const int W = p.W;
+        if (RAGGED)        // the contraction reads the whole padded plane and the workspace is not zeroed: 0 outside the frame
+            for (int e = threadIdx.x; e < HW; e += SC_BLOCK)
+                if (e / W >= d.H || e % W >= d.W) G[e] = 0.f;
+        lr_adjoint<RAGGED>(lr_lds, l, d, dhat, mfma, [=](int y, int x, float v) { G[y * W + x] = v; }, p.nfx);
     }
 }
+static constexpr auto k_lowres_planes = &k_lowres_planes_t<LowresArgs>;
+static constexpr auto k_lowres_planes_frames = &k_lowres_planes_t<LowresFramesArgs>;
 
 // The read-only products of a low-resolution observation (scarlet_observations_products_lowres): what the observation
 // sees of the state, forward only.  One workgroup per scene -- every scene, whatever `active` and `status` say, from its
@@ -303,55 +354,83 @@ struct LowresProductsArgs {
     int mfma;
 };
 
-__global__ __launch_bounds__(SC_BLOCK) void k_lowres_products(LowresProductsArgs a)
+// RAGGED (scarlet_observations_products_frames_lowres; LowresFrames above): the scene's own sizes bound every loop,
+// rendered and residual are written over the whole padded h x w plane, 0 outside the scene's own pixels, and a scene
+// whose `dims` row lr_scene_dims refuses gets zeros in all three.
+struct LowresProductsFramesArgs : LowresProductsArgs {
+    LowresFrames fr;
+};
+template <typename Args>
+__global__ __launch_bounds__(SC_BLOCK) void k_lowres_products_t(Args a)
 {
+    constexpr bool RAGGED = std::is_same<Args, LowresProductsFramesArgs>::value;
     extern __shared__ __align__(16) float lr_lds[];
     __shared__ double lred[SC_NWAVES];
     const int s = blockIdx.x;
-    const LowresDims d = a.d;
-    const LowresLds l = lowres_lds(d);
+    const LowresDims p = a.d;                  // the shape of the global arrays and of the LDS layout
+    LowresDims d = a.d;                        // the shape the scene runs on
+    const int HW = p.H * p.W, hw = p.h * p.w;
+    if constexpr (RAGGED) if (!lr_scene_dims(a.fr, s, p, d)) {
+        for (int e = threadIdx.x; e < d.B * hw; e += SC_BLOCK) {
+            if (a.rendered) a.rendered[(size_t)s * d.B * hw + e] = 0.f;
+            if (a.residual) a.residual[(size_t)s * d.B * hw + e] = 0.f;
+        }
+        if (a.loss && threadIdx.x < d.B) a.loss[(size_t)s * d.B + threadIdx.x] = 0;
+        return;
+    }
+    const LowresLds l = lowres_lds(p);
     const bool mfma = a.mfma != 0;
-    const int n = scene_ncomp(a.ncomp, s, a.K), c0 = a.cur[s] & 1, nf = d.nfy * d.nfx, HW = d.H * d.W, hw = d.h * d.w;
+    const int n = scene_ncomp(a.ncomp, s, a.K), c0 = a.cur[s] & 1, nf = p.nfy * p.nfx;
     const int ld2x = l.ld2x, nfy = d.nfy, nfx = d.nfx;
     float *X = lr_lds + l.x, *Y = lr_lds + l.p, *tile = lr_lds + l.p;
-    lr_load_factors(lr_lds, l, d, a.f, s);
+    lr_load_factors<RAGGED>(lr_lds, l, d, p, a.f, s);
     const float *sed = a.sed[c0] + (size_t)s * a.K * a.C + a.band0;
     const float *morph = a.morph[c0] + (size_t)s * a.K * HW;
     for (int c = 0; c < d.B; ++c) {
         // (the band before no longer reads the p region: lr_forward ended synchronised; its epilogue reads X, which is
         // written again only behind lr_project_tile's barriers)
-        for (int e = threadIdx.x; e < HW; e += SC_BLOCK) {
+        for (int e = threadIdx.x; e < d.H * d.W; e += SC_BLOCK) {
+            const int y = e / d.W, x = e % d.W, ge = RAGGED ? y * p.W + x : e;
             float acc = 0.f;
-            for (int k = 0; k < n; ++k) acc = fmaf(sed[(size_t)k * a.C + c], morph[(size_t)k * HW + e], acc);
-            tile[(e / d.W) * l.ldW + e % d.W] = acc;
+            for (int k = 0; k < n; ++k) acc = fmaf(sed[(size_t)k * a.C + c], morph[(size_t)k * HW + ge], acc);
+            tile[y * l.ldW + x] = acc;
         }
-        lr_project_tile(lr_lds, l, d, mfma);                       // (its first barrier also covers the factors)
+        lr_project_tile<RAGGED>(lr_lds, l, d, mfma);               // (its first barrier also covers the factors)
         const float2 *dhat = a.f.dhat + ((size_t)(a.f.dhat_per_scene ? s * d.B : 0) + c) * nf;
         // (the projection sits in X, which lr_forward reads expanded: expand through Y)
-        lr_expand(Y, ld2x, nfy, nfx, dhat, [=](int f, int g) { return lr_projected(X, ld2x, nfy, nfx, f, g); });
+        lr_expand<RAGGED>(Y, ld2x, nfy, nfx, dhat, [=](int f, int g) { return lr_projected(X, ld2x, nfy, nfx, f, g); }, p.nfx);
         __syncthreads();
         for (int e = threadIdx.x; e < 2 * nfy * ld2x; e += SC_BLOCK) X[e] = Y[e];
         __syncthreads();
-        lr_forward(lr_lds, l, d, mfma);
+        lr_forward<RAGGED>(lr_lds, l, d, mfma);
         const size_t plane = ((size_t)s * d.B + c) * hw;
         const float *img = a.images ? a.images + plane : nullptr;
         const float *wgt = a.weights ? a.weights + plane : nullptr;
         double loss = 0;
-        for (int e = threadIdx.x; e < hw; e += SC_BLOCK) {
-            const float r = X[(e / d.w) * l.ldw + e % d.w];
-            if (a.rendered) a.rendered[plane + e] = r;
+        for (int e = threadIdx.x; e < d.h * d.w; e += SC_BLOCK) {
+            const int i = e / d.w, j = e % d.w, ge = RAGGED ? i * p.w + j : e;
+            const float r = X[i * l.ldw + j];
+            if (a.rendered) a.rendered[plane + ge] = r;
             if (!img) continue;
-            const float v = img[e];
-            if (a.residual) a.residual[plane + e] = v - r;
-            const float dw = (wgt ? wgt[e] : a.weight_scalar) * (r - v);
+            const float v = img[ge];
+            if (a.residual) a.residual[plane + ge] = v - r;
+            const float dw = (wgt ? wgt[ge] : a.weight_scalar) * (r - v);
             loss += (double)dw * (double)dw;
         }
+        if (RAGGED)
+            for (int e = threadIdx.x; e < hw; e += SC_BLOCK) {
+                if (e / p.w < d.h && e % p.w < d.w) continue;
+                if (a.rendered) a.rendered[plane + e] = 0.f;
+                if (a.residual && img) a.residual[plane + e] = 0.f;
+            }
         if (a.loss) {
             loss = block_sum(loss, lred);
             if (threadIdx.x == 0) a.loss[(size_t)s * d.B + c] = 0.5 * loss;
         }
     }
 }
+static constexpr auto k_lowres_products = &k_lowres_products_t<LowresProductsArgs>;
+static constexpr auto k_lowres_products_frames = &k_lowres_products_t<LowresProductsFramesArgs>;
 
 // LowResObservation.render / its adjoint for n planes: plane p uses band[p] (NULL: 0) and the factors of scene[p] (NULL: 0)
 struct LowresOpArgs {
@@ -370,7 +449,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_lowres_render(LowresOpArgs a)
     const LowresLds l = lowres_lds(d);
     const int p = blockIdx.x, c = a.band ? a.band[p] : 0, s = a.scene ? a.scene[p] : 0, nf = d.nfy * d.nfx;
     float *X = lr_lds + l.x, *Y = lr_lds + l.p;
-    lr_load_factors(lr_lds, l, d, a.f, s);
+    lr_load_factors(lr_lds, l, d, d, a.f, s);
     lr_project(lr_lds, l, d, a.in + (size_t)p * d.H * d.W, a.mfma != 0);
     const float2 *dhat = a.f.dhat + ((size_t)(a.f.dhat_per_scene ? s * d.B : 0) + c) * nf;
     // (the projection sits in X, which lr_forward reads expanded: expand through Y)
@@ -391,7 +470,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_lowres_adjoint(LowresOpArgs a)
     const LowresLds l = lowres_lds(d);
     const int p = blockIdx.x, c = a.band ? a.band[p] : 0, s = a.scene ? a.scene[p] : 0, nf = d.nfy * d.nfx;
     float *X = lr_lds + l.x;
-    lr_load_factors(lr_lds, l, d, a.f, s);
+    lr_load_factors(lr_lds, l, d, d, a.f, s);
     const float *in = a.in + (size_t)p * d.h * d.w;
     for (int e = threadIdx.x; e < d.h * d.w; e += SC_BLOCK) X[(e / d.w) * l.ldw + e % d.w] = in[e];
     __syncthreads();

@@ -868,6 +868,27 @@ static int check_frames(const scarlet_batch *b, const int32_t *frame_hw, void *s
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
+// ... and for the `dims` table of a low-resolution observation of such scenes (scarlet_lowres_frames): a row outside
+// 1..max in any column (max6: H, W, h, w, nfy, nfx of the padded blocks), or whose H_s, W_s are not frame_hw[s], marks
+// the scene the same way.  k_lowres_planes_frames and k_lowres_products_frames test the row again (lr_scene_dims).
+__global__ void k_check_lowres_frames(const int *dims, const int *frame_hw, int S, LowresDims max6, int *status, int *active)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const int *q = dims + 6 * (size_t)s;
+    const int mx[6] = {max6.H, max6.W, max6.h, max6.w, max6.nfy, max6.nfx};
+    bool bad = q[0] != frame_hw[2 * s] || q[1] != frame_hw[2 * s + 1];
+    for (int i = 0; i < 6; ++i) bad = bad || q[i] < 1 || q[i] > mx[i];
+    if (bad) { status[s] |= SCARLET_STATUS_BAD_FRAME; active[s] = 0; }
+}
+static int check_lowres_frames(const scarlet_batch *b, const scarlet_lowres_frames *lf, const int32_t *frame_hw,
+                               const LowresDims &max6, void *stream)
+{
+    hipLaunchKernelGGL(k_check_lowres_frames, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
+                       (const int *)lf->dims, (const int *)frame_hw, b->S, max6, b->status, b->active);
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
 // the host-side check of the _frames entry points, after check_call: the struct, and what a ragged-frame batch does not take
 static int check_frames_call(const scarlet_batch *b, const scarlet_frames *f)
 {
@@ -2327,15 +2348,20 @@ static void lrs_expand(hipStream_t st, const LowresDims &d, const LowresFactors 
     hipLaunchKernelGGL(k_lrs_expand, dim3((d.nfy * d.nfx + SC_BLOCK - 1) / SC_BLOCK, planes), dim3(SC_BLOCK), 0, st, e);
 }
 // render of the chunk's planes: model (planes of H x W, an LrsOperand: lrs_planes for [planes][H][W]) -> out [planes][h][w]
+// u_per_scene: uy and ux are one table per scene, as vy and vx are with v_per_scene (scenes with their own frames, whose
+// tables are zero-padded to d: the chain runs on the padded extents and sums zeros there)
 static void lrs_forward(hipStream_t st, bool mfma, const LowresDims &d, const LowresFactors &f, const LrsBuffers &u,
-                        const LrsScratch &s, const LrsPlanes &pl, int planes, const LrsOperand &model, float *out)
+                        const LrsScratch &s, const LrsPlanes &pl, int planes, const LrsOperand &model, float *out,
+                        bool u_per_scene = false)
 {
     const int ny2 = 2 * d.nfy, nx2 = 2 * d.nfx;
     const size_t vy_scene = f.v_per_scene ? (size_t)d.h * d.nfy : 0, vx_scene = f.v_per_scene ? (size_t)d.w * d.nfx : 0;
+    const size_t uy_scene = u_per_scene ? (size_t)d.nfy * d.H : 0, ux_scene = u_per_scene ? (size_t)d.nfx * d.W : 0;
     // T [H][2 nfx] = m [H][W] . (Re Ux | Im Ux)^T
-    lrs_gemm(st, mfma, model, lrs_factor(f.ux, 1, d.W, 2, d.nfx, 0), u.a, nx2, s.a, d.H, nx2, d.W, pl, planes);
+    lrs_gemm(st, mfma, model, lrs_factor(f.ux, 1, d.W, 2, d.nfx, ux_scene), u.a, nx2, s.a, d.H, nx2, d.W, pl, planes);
     // C [2 nfy][2 nfx] = (Re Uy; Im Uy) [2 nfy][H] . T
-    lrs_gemm(st, mfma, lrs_factor(f.uy, d.H, 1, 1, d.nfy, 0), lrs_real(u.a, nx2, 1, s.a), u.b, nx2, s.b, ny2, nx2, d.H, pl, planes);
+    lrs_gemm(st, mfma, lrs_factor(f.uy, d.H, 1, 1, d.nfy, uy_scene), lrs_real(u.a, nx2, 1, s.a), u.b, nx2, s.b, ny2, nx2, d.H, pl,
+             planes);
     lrs_expand(st, d, f, u, s, pl, planes);
     // R [2 nfy][w] = Z [2 nfy][2 nfx] . (Re Vx | Im Vx)^T = [Re R; -Im R]
     lrs_gemm(st, mfma, lrs_real(u.z, nx2, 1, s.b), lrs_factor(f.vx, 1, d.nfx, 1, d.nfx, vx_scene), u.a, d.w, s.a, ny2, d.w, nx2,
@@ -2346,10 +2372,12 @@ static void lrs_forward(hipStream_t st, bool mfma, const LowresDims &d, const Lo
 }
 // adjoint of the chunk's planes: resid [planes][h][w] -> out [planes][H][W]
 static void lrs_backward(hipStream_t st, bool mfma, const LowresDims &d, const LowresFactors &f, const LrsBuffers &u,
-                         const LrsScratch &s, const LrsPlanes &pl, int planes, const float *resid, float *out)
+                         const LrsScratch &s, const LrsPlanes &pl, int planes, const float *resid, float *out,
+                         bool u_per_scene = false)
 {
     const int ny2 = 2 * d.nfy, nx2 = 2 * d.nfx;
     const size_t vy_scene = f.v_per_scene ? (size_t)d.h * d.nfy : 0, vx_scene = f.v_per_scene ? (size_t)d.w * d.nfx : 0;
+    const size_t uy_scene = u_per_scene ? (size_t)d.nfy * d.H : 0, ux_scene = u_per_scene ? (size_t)d.nfx * d.W : 0;
     // A1 [2 nfy][w] = (Re Vy | Im Vy)^T . E
     lrs_gemm(st, mfma, lrs_factor(f.vy, 1, d.nfy, 1, d.nfy, vy_scene), lrs_real(resid, d.w, 1, (size_t)d.h * d.w), u.a, d.w, s.a,
              ny2, d.w, d.h, pl, planes);
@@ -2358,9 +2386,10 @@ static void lrs_backward(hipStream_t st, bool mfma, const LowresDims &d, const L
              pl, planes);
     lrs_expand(st, d, f, u, s, pl, planes);
     // G1 [2 nfy][W] = Z [2 nfy][2 nfx] . (Re Ux; Im Ux) = [Re G1; -Im G1]
-    lrs_gemm(st, mfma, lrs_real(u.z, nx2, 1, s.b), lrs_factor(f.ux, d.W, 1, 1, d.nfx, 0), u.a, d.W, s.a, ny2, d.W, nx2, pl, planes);
+    lrs_gemm(st, mfma, lrs_real(u.z, nx2, 1, s.b), lrs_factor(f.ux, d.W, 1, 1, d.nfx, ux_scene), u.a, d.W, s.a, ny2, d.W, nx2, pl,
+             planes);
     // G [H][W] = (Re Uy; Im Uy)^T . G1
-    lrs_gemm(st, mfma, lrs_factor(f.uy, 1, d.H, 2, d.nfy, 0), lrs_real(u.a, d.W, 1, s.a), out, d.W, (size_t)d.H * d.W, d.H, d.W,
+    lrs_gemm(st, mfma, lrs_factor(f.uy, 1, d.H, 2, d.nfy, uy_scene), lrs_real(u.a, d.W, 1, s.a), out, d.W, (size_t)d.H * d.W, d.H, d.W,
              ny2, pl, planes);
 }
 // planes per chunk of a call: what the scratch was sized for, lowered by LOWRES_CHUNK (never raised)
@@ -2374,6 +2403,7 @@ struct LrsFit {
     LowresArgs a;
     LrsScratch s;
     void *scratch;
+    bool u_per_scene;               // scenes with their own frames (scarlet_lowres_frames): a.f.uy / ux hold one table per scene
 };
 static void lrs_fit_planes(hipStream_t st, const LrsFit &f)
 {
@@ -2388,11 +2418,11 @@ static void lrs_fit_planes(hipStream_t st, const LrsFit &f)
         LrsModel m = {{a.sed[0], a.sed[1]}, {a.morph[0], a.morph[1]}, a.cur, a.ncomp, a.K, a.C, a.band0, (int)HW, u.m, f.s.m, pl};
         const int mblocks = (int)((HW + SC_BLOCK - 1) / SC_BLOCK);
         hipLaunchKernelGGL(k_lrs_model, dim3(mblocks < 1024 ? mblocks : 1024, n), dim3(SC_BLOCK), 0, st, m);
-        lrs_forward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, lrs_planes(u.m, d), u.d);
+        lrs_forward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, lrs_planes(u.m, d), u.d, f.u_per_scene);
         LrsResid r = {u.d, f.s.d, a.images, a.weights, a.weight_scalar, d.h * d.w, u.partials, a.loss_part, pl};
         hipLaunchKernelGGL(k_lrs_resid, dim3(LRS_LOSS_BLOCKS, n), dim3(SC_BLOCK), 0, st, r);
         hipLaunchKernelGGL(k_lrs_loss, dim3((n + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, r, n);
-        lrs_backward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, u.d, a.G + (size_t)p0 * HW);
+        lrs_backward(st, a.mfma != 0, d, a.f, u, f.s, pl, n, u.d, a.G + (size_t)p0 * HW, f.u_per_scene);
     }
 }
 static int64_t lowres_scratch_offset(const scarlet_batch *state, const scarlet_batch *ob)
@@ -2494,19 +2524,24 @@ static ObsKernel wide_contract_kernel(const ContractPlan &cp, bool prior)
 // Several observations: one pipeline, every iteration the observation step (the observations' G planes, the contraction
 // over them, L x n_obs, the step) and the tail.  `p` NULL: no prior; given: the passes that write a step are the PRIOR
 // instances (multiobs.h), which read the prior in the pass that already holds the factors and their gradients
-// frame_hw: the scenes' own frames (scarlet_fit_observations_frames; no prior, no low-resolution observation), or NULL.
-// Only the tail reads them: the morphologies and the observations' weights are zero outside a scene's frame, so the
+// frame_hw: the scenes' own frames (scarlet_fit_observations_frames, _frames_lowres; no prior), or NULL.
+// lrf: NULL, or n_obs pointers: the per-scene tables of the low-resolution observations of such scenes
+// (scarlet_fit_observations_frames_lowres; the caller has checked them against `lowres` and frame_hw).
+// Only the tail and the low-resolution kernels of such scenes read the frames: the morphologies and the observations' weights are zero outside a scene's frame, so the
 // planes, the contraction and the Lipschitz constants sum nothing there, and what a PSF's adjoint and the step write
 // outside is zeroed by the RAGGED constraint kernels before anything reads it
 static int fit_observations_call(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
                                  const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
                                  int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr,
-                                 bool large = false, const scarlet_prior *p = nullptr, const int32_t *frame_hw = nullptr)
+                                 bool large = false, const scarlet_prior *p = nullptr, const int32_t *frame_hw = nullptr,
+                                 const scarlet_lowres_frames *const *lrf = nullptr)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = check_counts(state, stream)) || (rc = check_frames(state, frame_hw, stream))) return rc;
+    for (int o = 0; lrf && o < n_obs; ++o)
+        if (lrf[o] && (rc = check_lowres_frames(state, lrf[o], frame_hw, lowres_dims(state, obs[o], lowres[o]), stream))) return rc;
     const WsLayout l = ws_layout(state, WS_FIX);
     WsLayout lo[SC_MAX_OBS];
     ObsArgs m = {};
@@ -2529,15 +2564,20 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
     }
     // low-resolution observations (lowres.h): their G planes and per-plane losses lie in the scarlet_lowres workspace
     // (`large`, scarlet_fit_observations_lowres_large: those that do not fit LDS take the streamed form, lowres_stream.h)
-    LowresArgs la[SC_MAX_OBS] = {};
+    LowresFramesArgs la[SC_MAX_OBS] = {};
     size_t la_lds[SC_MAX_OBS] = {};
     LrsFit ls[SC_MAX_OBS] = {};
     bool streamed[SC_MAX_OBS] = {};
     for (int o = 0; o < n_obs; ++o) {
         const scarlet_lowres *lr = lowres ? lowres[o] : nullptr;
         if (!lr) continue;
-        LowresArgs &a = la[o];
+        const scarlet_lowres_frames *lf = lrf ? lrf[o] : nullptr;
+        LowresFramesArgs &a = la[o];
         a.d = lowres_dims(state, obs[o], lr); a.f = lowres_factors(lr);
+        if (lf) {          // (a.d: the maxima, the shape of the padded blocks; every table is per scene)
+            a.f.uy = (const float2 *)lf->uy; a.f.ux = (const float2 *)lf->ux;
+            a.fr.dims = (const int *)lf->dims; a.fr.frame_hw = (const int *)frame_hw;
+        }
         a.S = state->S; a.K = state->K; a.C = state->B; a.band0 = band0[o];
         a.sed[0] = state->sed[0]; a.sed[1] = state->sed[1]; a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
         a.cur = state->cur; a.active = state->active; a.ncomp = state->n_components;
@@ -2545,13 +2585,14 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         a.G = (float *)lr->workspace;
         a.loss_part = (double *)((char *)lr->workspace + lowres_loss_offset(state, obs[o]));
         a.mfma = !opt(OPT_NO_LOWRES_MFMA);
-        streamed[o] = large && lowres_streamed(a.d);
+        streamed[o] = large && lowres_planes_plan(a.d, opt(OPT_LOWRES_STREAMED) != 0).form == LOWRES_PLANES_STREAMED;
         if (streamed[o]) {
             ls[o].a = a; ls[o].s = lrs_scratch(a.d, true);
             ls[o].scratch = (char *)lr->workspace + lowres_scratch_offset(state, obs[o]);
+            ls[o].u_per_scene = lf != nullptr;
         } else {
             la_lds[o] = lowres_lds_bytes(a.d);
-            if ((rc = allow_lds(k_lowres_planes, la_lds[o]))) return rc;
+            if ((rc = lf ? allow_lds(k_lowres_planes_frames, la_lds[o]) : allow_lds(k_lowres_planes, la_lds[o]))) return rc;
         }
         ObsView &v = m.obs[o];
         v.G = a.G; v.loss_part = a.loss_part; v.Fy = state->H; v.Fx = state->W; v.oy = v.ox = 0;
@@ -2587,7 +2628,8 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         for (int o = 0; o < n_obs; ++o) {
             if (lowres && lowres[o]) {
                 if (streamed[o]) lrs_fit_planes(st, ls[o]);
-                else hipLaunchKernelGGL(k_lowres_planes, dim3(m.S), dim3(SC_BLOCK), la_lds[o], st, la[o]);
+                else if (la[o].fr.dims) hipLaunchKernelGGL(k_lowres_planes_frames, dim3(m.S), dim3(SC_BLOCK), la_lds[o], st, la[o]);
+                else hipLaunchKernelGGL(k_lowres_planes, dim3(m.S), dim3(SC_BLOCK), la_lds[o], st, (LowresArgs)la[o]);
                 continue;
             }
             if (!lo[o].psf) continue;
@@ -2722,6 +2764,45 @@ extern "C" int scarlet_fit_observations_frames(scarlet_batch *state, const scarl
     if (!rc) rc = check_frames_call(state, f);
     return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
                                            nullptr, false, nullptr, f->frame_hw);
+}
+
+// The host checks of the per-scene tables of low-resolution observations (the _frames_lowres entry points), after
+// check_observations / check_lowres_products and check_frames_call; no device call
+static int check_lowres_frames_call(const scarlet_frames *f, const scarlet_lowres *const *lowres,
+                                    const scarlet_lowres_frames *const *lrf, int n_obs)
+{
+    for (int o = 0; o < n_obs; ++o) {
+        if (lrf[o] && !lowres[o])
+            return set_err(SCARLET_E_ARG, "scarlet_lowres_frames for an observation that has no scarlet_lowres");
+        if (lowres[o] && !lrf[o] && f->frame_hw)
+            return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames) with a low-resolution observation that has no "
+                                              "scarlet_lowres_frames: its operator would be that of the padded frame");
+        if (!lrf[o]) continue;
+        if (!f->frame_hw) return set_err(SCARLET_E_ARG, "scarlet_lowres_frames without frame_hw");
+        if (!lrf[o]->dims || !lrf[o]->uy || !lrf[o]->ux) return set_err(SCARLET_E_ARG, "scarlet_lowres_frames: null table");
+        if (!lowres[o]->v_per_scene || !lowres[o]->dhat_per_scene)
+            return set_err(SCARLET_E_ARG, "scarlet_lowres_frames: the scarlet_lowres needs v_per_scene = dhat_per_scene = 1");
+    }
+    return SCARLET_OK;
+}
+
+// scarlet_fit_observations_lowres_large / _wide (the state's channel count decides) for scenes with their own frames,
+// whose low-resolution observations bring their own operators (scarlet_lowres_frames); `c` may be NULL
+extern "C" int scarlet_fit_observations_frames_lowres(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c,
+                                                      scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                                      const scarlet_lowres_frames *const *lowres_frames, const int32_t *band0,
+                                                      int n_obs, int max_iter, double e_rel, int approximate_L, int check_every,
+                                                      void *stream)
+{
+    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+    if (!lowres || !lowres_frames)
+        return set_err(SCARLET_E_ARG, "null low-resolution list (pass arrays of n_obs pointers, NULL = same grid / no tables of its own)");
+    const int bmax = state && state->B > SC_BMAX ? SC_CMAX : SC_BMAX;
+    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, lowres, true, bmax);
+    if (!rc) rc = check_frames_call(state, f);
+    if (!rc) rc = check_lowres_frames_call(f, lowres, lowres_frames, n_obs);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
+                                           lowres, true, nullptr, f->frame_hw, lowres_frames);
 }
 
 // scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused
@@ -3251,25 +3332,31 @@ static int check_lowres_products(const scarlet_batch *state, const scarlet_batch
     return SCARLET_OK;
 }
 // one evaluation, checked before.  model: the state's `model` output [S][C][H][W] that this call has written, or NULL
+// lf, frame_hw: the observation's per-scene tables and the scenes' frames (scarlet_observations_products_frames_lowres), or NULL
 static int launch_lowres_products(const scarlet_batch *state, const scarlet_batch *ob, const scarlet_lowres *lr, int band0,
-                                  const scarlet_products *o, const float *model, void *scratch, hipStream_t st)
+                                  const scarlet_products *o, const float *model, void *scratch, hipStream_t st,
+                                  const scarlet_lowres_frames *lf = nullptr, const int32_t *frame_hw = nullptr)
 {
-    const LowresDims d = lowres_dims(state, ob, lr);
+    const LowresDims d = lowres_dims(state, ob, lr);          // (with lf: the maxima, the shape of the padded blocks)
     const LowresProductsPlan p = lowres_products_plan_of(state, ob, lr, model != nullptr);
-    const LowresFactors f = lowres_factors(lr);
+    LowresFactors f = lowres_factors(lr);
+    if (lf) { f.uy = (const float2 *)lf->uy; f.ux = (const float2 *)lf->ux; }
     const bool mfma = !opt(OPT_NO_LOWRES_MFMA);
     const float *images = (o->residual || o->loss) ? ob->images : nullptr;
     const int K = state->K, C = state->B, HW = d.H * d.W, hw = d.h * d.w;
     int rc;
     switch (p.form) {
     case LOWRES_PRODUCTS_LDS: {
-        LowresProductsArgs a = {};
+        LowresProductsFramesArgs a = {};
         a.d = d; a.f = f; a.K = K; a.C = C; a.band0 = band0;
         a.sed[0] = state->sed[0]; a.sed[1] = state->sed[1]; a.morph[0] = state->morph[0]; a.morph[1] = state->morph[1];
         a.cur = state->cur; a.ncomp = state->n_components;
         a.images = images; a.weights = ob->weights; a.weight_scalar = ob->weight_scalar;
         a.rendered = o->rendered; a.residual = o->residual; a.loss = o->loss; a.mfma = mfma;
-        if ((rc = launch_lds(k_lowres_products, dim3(state->S), dim3(SC_BLOCK), p.lds, st, a))) return rc;
+        if (lf) {
+            a.fr.dims = (const int *)lf->dims; a.fr.frame_hw = (const int *)frame_hw;
+            if ((rc = launch_lds(k_lowres_products_frames, dim3(state->S), dim3(SC_BLOCK), p.lds, st, a))) return rc;
+        } else if ((rc = launch_lds(k_lowres_products, dim3(state->S), dim3(SC_BLOCK), p.lds, st, (LowresProductsArgs)a))) return rc;
         break;
     }
     case LOWRES_PRODUCTS_STREAMED: {
@@ -3289,7 +3376,7 @@ static int launch_lowres_products(const scarlet_batch *state, const scarlet_batc
                 m = lrs_planes(model + (size_t)(band0 + p0) * HW, d);
                 m.scene = (size_t)(C - d.B) * HW;
             }
-            lrs_forward(st, mfma, d, f, u, p.s, pl, n, m, u.d);
+            lrs_forward(st, mfma, d, f, u, p.s, pl, n, m, u.d, lf != nullptr);
             LrsFinish fin = {u.d, p.s.d, images, ob->weights, ob->weight_scalar, hw, o->rendered, o->residual,
                              o->loss ? u.partials : nullptr, p0};
             hipLaunchKernelGGL(k_lrs_products_finish, dim3(LRS_LOSS_BLOCKS, n), dim3(SC_BLOCK), 0, st, fin);
@@ -3321,11 +3408,13 @@ extern "C" int64_t scarlet_lowres_products_scratch_bytes_wide(const scarlet_batc
 }
 
 // the evaluations of scarlet_observations_products; lowres: NULL, or n_obs pointers (NULL = on the model's grid)
-// frame_hw: the scenes' own frames (scarlet_observations_products_frames; never with `lowres`), or NULL
+// frame_hw: the scenes' own frames (scarlet_observations_products_frames, _frames_lowres), or NULL
+// lrf: NULL, or n_obs pointers: the per-scene tables of the low-resolution observations of such scenes (checked by the caller)
 static int observations_products_call(const scarlet_batch *state, scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
                                       const int32_t *band0, int n_obs, const scarlet_products *state_out,
                                       const scarlet_products *out, void *scratch, int64_t scratch_bytes, void *stream,
-                                      int bmax = SC_BMAX, const int32_t *frame_hw = nullptr)
+                                      int bmax = SC_BMAX, const int32_t *frame_hw = nullptr,
+                                      const scarlet_lowres_frames *const *lrf = nullptr)
 {
     if (!state) return set_err(SCARLET_E_ARG, "null batch");
     if (n_obs < 0 || n_obs > SCARLET_MAX_OBSERVATIONS || (n_obs > 0 && (!obs || !band0 || !out)))
@@ -3364,7 +3453,8 @@ static int observations_products_call(const scarlet_batch *state, scarlet_batch 
     for (int i = 0; i < n_obs; ++i) {
         if (!products_any(&out[i])) continue;
         if (lowres && lowres[i])
-            rc = launch_lowres_products(state, obs[i], lowres[i], band0[i], &out[i], model, scratch, (hipStream_t)stream);
+            rc = launch_lowres_products(state, obs[i], lowres[i], band0[i], &out[i], model, scratch, (hipStream_t)stream,
+                                        lrf ? lrf[i] : nullptr, frame_hw);
         else rc = launch_products(state, obs[i], band0[i], &out[i], scratch, (hipStream_t)stream, frame_hw);
         if (rc) return rc;
     }
@@ -3408,6 +3498,27 @@ extern "C" int scarlet_observations_products_frames(const scarlet_batch *state, 
     if (int rc = check_frames_call(state, f)) return rc;
     return observations_products_call(state, obs, nullptr, band0, n_obs, state_out, out, scratch, scratch_bytes, stream,
                                       state->B > SC_BMAX ? SC_CMAX : SC_BMAX, f->frame_hw);
+}
+
+// scarlet_observations_products_lowres / _wide (the state's channel count decides) of scenes with their own frames whose
+// low-resolution observations bring their own operators: their rendered and residual are zero outside each scene's own
+// h_s x w_s pixels, the loss runs over those
+extern "C" int scarlet_observations_products_frames_lowres(const scarlet_batch *state, const scarlet_frames *f,
+                                                           scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                                           const scarlet_lowres_frames *const *lowres_frames,
+                                                           const int32_t *band0, int n_obs, const scarlet_products *state_out,
+                                                           const scarlet_products *out, void *scratch, int64_t scratch_bytes,
+                                                           void *stream)
+{
+    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+    if (!state) return set_err(SCARLET_E_ARG, "null batch");
+    if (!lowres || !lowres_frames)
+        return set_err(SCARLET_E_ARG, "null low-resolution list (pass arrays of n_obs pointers, NULL = same grid / no tables of its own)");
+    if (n_obs < 0 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "products: bad observation list");
+    if (int rc = check_frames_call(state, f)) return rc;
+    if (int rc = check_lowres_frames_call(f, lowres, lowres_frames, n_obs)) return rc;
+    return observations_products_call(state, obs, lowres, band0, n_obs, state_out, out, scratch, scratch_bytes, stream,
+                                      state->B > SC_BMAX ? SC_CMAX : SC_BMAX, f->frame_hw, lowres_frames);
 }
 
 // diagnostics: contract_plan (launch_plan.h) of a joint fit with K components over C model channels:

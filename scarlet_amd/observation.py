@@ -219,7 +219,8 @@ class LowResObservation(Observation):
 
         Sets ``lr_shape`` (the rows and columns of the observation that lie inside the model frame), ``covers`` (they
         are all of them), ``_band_slice``, ``origin`` / ``step`` (the model-frame position of pixel (0, 0) and the pixel
-        ratio per axis) and ``factors`` (complex128; `factors_f32` and the device tensors derive from it)."""
+        ratio per axis), ``model_psf`` (the model frame's PSF image the kernels were matched to) and ``factors``
+        (complex128; `factors_f32` and the device tensors derive from it)."""
         from . import resampling as rs
         _match_dtype_and_bands(self, model_frame)
         assert model_frame.wcs is not None and model_frame.psfs is not None, "the model frame needs a WCS and a PSF"
@@ -241,6 +242,7 @@ class LowResObservation(Observation):
         self.origin = (float(y_at[0]), float(x_at[0]))       # (of the first pixel inside: pixel (0, 0) when `covers`)
         self.step = (float(y_at[1] - y_at[0]) if len(y_at) > 1 else 1.0, float(x_at[1] - x_at[0]) if len(x_at) > 1 else 1.0)
         model_psf = np.asarray(model_frame.psfs.image)[0]
+        self.model_psf = model_psf                       # (the batch classes check that the scenes of a batch share it)
         fine, coarse = rs.match_psfs(model_psf, np.asarray(self.frame.psfs.image), model_frame.wcs, self.frame.wcs)
         self._diff_kernels = rs.difference_kernel(coarse, fine)
         self._factors = None
