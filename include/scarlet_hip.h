@@ -71,6 +71,9 @@ extern "C" {
 #define SCARLET_STATUS_NONFINITE         2  /* NaN/Inf met in centroid or normalisation   */
 #define SCARLET_STATUS_BAD_COUNT         4  /* n_components[s] outside 1..K: the scene is
                                                left untouched and inactive                 */
+#define SCARLET_STATUS_BAD_OPTION       32  /* a row of scarlet_update_options of this scene holds an
+                                               unknown or out-of-range value: the scene is left
+                                               untouched and inactive                      */
 #define SCARLET_STATUS_BAD_INIT          8  /* bad input of scarlet_init_sources in this scene:
                                                it is left untouched and inactive           */
 #define SCARLET_STATUS_BAD_FRAME        16  /* frame_hw[s] outside 1..H x 1..W: the scene is
@@ -95,6 +98,10 @@ extern "C" {
 #define SCARLET_NORM_SED       0
 #define SCARLET_NORM_MORPH     1
 #define SCARLET_NORM_MORPH_MAX 2
+#define SCARLET_NORM_NONE      3   /* scarlet_update_options only: the update does not normalise */
+/* scarlet_update_options::positive -- update.positive_sed / positive_morph / positive (update.py:13-32) */
+#define SCARLET_POSITIVE_SED   1
+#define SCARLET_POSITIVE_MORPH 2
 
 const char *scarlet_version(void);
 const char *scarlet_last_error(void);
@@ -431,6 +438,55 @@ int scarlet_source_update_constrained(scarlet_batch *b, const scarlet_constraint
 int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
                                          const int32_t *band0, int n_obs, int max_iter, double e_rel,
                                          int approximate_L, int check_every, void *stream);
+
+/* The stock update functions' other options (update.symmetric(algorithm=, strength=), update.monotonic(use_nearest=,
+ * thresh=), update.positive / positive_sed / positive_morph, update.normalized(type=); update.py:13-199): what a user who
+ * overrides PointSource / ExtendedSource.update (source.py:402-440, "can be overwritten if a different set of constraints or
+ * update functions is desired") changes most often, per component.  scarlet_batch does not change; the options travel in a
+ * struct of their own beside scarlet_constraints, device memory owned by the caller, indexed like the batch.  They need no
+ * workspace.  The order of the pipeline stays that of source.py:402-440: max_pixel, (symmetric: the centroid every fifth
+ * iteration whatever the algorithm, then the symmetry), (monotonic: the sweep), sparse_l0 / sparse_l1, positive, normalized.
+ *   - o == NULL is SCARLET_E_ARG.  With every member NULL the three entry points ARE scarlet_fit_constrained (p = NULL),
+ *     scarlet_source_update_constrained (p = NULL) and scarlet_fit_observations_constrained, bit for bit; `c` may be NULL.
+ *   - Rows of absent components and of inactive scenes are not read.
+ *   - Before anything else one thread per scene checks the rows of the scene's present components on the device
+ *     (k_check_options): an unknown algorithm, normalisation or positive value, a strength outside [0, 1], a thresh outside
+ *     [0, 1), or a thresh != 0 with mono_nearest (the reference raises ValueError, operator.py:107-110) gives the scene
+ *     SCARLET_STATUS_BAD_OPTION and active = 0; the scene is left untouched (also by the constructors' update) and the
+ *     other scenes go on.
+ *   - SCARLET_E_NOTIMPL, found on the host before any launch: a batch with `group` (layers are tied to soft symmetry with
+ *     shift = None), a wide state (state->B > 8).  There is no prior, no scarlet_frames and no low-resolution argument.
+ *   - A batch with options takes the general path: no one-launch iteration, one pipeline, no box stage beyond 64 pixels; the
+ *     full-frame forms of the constraint kernels (their options instances, engine.h) serve every component.
+ *   - sym_algorithm: SCARLET_SYM_KSPACE still falls back to soft symmetry with strength 1 while the component has no shift
+ *     (NaN); the in-place operators (_SOFT, _SDSS) act on the whole array where the centre is the array's middle, k-space is
+ *     a no-op there (uncentered_operator, operator.py:203-204).  sym_strength is read for _SOFT only.
+ *   - mono_nearest: the reference pixel is the first neighbour of largest cosine towards the peak (operator.py:591-600):
+ *     x = min(x, x_ref), swept ring by ring (the reference pixel lies on the previous Chebyshev ring), exact in any precision.
+ *   - positive: bit 0 (SCARLET_POSITIVE_SED) clamps the SED at 0, bit 1 (SCARLET_POSITIVE_MORPH) the morphology.
+ *   - normalize: _MORPH_MAX divides the morphology by its maximum and multiplies the SED by it, _MORPH does the same with
+ *     morph.sum(), _SED divides the SED by sed.sum() and multiplies the morphology by it, _NONE leaves both.  A norm that is
+ *     not positive and finite sets SCARLET_STATUS_NONFINITE.  The convergence sums are taken on what is written. */
+typedef struct scarlet_update_options {      /* device [S][K] each, or NULL = the default */
+    const uint8_t *sym_algorithm;   /* SCARLET_SYM_KSPACE (default) | _SOFT | _SDSS                                    */
+    const float   *sym_strength;    /* soft only; default 0.5 (update.py:170); in [0, 1]                               */
+    const uint8_t *mono_nearest;    /* 0 (default): weighted sweep; 1: nearest neighbour                               */
+    const float   *mono_thresh;     /* default 0; in [0, 1); must be 0 where mono_nearest                              */
+    const uint8_t *positive;        /* bit 0 sed, bit 1 morph; default 3                                               */
+    const uint8_t *normalize;       /* SCARLET_NORM_MORPH_MAX (default) | _MORPH | _SED | _NONE                        */
+} scarlet_update_options;           /* 48 bytes */
+
+/* scarlet_fit_constrained (p = NULL) with update options; c may be NULL */
+int scarlet_fit_options(scarlet_batch *b, const scarlet_constraints *c /* or NULL */, const scarlet_update_options *o,
+                        int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
+/* scarlet_source_update_constrained (p = NULL) with update options: the constructors' update() (in_iteration = 0) leaves
+ * scenes with SCARLET_STATUS_BAD_OPTION, _BAD_INIT or _BAD_COUNT untouched */
+int scarlet_source_update_options(scarlet_batch *b, const scarlet_constraints *c /* or NULL */, const scarlet_update_options *o,
+                                  int in_iteration, void *stream);
+/* scarlet_fit_observations_constrained with update options on the state (same-grid observations, state->B <= 8) */
+int scarlet_fit_observations_options(scarlet_batch *state, const scarlet_constraints *c /* or NULL */,
+                                     const scarlet_update_options *o, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                     int max_iter, double e_rel, int approximate_L, int check_every, void *stream);
 
 /* Ragged frames: scenes of different frame sizes in one batch.  scarlet_batch does not change; the shapes travel in a
  * struct of their own.  frame_hw: device [S][2] int32 (h, w), or NULL = every scene is H x W (the _frames entry points then

@@ -39,11 +39,14 @@ OK, E_ARG, E_TOO_LARGE, E_HIP, E_NOTIMPL = 0, -1, -2, -3, -4
 FLAG_SED_NOT_CONVERGED, FLAG_MORPH_NOT_CONVERGED, FLAG_EDGE_PIXELS, FLAG_NO_VALID_PIXELS = 1, 2, 4, 8
 STATUS_CENTER_AT_EDGE, STATUS_NONFINITE, STATUS_BAD_COUNT, STATUS_BAD_INIT = 1, 2, 4, 8
 STATUS_BAD_FRAME = 16
+STATUS_BAD_OPTION = 32
 INIT_EXTENDED, INIT_POINT = 0, 1           # SCARLET_INIT_*
 MAX_LAYERS = 8                             # SCARLET_MAX_LAYERS
 SYM_KSPACE, SYM_SOFT, SYM_SDSS = 0, 1, 2
 SYM_FULL_WINDOW = 16
 NORM_SED, NORM_MORPH, NORM_MORPH_MAX = 0, 1, 2
+NORM_NONE = 3                              # scarlet_update_options only
+POSITIVE_SED, POSITIVE_MORPH = 1, 2        # SCARLET_POSITIVE_* (bits of scarlet_update_options::positive)
 MAX_SIDE, MAX_COMPONENTS = 1024, 256       # SCARLET_MAX_SIDE, SCARLET_MAX_COMPONENTS
 MAX_OBSERVATIONS = 8                       # SCARLET_MAX_OBSERVATIONS
 MAX_CHANNELS = 32                          # SCARLET_MAX_CHANNELS (from_observations(..., wide=True))
@@ -101,6 +104,12 @@ class ScarletPrior(Structure):
 class ScarletConstraints(Structure):
     """struct scarlet_constraints of include/scarlet_hip.h (field order must match)."""
     _fields_ = [("symmetric", c_void_p), ("monotonic", c_void_p), ("l0_thresh", c_void_p), ("l1_thresh", c_void_p)]
+
+
+class ScarletUpdateOptions(Structure):
+    """struct scarlet_update_options of include/scarlet_hip.h (field order must match)."""
+    _fields_ = [("sym_algorithm", c_void_p), ("sym_strength", c_void_p), ("mono_nearest", c_void_p), ("mono_thresh", c_void_p),
+                ("positive", c_void_p), ("normalize", c_void_p)]
 
 
 class ScarletLowres(Structure):
@@ -164,6 +173,12 @@ _SIGNATURES = {
     "scarlet_source_update_constrained": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletPrior), c_int, _P]),
     "scarlet_fit_observations_constrained": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints),
                                                      POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
+    "scarlet_fit_options": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletUpdateOptions), c_int, c_double,
+                                    c_int, c_int, _P]),
+    "scarlet_source_update_options": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletUpdateOptions), c_int,
+                                              _P]),
+    "scarlet_fit_observations_options": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(ScarletUpdateOptions),
+                                                 POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),
     "scarlet_lowres_workspace_bytes": (c_int64, [POINTER(ScarletBatch), POINTER(ScarletBatch), POINTER(ScarletLowres)]),
     "scarlet_fit_observations_lowres": (c_int, [POINTER(ScarletBatch), POINTER(ScarletConstraints), POINTER(POINTER(ScarletBatch)),
                                                 POINTER(POINTER(ScarletLowres)), _P, c_int, c_int, c_double, c_int, c_int, _P]),

@@ -216,6 +216,119 @@ def constraint_arrays(value, S, K, kind, group=None):
     return out
 
 
+_SYMMETRY_NAMES = {"kspace": _lib.SYM_KSPACE, "soft": _lib.SYM_SOFT, "sdss": _lib.SYM_SDSS}
+_POSITIVE_NAMES = {"both": _lib.POSITIVE_SED | _lib.POSITIVE_MORPH, "sed": _lib.POSITIVE_SED, "morph": _lib.POSITIVE_MORPH,
+                   "none": 0}
+_NORMALIZATION_NAMES = {"morph_max": _lib.NORM_MORPH_MAX, "morph": _lib.NORM_MORPH, "sed": _lib.NORM_SED, "none": _lib.NORM_NONE}
+
+
+def _setting_array(value, S, K, name, entry, dtype, default):
+    """`value` as an (S, K) host array with the broadcasting of `constraint_arrays`: one value, a (K,) sequence, an (S, K)
+    array or S per-scene lists of at most K entries (the rest keeps `default`).  `entry` maps one item to its stored value
+    and raises ValueError for a bad one."""
+    out = np.full((S, K), default, dtype=dtype)
+    if hasattr(value, "detach"):
+        value = value.detach().cpu().numpy()
+    if isinstance(value, (str, bytes)) or is_scalar_setting(value):
+        out[:] = entry(value.item() if hasattr(value, "ndim") else value)
+        return out
+    seq = list(value)
+    rows = [hasattr(r, "__len__") and not isinstance(r, (str, bytes)) for r in seq]
+    if any(rows):
+        if not all(rows):
+            raise ValueError("%s: a mix of per-scene rows and single entries" % name)
+        if len(seq) != S:
+            raise ValueError("%s: %d per-scene rows for S = %d scenes" % (name, len(seq), S))
+        for s_, r in enumerate(seq):
+            r = list(r)
+            if len(r) > K:
+                raise ValueError("%s: scene %d has %d entries, more than K = %d" % (name, s_, len(r), K))
+            if any(hasattr(v, "__len__") and not isinstance(v, (str, bytes)) for v in r):
+                raise ValueError("%s must be one value, (K,) = (%d,), (S, K) = (%d, %d) or S per-scene lists" % (name, K, S, K))
+            out[s_, :len(r)] = [entry(v) for v in r]
+    else:
+        if len(seq) != K:
+            raise ValueError("%s: %d entries for K = %d components per scene" % (name, len(seq), K))
+        out[:] = np.array([entry(v) for v in seq], dtype=dtype)[None, :]
+    return out
+
+
+class UpdateOptions(object):
+    """The options of the reference's stock update functions for the components of a batch: what a user who overrides
+    PointSource / ExtendedSource.update (source.py:402-440) to call them with other arguments passes as
+    `BlendBatch(..., update=UpdateOptions(...))`.  The pipeline's order stays the reference's.
+
+    symmetry : "kspace" (default) | "soft" | "sdss" -- update.symmetric(algorithm=)
+    strength : soft symmetry's strength in [0, 1], default 0.5 (update.py:170)
+    use_nearest : update.monotonic(use_nearest=): the nearest-neighbour sweep instead of the weighted one
+    monotonic_thresh : update.monotonic(thresh=) in [0, 1); must be 0 with use_nearest (the reference raises ValueError)
+    positive : "both" (update.positive) | "sed" (positive_sed) | "morph" (positive_morph) | "none"
+    normalization : "morph_max" (default) | "morph" | "sed" -- update.normalized(type=) -- | "none"
+
+    Each is one value for the batch or one per component, broadcast like the constraint switches (`constraint_arrays`): a
+    (K,) sequence, an (S, K) array, or S per-scene lists for ragged counts.  Names may be given as the library's integers.
+    `arrays(S, K)` checks everything on the host (ValueError) and needs no device."""
+
+    FIELDS = ("sym_algorithm", "sym_strength", "mono_nearest", "mono_thresh", "positive", "normalize")
+
+    def __init__(self, symmetry="kspace", strength=0.5, use_nearest=False, monotonic_thresh=0, positive="both",
+                 normalization="morph_max"):
+        self.symmetry, self.strength, self.use_nearest = symmetry, strength, use_nearest
+        self.monotonic_thresh, self.positive, self.normalization = monotonic_thresh, positive, normalization
+
+    def arrays(self, S, K):
+        """{member of scarlet_update_options: (S, K) host array}; ValueError for an unknown name, a number out of range or
+        use_nearest with a thresh."""
+        S, K = int(S), int(K)
+
+        def named(table, what):
+            def entry(v):
+                if isinstance(v, bytes):
+                    v = v.decode()
+                if isinstance(v, str):
+                    if v.lower() not in table:
+                        raise ValueError("%s: unknown value %r (one of %s)" % (what, v, ", ".join(sorted(table))))
+                    return table[v.lower()]
+                if isinstance(v, (bool, float)) or v is None or int(v) not in table.values():
+                    raise ValueError("%s: unknown value %r (one of %s)" % (what, v, ", ".join(sorted(table))))
+                return int(v)
+            return entry
+
+        def number(what, lo, hi, closed):
+            def entry(v):
+                if v is None or isinstance(v, (str, bytes)):
+                    raise ValueError("%s: %r is not a number" % (what, v))
+                v = float(v)
+                if not (lo <= v <= hi if closed else lo <= v < hi):
+                    raise ValueError("%s = %r lies outside [%g, %g%s" % (what, v, lo, hi, "]" if closed else ")"))
+                return v
+            return entry
+
+        def switch(v):
+            if v is None or isinstance(v, (str, bytes)):
+                raise ValueError("use_nearest: %r is not a switch value" % (v,))
+            return 1 if bool(v) else 0
+
+        out = {
+            "sym_algorithm": _setting_array(self.symmetry, S, K, "symmetry", named(_SYMMETRY_NAMES, "symmetry"), np.uint8,
+                                            _lib.SYM_KSPACE),
+            "sym_strength": _setting_array(self.strength, S, K, "strength", number("strength", 0.0, 1.0, True), np.float32, 0.5),
+            "mono_nearest": _setting_array(self.use_nearest, S, K, "use_nearest", switch, np.uint8, 0),
+            "mono_thresh": _setting_array(self.monotonic_thresh, S, K, "monotonic_thresh",
+                                          number("monotonic_thresh", 0.0, 1.0, False), np.float32, 0.0),
+            "positive": _setting_array(self.positive, S, K, "positive", named(_POSITIVE_NAMES, "positive"), np.uint8,
+                                       _POSITIVE_NAMES["both"]),
+            "normalize": _setting_array(self.normalization, S, K, "normalization", named(_NORMALIZATION_NAMES, "normalization"),
+                                        np.uint8, _lib.NORM_MORPH_MAX),
+        }
+        bad = (out["mono_nearest"] != 0) & (out["mono_thresh"] != 0)
+        if bad.any():
+            s, k = [int(v[0]) for v in np.nonzero(bad)]
+            raise ValueError("use_nearest with monotonic_thresh = %g (scene %d, component %d): Thresholding does not work with "
+                             "nearest neighbor monotonicity" % (float(out["mono_thresh"][s, k]), s, k))
+        return out
+
+
 def _check_obs_psfs(psfs, S, B, name, shapes="(B, P, P) or (S, B, P, P)"):
     """The observed PSFs are one set for every scene or one per scene."""
     if np.ndim(psfs) not in (3, 4) or tuple(np.shape(psfs)[:-2]) not in ((B,), (S, B)):
@@ -472,13 +585,27 @@ class BlendBatch(object):
         (S, B, H, W) weights with the frame mask multiplied in).  Centres are in the scene's own coordinates.  Such a
         batch takes no `group` and no prior; `init_sources` starts extended sources only.  A joint fit gets its frames
         from its observations (`ObservationBatch(frame_shapes=...)`), not from this keyword.
+    update : None (the stock pipeline of source.py:402-440), or an `UpdateOptions`: each component's symmetry algorithm and
+        strength, sweep (weighted with a thresh, or nearest neighbour), positivity and normalisation, on the device
+        (scarlet_update_options).  Such a batch takes the general path, and no `group`, prior, ragged frames, `wide=True` or
+        low-resolution observation (NotImplementedError).  A scene whose options were corrupted on the device gets
+        STATUS_BAD_OPTION and is left untouched and inactive (`raise_on_status` names it).
     """
 
     def __init__(self, images, centers, weights=None, symmetric=True, monotonic=True,
                  l0_thresh=None, l1_thresh=None, centroid_weight=None, mse_capacity=256,
                  device=None, group=None, n_components=None, _frame=None, _morph=True, frame_shapes=None,
-                 _frames=None):
+                 _frames=None, update=None):
         frames = _frames             # (from_observations: the checked shapes of its observations, for the state)
+        if update is not None:       # host-side refusals first: they need no device
+            if not isinstance(update, UpdateOptions):
+                raise ValueError("update must be an UpdateOptions (or None), not %r" % type(update).__name__)
+            if group is not None:
+                raise NotImplementedError("a batch with update= (UpdateOptions) does not take group=: the layers of a "
+                                          "multi-component source are tied to soft symmetry")
+            if frames is not None or frame_shapes is not None or _is_frame_list(images):
+                raise NotImplementedError("a batch with update= (UpdateOptions) does not take frame_shapes / a list of frames "
+                                          "(ragged frames)")
         if frame_shapes is not None or _is_frame_list(images):      # host-side checks first: they need no device
             images, frames, weights, centers, n_components = ragged_frame_inputs(images, centers, frame_shapes, weights, group,
                                                                                   n_components)
@@ -588,6 +715,14 @@ class BlendBatch(object):
         self._cons = _lib.ScarletConstraints()      # members NULL for the settings given as scalars
         for name, x in self.constraints.items():
             setattr(self._cons, name, x.data_ptr())
+        # update options (scarlet_update_options): checked on the host, then one (S, K) device array per member
+        self.update_options, self._upd = None, None
+        if update is not None:
+            host = update.arrays(S, K)
+            self.update_options = {name: torch.as_tensor(a).to(device=self.device).contiguous() for name, a in host.items()}
+            self._upd = _lib.ScarletUpdateOptions()
+            for name, x in self.update_options.items():
+                setattr(self._upd, name, x.data_ptr())
         cw = default_centroid_weight() if centroid_weight is None else np.asarray(centroid_weight, dtype=np.float64)
         assert cw.ndim == 2 and cw.shape[0] == cw.shape[1] and cw.shape[0] % 2 == 1
         self.centroid_weight = torch.as_tensor(cw).to(**f64).contiguous()
@@ -609,6 +744,10 @@ class BlendBatch(object):
     # Every call into the library's loops goes through these two and _fit_observations.  The *_constrained entry points
     # with a NULL member read that setting from the batch's scalars, and with prior = NULL step without one.
     def _lib_fit(self, ps, max_iter, e_rel, approximate_L, check_every):
+        if self._upd is not None:                   # (never with a prior or ragged frames: refused before)
+            return _lib.check(_lib.lib.scarlet_fit_options(
+                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(max_iter), float(e_rel),
+                int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
         if self.frame_shapes is not None:           # (never with a prior: _refuse_frames_prior)
             return _lib.check(_lib.lib.scarlet_fit_frames(
                 ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(max_iter), float(e_rel),
@@ -618,6 +757,9 @@ class BlendBatch(object):
             float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
 
     def _lib_update(self, ps, in_iteration):
+        if self._upd is not None:
+            return _lib.check(_lib.lib.scarlet_source_update_options(
+                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(in_iteration), _lib.stream_ptr()))
         if self.frame_shapes is not None:
             return _lib.check(_lib.lib.scarlet_source_update_frames(
                 ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(in_iteration), _lib.stream_ptr()))
@@ -759,6 +901,10 @@ class BlendBatch(object):
 
     def raise_on_status(self):
         st = self.status.cpu().numpy()
+        if (st & _lib.STATUS_BAD_OPTION).any():
+            bad = np.nonzero(st & _lib.STATUS_BAD_OPTION)[0]
+            raise ValueError("update options of scenes {} hold an unknown or out-of-range value (BAD_OPTION); they were left "
+                             "untouched and inactive".format(bad.tolist()))
         if (st & _lib.STATUS_BAD_FRAME).any():
             bad = np.nonzero(st & _lib.STATUS_BAD_FRAME)[0]
             raise ValueError("frame_shapes of scenes {} lie outside 1..{} x 1..{}; they were left untouched and "
@@ -948,13 +1094,14 @@ class BlendBatch(object):
         args = (bg.ctypes.data_as(ctypes.c_void_p), float(thresh),
                 None if sc is None else sc.ctypes.data_as(ctypes.c_void_p), int(bool(init_symmetric)),
                 int(self.monotonic if init_monotonic is None else bool(init_monotonic)),
-                int(bool(run_update) and not self.constrained), _lib.stream_ptr())
+                int(bool(run_update) and not self.constrained and self._upd is None), _lib.stream_ptr())
         if self.frame_shapes is not None:           # each scene's start on its own frame
             rc = _lib.lib.scarlet_init_extended_frames(ctypes.byref(self._c), ctypes.byref(self._frames), *args)
         else:
             rc = _lib.lib.scarlet_init_extended(ctypes.byref(self._c), *args)
         _lib.check(rc)
-        if run_update and self.constrained:       # the constructors' update() with each component's own settings
+        if run_update and (self.constrained or self._upd is not None):
+            # the constructors' update() with each component's own settings and update options
             self.update_sources()
         return self
 
@@ -1052,14 +1199,14 @@ class BlendBatch(object):
         spec.thresh = float(thresh)
         spec.init_symmetric = int(bool(init_symmetric))
         spec.init_monotonic = int(self.monotonic if init_monotonic is None else bool(init_monotonic))
-        spec.run_update = int(bool(run_update) and not self.constrained)
+        spec.run_update = int(bool(run_update) and not self.constrained and self._upd is None)
         if self.frame_shapes is not None:
             _lib.check(_lib.lib.scarlet_init_sources_frames(ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(spec),
                                                             _lib.stream_ptr()))
         else:
             _lib.check(_lib.lib.scarlet_init_sources(ctypes.byref(self._c), ctypes.byref(spec), _lib.stream_ptr()))
         self._init_checked = True
-        if run_update and self.constrained:
+        if run_update and (self.constrained or self._upd is not None):
             # the constructors' update() with each component's own settings; scenes with STATUS_BAD_INIT stay untouched
             self.update_sources()
         return self
@@ -1081,6 +1228,7 @@ class BlendBatch(object):
             `L_components` then holds the constants each component stepped with.  Shapes are those of this batch: for
             one made by `from_observations` the SEDs are (S, K, C) over the model frame's C channels."""
         self._refuse_frames_prior(prior)
+        self._refuse_update_prior(prior)
         self._ensure_mse_capacity(max_iter)
         self.active.fill_(1)          # a new fit() call iterates again, like the reference
         if self._init_checked:        # ... except the scenes whose init_sources input was bad
@@ -1096,7 +1244,12 @@ class BlendBatch(object):
         Python-level update() override path).  A batch made by `from_observations` runs one iteration
         of scarlet_fit_observations_constrained (scarlet_fit_observations_prior with one).  `prior`: as in `fit`."""
         self._refuse_frames_prior(prior)
+        self._refuse_update_prior(prior)
         self._ensure_mse_capacity(1)
+        if self._upd is not None and self._observations is None:
+            # one iteration of scarlet_fit_options: its device check of the options comes before the gradient step
+            self._lib_fit(None, 1, e_rel, approximate_L, 0)
+            return
         if self._observations is not None:
             if self._init_checked:
                 self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
@@ -1119,6 +1272,10 @@ class BlendBatch(object):
             raise NotImplementedError("a ragged-frame batch (frame_shapes) does not take a prior")
 
     # ------------------------------------------------------------------ priors
+    def _refuse_update_prior(self, prior):
+        if prior is not None and self._upd is not None:
+            raise NotImplementedError("a batch with update= (UpdateOptions) does not take a prior")
+
     def _prior_struct(self, quad):
         """scarlet_prior with the quadratic part bound to this batch and L_comp = L_components."""
         t = self.torch
@@ -1219,6 +1376,12 @@ class BlendBatch(object):
             raise NotImplementedError("from_observations does not take frame_shapes (ragged frames): they belong to the "
                                       "observations, ObservationBatch(..., frame_shapes=...) or ObservationBatch.from_frames")
         obs = list(observations)
+        if kwargs.get("update") is not None:        # update options: same-grid observations, at most 8 model channels
+            if wide:
+                raise NotImplementedError("from_observations: update= (UpdateOptions) with wide=True is not implemented")
+            if any(isinstance(o, LowResObservationBatch) for o in obs):
+                raise NotImplementedError("from_observations: update= (UpdateOptions) with a low-resolution observation is not "
+                                          "implemented")
         if not 1 <= len(obs) <= _lib.MAX_OBSERVATIONS:
             raise ValueError("from_observations: 1 to %d observations, not %d" % (_lib.MAX_OBSERVATIONS, len(obs)))
         if not all(isinstance(o, ObservationBatch) for o in obs):      # (a LowResObservationBatch is one)
@@ -1396,6 +1559,9 @@ class BlendBatch(object):
         if any(x is not None for x in self._lowres):
             none = ctypes.POINTER(_lib.ScarletLowres)()
             lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+        if self._upd is not None:                   # (same grid, C <= 8, no prior, uniform frames: refused before)
+            return _lib.check(_lib.lib.scarlet_fit_observations_options(
+                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), ptrs, band0, *tail))
         if self.frame_shapes is not None and lows is not None:      # (each low-resolution observation with its own tables)
             return _lib.check(_lib.lib.scarlet_fit_observations_frames_lowres(
                 ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ptrs, lows, self._lowres_frames(),

@@ -509,6 +509,54 @@ __device__ __forceinline__ float comp_l1(const UpdateArgs &a, int c) { return a.
 // a scene the constructors' update leaves alone (SCARLET_STATUS_BAD_INIT / BAD_COUNT under scarlet_source_update_constrained)
 __device__ __forceinline__ bool update_skips_scene(const UpdateArgs &a, int s) { return a.skip_status && (a.status[s] & a.skip_status); }
 
+// scarlet_update_options: the arguments of the OPTIONS instances of the constraint kernels (k_source_update<MODE, false,
+// UpdateArgsOpt>, k_source_update_w_opt).  A type of its own, so that the kernels of batches without options keep their
+// arguments and their code: everything the options add is behind `if constexpr (has_update_options<A>)`.
+struct UpdateArgsOpt : UpdateArgs {
+    // [S*K] each, or NULL = the default.  Read through comp_options() only
+    const uint8_t *sym_algorithm; const float *sym_strength;
+    const uint8_t *mono_nearest; const float *mono_thresh;
+    const uint8_t *positive, *normalize;
+};
+template <class A> constexpr bool has_update_options = false;
+template <> constexpr bool has_update_options<UpdateArgsOpt> = true;
+// The options of component c; without options the stock pipeline's values (source.py:402-440) as constants.  c is uniform
+// (see comp_symmetric): scalar loads, scalar branches.
+struct CompOptions {
+    int sym_algorithm; float sym_strength;     // update.symmetric(algorithm=, strength=)
+    bool nearest; float thresh;                // update.monotonic(use_nearest=, thresh=)
+    bool pos_sed, pos_morph;                   // update.positive / positive_sed / positive_morph
+    int norm;                                  // update.normalized(type=), or SCARLET_NORM_NONE
+};
+template <class A>
+__device__ __forceinline__ CompOptions comp_options(const A &a, int c)
+{
+    CompOptions o = {SCARLET_SYM_KSPACE, 0.5f, false, 0.f, true, true, SCARLET_NORM_MORPH_MAX};
+    if constexpr (has_update_options<A>) {
+        if (a.sym_algorithm) o.sym_algorithm = a.sym_algorithm[c];
+        if (a.sym_strength) o.sym_strength = a.sym_strength[c];
+        if (a.mono_nearest) o.nearest = a.mono_nearest[c] != 0;
+        if (a.mono_thresh) o.thresh = a.mono_thresh[c];
+        if (a.positive) { o.pos_sed = a.positive[c] & SCARLET_POSITIVE_SED; o.pos_morph = a.positive[c] & SCARLET_POSITIVE_MORPH; }
+        if (a.normalize) o.norm = a.normalize[c];
+    }
+    return o;
+}
+// one row of the options is admissible (k_check_options, scarlet_hip.hip: a scene with a row that is not gets
+// SCARLET_STATUS_BAD_OPTION and is never touched)
+__device__ __forceinline__ bool options_ok(const CompOptions &o)
+{
+    return (unsigned)o.sym_algorithm <= SCARLET_SYM_SDSS && o.sym_strength >= 0.f && o.sym_strength <= 1.f &&
+           o.thresh >= 0.f && o.thresh < 1.f && !(o.nearest && o.thresh != 0.f) && (unsigned)o.norm <= SCARLET_NORM_NONE;
+}
+// the SED's part of update.positive and update.normalized: the sum of the clamped SED (the norm of type "sed")
+__device__ __forceinline__ float positive_sed_sum(const float *sed, int B, bool pos_sed)
+{
+    float n = 0.f;
+    for (int b = 0; b < B; ++b) { const float v = sed[b]; n += (pos_sed && v < 0.f) ? 0.f : v; }
+    return n;
+}
+
 // Ragged frames: scene s's own frame (h, w) out of frame_hw, as uniform values (s is uniform: scalar loads).  False for an
 // entry outside 1..H x 1..W (k_check_frames gave the scene SCARLET_STATUS_BAD_FRAME): the caller returns before it reads
 // a plane, so an entry is never a loop bound unless it lies inside the padded plane.
@@ -550,10 +598,14 @@ __device__ __forceinline__ float update_step_morph(const UpdateArgs &a, int s, i
 // RAGGED: the component's scene has its own frame (UpdateArgs::frame_hw) in the top-left corner of the H x W plane.  The
 // tile is built with the scene's bounds (every operator takes its bounds from the tile), only the scene's pixels are
 // loaded from the stride-W plane, and the rest of the plane is written as zero.  LDS is laid out for the padded frame.
-template <int MODE, bool RAGGED = false>
-__global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
+// A = UpdateArgsOpt: the OPTIONS instance (scarlet_update_options; uniform frames only) -- each component's own symmetry
+// algorithm and strength, sweep (weighted with its thresh, or nearest neighbour), positivity and normalisation.
+template <int MODE, bool RAGGED = false, class A = UpdateArgs>
+__global__ __launch_bounds__(SC_BLOCK) void k_source_update(A a)
 {
     constexpr bool GT = MODE == 2;
+    constexpr bool OPT = has_update_options<A>;
+    static_assert(!(OPT && RAGGED), "no options instance for ragged frames");
     extern __shared__ __align__(16) float lds[];
     const int c = blockIdx.x, s = c / a.K;
     if (!a.force_it0 && !a.active[s]) return;
@@ -561,6 +613,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     if (a.only_flagged && !a.only_flagged[c]) return;
     if (update_skips_scene(a, s)) return;
     const bool symmetric = comp_symmetric(a, c), monotonic = comp_monotonic(a, c);
+    const CompOptions co = comp_options(a, c);
     // PH x PW: the plane in HBM (what LDS and the scratch are laid out for);  H x W: the frame the operators see
     const int PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
     int fh = PH, fw = PW;
@@ -635,23 +688,37 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
         }
         // update.symmetric(algorithm="kspace") (source.py:432): shift None -> soft, s=1
         const bool none = (dy != dy);
+        if constexpr (OPT) {
+            // update.symmetric(algorithm=, strength=): "kspace" without a shift is soft symmetry with strength 1 (operator.py:337-339)
+            const bool soft1 = co.sym_algorithm == SCARLET_SYM_KSPACE && none;
+            symmetry_tile(t, cy, cx, soft1 ? SCARLET_SYM_SOFT : co.sym_algorithm, soft1 ? 1.0f : co.sym_strength, dy, dx,
+                          false, 0.f, scr, av, bv, cv, zv, stage, GT);
+        } else
         symmetry_tile(t, cy, cx, none ? SCARLET_SYM_SOFT : SCARLET_SYM_KSPACE, 1.0f, dy, dx,
                       false, 0.f, scr, av, bv, cv, zv, stage, GT);
     }
     int lstop = 1 << 30;          // last sweep level computed (early exit); pixels beyond are <= 0 -> 0
-    if (monotonic) {                                                                     // source.py:436
+    // options: the weighted sweep's thresh; the nearest-neighbour sweep, and a weighted sweep whose component keeps its
+    // negative pixels (the early exit relies on positivity), run to the end and leave lstop where it is
+    const float mthresh = OPT ? co.thresh : 0.f;
+    bool stock_sweep = monotonic;
+    if constexpr (OPT) {
+        if (monotonic && co.nearest) { nearest_monotonic_tile(t, cy, cx); stock_sweep = false; }
+        else if (monotonic && !co.pos_morph) { monotonic_tile<false, float>(t, cy, cx, mthresh); stock_sweep = false; }
+    }
+    if (stock_sweep) {                                                                   // source.py:436
         if (!GT && a.hybrid_sweep) {
             // tile in LDS: levels 1 .. 46 on one wave without barriers (wave_ops.h; a sweep usually stops
             // before), the rest level-synchronously on the whole workgroup
             if (threadIdx.x < SC_WAVE) {
                 int done, quiet;
-                wave_monotonic<float>(t, cy, cx, 0.f, &done, &quiet);
+                wave_monotonic<float>(t, cy, cx, mthresh, &done, &quiet);
                 if (threadIdx.x == 0) { hyb[0] = done; hyb[1] = quiet; }
             }
             __syncthreads();
             lstop = hyb[0];
             if (lstop == (1 << 30))
-                lstop = monotonic_tile<false, float>(t, cy, cx, 0.f, &lastpos, 0.f, SC_COMPACT_LAST + 1, SC_COMPACT_LAST - hyb[1]);
+                lstop = monotonic_tile<false, float>(t, cy, cx, mthresh, &lastpos, 0.f, SC_COMPACT_LAST + 1, SC_COMPACT_LAST - hyb[1]);
         } else if (GT && a.hybrid_sweep && stage_floats(hp, wp) >= SC_BOX_FLOATS) {
             // plane in HBM: the pixels of levels 1 .. 46 (and their closer neighbours) lie within 23 pixels of the
             // peak -- that box goes to LDS, one wave sweeps it without barriers, the box goes back, and the
@@ -668,7 +735,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
             __syncthreads();
             if (threadIdx.x < SC_WAVE) {
                 int done, quiet;
-                wave_monotonic<float>(bt, cy - by0, cx - bx0, 0.f, &done, &quiet);
+                wave_monotonic<float>(bt, cy - by0, cx - bx0, mthresh, &done, &quiet);
                 if (threadIdx.x == 0) { hyb[0] = done; hyb[1] = quiet; }
             }
             __syncthreads();
@@ -679,9 +746,9 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
             __syncthreads();
             lstop = hyb[0];
             if (lstop == (1 << 30))
-                lstop = monotonic_tile<false, float>(t, cy, cx, 0.f, &lastpos, 0.f, SC_COMPACT_LAST + 1, SC_COMPACT_LAST - hyb[1]);
+                lstop = monotonic_tile<false, float>(t, cy, cx, mthresh, &lastpos, 0.f, SC_COMPACT_LAST + 1, SC_COMPACT_LAST - hyb[1]);
         } else
-            lstop = monotonic_tile<false, float>(t, cy, cx, 0.f, &lastpos);
+            lstop = monotonic_tile<false, float>(t, cy, cx, mthresh, &lastpos);
     }
     if (threadIdx.x == 0) { a.centers[2 * c] = cy; a.centers[2 * c + 1] = cx; }
 
@@ -698,12 +765,16 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
             const float mag = fabsf(v) - l1;
             v = (v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f)) * (mag < 0.f ? 0.f : mag);
         }
+        if constexpr (OPT) { if ((co.pos_morph && v < 0.f) || sweep_level(y, x, cy, cx) > lstop) v = 0.f; }
+        else
         if (v < 0.f || sweep_level(y, x, cy, cx) > lstop) v = 0.f;
         return v;
     };
     float norm;
     double d2 = 0, n2 = 0;
-    if (vec4 && monotonic) {
+    // (options: the peak pixel is the maximum only after a sweep of non-negative values, and only "morph_max" asks for it)
+    const bool peak_is_max = !OPT || (co.norm == SCARLET_NORM_MORPH_MAX && co.pos_morph);
+    if (vec4 && monotonic && peak_is_max) {
         // one pass in float4 groups; morph.max() is the processed peak pixel after a sweep (see
         // wave_pipeline below); a NaN elsewhere shows up in the sums
         __syncthreads();
@@ -752,17 +823,27 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
     } else {
         float vmax = -INFINITY;
         bool anynan = false;
+        double vsum = 0;                                 // (options: morph.sum() of type "morph")
         for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
             const int y = i / W, x = i - y * W;
             const float v = sparse_plus(t.m[y * t.LW + x], y, x);
             t.m[y * t.LW + x] = v;
             anynan |= (v != v);
             vmax = fmaxf(vmax, v);
+            if constexpr (OPT) vsum += (double)v;
         }
         norm = block_max_nan(vmax, anynan, redf);
+        if constexpr (OPT) {
+            // update.normalized(type=) (update.py:35-68): "morph" by morph.sum(), "sed" by sed.sum() the other way round
+            if (co.norm == SCARLET_NORM_MORPH) norm = (float)block_sum(vsum, red);
+            else if (co.norm == SCARLET_NORM_SED) norm = positive_sed_sum(a.sed[wbuf] + (size_t)c * B, B, co.pos_sed);
+            else if (co.norm == SCARLET_NORM_NONE) norm = 1.0f;
+        }
         for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
             const int y = i / W, x = i - y * W;
-            const float v = t.m[y * t.LW + x] / norm;
+            float v = t.m[y * t.LW + x];
+            if constexpr (OPT) v = co.norm == SCARLET_NORM_SED ? v * norm : (co.norm == SCARLET_NORM_NONE ? v : v / norm);
+            else v = v / norm;
             const int gi = RAGGED ? y * PW + x : i;
             gm[gi] = v;
             if (gl) { const float d = gl[gi] - v; d2 += (double)(d * d); }
@@ -779,8 +860,13 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(UpdateArgs a)
         double d2s = 0, n2s = 0;
         for (int b = 0; b < B; ++b) {
             float v = gs[b];
+            if constexpr (OPT) {
+                if (co.pos_sed && v < 0.f) v = 0.f;
+                v = co.norm == SCARLET_NORM_SED ? v / norm : (co.norm == SCARLET_NORM_NONE ? v : v * norm);
+            } else {
             if (v < 0.f) v = 0.f;
             v = v * norm;
+            }
             gs[b] = v;
             if (gsl) { const float d = gsl[b] - v; d2s += (double)(d * d); }
             n2s += (double)(v * v);
@@ -886,9 +972,12 @@ __global__ void k_converge(int S, int K, const double *conv, int *flags, int *ac
 // k_source_update_w: the same pipeline with one WAVE per component (wave_ops.h), four
 // components per 256-thread workgroup, no workgroup barriers.  H, W <= 64.
 // RAGGED: as in k_source_update -- the tile has the scene's own bounds, the LDS layout is the padded frame's
-template <bool RAGGED = false>
-__device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave)
+// A = UpdateArgsOpt: the options instance, as in k_source_update
+template <bool RAGGED = false, class A = UpdateArgs>
+__device__ inline void wave_pipeline(const A &a, int c, float *lds_wave)
 {
+    constexpr bool OPT = has_update_options<A>;
+    static_assert(!(OPT && RAGGED), "no options instance for ragged frames");
     const int s = c / a.K;
     const int PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
     int fh = PH, fw = PW;
@@ -919,6 +1008,7 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
     int stat = 0;
     const bool grouped = a.group && a.group[c] >= 0;               // layer of a MultiComponentSource: centre from k_group_centers
     const bool symmetric = comp_symmetric(a, c), monotonic = comp_monotonic(a, c);
+    const CompOptions co = comp_options(a, c);
     if (!grouped) wave_max_pixel(t, cy, cx, stat);
     if (symmetric) {
         double dy = grouped ? (double)__builtin_nanf("") : a.shifts[2 * c], dx = grouped ? dy : a.shifts[2 * c + 1];
@@ -927,9 +1017,19 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
             if (lane == 0) { a.shifts[2 * c] = dy; a.shifts[2 * c + 1] = dx; }
         }
         const bool none = (dy != dy);
+        if constexpr (OPT) {
+            const bool soft1 = co.sym_algorithm == SCARLET_SYM_KSPACE && none;       // (operator.py:337-339)
+            wave_symmetry(t, cy, cx, soft1 ? SCARLET_SYM_SOFT : co.sym_algorithm, soft1 ? 1.0f : co.sym_strength, dy, dx,
+                          false, 0.f, vec);
+        } else
         wave_symmetry(t, cy, cx, none ? SCARLET_SYM_SOFT : SCARLET_SYM_KSPACE, 1.0f, dy, dx, false, 0.f, vec);
     }
     int lstop = 1 << 30;                // last sweep level computed; pixels beyond are <= 0 -> 0
+    if constexpr (OPT) {
+        // the nearest-neighbour sweep, and a weighted sweep whose component keeps its negative pixels, run to the end
+        if (monotonic && co.nearest) wave_nearest_monotonic<float>(t, cy, cx);
+        else if (monotonic) wave_monotonic<float>(t, cy, cx, co.thresh, co.pos_morph ? &lstop : nullptr);
+    } else
     if (monotonic) wave_monotonic<float>(t, cy, cx, 0.f, &lstop);
     if (lane == 0) { a.centers[2 * c] = cy; a.centers[2 * c + 1] = cx; }
     const float step_morph = update_step_morph(a, s, c);
@@ -943,12 +1043,15 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
             const float mag = fabsf(v) - l1;
             v = (v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f)) * (mag < 0.f ? 0.f : mag);
         }
+        if constexpr (OPT) { if ((co.pos_morph && v < 0.f) || sweep_level(y, x, cy, cx) > lstop) v = 0.f; }
+        else
         if (v < 0.f || sweep_level(y, x, cy, cx) > lstop) v = 0.f;
         return v;
     };
     float norm;
     double d2 = 0, n2 = 0;
-    if (vec4 && monotonic) {
+    const bool peak_is_max = !OPT || (co.norm == SCARLET_NORM_MORPH_MAX && co.pos_morph);     // (as in k_source_update)
+    if (vec4 && monotonic && peak_is_max) {
         // One pass in float4 groups.  After the sweep no pixel exceeds the peak pixel (each is capped
         // by a convex combination of pixels closer to the peak) and the maps above are monotone, so
         // morph.max() is the processed peak value; a NaN elsewhere shows up in the sums (see below).
@@ -993,17 +1096,26 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
     } else {
         float vmax = -INFINITY;
         bool anynan = false;
+        double vsum = 0;                                 // (options: morph.sum() of type "morph")
         for (int i = lane; i < HW; i += SC_WAVE) {
             float *p = &t.m[(i / W) * t.LW + (i % W)];
             const float v = sparse_plus(*p, i / W, i % W);
             *p = v;
             anynan |= (v != v);
             vmax = fmaxf(vmax, v);
+            if constexpr (OPT) vsum += (double)v;
         }
         norm = wave_max(vmax);
         if (__any(anynan)) norm = __builtin_nanf("");
+        if constexpr (OPT) {                             // update.normalized(type=), as in k_source_update
+            if (co.norm == SCARLET_NORM_MORPH) norm = (float)wave_sum(vsum);
+            else if (co.norm == SCARLET_NORM_SED) norm = positive_sed_sum(a.sed[wbuf] + (size_t)c * B, B, co.pos_sed);
+            else if (co.norm == SCARLET_NORM_NONE) norm = 1.0f;
+        }
         for (int i = lane; i < HW; i += SC_WAVE) {
-            const float v = t.m[(i / W) * t.LW + (i % W)] / norm;
+            float v = t.m[(i / W) * t.LW + (i % W)];
+            if constexpr (OPT) v = co.norm == SCARLET_NORM_SED ? v * norm : (co.norm == SCARLET_NORM_NONE ? v : v / norm);
+            else v = v / norm;
             const int gi = RAGGED ? (i / W) * PW + (i % W) : i;
             gm[gi] = v;
             if (gl) { const float d = gl[gi] - v; d2 += (double)(d * d); }
@@ -1019,8 +1131,13 @@ __device__ inline void wave_pipeline(const UpdateArgs &a, int c, float *lds_wave
     double d2s = 0, n2s = 0;
     if (lane < B) {
         float v = gs[lane];
+        if constexpr (OPT) {
+            if (co.pos_sed && v < 0.f) v = 0.f;
+            v = co.norm == SCARLET_NORM_SED ? v / norm : (co.norm == SCARLET_NORM_NONE ? v : v * norm);
+        } else {
         if (v < 0.f) v = 0.f;
         v = v * norm;
+        }
         gs[lane] = v;
         if (gsl) { const float d = gsl[lane] - v; d2s = (double)(d * d); }
         n2s = (double)(v * v);
@@ -1044,6 +1161,19 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w(UpdateArgs a)
     if (update_skips_scene(a, c / a.K)) return;
     const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;      // wave_tile_floats (wave_ops.h)
     wave_pipeline(a, c, lds + (size_t)wid * per_wave);
+}
+// ... for a batch with update options (scarlet_update_options)
+__global__ __launch_bounds__(SC_BLOCK) void k_source_update_w_opt(UpdateArgsOpt a)
+{
+    extern __shared__ __align__(16) float lds[];
+    const int wid = threadIdx.x / SC_WAVE;
+    const int c = uniform((int)(blockIdx.x * SC_NWAVES + wid));
+    if (c >= a.S * a.K) return;
+    if (!a.force_it0 && !a.active[c / a.K]) return;
+    if (c % a.K >= scene_ncomp(a.ncomp, c / a.K, a.K)) return;
+    if (update_skips_scene(a, c / a.K)) return;
+    const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;
+    wave_pipeline<false, UpdateArgsOpt>(a, c, lds + (size_t)wid * per_wave);
 }
 // ... for a batch whose scenes have their own frames (UpdateArgs::frame_hw)
 __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w_ragged(UpdateArgs a)

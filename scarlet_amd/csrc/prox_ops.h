@@ -200,6 +200,67 @@ __device__ inline int monotonic_tile(const TileT<T> &t, int cy, int cx, T thresh
 }
 
 // ------------------------------------------------------------------------------------
+// a10  the nearest-neighbour sweep, operator.prox_strict_monotonic(use_nearest=True) (operator.py:104-113, 591-600;
+// operators_pybind11.cc:11-25 with thresh = 0): x = min(x, x_ref) in order of distance, where x_ref is the pixel's first
+// neighbour of largest cosine towards the peak among the in-bounds, strictly closer ones.  In closed form, for a pixel at
+// offset (X, Y) from the peak with A = max(|X|, |Y|) >= 1 and b = min(|X|, |Y|): the candidates' cosines are, up to the
+// common 1 / r, A (one step along the major axis), (A + b) / sqrt2 (that step and one along the minor axis), b and
+// (A - b) / sqrt2 -- the last two are never the largest, the first two are always in bounds and strictly closer (they lie
+// between the pixel and the peak) and never equal ((A + b)^2 = 2 A^2 has no integer solution but 0).  So the reference
+// pixel is one step towards the peak along the major axis, and along the minor axis too iff (A + b)^2 > 2 A^2: integer
+// arithmetic, no table.  It lowers max(|X|, |Y|) by exactly one, i.e. it lies on the previous Chebyshev ring: the pixels
+// of one ring are independent, and a ring-by-ring sweep gives the bits of any distance order (tests/
+// test_update_option_cases.py checks both statements against the oracle's table for every centre of small frames).
+// min is exact: the float32 result is that of the reference's float64 sweep on the same values.
+// offset (in elements of a stride-LW plane) from the pixel at (X, Y) != (0, 0) off the peak to its reference pixel
+__device__ __forceinline__ int nearest_ref_offset(int X, int Y, int LW)
+{
+    const int ax = X < 0 ? -X : X, ay = Y < 0 ? -Y : Y;
+    const int A = ax > ay ? ax : ay, b = ax > ay ? ay : ax;
+    const bool diag = (A + b) * (A + b) > 2 * A * A;               // (A <= SCARLET_MAX_SIDE: far inside int)
+    const int sx = (ax == A || diag) ? (X > 0 ? -1 : 1) : 0;       // (stepping along an axis implies a non-zero offset on it)
+    const int sy = (ay == A || diag) ? (Y > 0 ? -1 : 1) : 0;
+    return sy * LW + sx;
+}
+// pixel i (0 <= i < 2 a) of side 0..3 of the Chebyshev ring a around the peak, as its offset: every pixel of the ring
+// belongs to exactly one (side, i) -- top row from the left corner, right column downwards, bottom row leftwards, left
+// column upwards, each without its last corner
+__device__ __forceinline__ void ring_pixel(int a, int side, int i, int &X, int &Y)
+{
+    switch (side) {
+    case 0: X = -a + i; Y = -a; break;
+    case 1: X = a; Y = -a + i; break;
+    case 2: X = a - i; Y = a; break;
+    default: X = -a; Y = a - i;
+    }
+}
+// one ring pixel: x = min(x, x_ref) as std::min does it (a NaN reference leaves the pixel); outside the tile: nothing
+template <typename T>
+__device__ __forceinline__ void nearest_ring_step(const TileT<T> &t, int cy, int cx, int X, int Y)
+{
+    const int y = cy + Y, x = cx + X;
+    if ((unsigned)y >= (unsigned)t.H || (unsigned)x >= (unsigned)t.W) return;
+    T *p = t.m + y * t.LW + x;
+    const T ref = p[nearest_ref_offset(X, Y, t.LW)], cur = *p;
+    if (ref < cur) *p = ref;
+}
+// the workgroup-level sweep (tile in LDS or plane in HBM): one barrier per ring
+template <typename T>
+__device__ inline void nearest_monotonic_tile(const TileT<T> &t, int cy, int cx)
+{
+    const int amax = max(max(cy, t.H - 1 - cy), max(cx, t.W - 1 - cx));
+    for (int a = 1; a <= amax; ++a) {
+        for (int i = threadIdx.x; i < 8 * a; i += SC_BLOCK) {
+            const int side = i / (2 * a);
+            int X, Y;
+            ring_pixel(a, side, i - side * 2 * a, X, Y);
+            nearest_ring_step(t, cy, cx, X, Y);
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // a15  window selection of operator.uncentered_operator (operator.py:197-219).
 // Returns false when `center` is the array middle (H/2, W/2): the reference then applies
 // the operator to the WHOLE array and discards a returned copy (Appendix A.1).

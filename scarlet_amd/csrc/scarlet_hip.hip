@@ -341,7 +341,8 @@ static int launch_operator(OpArgs a, void *stream)
     if (a.n == 0) return SCARLET_OK;
     int rc = ensure_tables();
     if (rc) return rc;
-    // the update's choice of form without a workspace behind it; the nearest-neighbour sweep has no wave form
+    // the update's choice of form without a workspace behind it; this operator's nearest-neighbour sweep stays on the
+    // workgroup form (the ring sweep on one wave, wave_nearest_monotonic, serves the update's options instance)
     const UpdatePlan p = update_plan(a.H, a.W, {a.op != OP_MONO_NEAREST && !opt(OPT_FORCE_BLOCK_UPDATE)});
     hipStream_t st = (hipStream_t)stream;
     DevBuf gscratch;                          // released on every path, after the kernel has finished
@@ -865,6 +866,40 @@ static int check_frames(const scarlet_batch *b, const int32_t *frame_hw, void *s
     if (!frame_hw) return SCARLET_OK;
     hipLaunchKernelGGL(k_check_frames, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
                        (const int *)frame_hw, b->S, b->H, b->W, b->status, b->active);
+    HIP_TRY(hipGetLastError());
+    return SCARLET_OK;
+}
+// ---- update options (scarlet_update_options).  Inside the library `o` may be NULL, and one with every member NULL counts
+// as none: the stock pipeline, the kernels and the paths of a batch without options.
+static bool opts_any(const scarlet_update_options *o)
+{
+    return o && (o->sym_algorithm || o->sym_strength || o->mono_nearest || o->mono_thresh || o->positive || o->normalize);
+}
+template <> constexpr bool has_update_options<scarlet_update_options> = true;      // (comp_options reads the struct itself)
+// One thread per scene, before anything else of the call: a scene one of whose present components has an inadmissible row
+// (options_ok, engine.h; a `positive` beyond its two bits) gets SCARLET_STATUS_BAD_OPTION and active = 0.  The rows of
+// inactive scenes (respect_active: the calls that iterate), of scenes a constructor call leaves alone (skip_status) and of
+// absent components are not read.
+__global__ void k_check_options(scarlet_update_options o, const int *ncomp, int S, int K, int respect_active, int skip_status,
+                                int *status, int *active)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    if (respect_active && !active[s]) return;
+    if (skip_status && (status[s] & skip_status)) return;
+    const int n = scene_ncomp(ncomp, s, K);
+    bool ok = true;
+    for (int k = 0; k < n; ++k) {
+        const int c = s * K + k;
+        ok = ok && options_ok(comp_options(o, c)) && !(o.positive && o.positive[c] > (SCARLET_POSITIVE_SED | SCARLET_POSITIVE_MORPH));
+    }
+    if (!ok) { status[s] |= SCARLET_STATUS_BAD_OPTION; active[s] = 0; }
+}
+static int check_options(const scarlet_batch *b, const scarlet_update_options *o, int respect_active, int skip_status, void *stream)
+{
+    if (!opts_any(o)) return SCARLET_OK;
+    hipLaunchKernelGGL(k_check_options, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
+                       *o, (const int *)b->n_components, b->S, b->K, respect_active, skip_status, b->status, b->active);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
@@ -1778,7 +1813,9 @@ __global__ void k_zero_int(int *p) { *p = 0; }
 // L_comp: the constants each component stepped with (scarlet_prior::L_comp), or NULL: the scene's
 // cons: the components' own switches, or NULL: the batch's.  skip_status: status bits of the scenes a constructor call leaves alone
 // frame_hw: scarlet_frames::frame_hw of the batch (or of the view: advanced to its first scene), or NULL
-struct UpdateOpts { const double *L_comp; const scarlet_constraints *cons; int skip_status; const int32_t *frame_hw; };
+// upd: the batch's update options (never with frame_hw, group or a box stage), or NULL: the stock pipeline
+struct UpdateOpts { const double *L_comp; const scarlet_constraints *cons; int skip_status; const int32_t *frame_hw;
+                    const scarlet_update_options *upd; };
 // in_iteration = 0: the constructors' call (UpdateArgs::force_it0)
 static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, void *stream, const UpdateOpts &o)
 {
@@ -1803,9 +1840,10 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.frame_hw = (const int *)o.frame_hw;
     const bool ragged = o.frame_hw != nullptr;
     if (ragged && b->group) return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames) with group: not implemented");
+    if (o.upd && (ragged || b->group)) return set_err(SCARLET_E_NOTIMPL, "update options with ragged frames or group: not implemented");
     u.hybrid_sweep = opt(OPT_NO_HYBRID_SWEEP) ? 0 : 1;
     // (a ragged-frame batch runs no box stage: the box kernels take their bounds from the batch's frame)
-    const UpdatePlan p = update_plan(b->H, b->W, {!opt(OPT_FORCE_BLOCK_UPDATE), true, b->monotonic && !opt(OPT_NO_BOX) && !ragged,
+    const UpdatePlan p = update_plan(b->H, b->W, {!opt(OPT_FORCE_BLOCK_UPDATE), true, b->monotonic && !opt(OPT_NO_BOX) && !ragged && !o.upd,
                                                   !opt(OPT_NO_BOX2), !opt(OPT_NO_EXACT)});
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(b->S * b->K), block(SC_BLOCK);
@@ -1849,6 +1887,24 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
         case FORM_TILE_GSCRATCH: rc = launch_lds(k_source_update<1, true>, grid, block, p.lds, st, u); break;
         case FORM_TILE: rc = launch_lds(k_source_update<0, true>, grid, block, p.lds, st, u); break;
         default: rc = launch_lds(k_source_update<2, true>, grid, block, p.lds, st, u);
+        }
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+        return SCARLET_OK;
+    }
+    if (o.upd) {                // the options instances of the same forms (engine.h UpdateArgsOpt); no box stage ran
+        UpdateArgsOpt uo;
+        static_cast<UpdateArgs &>(uo) = u;
+        uo.sym_algorithm = o.upd->sym_algorithm; uo.sym_strength = o.upd->sym_strength;
+        uo.mono_nearest = o.upd->mono_nearest; uo.mono_thresh = o.upd->mono_thresh;
+        uo.positive = o.upd->positive; uo.normalize = o.upd->normalize;
+        switch (p.form) {
+        case FORM_WAVE:
+            rc = launch_lds(k_source_update_w_opt, dim3((b->S * b->K + SC_NWAVES - 1) / SC_NWAVES), block, p.lds, st, uo);
+            break;
+        case FORM_TILE_GSCRATCH: rc = launch_lds(k_source_update<1, false, UpdateArgsOpt>, grid, block, p.lds, st, uo); break;
+        case FORM_TILE: rc = launch_lds(k_source_update<0, false, UpdateArgsOpt>, grid, block, p.lds, st, uo); break;
+        default: rc = launch_lds(k_source_update<2, false, UpdateArgsOpt>, grid, block, p.lds, st, uo);
         }
         if (rc) return rc;
         HIP_TRY(hipGetLastError());
@@ -2089,17 +2145,20 @@ extern "C" int scarlet_backward_step_prior(scarlet_batch *b, const scarlet_prior
 }
 
 static int update_call(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int in_iteration, void *stream,
-                       const int32_t *frame_hw = nullptr)
+                       const int32_t *frame_hw = nullptr, const scarlet_update_options *upd = nullptr)
 {
+    if (!opts_any(upd)) upd = nullptr;
     int rc = check_counts(b, stream);
     if (!rc) rc = check_frames(b, frame_hw, stream);
-    if (rc) return rc;
     // the constructors' call (in_iteration = 0) ignores `active`: a scene the initialisation refused stays untouched
-    // (BAD_COUNT scenes have no present component, scene_ncomp)
+    // (BAD_COUNT scenes have no present component, scene_ncomp), and so does one whose options are refused here
     const bool any = cons_any(c);
-    const int skip = (any && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
+    const int skip = ((any || upd) && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
+    if (!rc) rc = check_options(b, upd, in_iteration ? 1 : 0, skip, stream);
+    if (rc) return rc;
     return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, stream,
-                         {p ? p->L_comp : nullptr, any ? c : nullptr, skip, frame_hw});
+                         {p ? p->L_comp : nullptr, any ? c : nullptr, (upd && !in_iteration) ? skip | SCARLET_STATUS_BAD_OPTION : skip,
+                          frame_hw, upd});
 }
 extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *stream)
 {
@@ -2121,15 +2180,24 @@ extern "C" int scarlet_source_update_constrained(scarlet_batch *b, const scarlet
 // One observation: the fused launch where it applies (never with a prior), two half-batches on two streams where the
 // layout splits the batch (see split_views; never with a prior), the general step otherwise.
 // frame_hw: the scenes' own frames (scarlet_fit_frames; never with a prior), or NULL
+// upd: update options (scarlet_fit_options; never with a prior or frame_hw): the general step on one pipeline, or NULL
 static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const scarlet_prior *p, int max_iter, double e_rel,
-                    int approximate_L, int check_every, void *stream, const int32_t *frame_hw = nullptr)
+                    int approximate_L, int check_every, void *stream, const int32_t *frame_hw = nullptr,
+                    const scarlet_update_options *upd = nullptr)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
-    if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream))) return rc;
+    if (!opts_any(upd)) upd = nullptr;
+    if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream)) || (rc = check_options(b, upd, 1, 0, stream)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const WsLayout l = ws_layout(b, WS_FIX);
-    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw};
+    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw, upd};
+    if (upd)     // gradients, step, the constraint kernels' options instances, convergence test
+        return fit_loop(b, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
+            const int r = backward_impl(b, l, approximate_L, 0, stream);
+            return r ? r : iteration_tail(b, l, e_rel, stream, uo);
+        });
     if (p)       // gradients, prior step, constraints, convergence test
         return fit_loop(b, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
             int r = backward_impl(b, l, approximate_L, 1, stream);
@@ -2193,6 +2261,29 @@ extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constrain
 {
     const int rc = check_call(b, true, c, false, p, max_iter);
     return rc ? rc : fit_call(b, c, p, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+// ---- update options (scarlet_update_options): scarlet_fit_constrained / scarlet_source_update_constrained without a prior
+// and with the options; one with every member NULL IS that call
+static int check_options_call(const scarlet_batch *b, const scarlet_update_options *o)
+{
+    if (!o) return set_err(SCARLET_E_ARG, "options is NULL (pass a scarlet_update_options with NULL members for the defaults)");
+    if (b && b->group) return set_err(SCARLET_E_NOTIMPL, "update options with group: the layers of a multi-component source are tied to soft symmetry");
+    return SCARLET_OK;
+}
+extern "C" int scarlet_fit_options(scarlet_batch *b, const scarlet_constraints *c, const scarlet_update_options *o, int max_iter,
+                                   double e_rel, int approximate_L, int check_every, void *stream)
+{
+    int rc = check_options_call(b, o);
+    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
+    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, nullptr, o);
+}
+extern "C" int scarlet_source_update_options(scarlet_batch *b, const scarlet_constraints *c, const scarlet_update_options *o,
+                                             int in_iteration, void *stream)
+{
+    int rc = check_options_call(b, o);
+    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr);
+    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, nullptr, o);
 }
 
 // ---- scenes with their own frames (scarlet_frames): scarlet_fit_constrained / scarlet_source_update_constrained without
@@ -2534,12 +2625,14 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
                                  const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
                                  int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr,
                                  bool large = false, const scarlet_prior *p = nullptr, const int32_t *frame_hw = nullptr,
-                                 const scarlet_lowres_frames *const *lrf = nullptr)
+                                 const scarlet_lowres_frames *const *lrf = nullptr, const scarlet_update_options *upd = nullptr)
 {
     int rc;
     if (!cons_any(cons)) cons = nullptr;
+    if (!opts_any(upd)) upd = nullptr;        // (update options of the state, scarlet_fit_observations_options: the tail reads them)
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = check_counts(state, stream)) || (rc = check_frames(state, frame_hw, stream))) return rc;
+    if ((rc = check_counts(state, stream)) || (rc = check_frames(state, frame_hw, stream)) || (rc = check_options(state, upd, 1, 0, stream)))
+        return rc;
     for (int o = 0; lrf && o < n_obs; ++o)
         if (lrf[o] && (rc = check_lowres_frames(state, lrf[o], frame_hw, lowres_dims(state, obs[o], lowres[o]), stream))) return rc;
     const WsLayout l = ws_layout(state, WS_FIX);
@@ -2622,7 +2715,7 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         else hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
     };
     // with a prior the sparse_l0 / sparse_l1 cut uses each component's own step (update.py:71-82)
-    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw};
+    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw, upd};
     return fit_loop(state, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
         prof_start(0, st);
         for (int o = 0; o < n_obs; ++o) {
@@ -2709,6 +2802,19 @@ extern "C" int scarlet_fit_observations_constrained(scarlet_batch *state, const 
 {
     const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter);
     return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+}
+
+// scarlet_fit_observations_constrained with update options on the state: same-grid observations, at most 8 model channels
+extern "C" int scarlet_fit_observations_options(scarlet_batch *state, const scarlet_constraints *c, const scarlet_update_options *o,
+                                                scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter,
+                                                double e_rel, int approximate_L, int check_every, void *stream)
+{
+    int rc = check_options_call(state, o);
+    if (!rc && state && state->B > SC_BMAX)
+        rc = set_err(SCARLET_E_NOTIMPL, "update options with a wide state (more than 8 model channels): not implemented");
+    if (!rc) rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter);
+    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
+                                           nullptr, false, nullptr, nullptr, nullptr, o);
 }
 
 extern "C" int scarlet_fit_observations_lowres(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,

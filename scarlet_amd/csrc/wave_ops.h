@@ -478,6 +478,29 @@ __device__ inline void wave_monotonic(const TileT<T> &t, int cy, int cx, T thres
     if (last_level) *last_level = done;
 }
 
+// ---------------------------------------------------------------- a10 nearest-neighbour sweep
+// The ring-by-ring sweep of prox_ops.h (nearest_ref_offset) on one wave: ring a holds 8 a pixels, lane i takes pixel i of
+// each of the four sides (two trips from a = 33 on).  A pixel reads its own value and one on the ring before, whose stores
+// precede the reads in the wave's program order: LDS operations of one wave complete in order, so wave_sync() between two
+// rings is all the ordering there is -- no barrier.  The sweep has no early exit: min keeps a positive pixel positive as
+// long as its chain towards the peak is, and at most 63 rings of one or two trips are cheap beside the weighted sweep.
+template <typename T>
+__device__ inline void wave_nearest_monotonic(const TileT<T> &t, int cy, int cx)
+{
+    const int amax = max(max(cy, t.H - 1 - cy), max(cx, t.W - 1 - cx));
+    for (int a = 1; a <= amax; ++a) {
+        for (int i = lane_id(); i < 2 * a; i += SC_WAVE) {
+#pragma unroll
+            for (int side = 0; side < 4; ++side) {
+                int X, Y;
+                ring_pixel(a, side, i, X, Y);
+                nearest_ring_step(t, cy, cx, X, Y);
+            }
+        }
+        wave_sync();
+    }
+}
+
 // ---------------------------------------------------------------- a16 flip symmetry
 template <typename T>
 __device__ inline void wave_flip_symmetry(const TileT<T> &t, const SymWindow &s, bool sdss, T strength)
