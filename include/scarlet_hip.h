@@ -512,7 +512,10 @@ int scarlet_fit_observations_options(scarlet_batch *state, const scarlet_constra
  *     every B and with or without per-component switches.  No eight-wave or persistent kernel takes such a batch; every
  *     other one takes the general path, and none runs a box stage beyond 64 pixels;
  *   - SCARLET_E_NOTIMPL, found on the host before any launch: frame_hw with b->group; scarlet_init_sources_frames with
- *     spec->kind (extended sources only).  Priors and scarlet_fit_multi have no _frames form; the joint fit against
+ *     spec->kind (extended sources only).  Point sources and multi-component sources (b->group) on ragged frames go
+ *     through entry points of their own: scarlet_fit_frames_grouped, scarlet_source_update_frames_grouped and
+ *     scarlet_init_sources_frames_mixed, below.  Priors, update options and scarlet_fit_multi have no _frames form, and the
+ *     joint fits take no group with frame_hw; the joint fit against
  *     same-grid observations has one (scarlet_fit_observations_frames, below), and so has the joint fit against
  *     low-resolution observations, each scene with its own operator (struct scarlet_lowres_frames,
  *     scarlet_fit_observations_frames_lowres, further below).  f == NULL is SCARLET_E_ARG. */
@@ -534,6 +537,29 @@ int scarlet_check_frames(scarlet_batch *b, const scarlet_frames *f, void *stream
 int scarlet_init_extended_frames(scarlet_batch *b, const scarlet_frames *f, const float *bg_rms_host, float thresh,
                                  const float *sed_scale_host, int init_symmetric, int init_monotonic, int run_update,
                                  void *stream);
+
+/* Ragged frames with multi-component sources (b->group) and point sources.  The four calls above keep refusing frame_hw
+ * with b->group, and scarlet_init_sources_frames keeps refusing spec->kind; these three take them.
+ *   - scarlet_fit_frames_grouped / scarlet_source_update_frames_grouped follow the contract of scarlet_fit_frames /
+ *     scarlet_source_update_frames, and b->group is allowed: the shared centre (and, every fifth iteration, the shift) of
+ *     each source is measured on its scene's own frame -- the patch around the previous centre is clipped to h x w, so the
+ *     centroid's radius is cut at the scene's own last row and column, as the reference cuts it for the scene alone --
+ *     and the update kernels take that centre as given.  With b->group == NULL they ARE those two calls; with
+ *     f->frame_hw == NULL they ARE scarlet_fit_constrained / scarlet_source_update_constrained without a prior; both bit
+ *     for bit.  Groups never take a one-launch iteration: such a batch runs the general path.
+ *   - scarlet_init_sources_frames_mixed is scarlet_init_sources on each scene's own frame, with spec->kind and b->group
+ *     honoured: a point source's centre test and the clipping of the pasted model PSF are the own frame's; the layers of
+ *     a multi-component source are cut from the extended start on the own frame, and their least-squares SEDs sum over
+ *     the scene's pixels only.  Everything outside a frame is written as zero.  Bad scenes follow scarlet_init_sources
+ *     (SCARLET_STATUS_BAD_INIT) and the device check of the frames (SCARLET_STATUS_BAD_FRAME).  With f->frame_hw == NULL
+ *     it IS scarlet_init_sources.
+ * f == NULL is SCARLET_E_ARG.  The products of such a batch do not depend on the groups: pass scarlet_batch_products_frames
+ * a copy of the batch struct with group = NULL; there is no products entry point of its own. */
+int scarlet_fit_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */, int max_iter,
+                               double e_rel, int approximate_L, int check_every, void *stream);
+int scarlet_source_update_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
+                                         int in_iteration, void *stream);
+/* (scarlet_init_sources_frames_mixed is declared beside scarlet_init_sources_frames, after struct scarlet_init_spec) */
 
 /* scarlet_fit_observations_constrained for scenes with their own frames (c may be NULL: the state's scalars).  The state
  * may span up to SCARLET_MAX_CHANNELS channels: with state->B > 8 the call is scarlet_fit_observations_wide without a prior
@@ -932,6 +958,9 @@ typedef struct scarlet_init_spec {
 int scarlet_init_sources(scarlet_batch *b, const scarlet_init_spec *spec, void *stream);
 /* ... on each scene's own frame (scarlet_frames): extended sources only, spec->kind must be NULL */
 int scarlet_init_sources_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_init_spec *spec, void *stream);
+/* ... every stock source type on each scene's own frame: spec->kind and b->group are honoured (see "Ragged frames with
+ * multi-component sources" above); with f->frame_hw == NULL it IS scarlet_init_sources */
+int scarlet_init_sources_frames_mixed(scarlet_batch *b, const scarlet_frames *f, const scarlet_init_spec *spec, void *stream);
 
 /* Row a3b set-up: FFT the difference kernel into the workspace (K-hat at the reference's FFT
  * shape next_fast_len(N + P + 3), fft.py:68-106) and create the batched hipFFT plans (cached

@@ -23,7 +23,7 @@ from .source import (SourceInitError, get_pixel_sed, get_psf_sed, get_best_fit_s
                      ExtendedSource, MultiComponentSource, RandomSource)
 from .observation import Frame, Observation, LowResObservation
 from .blend import Blend
-from .batch import BlendBatch, BatchProducts, ObservationBatch, LowResObservationBatch, UpdateOptions
+from .batch import BlendBatch, BatchProducts, ObservationBatch, LowResObservationBatch, UpdateOptions, SourceSpec
 from .prior import QuadraticPrior
 from . import bbox, cache, component, source, observation, blend, batch, synth, distributed, io, prior
 

@@ -231,6 +231,11 @@ _SIGNATURES = {
     "scarlet_check_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), _P]),
     "scarlet_init_extended_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), _P, c_float, _P, c_int, c_int, c_int, _P]),
     "scarlet_init_sources_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletInitSpec), _P]),
+    "scarlet_fit_frames_grouped": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints), c_int,
+                                           c_double, c_int, c_int, _P]),
+    "scarlet_source_update_frames_grouped": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),
+                                                     c_int, _P]),
+    "scarlet_init_sources_frames_mixed": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletInitSpec), _P]),
     "scarlet_batch_products_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletProducts), _P, c_int64, _P]),
     "scarlet_fit_observations_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),
                                                 POINTER(POINTER(ScarletBatch)), _P, c_int, c_int, c_double, c_int, c_int, _P]),

@@ -542,6 +542,125 @@ class LowResObservationBatch(ObservationBatch):
         return lr, keep
 
 
+_SOURCE_KINDS = ("extended", "point", "multi")
+
+
+class SourceSpec(object):
+    """One source of a catalogue for `BlendBatch.from_catalog`: a small host object.
+
+    center : (y, x) integer pixel centre in the scene's own coordinates
+    kind : "extended" (ExtendedSource, the default) | "point" (PointSource) | "multi" (MultiComponentSource)
+    flux_percentiles : multi only: the n boundaries between its n + 1 layers, ascending inside (0, 100); default [25]
+    symmetric, monotonic, l0_thresh, l1_thresh : as the reference's sources carry them; the layers of a multi source
+        share them by construction"""
+    __slots__ = ("center", "kind", "flux_percentiles", "symmetric", "monotonic", "l0_thresh", "l1_thresh")
+
+    def __init__(self, center, kind="extended", flux_percentiles=None, symmetric=True, monotonic=True, l0_thresh=None,
+                 l1_thresh=None):
+        self.center, self.kind, self.flux_percentiles = center, kind, flux_percentiles
+        self.symmetric, self.monotonic, self.l0_thresh, self.l1_thresh = symmetric, monotonic, l0_thresh, l1_thresh
+
+    def layers(self, where="source"):
+        """Number of components the source expands to; ValueError (naming `where`) for an unknown kind, percentiles on a
+        source that is not multi, percentiles not ascending inside (0, 100) or more than MAX_LAYERS layers."""
+        if self.kind not in _SOURCE_KINDS:
+            raise ValueError("%s: unknown source kind %r (one of %s)" % (where, self.kind, ", ".join(_SOURCE_KINDS)))
+        if self.kind != "multi":
+            if self.flux_percentiles is not None:
+                raise ValueError("%s: flux_percentiles belong to a multi source, not to kind %r" % (where, self.kind))
+            return 1
+        p = np.asarray([25] if self.flux_percentiles is None else self.flux_percentiles, dtype=np.float64).reshape(-1)
+        if p.size < 1 or not (np.all(p > 0) and np.all(p < 100) and np.all(np.diff(p) > 0)):
+            raise ValueError("%s: flux_percentiles %s must be ascending inside (0, 100)" % (where, p.tolist()))
+        if p.size + 1 > _lib.MAX_LAYERS:
+            raise ValueError("%s: %d flux_percentiles give %d layers, at most %d (SCARLET_MAX_LAYERS) are supported"
+                             % (where, p.size, p.size + 1, _lib.MAX_LAYERS))
+        return int(p.size) + 1
+
+
+def catalog_arrays(shapes, catalog):
+    """A catalogue -- one list of `SourceSpec`s per scene, lengths differ -- as the arrays a batch holds (no device needed).
+
+    shapes : (S, 2) integers, every scene's own frame (h_s, w_s)
+    Returns a dict: `centers` (S, K, 2) int32 padded to K = the largest number of components of a scene, `n_components`
+    (S,) int32, `group` (S, K) int32 (a fresh id per multi source of its scene, -1 elsewhere), `kind` (S, K) int32 of
+    INIT_EXTENDED / INIT_POINT (the layers of a multi source read as extended; ignored by the library), `percentiles`
+    (S, K) float32 (at layer j >= 1 of a multi source the boundary below it, 0 elsewhere), `symmetric`, `monotonic`
+    (S, K) uint8 and `l0_thresh`, `l1_thresh` (S, K) float32 (-1 = off) as `constraint_arrays` stores them, and `sources`,
+    per scene the list of (first component, layers) of its sources.  ValueError, naming scene and source, for an unknown
+    kind, bad percentiles, too many layers, percentiles on a source that is not multi, a centre outside its own frame, an
+    empty scene, or too many components."""
+    shapes = np.asarray(shapes).reshape(-1, 2)
+    S = len(shapes)
+    if len(catalog) != S:
+        raise ValueError("from_catalog: %d catalogues for %d scenes" % (len(catalog), S))
+    rows, sources = [], []
+    for s, specs in enumerate(catalog):
+        specs = list(specs)
+        if not specs:
+            raise ValueError("from_catalog: scene %d has no sources" % s)
+        comps, table = [], []
+        for i, sp in enumerate(specs):
+            where = "from_catalog: scene %d, source %d" % (s, i)
+            if not isinstance(sp, SourceSpec):
+                raise ValueError("%s is not a SourceSpec" % where)
+            n = sp.layers(where)
+            c = np.asarray(sp.center).reshape(-1)
+            if c.size != 2 or not np.all(c == np.round(c)):
+                raise ValueError("%s: the centre must be two integers (y, x), not %r" % (where, sp.center))
+            y, x = int(c[0]), int(c[1])
+            if not (0 <= y < shapes[s, 0] and 0 <= x < shapes[s, 1]):
+                raise ValueError("%s: centre (%d, %d) lies outside the scene's own %d x %d frame" % (where, y, x, shapes[s, 0], shapes[s, 1]))
+            perc = [0.0] if sp.kind != "multi" else [0.0] + [float(v) for v in ([25] if sp.flux_percentiles is None else sp.flux_percentiles)]
+            for v in (sp.l0_thresh, sp.l1_thresh):
+                if v is not None and float(v) != float(v):
+                    raise ValueError("%s: NaN is not a threshold" % where)
+            table.append((len(comps), n))
+            for j in range(n):
+                comps.append(dict(center=(y, x), group=i if sp.kind == "multi" else -1,
+                                  kind=_lib.INIT_POINT if sp.kind == "point" else _lib.INIT_EXTENDED, perc=perc[j],
+                                  symmetric=1 if sp.symmetric else 0, monotonic=1 if sp.monotonic else 0,
+                                  l0_thresh=-1.0 if sp.l0_thresh is None or sp.l0_thresh < 0 else float(sp.l0_thresh),
+                                  l1_thresh=-1.0 if sp.l1_thresh is None or sp.l1_thresh < 0 else float(sp.l1_thresh)))
+        if len(comps) > _lib.MAX_COMPONENTS:
+            raise ValueError("from_catalog: scene %d expands to %d components, at most %d are supported" % (s, len(comps), _lib.MAX_COMPONENTS))
+        rows.append(comps)
+        sources.append(table)
+    K = max(len(r) for r in rows)
+    out = dict(centers=np.zeros((S, K, 2), np.int32), n_components=np.array([len(r) for r in rows], np.int32),
+               group=np.full((S, K), -1, np.int32), kind=np.full((S, K), _lib.INIT_EXTENDED, np.int32),
+               percentiles=np.zeros((S, K), np.float32), symmetric=np.zeros((S, K), np.uint8),
+               monotonic=np.zeros((S, K), np.uint8), l0_thresh=np.full((S, K), -1.0, np.float32),
+               l1_thresh=np.full((S, K), -1.0, np.float32), sources=sources)
+    for s, r in enumerate(rows):
+        for k, comp in enumerate(r):
+            out["centers"][s, k] = comp["center"]
+            for name in ("group", "kind", "symmetric", "monotonic", "l0_thresh", "l1_thresh"):
+                out[name][s, k] = comp[name]
+            out["percentiles"][s, k] = comp["perc"]
+    return out
+
+
+def catalog_frames(cutouts):
+    """The cut-outs of `from_catalog` as (list of per-scene arrays or the block, (S, 2) int32 shapes, uniform) -- no device
+    needed.  ValueError for scenes of differing B or a wrong shape."""
+    if _is_frame_list(cutouts):
+        arrs = list(cutouts)
+        for s, a in enumerate(arrs):
+            if min(np.shape(a)) < 1:
+                raise ValueError("from_catalog: scene %d must be (B, h, w) with every side >= 1, not %s" % (s, tuple(np.shape(a))))
+            if np.shape(a)[0] != np.shape(arrs[0])[0]:
+                raise ValueError("from_catalog: scene %d has B = %d bands, scene 0 has %d" % (s, np.shape(a)[0], np.shape(arrs[0])[0]))
+        shapes = np.array([np.shape(a)[1:] for a in arrs], dtype=np.int32)
+        return arrs, shapes, bool((shapes == shapes[0]).all())
+    if isinstance(cutouts, (list, tuple)):
+        raise ValueError("from_catalog: the cut-outs must be a list of (B, h, w) arrays or one (S, B, H, W) block")
+    if np.ndim(cutouts) != 4:
+        raise ValueError("from_catalog: the cut-outs must be a list of (B, h, w) arrays or one (S, B, H, W) block")
+    S, _, H, W = (int(v) for v in np.shape(cutouts))
+    return cutouts, np.tile(np.array([[H, W]], np.int32), (S, 1)), True
+
+
 class BatchProducts(object):
     """What `BlendBatch.products` returns: device tensors, None for what was not asked for.  For a batch made by
     `from_observations`, `rendered`, `residual` and `loss` are lists with one entry per observation.  `components`
@@ -583,7 +702,8 @@ class BlendBatch(object):
         padded planes and is fitted as the reference fits the (B, h_s, w_s) scene alone -- pixels outside do not exist
         for the constraints, stay exactly zero in the morphologies and carry zero weight (the batch materialises
         (S, B, H, W) weights with the frame mask multiplied in).  Centres are in the scene's own coordinates.  Such a
-        batch takes no `group` and no prior; `init_sources` starts extended sources only.  A joint fit gets its frames
+        batch takes no `group` and no prior; `init_sources` starts extended sources only (`from_catalog` makes the
+        ragged-frame batch that holds point and multi-component sources as well).  A joint fit gets its frames
         from its observations (`ObservationBatch(frame_shapes=...)`), not from this keyword.
     update : None (the stock pipeline of source.py:402-440), or an `UpdateOptions`: each component's symmetry algorithm and
         strength, sweep (weighted with a thresh, or nearest neighbour), positivity and normalisation, on the device
@@ -595,8 +715,9 @@ class BlendBatch(object):
     def __init__(self, images, centers, weights=None, symmetric=True, monotonic=True,
                  l0_thresh=None, l1_thresh=None, centroid_weight=None, mse_capacity=256,
                  device=None, group=None, n_components=None, _frame=None, _morph=True, frame_shapes=None,
-                 _frames=None, update=None):
+                 _frames=None, update=None, _grouped_frames=False):
         frames = _frames             # (from_observations: the checked shapes of its observations, for the state)
+        # (_grouped_frames: from_catalog -- a ragged-frame batch with group=, through the library's _grouped entry points)
         if update is not None:       # host-side refusals first: they need no device
             if not isinstance(update, UpdateOptions):
                 raise ValueError("update must be an UpdateOptions (or None), not %r" % type(update).__name__)
@@ -607,8 +728,8 @@ class BlendBatch(object):
                 raise NotImplementedError("a batch with update= (UpdateOptions) does not take frame_shapes / a list of frames "
                                           "(ragged frames)")
         if frame_shapes is not None or _is_frame_list(images):      # host-side checks first: they need no device
-            images, frames, weights, centers, n_components = ragged_frame_inputs(images, centers, frame_shapes, weights, group,
-                                                                                  n_components)
+            images, frames, weights, centers, n_components = ragged_frame_inputs(
+                images, centers, frame_shapes, weights, None if _grouped_frames else group, n_components)
         torch = _lib.require_gpu()
         self.torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -683,6 +804,7 @@ class BlendBatch(object):
         self.fix_sed = None
         self.fix_morph = None
         self._init_checked = False    # init_sources ran: scenes may carry STATUS_BAD_INIT
+        self._catalog = None          # from_catalog: the tables of catalog_arrays, for init_catalog and source()
         self.group = None
         if group is not None:
             g = np.asarray(group, dtype=np.int32).reshape(S, K)
@@ -749,7 +871,8 @@ class BlendBatch(object):
                 ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(max_iter), float(e_rel),
                 int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
         if self.frame_shapes is not None:           # (never with a prior: _refuse_frames_prior)
-            return _lib.check(_lib.lib.scarlet_fit_frames(
+            fit_frames = _lib.lib.scarlet_fit_frames_grouped if self._catalog is not None else _lib.lib.scarlet_fit_frames
+            return _lib.check(fit_frames(
                 ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(max_iter), float(e_rel),
                 int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
         return _lib.check(_lib.lib.scarlet_fit_constrained(
@@ -761,7 +884,9 @@ class BlendBatch(object):
             return _lib.check(_lib.lib.scarlet_source_update_options(
                 ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(in_iteration), _lib.stream_ptr()))
         if self.frame_shapes is not None:
-            return _lib.check(_lib.lib.scarlet_source_update_frames(
+            update_frames = (_lib.lib.scarlet_source_update_frames_grouped if self._catalog is not None
+                             else _lib.lib.scarlet_source_update_frames)
+            return _lib.check(update_frames(
                 ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(in_iteration), _lib.stream_ptr()))
         return _lib.check(_lib.lib.scarlet_source_update_constrained(
             ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(in_iteration),
@@ -980,7 +1105,11 @@ class BlendBatch(object):
             nbytes = _lib.lib.scarlet_products_scratch_bytes(ctypes.byref(self._c), ctypes.byref(ps))
             scratch = self._products_scratch(nbytes)
             if self.frame_shapes is not None:       # nothing outside each scene's own frame
-                _lib.check(_lib.lib.scarlet_batch_products_frames(ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(ps),
+                c = self._c
+                if self.group is not None:          # (from_catalog: the products do not depend on the groups)
+                    c = _lib.ScarletBatch.from_buffer_copy(self._c)
+                    c.group = None
+                _lib.check(_lib.lib.scarlet_batch_products_frames(ctypes.byref(c), ctypes.byref(self._frames), ctypes.byref(ps),
                                                                   _lib.ptr(scratch), int(nbytes), _lib.stream_ptr()))
                 return res
             _lib.check(_lib.lib.scarlet_batch_products(ctypes.byref(self._c), ctypes.byref(ps), _lib.ptr(scratch), int(nbytes),
@@ -1126,9 +1255,12 @@ class BlendBatch(object):
         group of more than MAX_LAYERS members, percentiles not ascending inside (0, 100)) gives those scenes
         STATUS_BAD_INIT and leaves them untouched and inactive (`raise_on_status` names them).
 
-        A ragged-frame batch (`frame_shapes`) starts extended sources only: `kind` raises NotImplementedError."""
+        A ragged-frame batch (`frame_shapes`) starts extended sources only: `kind` raises NotImplementedError.  One made
+        by `from_catalog` starts every kind on each scene's own frame (scarlet_init_sources_frames_mixed; `init_catalog`
+        passes the catalogue's tables)."""
         self._refuse_single_init()
-        if self.frame_shapes is not None and kind is not None:
+        mixed = self.frame_shapes is not None and self._catalog is not None       # (from_catalog: every stock source type)
+        if self.frame_shapes is not None and kind is not None and not mixed:
             raise NotImplementedError("init_sources on a ragged-frame batch starts extended sources only (kind must be None)")
         t = self.torch
         S, K, B = self.S, self.K, self.B
@@ -1200,7 +1332,10 @@ class BlendBatch(object):
         spec.init_symmetric = int(bool(init_symmetric))
         spec.init_monotonic = int(self.monotonic if init_monotonic is None else bool(init_monotonic))
         spec.run_update = int(bool(run_update) and not self.constrained and self._upd is None)
-        if self.frame_shapes is not None:
+        if mixed:
+            _lib.check(_lib.lib.scarlet_init_sources_frames_mixed(ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(spec),
+                                                                  _lib.stream_ptr()))
+        elif self.frame_shapes is not None:
             _lib.check(_lib.lib.scarlet_init_sources_frames(ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(spec),
                                                             _lib.stream_ptr()))
         else:
@@ -1210,6 +1345,78 @@ class BlendBatch(object):
             # the constructors' update() with each component's own settings; scenes with STATUS_BAD_INIT stay untouched
             self.update_sources()
         return self
+
+    # ------------------------------------------------------------------ catalogues
+    @classmethod
+    def from_catalog(cls, cutouts, catalog, weights=None, **kwargs):
+        """A batch made from survey cut-outs and one catalogue per cut-out: stars, plain galaxies and multi-component
+        galaxies in scenes with their own frame sizes.
+
+        cutouts : a list of S arrays (B, h_s, w_s), or one (S, B, H, W) block
+        catalog : S lists of `SourceSpec`, lengths differ; every source expands to its layers (adjacent components, one
+            group per multi source: `catalog_arrays`)
+        weights : as `BlendBatch` takes them (a list of per-scene arrays for ragged cut-outs)
+        kwargs : centroid_weight, mse_capacity, device
+
+        The batch keeps `sources` (per scene the (first component, layers) of its sources: `source(s, i)`) and the kind and
+        percentile tables for `init_catalog`.  Uniform cut-outs (a block, or a list of equal shapes) give exactly
+        `BlendBatch(images, centers, group=, n_components=, symmetric=, ...)`; ragged ones a ragged-frame batch that also
+        takes `group` -- every scene is started and fitted on its own frame, as the reference does for the scene alone
+        (scarlet_init_sources_frames_mixed, scarlet_fit_frames_grouped).  Priors, `update=`, joint fits and the
+        single-scene `Blend` stay out of scope for such a batch.  Every check of the input is made on the host
+        (ValueError naming scene and source) before the device is asked for."""
+        for name in ("centers", "group", "n_components", "frame_shapes", "symmetric", "monotonic", "l0_thresh", "l1_thresh"):
+            if name in kwargs:
+                raise ValueError("from_catalog: %s comes from the catalogue" % name)
+        if kwargs.get("update") is not None:
+            raise NotImplementedError("from_catalog does not take update= (UpdateOptions)")
+        images, shapes, uniform = catalog_frames(cutouts)
+        t = catalog_arrays(shapes, catalog)
+        S, K = t["group"].shape
+        full = bool((t["n_components"] == K).all())
+        present = np.arange(K)[None, :] < t["n_components"][:, None]
+        settings = {}
+        for name in _SWITCHES + _THRESHOLDS:       # one value for the batch where the catalogue agrees on it
+            vals = np.unique(t[name][present])
+            if vals.size == 1:
+                v = vals[0]
+                settings[name] = bool(v) if name in _SWITCHES else (None if v < 0 else float(v))
+            else:
+                settings[name] = t[name]
+        group = t["group"] if (t["group"] >= 0).any() else None
+        if uniform:
+            block = np.stack([np.asarray(a) for a in images]) if isinstance(images, list) else images
+            if isinstance(weights, (list, tuple)) and _is_frame_list(weights):      # per-scene weights of equal shapes
+                weights = np.stack([np.asarray(w) for w in weights])
+            b = cls(block, t["centers"], weights=weights, group=group, n_components=None if full else t["n_components"],
+                    **settings, **kwargs)
+        else:
+            b = cls(images, t["centers"], weights=weights, group=group, n_components=None if full else t["n_components"],
+                    _grouped_frames=True, **settings, **kwargs)
+        b._catalog = t
+        b.sources = t["sources"]
+        return b
+
+    def init_catalog(self, bg_rms, obs_psfs=None, model_psf=None, thresh=1.0):
+        """Start every source of the catalogue by its own constructor (ExtendedSource, PointSource,
+        MultiComponentSource), on its scene's own frame, and run the constructors' update() once: `init_sources` with
+        the kind and percentile tables `from_catalog` kept.  Bad scenes follow `init_sources`: STATUS_BAD_INIT, left
+        untouched and inactive, named by `raise_on_status`."""
+        if self._catalog is None:
+            raise ValueError("init_catalog: the batch was not made by from_catalog")
+        t = self._catalog
+        kind = t["kind"] if (t["kind"] == _lib.INIT_POINT).any() else None
+        return self.init_sources(bg_rms, kind=kind, flux_percentiles=None if self.group is None else t["percentiles"],
+                                 obs_psfs=obs_psfs, model_psf=model_psf, thresh=thresh)
+
+    def source(self, s, i):
+        """Current (sed, morph) of source i of scene s of a batch made by `from_catalog`: (n_layers, B) and
+        (n_layers, h_s, w_s) tensors, the morphologies on the scene's own frame as `scene(s)` gives them."""
+        if self._catalog is None:
+            raise ValueError("source: the batch was not made by from_catalog")
+        first, n = self.sources[s][i]
+        sed, morph = self.scene(s)
+        return sed[first:first + n], morph[first:first + n]
 
     def update_sources(self):
         """Run the constraint pipeline once with it=0 (what the source constructors do)."""
@@ -1259,6 +1466,10 @@ class BlendBatch(object):
         if prior is not None:
             quad, given, fns = _prior.split_priors(prior)
             self._prior_iteration(self._prior_struct(quad), given, fns, float(e_rel), int(bool(approximate_L)))
+            return
+        if self.frame_shapes is not None and self.group is not None:
+            # (from_catalog) one iteration of scarlet_fit_frames_grouped: its device check of the frames comes first
+            self._lib_fit(None, 1, e_rel, approximate_L, 0)
             return
         s = _lib.stream_ptr()
         if self.frame_shapes is not None:           # the device check first: the gradient kernels skip the scenes it refuses

@@ -884,18 +884,28 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update(A a)
 // PSF-weighted centroid.  _morph is materialised only on the patch both windows can touch (the centroid's radius
 // + 2 around the previous centre, clipped to the frame: inside it every bounds decision equals the frame's).
 // The new centre (and shift) is written to EVERY layer of the source; the update kernels take it as given.
+// RAGGED: the scene's own frame (frame_hw) in the top-left corner of the H x W planes.  The patch is clipped to h_s x w_s,
+// so the windows of wave_max_pixel and wave_centroid end where the scene ends (the centroid's radius is cut at the
+// scene's own last row and column, as the reference cuts it for the scene alone); rows of the plane keep stride W.  A
+// scene with a bad entry is skipped (k_check_frames marked it), and a centre outside the own frame -- never produced by
+// the engine -- is pulled onto it and flagged, as max_pixel_tile does, so that the patch is never empty.
 __host__ __device__ inline size_t group_centers_lds_bytes(int centroid_P)
 {
     const int R = centroid_P / 2 + 2;                 // the patch: 2 R + 1 rows of stride PW = 2 R + 2
     return sizeof(float) * (size_t)(2 * R + 1) * (2 * R + 2);
 }
+template <bool RAGGED = false>
 __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
 {
     extern __shared__ __align__(16) float lds[];
     const int s = blockIdx.x;
     if (!a.force_it0 && !a.active[s]) return;
     if (update_skips_scene(a, s)) return;
-    const int K = a.K, B = a.B, H = a.H, W = a.W, HW = H * W, lane = threadIdx.x;
+    // GH x GW: the planes in HBM;  H x W: the frame the windows see
+    const int K = a.K, B = a.B, GH = a.H, GW = a.W, HW = GH * GW, lane = threadIdx.x;
+    int fh = GH, fw = GW;
+    if (RAGGED && !frame_ok(a.frame_hw, s, GH, GW, fh, fw)) return;
+    const int H = fh, W = fw;
     const int c0 = a.cur[s], wbuf = a.in_iteration ? 1 - c0 : c0;
     const int it = a.force_it0 ? 0 : a.it[s] + (a.in_iteration ? 1 : 0);
     const int R = a.centroid_P / 2 + 2, PW = 2 * R + 1 + 1;                      // patch radius, LDS row stride
@@ -906,6 +916,11 @@ __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
         int k1 = k0 + 1;
         while (k1 < n && a.group[s * K + k1] == g) ++k1;
         int cy = a.centers[2 * (s * K + k0)], cx = a.centers[2 * (s * K + k0) + 1];
+        int stat = 0;
+        if (RAGGED && (cy < 0 || cy >= H || cx < 0 || cx >= W)) {
+            stat = SCARLET_STATUS_CENTER_AT_EDGE;
+            cy = min(max(cy, 0), H - 1); cx = min(max(cx, 0), W - 1);
+        }
         const int py0 = max(0, cy - R), px0 = max(0, cx - R);
         const int ph = min(H, cy + R + 1) - py0, pw = min(W, cx + R + 1) - px0;
         for (int i = lane; i < ph * pw; i += SC_WAVE) {
@@ -915,13 +930,13 @@ __global__ __launch_bounds__(SC_WAVE) void k_group_centers(UpdateArgs a)
                 const float *sed = a.sed[wbuf] + (size_t)(s * K + k) * B;
                 float ssum = 0.f;
                 for (int b = 0; b < B; ++b) ssum += sed[b];
-                acc += a.morph[wbuf][(size_t)(s * K + k) * HW + (py0 + y) * W + px0 + x] * ssum;
+                acc += a.morph[wbuf][(size_t)(s * K + k) * HW + (py0 + y) * GW + px0 + x] * ssum;
             }
             lds[y * PW + x] = acc;
         }
         wave_sync();
         Tile t; t.H = ph; t.W = pw; t.LW = PW; t.m = lds;
-        int stat = 0, ly = cy - py0, lx = cx - px0;
+        int ly = cy - py0, lx = cx - px0;
         wave_max_pixel(t, ly, lx, stat);
         double dy = a.shifts[2 * (s * K + k0)], dx = a.shifts[2 * (s * K + k0) + 1];
         bool new_shift = false;

@@ -225,15 +225,20 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_extended_rows(InitSrcArgs a, 
 
 // ---- PointSource (source.py:360-380): the model PSF pasted with its centre on the pixel and clipped to the frame
 // (a single 1 without one); SED = pixel / obs peak
+// RAGGED: the centre test and the clipping of the paste are the scene's own frame's (frame_hw); the walk covers the whole
+// H x W plane with its own strides, so every pixel outside the frame is written as zero
+template <bool RAGGED = false>
 __global__ __launch_bounds__(SC_BLOCK) void k_init_point(InitSrcArgs a)
 {
     const int c = blockIdx.x, s = c / a.K, H = a.H, W = a.W, HW = H * W, B = a.B;
     __shared__ float sed_s[SC_BMAX];
     if (c - s * a.K >= a.ncomp[s] || init_kind(a, c) != SCARLET_INIT_POINT) return;
+    int fh = H, fw = W;
+    if (RAGGED && !frame_ok(a.frame_hw, s, H, W, fh, fw)) return;
     const int wbuf = a.cur[s];
     float *gm = a.morph[wbuf] + (size_t)c * HW, *gs = a.sed[wbuf] + (size_t)c * B;
     const int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
-    if (cy < 0 || cy >= H || cx < 0 || cx >= W) { init_empty_outside(gm, gs, HW, B, &a.flags[c], &a.status[s]); return; }
+    if (cy < 0 || cy >= fh || cx < 0 || cx >= fw) { init_empty_outside(gm, gs, HW, B, &a.flags[c], &a.status[s]); return; }
     init_pixel_sed(a, s, cy, cx, nullptr, sed_s);
     const int R = (a.P - 1) / 2;
     for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
@@ -241,6 +246,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_point(InitSrcArgs a)
         float v;
         if (a.model_psf) v = (dy >= 0 && dy < a.P && dx >= 0 && dx < a.P) ? a.model_psf[dy * a.P + dx] : 0.f;
         else v = (i / W == cy && i % W == cx) ? 1.f : 0.f;
+        if (RAGGED && (i / W >= fh || i % W >= fw)) v = 0.f;
         gm[i] = v;
     }
     if (threadIdx.x < B) gs[threadIdx.x] = sed_s[threadIdx.x];
@@ -259,46 +265,53 @@ __device__ __forceinline__ double layer_value(double m, int j, int n, const doub
     return m > tcut[j] ? m - tcut[j] : 0.0;
 }
 
-template <bool GT>
+// RAGGED: the scene's own frame (frame_hw) in the top-left corner of planes of PH x PW pixels.  The detection tile, the
+// layer cuts, the layers' maxima and the normal equations run over the scene's h_s x w_s pixels only; images and
+// morphologies are addressed with the planes' strides, the float64 tile has row stride PW + 1, and every layer's plane is
+// written as zero outside the frame.
+template <bool GT, bool RAGGED = false>
 __global__ __launch_bounds__(SC_BLOCK) void k_init_layers(InitSrcArgs a, double *gtile)
 {
     extern __shared__ __align__(16) double ldsd[];
-    const int c = blockIdx.x, s = c / a.K, k = c - s * a.K, H = a.H, W = a.W, HW = H * W, B = a.B;
+    const int c = blockIdx.x, s = c / a.K, k = c - s * a.K, PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
     __shared__ double red[SC_NWAVES], tcut[SCARLET_MAX_LAYERS + 1], gram[SCARLET_MAX_LAYERS][SCARLET_MAX_LAYERS],
         rhs[SCARLET_MAX_LAYERS][SC_BMAX];
     __shared__ float redf[SC_NWAVES], sed_s[SC_BMAX], mmax_s, lmax[SCARLET_MAX_LAYERS];
     __shared__ int singular_s;
     const int ns = a.ncomp[s];
     if (k >= ns || !a.group || a.group[c] < 0 || (k > 0 && a.group[c - 1] == a.group[c])) return;
+    int fh = PH, fw = PW;
+    if (RAGGED && !frame_ok(a.frame_hw, s, PH, PW, fh, fw)) return;
+    const int H = fh, W = fw, HW = H * W;
     int n = 1;
     while (k + n < ns && a.group[c + n] == a.group[c]) ++n;
     n = uniform(n);                                   // k_init_check left at most SCARLET_MAX_LAYERS
     const int wbuf = a.cur[s];
-    float *gm0 = a.morph[wbuf] + (size_t)c * HW, *gs0 = a.sed[wbuf] + (size_t)c * B;
+    float *gm0 = a.morph[wbuf] + (size_t)c * PHW, *gs0 = a.sed[wbuf] + (size_t)c * B;
     const int cy = a.centers[2 * c], cx = a.centers[2 * c + 1];
     if (cy < 0 || cy >= H || cx < 0 || cx >= W) {
         for (int j = 0; j < n; ++j)
-            init_empty_outside(gm0 + (size_t)j * HW, gs0 + (size_t)j * B, HW, B, &a.flags[c + j], &a.status[s]);
+            init_empty_outside(gm0 + (size_t)j * PHW, gs0 + (size_t)j * B, PHW, B, &a.flags[c + j], &a.status[s]);
         return;
     }
     const float mmax = init_model_psf_max(a, redf);
     if (threadIdx.x == 0) mmax_s = mmax;
     __syncthreads();
     init_pixel_sed(a, s, cy, cx, a.model_psf ? &mmax_s : nullptr, sed_s);
-    TileT<double> t; t.H = H; t.W = W; t.LW = W + 1;
-    t.m = GT ? gtile + (size_t)c * H * (W + 1) : ldsd;
-    const float *img = a.images + (size_t)s * B * HW;
+    TileT<double> t; t.H = H; t.W = W; t.LW = PW + 1;
+    t.m = GT ? gtile + (size_t)c * PH * (PW + 1) : ldsd;
+    const float *img = a.images + (size_t)s * B * PHW;
     double bg[SC_BMAX], cutoff;
     init_scene_bg(a, s, bg);
-    const int lstop = init_detect_tile<GT>(t, img, B, cy, cx, sed_s, bg, a.thresh, a.group_symmetric,
-                                           a.do_monotonic, a.no_hybrid, cutoff);
+    const int lstop = init_detect_tile<GT, RAGGED>(t, img, B, cy, cx, sed_s, bg, a.thresh, a.group_symmetric,
+                                                   a.do_monotonic, a.no_hybrid, cutoff, PW, PHW);
     double cnt = 0;
     for (int i = threadIdx.x; i < HW; i += SC_BLOCK)
         if (init_kept(t, i, cy, cx, cutoff, lstop)) cnt += 1;
     cnt = block_sum(cnt, red);                        // (its barriers also order the tile reads below)
     if (cnt == 0) {                                   // SourceInitError: every member gets NO_VALID_PIXELS
         for (int j = 0; j < n; ++j) {
-            for (int i = threadIdx.x; i < HW; i += SC_BLOCK) gm0[(size_t)j * HW + i] = 0.f;
+            for (int i = threadIdx.x; i < PHW; i += SC_BLOCK) gm0[(size_t)j * PHW + i] = 0.f;
             if (threadIdx.x < B) gs0[(size_t)j * B + threadIdx.x] = 0.f;
         }
         if (threadIdx.x < n)
@@ -348,9 +361,12 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_layers(InitSrcArgs a, double 
         }
         return;
     }
-    for (int j = 0; j < n; ++j)
+    for (int j = 0; j < n; ++j) {
         for (int i = threadIdx.x; i < HW; i += SC_BLOCK)
-            gm0[(size_t)j * HW + i] = (float)layer_value(t.m[(i / W) * t.LW + (i % W)], j, n, tcut) / lmax[j];
+            gm0[(size_t)j * PHW + (RAGGED ? (i / W) * PW + (i % W) : i)] =
+                (float)layer_value(t.m[(i / W) * t.LW + (i % W)], j, n, tcut) / lmax[j];
+        if (RAGGED) zero_outside_frame(gm0 + (size_t)j * PHW, PH, PW, H, W, threadIdx.x, SC_BLOCK);
+    }
     // the normal equations: gram[j][q] = sum_i M_j M_q, rhs[j][b] = sum_i M_j D_b, one column q (or band) per pass
     for (int q = 0; q < n + B; ++q) {
         double acc[SCARLET_MAX_LAYERS];
@@ -359,7 +375,7 @@ __global__ __launch_bounds__(SC_BLOCK) void k_init_layers(InitSrcArgs a, double 
         for (int i = threadIdx.x; i < HW; i += SC_BLOCK) {
             const double m = t.m[(i / W) * t.LW + (i % W)];
             const double o = q < n ? (double)((float)layer_value(m, q, n, tcut) / lmax[q])
-                                   : (double)img[(size_t)(q - n) * HW + i];
+                                   : (double)img[(size_t)(q - n) * PHW + (RAGGED ? (i / W) * PW + (i % W) : i)];
 #pragma unroll
             for (int j = 0; j < SCARLET_MAX_LAYERS; ++j)
                 if (j < n) acc[j] += (double)((float)layer_value(m, j, n, tcut) / lmax[j]) * o;

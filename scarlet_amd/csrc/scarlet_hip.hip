@@ -1839,7 +1839,8 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.skip_status = o.skip_status;
     u.frame_hw = (const int *)o.frame_hw;
     const bool ragged = o.frame_hw != nullptr;
-    if (ragged && b->group) return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames) with group: not implemented");
+    // (ragged frames with group: only the _grouped / _mixed entry points get here -- check_frames_call refuses the pair
+    // for every other one)
     if (o.upd && (ragged || b->group)) return set_err(SCARLET_E_NOTIMPL, "update options with ragged frames or group: not implemented");
     u.hybrid_sweep = opt(OPT_NO_HYBRID_SWEEP) ? 0 : 1;
     // (a ragged-frame batch runs no box stage: the box kernels take their bounds from the batch's frame)
@@ -1848,7 +1849,9 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(b->S * b->K), block(SC_BLOCK);
     // MultiComponentSource: the shared centre of every source first (one wave per scene)
-    if (b->group && (rc = launch_lds(k_group_centers, dim3(b->S), dim3(SC_WAVE), group_centers_lds_bytes(b->centroid_P), st, u)))
+    // (ragged: on each scene's own frame, so that the centroid's radius is cut at the scene's ends)
+    if (b->group && (rc = ragged ? launch_lds(k_group_centers<true>, dim3(b->S), dim3(SC_WAVE), group_centers_lds_bytes(b->centroid_P), st, u)
+                                 : launch_lds(k_group_centers<false>, dim3(b->S), dim3(SC_WAVE), group_centers_lds_bytes(b->centroid_P), st, u)))
         return rc;
     if (p.box != BOX_NONE) {
         // frames beyond the wave-level tile: the pipeline on the box around each peak (boxupdate.h); the kernels below
@@ -2300,6 +2303,27 @@ extern "C" int scarlet_source_update_frames(scarlet_batch *b, const scarlet_fram
 {
     int rc = check_call(b, c != nullptr, c, false, nullptr);
     if (!rc) rc = check_frames_call(b, f);
+    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw);
+}
+// ... and with group (the layers of multi-component sources): k_group_centers<RAGGED> measures each source's shared
+// centre on its scene's own frame in front of the RAGGED update kernels.  Without group they are the two calls above,
+// without frame_hw scarlet_fit_constrained / scarlet_source_update_constrained.
+static int check_frames_grouped_call(const scarlet_frames *f)
+{
+    return f ? SCARLET_OK : set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+}
+extern "C" int scarlet_fit_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c, int max_iter,
+                                          double e_rel, int approximate_L, int check_every, void *stream)
+{
+    int rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
+    if (!rc) rc = check_frames_grouped_call(f);
+    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, f->frame_hw);
+}
+extern "C" int scarlet_source_update_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
+                                                    int in_iteration, void *stream)
+{
+    int rc = check_call(b, c != nullptr, c, false, nullptr);
+    if (!rc) rc = check_frames_grouped_call(f);
     return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw);
 }
 extern "C" int scarlet_check_frames(scarlet_batch *b, const scarlet_frames *f, void *stream)
@@ -3099,7 +3123,9 @@ extern "C" int scarlet_init_extended_frames(scarlet_batch *b, const scarlet_fram
 }
 
 // ---- scarlet_init_sources (initsrc.h): every stock source type, per-scene noise and PSF peaks
-static int init_sources_call(scarlet_batch *b, const scarlet_init_spec *spec, void *stream, const int32_t *frame_hw)
+// mixed: scarlet_init_sources_frames_mixed -- with frame_hw, `kind` and b->group are honoured on each scene's own frame
+static int init_sources_call(scarlet_batch *b, const scarlet_init_spec *spec, void *stream, const int32_t *frame_hw,
+                             bool mixed = false)
 {
     int rc;
     if (!spec) return set_err(SCARLET_E_ARG, "null init spec");
@@ -3121,12 +3147,13 @@ static int init_sources_call(scarlet_batch *b, const scarlet_init_spec *spec, vo
     a.frame_hw = (const int *)frame_hw;
     const bool ragged = frame_hw != nullptr;
     // ragged frames: extended sources only -- `kind` must be NULL (it lives on the device: its values cannot be looked at
-    // before the launch); check_frames_call refused groups
-    if (ragged && spec->kind)
+    // before the launch); check_frames_call refused groups.  scarlet_init_sources_frames_mixed (`mixed`) takes both
+    if (ragged && !mixed && spec->kind)
         return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames): scarlet_init_sources_frames starts extended sources only (kind must be NULL)");
     const InitTilePlan t = init_tile_plan(b->H, b->W, (size_t)b->S * b->K);
     if (t.in_lds && ((rc = allow_lds(k_init_extended_rows<false>, t.lds)) || (rc = allow_lds(k_init_layers<false>, t.lds)) ||
-                     (ragged && (rc = allow_lds(k_init_extended_rows<false, true>, t.lds)))))
+                     (ragged && (rc = allow_lds(k_init_extended_rows<false, true>, t.lds))) ||
+                     (ragged && b->group && (rc = allow_lds(k_init_layers<false, true>, t.lds)))))
         return rc;
     if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -3137,11 +3164,15 @@ static int init_sources_call(scarlet_batch *b, const scarlet_init_spec *spec, vo
     hipLaunchKernelGGL(k_init_check, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, st, a);
     const dim3 grid(b->S * b->K);
     if (ragged) {
-        if (t.in_lds) hipLaunchKernelGGL((k_init_extended_rows<false, true>), grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
-        else {
+        if (t.in_lds) {
+            hipLaunchKernelGGL((k_init_extended_rows<false, true>), grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
+            if (b->group) hipLaunchKernelGGL((k_init_layers<false, true>), grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
+        } else {
             DEV_ALLOC(gtile, t.hbm);
             hipLaunchKernelGGL((k_init_extended_rows<true, true>), grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
+            if (b->group) hipLaunchKernelGGL((k_init_layers<true, true>), grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
         }
+        if (spec->kind) hipLaunchKernelGGL(k_init_point<true>, grid, dim3(SC_BLOCK), 0, st, a);
     } else if (t.in_lds) {
         hipLaunchKernelGGL(k_init_extended_rows<false>, grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
         if (b->group) hipLaunchKernelGGL(k_init_layers<false>, grid, dim3(SC_BLOCK), t.lds, st, a, (double *)nullptr);
@@ -3150,7 +3181,7 @@ static int init_sources_call(scarlet_batch *b, const scarlet_init_spec *spec, vo
         hipLaunchKernelGGL(k_init_extended_rows<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
         if (b->group) hipLaunchKernelGGL(k_init_layers<true>, grid, dim3(SC_BLOCK), 0, st, a, gtile.as<double>());
     }
-    if (!ragged) hipLaunchKernelGGL(k_init_point, grid, dim3(SC_BLOCK), 0, st, a);
+    if (!ragged) hipLaunchKernelGGL(k_init_point<false>, grid, dim3(SC_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (spec->run_update) {                          // the constructors' self.update(), on the scenes initialised here
         scarlet_batch c = *b;
@@ -3174,6 +3205,14 @@ extern "C" int scarlet_init_sources_frames(scarlet_batch *b, const scarlet_frame
     int rc = check_batch(b);
     if (!rc) rc = check_frames_call(b, f);
     return rc ? rc : init_sources_call(b, spec, stream, f->frame_hw);
+}
+// ... every stock source type on each scene's own frame: spec->kind and b->group are honoured (k_init_point<RAGGED>,
+// k_init_layers<GT, RAGGED>); with frame_hw = NULL it is scarlet_init_sources
+extern "C" int scarlet_init_sources_frames_mixed(scarlet_batch *b, const scarlet_frames *f, const scarlet_init_spec *spec, void *stream)
+{
+    int rc = check_batch(b);
+    if (!rc) rc = check_frames_grouped_call(f);
+    return rc ? rc : init_sources_call(b, spec, stream, f->frame_hw, true);
 }
 
 // ---- convergence sums for the Python-override path (the built-in pipeline computes them itself)
