@@ -187,8 +187,11 @@ __device__ inline double jacobi_lambda_max(double *A, int n, int ld)
 // p, p', p'' > 0 to the right of the largest one, so Newton's iteration started at the
 // trace (>= lambda_max) decreases monotonically onto it.  ~10 x fewer dependent
 // instructions than a Jacobi sweep; the root's conditioning is that of the eigenvalue
-// (error ~1e-16 separated, ~1e-8 relative for a double top eigenvalue; a cluster of three or four is returned from
-// above, within the start's distance or ~2e-5, whichever is smaller).
+// (error ~1e-16 separated).  A top eigenvalue of multiplicity m is returned from ABOVE: the iteration stops on the
+// floor p(x) <= 2^-47 x^4 below, at a relative distance (2^-47 / prod (1 - lambda_j / lambda_1))^(1/m) over the other
+// eigenvalues j -- measured up to 1.6e-7 for a double top at n = 4 (1.4e-7 with the others at 0.5 and 0.2), 2.3e-5 for
+// the rotated cluster (1, 1, 1, 0.3), 2.1e-5 on the device (profiles/lipschitz_rel_err.txt) -- or within the start's
+// distance, whichever is smaller (tests/lipschitz_cases.py charpoly_upper is this bound).
 // Replaces np.linalg.eigvals(...).max() of blend.py:216-218.
 __device__ inline double lambda_max_charpoly4(const double *A, int n, int ld)
 {
@@ -294,63 +297,6 @@ __device__ inline void block_lipschitz(double *G, int K, int ldK, double *ATA, i
         if (lane == 0) L[wid] = l;
     }
     __syncthreads();
-}
-
-// Register-resident variant for the fused kernel: the whole (padded) N x N matrix lives in
-// VGPRs of ONE lane, loops fully unrolled (no LDS round trips on the rotation chain).
-// Rotation angles are computed in float32 (one v_rcp/v_sqrt each), then (c, s) is
-// re-orthonormalised in float64 with one Newton step, so the similarity transforms stay
-// orthogonal to ~1e-14 while the scalar part costs a handful of instructions; an angle
-// that is only float32-accurate merely leaves a 1e-7-relative off-diagonal residue that the
-// next sweep removes.  Eigenvalues are accurate to float64 round-off.
-template <int N>
-__device__ inline double jacobi_lambda_max_reg(const double *Ain, int n, int ld)
-{
-    double A[N][N];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < N; ++j) A[i][j] = (i < n && j < n) ? Ain[i * ld + j] : 0.0;
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        double off = 0, diag = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            diag += A[i][i] * A[i][i];
-#pragma unroll
-            for (int j = i + 1; j < N; ++j) off += A[i][j] * A[i][j];
-        }
-        if (off <= 1e-30 * diag) break;
-#pragma unroll
-        for (int p = 0; p < N - 1; ++p)
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = A[p][q];
-                if (apq != 0.0) {
-                    const float th = (float)((A[q][q] - A[p][p]) / (2.0 * apq));
-                    const float tf = (th >= 0.f ? 1.f : -1.f) / (fabsf(th) + sqrtf(th * th + 1.f));
-                    const float cf = 1.0f / sqrtf(tf * tf + 1.f);
-                    double c = (double)cf, sn = (double)(tf * cf);
-                    const double fix = 1.5 - 0.5 * (c * c + sn * sn);      // Newton step of rsqrt
-                    c *= fix; sn *= fix;
-#pragma unroll
-                    for (int r = 0; r < N; ++r) {
-                        const double arp = A[r][p], arq = A[r][q];
-                        A[r][p] = c * arp - sn * arq;
-                        A[r][q] = sn * arp + c * arq;
-                    }
-#pragma unroll
-                    for (int r = 0; r < N; ++r) {
-                        const double apr = A[p][r], aqr = A[q][r];
-                        A[p][r] = c * apr - sn * aqr;
-                        A[q][r] = sn * apr + c * aqr;
-                    }
-                }
-            }
-    }
-    double l = A[0][0];
-#pragma unroll
-    for (int i = 1; i < N; ++i) l = fmax(l, A[i][i]);
-    return l;
 }
 
 // ------------------------------------------------------------------------------------
