@@ -456,6 +456,10 @@ int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_con
  *     other scenes go on.
  *   - SCARLET_E_NOTIMPL, found on the host before any launch: a batch with `group` (layers are tied to soft symmetry with
  *     shift = None), a wide state (state->B > 8).  There is no prior, no scarlet_frames and no low-resolution argument.
+ *     Groups and ragged frames with options go through scarlet_fit_frames_options /
+ *     scarlet_source_update_frames_options (declared after struct scarlet_frames, below): a layer takes its source's shared
+ *     centre as given and has no shift, so _KSPACE is soft symmetry with strength 1 for it, _SOFT uses its strength and
+ *     _SDSS is sdss; the norms of type _MORPH and _SED sum the pixels of the scene's own frame only.
  *   - A batch with options takes the general path: no one-launch iteration, one pipeline, no box stage beyond 64 pixels; the
  *     full-frame forms of the constraint kernels (their options instances, engine.h) serve every component.
  *   - sym_algorithm: SCARLET_SYM_KSPACE still falls back to soft symmetry with strength 1 while the component has no shift
@@ -514,7 +518,9 @@ int scarlet_fit_observations_options(scarlet_batch *state, const scarlet_constra
  *   - SCARLET_E_NOTIMPL, found on the host before any launch: frame_hw with b->group; scarlet_init_sources_frames with
  *     spec->kind (extended sources only).  Point sources and multi-component sources (b->group) on ragged frames go
  *     through entry points of their own: scarlet_fit_frames_grouped, scarlet_source_update_frames_grouped and
- *     scarlet_init_sources_frames_mixed, below.  Priors, update options and scarlet_fit_multi have no _frames form, and the
+ *     scarlet_init_sources_frames_mixed, below; update options on ragged frames (with or without
+ *     b->group) through scarlet_fit_frames_options and scarlet_source_update_frames_options, below.  Priors and
+ *     scarlet_fit_multi have no _frames form, and the
  *     joint fits take no group with frame_hw; the joint fit against
  *     same-grid observations has one (scarlet_fit_observations_frames, below), and so has the joint fit against
  *     low-resolution observations, each scene with its own operator (struct scarlet_lowres_frames,
@@ -560,6 +566,29 @@ int scarlet_fit_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const 
 int scarlet_source_update_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
                                          int in_iteration, void *stream);
 /* (scarlet_init_sources_frames_mixed is declared beside scarlet_init_sources_frames, after struct scarlet_init_spec) */
+
+/* Ragged frames, groups and update options together: a catalogue whose sources carry the stock update functions' options.
+ * The contract of the two _grouped calls above with scarlet_update_options beside the constraints:
+ *   - b->group is allowed.  f == NULL or o == NULL is SCARLET_E_ARG.
+ *   - With f->frame_hw == NULL and b->group == NULL they ARE scarlet_fit_options / scarlet_source_update_options; with every
+ *     member of `o` NULL they ARE scarlet_fit_frames_grouped / scarlet_source_update_frames_grouped; both bit for bit.
+ *   - A point or extended source runs the options pipeline on its scene's own bounds.  A multi-component source's shared
+ *     centre (and, every fifth iteration, if it is symmetric, the centroid) is measured on the flux-weighted sum of its
+ *     layers before any option acts; each layer then gets the symmetry (no shift: _KSPACE is soft with strength 1), the
+ *     sweep, the positivity variant and the normalisation of its own row.
+ *   - The device checks run first, in the order counts, frames, options: a scene may carry SCARLET_STATUS_BAD_FRAME and
+ *     _BAD_OPTION together and is then never touched.  The constructors' update (in_iteration = 0) also leaves
+ *     _BAD_INIT and _BAD_COUNT scenes untouched.
+ *   - Pixels outside a scene's frame are no neighbour, partner, ring pixel or window pixel of any operator and are exactly
+ *     0.0f in both morphology buffers after every call.
+ *   - Such a batch takes the general path on one pipeline: no one-launch iteration, no box stage, the workspace and the
+ *     dynamic LDS of the padded (H, W) forms.  There is no prior and no init entry point of its own: start the sources with
+ *     run_update = 0 and call scarlet_source_update_frames_options with in_iteration = 0. */
+int scarlet_fit_frames_options(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
+                               const scarlet_update_options *o, int max_iter, double e_rel, int approximate_L,
+                               int check_every, void *stream);
+int scarlet_source_update_frames_options(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c /* or NULL */,
+                                         const scarlet_update_options *o, int in_iteration, void *stream);
 
 /* scarlet_fit_observations_constrained for scenes with their own frames (c may be NULL: the state's scalars).  The state
  * may span up to SCARLET_MAX_CHANNELS channels: with state->B > 8 the call is scarlet_fit_observations_wide without a prior

@@ -235,6 +235,10 @@ _SIGNATURES = {
                                            c_double, c_int, c_int, _P]),
     "scarlet_source_update_frames_grouped": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),
                                                      c_int, _P]),
+    "scarlet_fit_frames_options": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),
+                                           POINTER(ScarletUpdateOptions), c_int, c_double, c_int, c_int, _P]),
+    "scarlet_source_update_frames_options": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),
+                                                     POINTER(ScarletUpdateOptions), c_int, _P]),
     "scarlet_init_sources_frames_mixed": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletInitSpec), _P]),
     "scarlet_batch_products_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletProducts), _P, c_int64, _P]),
     "scarlet_fit_observations_frames": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFrames), POINTER(ScarletConstraints),

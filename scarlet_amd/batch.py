@@ -552,13 +552,24 @@ class SourceSpec(object):
     kind : "extended" (ExtendedSource, the default) | "point" (PointSource) | "multi" (MultiComponentSource)
     flux_percentiles : multi only: the n boundaries between its n + 1 layers, ascending inside (0, 100); default [25]
     symmetric, monotonic, l0_thresh, l1_thresh : as the reference's sources carry them; the layers of a multi source
-        share them by construction"""
-    __slots__ = ("center", "kind", "flux_percentiles", "symmetric", "monotonic", "l0_thresh", "l1_thresh")
+        share them by construction
+    symmetry, strength, use_nearest, monotonic_thresh, positive, normalization : the stock update functions' options of
+        this source, with the values `UpdateOptions` takes; None (the default) = the batch's default
+        (`from_catalog(update=)`, else the stock pipeline's).  The layers of a multi source share them."""
+    OPTION_FIELDS = ("symmetry", "strength", "use_nearest", "monotonic_thresh", "positive", "normalization")
+    __slots__ = ("center", "kind", "flux_percentiles", "symmetric", "monotonic", "l0_thresh", "l1_thresh") + OPTION_FIELDS
 
     def __init__(self, center, kind="extended", flux_percentiles=None, symmetric=True, monotonic=True, l0_thresh=None,
-                 l1_thresh=None):
+                 l1_thresh=None, symmetry=None, strength=None, use_nearest=None, monotonic_thresh=None, positive=None,
+                 normalization=None):
         self.center, self.kind, self.flux_percentiles = center, kind, flux_percentiles
         self.symmetric, self.monotonic, self.l0_thresh, self.l1_thresh = symmetric, monotonic, l0_thresh, l1_thresh
+        self.symmetry, self.strength, self.use_nearest = symmetry, strength, use_nearest
+        self.monotonic_thresh, self.positive, self.normalization = monotonic_thresh, positive, normalization
+
+    def has_options(self):
+        """True when the source sets one of the update options itself."""
+        return any(getattr(self, name) is not None for name in self.OPTION_FIELDS)
 
     def layers(self, where="source"):
         """Number of components the source expands to; ValueError (naming `where`) for an unknown kind, percentiles on a
@@ -638,6 +649,49 @@ def catalog_arrays(shapes, catalog):
             for name in ("group", "kind", "symmetric", "monotonic", "l0_thresh", "l1_thresh"):
                 out[name][s, k] = comp[name]
             out["percentiles"][s, k] = comp["perc"]
+    return out
+
+
+def catalog_option_arrays(catalog, update=None):
+    """The update options of a catalogue as the (S, K) tables of `UpdateOptions.arrays`, one row per component in the
+    layout of `catalog_arrays` (no device needed), or None where nothing asks for options.
+
+    update : None, or an `UpdateOptions` whose fields are single values: the default of every source.  A `SourceSpec`
+        field that is not None overrides it; the layers of a multi source share their source's options.
+    Returns None when `update` is None and no source sets an option -- such a catalogue takes the route of a catalogue
+    without options -- else {member of scarlet_update_options: (S, K) host array}; rows of absent components hold the
+    stock pipeline's values and are never read.  ValueError, naming scene and source, for an unknown name, a strength
+    outside [0, 1], a thresh outside [0, 1) or use_nearest with a thresh; ValueError for an `update` with per-component
+    arrays (they come from the catalogue)."""
+    if update is not None:
+        if not isinstance(update, UpdateOptions):
+            raise ValueError("from_catalog: update must be an UpdateOptions (or None), not %r" % type(update).__name__)
+        for name in SourceSpec.OPTION_FIELDS:
+            v = getattr(update, name)
+            if not (isinstance(v, (str, bytes)) or is_scalar_setting(v)):
+                raise ValueError("from_catalog: update.%s per component comes from the catalogue (SourceSpec(%s=...)); "
+                                 "update= takes single values, the batch's defaults" % (name, name))
+    if update is None and not any(isinstance(sp, SourceSpec) and sp.has_options() for specs in catalog for sp in specs):
+        return None
+    base = UpdateOptions() if update is None else update
+    rows = []
+    for s, specs in enumerate(catalog):
+        comps = []
+        for i, sp in enumerate(specs):
+            kw = {name: getattr(base, name) if getattr(sp, name) is None else getattr(sp, name)
+                  for name in SourceSpec.OPTION_FIELDS}
+            try:
+                one = UpdateOptions(**kw).arrays(1, 1)
+            except ValueError as e:
+                raise ValueError("from_catalog: scene %d, source %d: %s" % (s, i, e))
+            comps += [one] * sp.layers("from_catalog: scene %d, source %d" % (s, i))
+        rows.append(comps)
+    S, K = len(rows), max(len(r) for r in rows)
+    out = UpdateOptions().arrays(S, K)
+    for s, r in enumerate(rows):
+        for k, one in enumerate(r):
+            for name in UpdateOptions.FIELDS:
+                out[name][s, k] = one[name][0, 0]
     return out
 
 
@@ -805,6 +859,7 @@ class BlendBatch(object):
         self.fix_morph = None
         self._init_checked = False    # init_sources ran: scenes may carry STATUS_BAD_INIT
         self._catalog = None          # from_catalog: the tables of catalog_arrays, for init_catalog and source()
+        self._catalog_options = False  # from_catalog with update options: the _frames_options entry points
         self.group = None
         if group is not None:
             g = np.asarray(group, dtype=np.int32).reshape(S, K)
@@ -866,6 +921,10 @@ class BlendBatch(object):
     # Every call into the library's loops goes through these two and _fit_observations.  The *_constrained entry points
     # with a NULL member read that setting from the batch's scalars, and with prior = NULL step without one.
     def _lib_fit(self, ps, max_iter, e_rel, approximate_L, check_every):
+        if self._catalog_options:                   # (never with a prior: _refuse_update_prior)
+            return _lib.check(_lib.lib.scarlet_fit_frames_options(
+                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ctypes.byref(self._upd),
+                int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
         if self._upd is not None:                   # (never with a prior or ragged frames: refused before)
             return _lib.check(_lib.lib.scarlet_fit_options(
                 ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(max_iter), float(e_rel),
@@ -880,6 +939,10 @@ class BlendBatch(object):
             float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
 
     def _lib_update(self, ps, in_iteration):
+        if self._catalog_options:
+            return _lib.check(_lib.lib.scarlet_source_update_frames_options(
+                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ctypes.byref(self._upd),
+                int(in_iteration), _lib.stream_ptr()))
         if self._upd is not None:
             return _lib.check(_lib.lib.scarlet_source_update_options(
                 ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(in_iteration), _lib.stream_ptr()))
@@ -1348,7 +1411,7 @@ class BlendBatch(object):
 
     # ------------------------------------------------------------------ catalogues
     @classmethod
-    def from_catalog(cls, cutouts, catalog, weights=None, **kwargs):
+    def from_catalog(cls, cutouts, catalog, weights=None, update=None, **kwargs):
         """A batch made from survey cut-outs and one catalogue per cut-out: stars, plain galaxies and multi-component
         galaxies in scenes with their own frame sizes.
 
@@ -1356,22 +1419,29 @@ class BlendBatch(object):
         catalog : S lists of `SourceSpec`, lengths differ; every source expands to its layers (adjacent components, one
             group per multi source: `catalog_arrays`)
         weights : as `BlendBatch` takes them (a list of per-scene arrays for ragged cut-outs)
+        update : None, or an `UpdateOptions` of single values: the batch's default for the update options every
+            `SourceSpec` may set itself (symmetry, strength, use_nearest, monotonic_thresh, positive, normalization;
+            `catalog_option_arrays`).  Per-component arrays raise ValueError: they come from the catalogue.
         kwargs : centroid_weight, mse_capacity, device
 
         The batch keeps `sources` (per scene the (first component, layers) of its sources: `source(s, i)`) and the kind and
         percentile tables for `init_catalog`.  Uniform cut-outs (a block, or a list of equal shapes) give exactly
         `BlendBatch(images, centers, group=, n_components=, symmetric=, ...)`; ragged ones a ragged-frame batch that also
         takes `group` -- every scene is started and fitted on its own frame, as the reference does for the scene alone
-        (scarlet_init_sources_frames_mixed, scarlet_fit_frames_grouped).  Priors, `update=`, joint fits and the
-        single-scene `Blend` stay out of scope for such a batch.  Every check of the input is made on the host
-        (ValueError naming scene and source) before the device is asked for."""
+        (scarlet_init_sources_frames_mixed, scarlet_fit_frames_grouped).  A catalogue in which nothing sets an update
+        option, with `update=None`, is exactly that batch.  Anything else -- an explicit `update=UpdateOptions()` and
+        uniform cut-outs included -- carries each component's options on the device and runs the constraint kernels'
+        options instances on each scene's own frame (scarlet_fit_frames_options, scarlet_source_update_frames_options):
+        the general path on one pipeline; `init_catalog` starts the sources and then runs the constructors' update with
+        the options, and a scene whose options were corrupted on the device gets STATUS_BAD_OPTION and is left untouched.
+        Priors, joint fits and the single-scene `Blend` stay out of scope for a catalogue batch.  Every check of the input
+        is made on the host (ValueError naming scene and source) before the device is asked for."""
         for name in ("centers", "group", "n_components", "frame_shapes", "symmetric", "monotonic", "l0_thresh", "l1_thresh"):
             if name in kwargs:
                 raise ValueError("from_catalog: %s comes from the catalogue" % name)
-        if kwargs.get("update") is not None:
-            raise NotImplementedError("from_catalog does not take update= (UpdateOptions)")
         images, shapes, uniform = catalog_frames(cutouts)
         t = catalog_arrays(shapes, catalog)
+        options = catalog_option_arrays(catalog, update)
         S, K = t["group"].shape
         full = bool((t["n_components"] == K).all())
         present = np.arange(K)[None, :] < t["n_components"][:, None]
@@ -1395,7 +1465,18 @@ class BlendBatch(object):
                     _grouped_frames=True, **settings, **kwargs)
         b._catalog = t
         b.sources = t["sources"]
+        if options is not None:
+            b._set_catalog_options(options)
         return b
+
+    def _set_catalog_options(self, host):
+        """(from_catalog) the catalogue's update options on the device; from here on the batch calls the library's
+        _frames_options entry points, which take its group and its frames (frame_hw NULL for uniform cut-outs)"""
+        self.update_options = {name: self.torch.as_tensor(a).to(device=self.device).contiguous() for name, a in host.items()}
+        self._upd = _lib.ScarletUpdateOptions()
+        for name, x in self.update_options.items():
+            setattr(self._upd, name, x.data_ptr())
+        self._catalog_options = True
 
     def init_catalog(self, bg_rms, obs_psfs=None, model_psf=None, thresh=1.0):
         """Start every source of the catalogue by its own constructor (ExtendedSource, PointSource,
@@ -1454,7 +1535,8 @@ class BlendBatch(object):
         self._refuse_update_prior(prior)
         self._ensure_mse_capacity(1)
         if self._upd is not None and self._observations is None:
-            # one iteration of scarlet_fit_options: its device check of the options comes before the gradient step
+            # one iteration of scarlet_fit_options -- for a catalogue batch of scarlet_fit_frames_options: the device checks
+            # (counts, frames, options) come before the gradient step
             self._lib_fit(None, 1, e_rel, approximate_L, 0)
             return
         if self._observations is not None:

@@ -544,14 +544,17 @@ __device__ __forceinline__ float update_step_morph(const UpdateArgs &a, int s, i
 // RAGGED: the component's scene has its own frame (UpdateArgs::frame_hw) in the top-left corner of the H x W plane.  The
 // tile is built with the scene's bounds (every operator takes its bounds from the tile), only the scene's pixels are
 // loaded from the stride-W plane, and the rest of the plane is written as zero.  LDS is laid out for the padded frame.
-// A = UpdateArgsOpt: the OPTIONS instance (scarlet_update_options; uniform frames only) -- each component's own symmetry
-// algorithm and strength, sweep (weighted with its thresh, or nearest neighbour), positivity and normalisation.
+// A = UpdateArgsOpt: the OPTIONS instance (scarlet_update_options) -- each component's own symmetry algorithm and strength,
+// sweep (weighted with its thresh, or nearest neighbour), positivity and normalisation.  A layer of a multi-component
+// source (`group`) takes its centre as given and has no shift: "kspace" is then soft symmetry with strength 1.
+// RAGGED with options (a catalogue batch, scarlet_fit_frames_options): every tail below walks the scene's h x w pixels and
+// indexes the plane with its stride PW, the norms of type "morph" / "sed" sum the scene's pixels only, and
+// zero_outside_frame closes every path.
 template <int MODE, bool RAGGED = false, class A = UpdateArgs>
 __global__ __launch_bounds__(SC_BLOCK) void k_source_update(A a)
 {
     constexpr bool GT = MODE == 2;
     constexpr bool OPT = has_update_options<A>;
-    static_assert(!(OPT && RAGGED), "no options instance for ragged frames");
     extern __shared__ __align__(16) float lds[];
     const int c = blockIdx.x, s = c / a.K;
     if (!a.force_it0 && !a.active[s]) return;
@@ -938,7 +941,6 @@ template <bool RAGGED = false, class A = UpdateArgs>
 __device__ inline void wave_pipeline(const A &a, int c, float *lds_wave)
 {
     constexpr bool OPT = has_update_options<A>;
-    static_assert(!(OPT && RAGGED), "no options instance for ragged frames");
     const int s = c / a.K;
     const int PH = a.H, PW = a.W, PHW = PH * PW, B = a.B;
     int fh = PH, fw = PW;
@@ -1135,6 +1137,19 @@ __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w_opt(UpdateArgsOpt 
     if (update_skips_scene(a, c / a.K)) return;
     const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;
     wave_pipeline<false, UpdateArgsOpt>(a, c, lds + (size_t)wid * per_wave);
+}
+// ... for a batch with both (scarlet_fit_frames_options)
+__global__ __launch_bounds__(SC_BLOCK) void k_source_update_w_ragged_opt(UpdateArgsOpt a)
+{
+    extern __shared__ __align__(16) float lds[];
+    const int wid = threadIdx.x / SC_WAVE;
+    const int c = uniform((int)(blockIdx.x * SC_NWAVES + wid));
+    if (c >= a.S * a.K) return;
+    if (!a.force_it0 && !a.active[c / a.K]) return;
+    if (c % a.K >= scene_ncomp(a.ncomp, c / a.K, a.K)) return;
+    if (update_skips_scene(a, c / a.K)) return;
+    const int per_wave = a.H * tile_stride(a.W) + SC_WAVE_VEC_FLOATS;
+    wave_pipeline<true, UpdateArgsOpt>(a, c, lds + (size_t)wid * per_wave);
 }
 // ... for a batch whose scenes have their own frames (UpdateArgs::frame_hw)
 __global__ __launch_bounds__(SC_BLOCK) void k_source_update_w_ragged(UpdateArgs a)

@@ -879,13 +879,14 @@ template <> constexpr bool has_update_options<scarlet_update_options> = true;   
 // One thread per scene, before anything else of the call: a scene one of whose present components has an inadmissible row
 // (options_ok, engine.h; a `positive` beyond its two bits) gets SCARLET_STATUS_BAD_OPTION and active = 0.  The rows of
 // inactive scenes (respect_active: the calls that iterate), of scenes a constructor call leaves alone (skip_status) and of
-// absent components are not read.
+// absent components are not read.  also_status: an inactive scene with one of these bits is checked all the same
+// (SCARLET_STATUS_BAD_FRAME with ragged frames: the frame check in front deactivates a scene, which then carries both bits).
 __global__ void k_check_options(scarlet_update_options o, const int *ncomp, int S, int K, int respect_active, int skip_status,
-                                int *status, int *active)
+                                int also_status, int *status, int *active)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
-    if (respect_active && !active[s]) return;
+    if (respect_active && !active[s] && !(status[s] & also_status)) return;
     if (skip_status && (status[s] & skip_status)) return;
     const int n = scene_ncomp(ncomp, s, K);
     bool ok = true;
@@ -895,11 +896,12 @@ __global__ void k_check_options(scarlet_update_options o, const int *ncomp, int 
     }
     if (!ok) { status[s] |= SCARLET_STATUS_BAD_OPTION; active[s] = 0; }
 }
-static int check_options(const scarlet_batch *b, const scarlet_update_options *o, int respect_active, int skip_status, void *stream)
+static int check_options(const scarlet_batch *b, const scarlet_update_options *o, int respect_active, int skip_status, void *stream,
+                         int also_status = 0)
 {
     if (!opts_any(o)) return SCARLET_OK;
     hipLaunchKernelGGL(k_check_options, dim3((b->S + SC_BLOCK - 1) / SC_BLOCK), dim3(SC_BLOCK), 0, (hipStream_t)stream,
-                       *o, (const int *)b->n_components, b->S, b->K, respect_active, skip_status, b->status, b->active);
+                       *o, (const int *)b->n_components, b->S, b->K, respect_active, skip_status, also_status, b->status, b->active);
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
 }
@@ -1813,7 +1815,8 @@ __global__ void k_zero_int(int *p) { *p = 0; }
 // L_comp: the constants each component stepped with (scarlet_prior::L_comp), or NULL: the scene's
 // cons: the components' own switches, or NULL: the batch's.  skip_status: status bits of the scenes a constructor call leaves alone
 // frame_hw: scarlet_frames::frame_hw of the batch (or of the view: advanced to its first scene), or NULL
-// upd: the batch's update options (never with frame_hw, group or a box stage), or NULL: the stock pipeline
+// upd: the batch's update options (never with a box stage; with frame_hw or group only through the _frames_options entry
+// points, check_options_call refuses the pair for every other one), or NULL: the stock pipeline
 struct UpdateOpts { const double *L_comp; const scarlet_constraints *cons; int skip_status; const int32_t *frame_hw;
                     const scarlet_update_options *upd; };
 // in_iteration = 0: the constructors' call (UpdateArgs::force_it0)
@@ -1839,9 +1842,8 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
     u.skip_status = o.skip_status;
     u.frame_hw = (const int *)o.frame_hw;
     const bool ragged = o.frame_hw != nullptr;
-    // (ragged frames with group: only the _grouped / _mixed entry points get here -- check_frames_call refuses the pair
-    // for every other one)
-    if (o.upd && (ragged || b->group)) return set_err(SCARLET_E_NOTIMPL, "update options with ragged frames or group: not implemented");
+    // (ragged frames with group: only the _grouped / _mixed / _frames_options entry points get here -- check_frames_call
+    // refuses the pair for every other one; options with group or ragged frames: only the _frames_options ones)
     u.hybrid_sweep = opt(OPT_NO_HYBRID_SWEEP) ? 0 : 1;
     // (a ragged-frame batch runs no box stage: the box kernels take their bounds from the batch's frame)
     const UpdatePlan p = update_plan(b->H, b->W, {!opt(OPT_FORCE_BLOCK_UPDATE), true, b->monotonic && !opt(OPT_NO_BOX) && !ragged && !o.upd,
@@ -1882,46 +1884,31 @@ static int launch_update(scarlet_batch *b, const WsLayout &l, int in_iteration, 
         if (!l.has_gscratch) return set_err(SCARLET_E_ARG, "the workspace layout holds no symmetry scratch for this frame");
         u.gscratch = ws_at<float>(b, l.gscratch);
     }
-    if (ragged) {               // the same forms on each scene's own frame (engine.h RAGGED)
+    // the form's kernel out of the four instances of one (ragged, options) pair
+    auto run_form = [&](auto wave_k, auto tile_gscratch_k, auto tile_k, auto plane_k, const auto &args) -> int {
         switch (p.form) {
-        case FORM_WAVE:
-            rc = launch_lds(k_source_update_w_ragged, dim3((b->S * b->K + SC_NWAVES - 1) / SC_NWAVES), block, p.lds, st, u);
-            break;
-        case FORM_TILE_GSCRATCH: rc = launch_lds(k_source_update<1, true>, grid, block, p.lds, st, u); break;
-        case FORM_TILE: rc = launch_lds(k_source_update<0, true>, grid, block, p.lds, st, u); break;
-        default: rc = launch_lds(k_source_update<2, true>, grid, block, p.lds, st, u);
+        case FORM_WAVE:             // one wave per component, four components per workgroup (wave_ops.h)
+            return launch_lds(wave_k, dim3((b->S * b->K + SC_NWAVES - 1) / SC_NWAVES), block, p.lds, st, args);
+        case FORM_TILE_GSCRATCH: return launch_lds(tile_gscratch_k, grid, block, p.lds, st, args);
+        case FORM_TILE: return launch_lds(tile_k, grid, block, p.lds, st, args);
+        default:                    // operators in place on the plane in HBM / L2 (94 KB at 1024 x 1024)
+            return launch_lds(plane_k, grid, block, p.lds, st, args);
         }
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-        return SCARLET_OK;
-    }
-    if (o.upd) {                // the options instances of the same forms (engine.h UpdateArgsOpt); no box stage ran
+    };
+    if (o.upd) {                // the options instances (engine.h UpdateArgsOpt); no box stage ran
         UpdateArgsOpt uo;
         static_cast<UpdateArgs &>(uo) = u;
         uo.sym_algorithm = o.upd->sym_algorithm; uo.sym_strength = o.upd->sym_strength;
         uo.mono_nearest = o.upd->mono_nearest; uo.mono_thresh = o.upd->mono_thresh;
         uo.positive = o.upd->positive; uo.normalize = o.upd->normalize;
-        switch (p.form) {
-        case FORM_WAVE:
-            rc = launch_lds(k_source_update_w_opt, dim3((b->S * b->K + SC_NWAVES - 1) / SC_NWAVES), block, p.lds, st, uo);
-            break;
-        case FORM_TILE_GSCRATCH: rc = launch_lds(k_source_update<1, false, UpdateArgsOpt>, grid, block, p.lds, st, uo); break;
-        case FORM_TILE: rc = launch_lds(k_source_update<0, false, UpdateArgsOpt>, grid, block, p.lds, st, uo); break;
-        default: rc = launch_lds(k_source_update<2, false, UpdateArgsOpt>, grid, block, p.lds, st, uo);
-        }
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-        return SCARLET_OK;
-    }
-    switch (p.form) {
-    case FORM_WAVE:             // one wave per component, four components per workgroup (wave_ops.h)
-        rc = launch_lds(k_source_update_w, dim3((b->S * b->K + SC_NWAVES - 1) / SC_NWAVES), block, p.lds, st, u);
-        break;
-    case FORM_TILE_GSCRATCH: rc = launch_lds(k_source_update<1>, grid, block, p.lds, st, u); break;
-    case FORM_TILE: rc = launch_lds(k_source_update<0>, grid, block, p.lds, st, u); break;
-    default:                    // operators in place on the plane in HBM / L2 (94 KB at 1024 x 1024)
-        rc = launch_lds(k_source_update<2>, grid, block, p.lds, st, u);
-    }
+        // (ragged: on each scene's own frame -- a catalogue batch)
+        rc = ragged ? run_form(k_source_update_w_ragged_opt, k_source_update<1, true, UpdateArgsOpt>,
+                               k_source_update<0, true, UpdateArgsOpt>, k_source_update<2, true, UpdateArgsOpt>, uo)
+                    : run_form(k_source_update_w_opt, k_source_update<1, false, UpdateArgsOpt>,
+                               k_source_update<0, false, UpdateArgsOpt>, k_source_update<2, false, UpdateArgsOpt>, uo);
+    } else                      // the stock pipeline; ragged: the same forms on each scene's own frame (engine.h RAGGED)
+        rc = ragged ? run_form(k_source_update_w_ragged, k_source_update<1, true>, k_source_update<0, true>, k_source_update<2, true>, u)
+                    : run_form(k_source_update_w, k_source_update<1>, k_source_update<0>, k_source_update<2>, u);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return SCARLET_OK;
@@ -2157,7 +2144,7 @@ static int update_call(scarlet_batch *b, const scarlet_constraints *c, const sca
     // (BAD_COUNT scenes have no present component, scene_ncomp), and so does one whose options are refused here
     const bool any = cons_any(c);
     const int skip = ((any || upd) && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
-    if (!rc) rc = check_options(b, upd, in_iteration ? 1 : 0, skip, stream);
+    if (!rc) rc = check_options(b, upd, in_iteration ? 1 : 0, skip, stream, frame_hw ? SCARLET_STATUS_BAD_FRAME : 0);
     if (rc) return rc;
     return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, stream,
                          {p ? p->L_comp : nullptr, any ? c : nullptr, (upd && !in_iteration) ? skip | SCARLET_STATUS_BAD_OPTION : skip,
@@ -2183,7 +2170,8 @@ extern "C" int scarlet_source_update_constrained(scarlet_batch *b, const scarlet
 // One observation: the fused launch where it applies (never with a prior), two half-batches on two streams where the
 // layout splits the batch (see split_views; never with a prior), the general step otherwise.
 // frame_hw: the scenes' own frames (scarlet_fit_frames; never with a prior), or NULL
-// upd: update options (scarlet_fit_options; never with a prior or frame_hw): the general step on one pipeline, or NULL
+// upd: update options (scarlet_fit_options, scarlet_fit_frames_options; never with a prior): the general step on one
+// pipeline -- no one-launch iteration, no box stage -- or NULL
 static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const scarlet_prior *p, int max_iter, double e_rel,
                     int approximate_L, int check_every, void *stream, const int32_t *frame_hw = nullptr,
                     const scarlet_update_options *upd = nullptr)
@@ -2191,12 +2179,13 @@ static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const sca
     int rc;
     if (!cons_any(cons)) cons = nullptr;
     if (!opts_any(upd)) upd = nullptr;
-    if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream)) || (rc = check_options(b, upd, 1, 0, stream)))
+    if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream)) ||
+        (rc = check_options(b, upd, 1, 0, stream, frame_hw ? SCARLET_STATUS_BAD_FRAME : 0)))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     const WsLayout l = ws_layout(b, WS_FIX);
     const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw, upd};
-    if (upd)     // gradients, step, the constraint kernels' options instances, convergence test
+    if (upd)     // gradients, step, the constraint kernels' options instances (on the scenes' own frames with frame_hw), convergence test
         return fit_loop(b, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
             const int r = backward_impl(b, l, approximate_L, 0, stream);
             return r ? r : iteration_tail(b, l, e_rel, stream, uo);
@@ -2325,6 +2314,31 @@ extern "C" int scarlet_source_update_frames_grouped(scarlet_batch *b, const scar
     int rc = check_call(b, c != nullptr, c, false, nullptr);
     if (!rc) rc = check_frames_grouped_call(f);
     return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw);
+}
+// ... and with update options (a catalogue batch whose sources carry the stock update functions' options): the RAGGED x
+// OPTIONS instances of the constraint kernels, `group` allowed.  Without frame_hw and group they are scarlet_fit_options /
+// scarlet_source_update_options, with every member of `o` NULL the two _grouped calls above.  The device checks run in
+// the order counts, frames, options (fit_call, update_call).
+static int check_frames_options_call(const scarlet_frames *f, const scarlet_update_options *o)
+{
+    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
+    if (!o) return set_err(SCARLET_E_ARG, "options is NULL (pass a scarlet_update_options with NULL members for the defaults)");
+    return SCARLET_OK;
+}
+extern "C" int scarlet_fit_frames_options(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
+                                          const scarlet_update_options *o, int max_iter, double e_rel, int approximate_L,
+                                          int check_every, void *stream)
+{
+    int rc = check_frames_options_call(f, o);
+    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
+    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, f->frame_hw, o);
+}
+extern "C" int scarlet_source_update_frames_options(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
+                                                    const scarlet_update_options *o, int in_iteration, void *stream)
+{
+    int rc = check_frames_options_call(f, o);
+    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr);
+    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw, o);
 }
 extern "C" int scarlet_check_frames(scarlet_batch *b, const scarlet_frames *f, void *stream)
 {
