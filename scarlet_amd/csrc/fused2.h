@@ -217,6 +217,14 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
 #else
 #define QSTAMP(i) do { } while (0)
 #endif
+    // (diagnostic build -DSC_STAMP_SYM: slots 11 / 14 / 15 / 7 hold wave 0's times in front of its column sums, behind
+    // pair_ks_z, behind GEMM 1 and behind GEMM 2 -- the symmetry phase between stamps 8 / 12 / 13 / 9 split into work and
+    // waits -- instead of the clock and the launch-level words; tools/stamps.py, STAMP_SYM=1)
+#ifdef SC_STAMP_SYM
+#define YSTAMP(i) STAMP(i)
+#else
+#define YSTAMP(i) do { } while (0)
+#endif
     // absent components: the pair skips the constraints.  The per-scene word is read here, in front of every store of the
     // iteration, so that it is a scalar load beside the launch's other per-scene words; a re-entered iteration takes it
     // from place_s (below)
@@ -224,10 +232,13 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     if (X && a.ncomp && !(P && reentered)) n_present = scene_ncomp(a.ncomp, s, K);
     STAMP(0);
     // (diagnostics: the constant 100 MHz counter beside the shader clock of stamps 0 / 6 gives the clock the chip holds)
+#ifndef SC_STAMP_SYM
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 7] = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
 #ifdef SC_STAMP_PERIOD      // (diagnostic build: the start of the last two iterations, by parity, in slots 8 / 9 of the second half)
     if (P && a.stamps && tid == 0) a.stamps[(size_t)a.S * 16 + (size_t)s * 2 + (it_new & 1)] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
+#ifndef SC_STAMP_SYM
     if (P && a.stamps && tid == 0 && !reentered) {     // launch-level diagnostics: when and where this workgroup started
 #ifndef SC_STAMP_PROLOGUE
         a.stamps[(size_t)s * 16 + 14] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -235,6 +246,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         a.stamps[(size_t)s * 16 + 15] = (long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11))        // HW_ID
                                         | ((long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) << 32);   // XCC_ID
     }
+#endif
     // What the iteration's first phase leaves to the rest: the pair's component, its centre and shift, its half of the
     // cached Hankel vectors, the first group's images and (in LDS) the tiles, the SEDs and the Gram partials.
     const int slot = wid >> 1;
@@ -702,6 +714,7 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
                     }
                 }
                 rank1 = sy != 0.f;
+                YSTAMP(11);
                 if (rank1) pair_ks_colsums(t, sw, kg, zv);
             }
         }
@@ -714,13 +727,16 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
     f32x4 T[4][2];
     if (mine && mode == 1) {
         if (rank1) pair_ks_z(kg, vec + 256, zv);
+        YSTAMP(14);
         pair_ks_gemm1<true>(t, sw, kg, vec, half, T);
+        YSTAMP(15);
     }
     if (mine) pair_sync(3, std::false_type{});                         // B2: every read of X is done
 #if !defined(SC_STAMP_WORKER) && !defined(SC_STAMP_PROLOGUE)
     STAMP(13);
 #endif
     if (mine && mode == 1) pair_ks_gemm2<true>(t, sw, kg, vec, zv, half, T, sy, rank1);
+    YSTAMP(7);
     if (mine && mode == 2 && lead) wave_flip_symmetry<float>(t, sw, false, 1.0f);
     if (mine) pair_sync(4, std::false_type{});                         // B3
     STAMP(9);
@@ -1030,7 +1046,9 @@ __device__ __forceinline__ int iterate2_body(const FusedArgs &a, const int s, co
         }
     }
     STAMP(6);
+#ifndef SC_STAMP_SYM
     if (a.stamps && tid == 0) a.stamps[(size_t)s * 16 + 11] = (long long)__builtin_amdgcn_s_memrealtime();
+#endif
 #undef STAMP
 #undef QSTAMP
 #undef WSTAMP

@@ -156,6 +156,12 @@ __device__ __forceinline__ unsigned long long positive_lanes(float v) { return _
 __device__ __forceinline__ unsigned long long positive_lanes(double v) { return __builtin_amdgcn_fcmp(v, 0.0, 2 /* FCMP_OGT */); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// a + b that no multiplication in front of it is contracted into
+__device__ __forceinline__ float add_unfused(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
 __device__ __forceinline__ double fast_rcp(double x) { return 1.0 / x; }
 
 // Per-lane walker: everything that does not change along a walk (one per wedge and level
@@ -615,7 +621,7 @@ __device__ inline void pair_ks_z(const KsGeom &g, const float *cv, float *zv)
 // PEEL: the operand masking below is compiled only into the fetch of the last k-group (a uniform branch picks
 // the variant); the second code path costs registers in callers that inline both halves of the pair
 // decomposition (wave_kspace_symmetry), so only the pair kernel asks for it.
-template <int NTR, int NI, bool PEEL>
+template <int NTR, int NI, bool PEEL, bool TRIM>
 __device__ __forceinline__ void pair_ks_gemm1_impl(const Tile &t, const SymWindow &s, const KsGeom &g, const float *vec,
                                                    int half, f32x4 (&T)[4][2])
 {
@@ -657,23 +663,35 @@ __device__ __forceinline__ void pair_ks_gemm1_impl(const Tile &t, const SymWindo
         if (k0 + 16 > g.w) return fetch_as(k0, std::integral_constant<int, 1>{});
         return fetch_as(k0, std::integral_constant<int, 0>{});
     };
-    auto multiply = [&](const Ops &o) {
+    auto step = [&](const Ops &o, int j) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int tr = 0; tr < NTR; ++tr)
 #pragma unroll
-            for (int tr = 0; tr < NTR; ++tr)
-#pragma unroll
-                for (int i = 0; i < NI; ++i)
-                    T[tr][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[tr][j], o.b[i][j], T[tr][i], 0, 0, 0);
+            for (int i = 0; i < NI; ++i)
+                T[tr][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[tr][j], o.b[i][j], T[tr][i], 0, 0, 0);
+    };
+    // TRIM: step j of group k0 covers the columns k0 + 4 j .. k0 + 4 j + 3; in the last group the steps from
+    // ceil((w - k0) / 4) on multiply nothing but the zeros of the masked fetch and are not issued (w is wave-uniform:
+    // scalar branches between straight-line chains).  A skipped step would have added +-0 to every accumulator.
+    auto multiply = [&](const Ops &o, int k0) {
+        const int live = TRIM ? (g.w - k0 + 3) >> 2 : 4;
+        step(o, 0);
+        if (live > 1) {
+            step(o, 1);
+            if (live > 2) {
+                step(o, 2);
+                if (live > 3) step(o, 3);
+            }
+        }
     };
     // two groups per trip, ping-pong operand sets (no register copies)
     Ops o0 = fetch(0);
     for (int k0 = 0; k0 < g.wp; k0 += 32) {
         const Ops o1 = fetch(min(k0 + 16, g.wp - 16));
-        multiply(o0);
+        multiply(o0, k0);
         if (k0 + 16 < g.wp) {
             o0 = fetch(min(k0 + 32, g.wp - 16));
-            multiply(o1);
+            multiply(o1, k0 + 16);
         }
     }
     // rows of T beyond the window (last row tile only) came from the clamped row pointer: zero them
@@ -686,7 +704,7 @@ __device__ __forceinline__ void pair_ks_gemm1_impl(const Tile &t, const SymWindo
     }
 }
 
-template <bool PEEL = false>
+template <bool PEEL = false, bool TRIM = PEEL>
 __device__ inline void pair_ks_gemm1(const Tile &t, const SymWindow &s, const KsGeom &g, const float *vec,
                                      int half, f32x4 (&T)[4][2])
 {
@@ -696,16 +714,15 @@ __device__ inline void pair_ks_gemm1(const Tile &t, const SymWindow &s, const Ks
         for (int i = 0; i < 2; ++i) T[tr][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int ni = half < g.ntc ? (half + 2 < g.ntc ? 2 : 1) : 0;
     if (ni == 0) return;
-#define SC_G1(NTR_) do { if (ni == 2) pair_ks_gemm1_impl<NTR_, 2, PEEL>(t, s, g, vec, half, T);    \
-                         else pair_ks_gemm1_impl<NTR_, 1, PEEL>(t, s, g, vec, half, T); } while (0)
+#define SC_G1(NTR_) do { if (ni == 2) pair_ks_gemm1_impl<NTR_, 2, PEEL, TRIM>(t, s, g, vec, half, T);    \
+                         else pair_ks_gemm1_impl<NTR_, 1, PEEL, TRIM>(t, s, g, vec, half, T); } while (0)
     switch (g.ntr) { case 1: SC_G1(1); break; case 2: SC_G1(2); break; case 3: SC_G1(3); break; default: SC_G1(4); }
 #undef SC_G1
 }
 
-// GEMM 2 + epilogue in place for this wave's column tiles
-// PAIR: address arithmetic of the epilogue for the pair kernel (one address per column tile, the last row
-// tile alone checks the bottom edge); the other callers keep the form that costs them fewer registers
-template <int NTR, int NI, bool PAIR>
+// GEMM 2 + epilogue in place for this wave's column tiles.  This form is the reference: pair_ks_gemm2_trim (below,
+// the pair kernel's) must give its results bit for bit
+template <int NTR, int NI>
 __device__ __forceinline__ void pair_ks_gemm2_impl(const Tile &t, const SymWindow &s, const KsGeom &g, const float *vec,
                                                    const float *zv, int half, const f32x4 (&T)[4][2], float sy, bool rank1)
 {
@@ -736,20 +753,13 @@ __device__ __forceinline__ void pair_ks_gemm2_impl(const Tile &t, const SymWindo
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int jcol = ((half + 2 * i) << 4) + lr;
-            float *p0 = &m[(s.y0 + row0) * LW + s.x0 + jcol];     // one address per column tile, rows at + r LW
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = row0 + r;
                 // lanes outside the window combine a dummy slot (the B vector is dead after GEMM 1):
                 // no branches between the MFMA chains
-                if (PAIR) {
-                    // only the last row tile can leave the window at the bottom (h > 16 (NTR - 1))
-                    ok[i][r] = (tr < NTR - 1 || row < g.h) && jcol < g.w;
-                    pp[i][r] = ok[i][r] ? p0 + r * LW : dummy;
-                } else {
-                    ok[i][r] = row < g.h && jcol < g.w;
-                    pp[i][r] = ok[i][r] ? &m[(s.y0 + row) * LW + s.x0 + jcol] : dummy;
-                }
+                ok[i][r] = row < g.h && jcol < g.w;
+                pp[i][r] = ok[i][r] ? &m[(s.y0 + row) * LW + s.x0 + jcol] : dummy;
                 xin[i][r] = *pp[i][r];
             }
         }
@@ -774,14 +784,99 @@ __device__ __forceinline__ void pair_ks_gemm2_impl(const Tile &t, const SymWindo
     }
 }
 
-template <bool PAIR = false>
+// The pair kernel's form: the k-steps that sum nothing but rows of T beyond the window are not issued; one address per
+// column tile in the epilogue, and only the last row tile checks the bottom edge.  Bit for bit the results of the form
+// above, whose epilogue compiles, in one block per (NTR, NI), to a fused multiply-add for the rank-1 term and a plain
+// addition of the two halves: written out here, because with the chains in blocks of their own the compiler would fuse
+// or not fuse by block and change the last bit (tests/test_gpu_symmetry_trim.py)
+template <int NTR, int NI>
+__device__ __forceinline__ void pair_ks_gemm2_trim(const Tile &t, const SymWindow &s, const KsGeom &g, const float *vec,
+                                                   const float *zv, int half, const f32x4 (&T)[4][2], float sy, bool rank1)
+{
+    float *m = t.m;
+    const float *av = vec;
+    const int LW = t.LW, lane = lane_id(), lr = lane & 15, lq = lane >> 4;
+    // rank-1 term: row parity of (row - ry) depends on r only (16 tr and 4 lq are even)
+    float syr[4], zc[NI];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) syr[r] = rank1 ? (((r - g.ry) & 1) ? -sy : sy) : 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) zc[i] = rank1 ? zv[((half + 2 * i) << 4) + lr] : 0.f;
+    // Hankel operand: A[i][k] = av[i + k] depends on tr + tk only -- the 2 NTR - 1 distinct 16 x 4
+    // slices are read once, up front
+    float *dummy = const_cast<float *>(vec) + 128 + lane;
+    float ah[2 * NTR - 1][4];
+#pragma unroll
+    for (int d = 0; d < 2 * NTR - 1; ++d)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ah[d][r] = av[(d << 4) + lr + 4 * lq + r];
+    // k-step (tk = NTR - 1, r) sums the rows 16 (NTR - 1) + {r, 4 + r, 8 + r, 12 + r} of T, all of them beyond the
+    // window (zeroed by GEMM 1) from r = h - 16 (NTR - 1) on: those steps are not issued (h is wave-uniform: scalar
+    // branches between straight-line chains).  A skipped step would have added +-0 to every accumulator.
+    const int live = g.h - ((NTR - 1) << 4);
+#pragma unroll
+    for (int tr = 0; tr < NTR; ++tr) {
+        // the pixels this lane will combine with: requested before the MFMA chain, used after it
+        float xin[NI][4];
+        float *pp[NI][4];
+        bool ok[NI][4];
+        const int row0 = (tr << 4) + lq * 4;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int jcol = ((half + 2 * i) << 4) + lr;
+            float *p0 = &m[(s.y0 + row0) * LW + s.x0 + jcol];     // one address per column tile, rows at + r LW
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + r;
+                // lanes outside the window combine a dummy slot (the B vector is dead after GEMM 1);
+                // only the last row tile can leave the window at the bottom (h > 16 (NTR - 1))
+                ok[i][r] = (tr < NTR - 1 || row < g.h) && jcol < g.w;
+                pp[i][r] = ok[i][r] ? p0 + r * LW : dummy;
+                xin[i][r] = *pp[i][r];
+            }
+        }
+        f32x4 acc[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        auto step = [&](int tk, int r) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah[tr + tk][r], T[tk][i][r], acc[i], 0, 0, 0);
+        };
+#pragma unroll
+        for (int tk = 0; tk < NTR - 1; ++tk)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) step(tk, r);
+        step(NTR - 1, 0);
+        if (live > 1) {
+            step(NTR - 1, 1);
+            if (live > 2) {
+                step(NTR - 1, 2);
+                if (live > 3) step(NTR - 1, 3);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float x = xin[i][r];
+                const float y2 = fma_t(syr[r], zc[i], acc[i][r]);
+                const float hx = 0.5f * x, hy = 0.5f * y2;
+                *pp[i][r] = (x <= 0.f) ? 0.f : add_unfused(hx, hy);
+            }
+    }
+}
+
+template <bool TRIM = false>
 __device__ inline void pair_ks_gemm2(const Tile &t, const SymWindow &s, const KsGeom &g, const float *vec,
                                      const float *zv, int half, const f32x4 (&T)[4][2], float sy, bool rank1)
 {
     const int ni = half < g.ntc ? (half + 2 < g.ntc ? 2 : 1) : 0;
     if (ni == 0) return;
-#define SC_G2(NTR_) do { if (ni == 2) pair_ks_gemm2_impl<NTR_, 2, PAIR>(t, s, g, vec, zv, half, T, sy, rank1);   \
-                         else pair_ks_gemm2_impl<NTR_, 1, PAIR>(t, s, g, vec, zv, half, T, sy, rank1); } while (0)
+#define SC_G2(NTR_) do { if (TRIM) { if (ni == 2) pair_ks_gemm2_trim<NTR_, 2>(t, s, g, vec, zv, half, T, sy, rank1);         \
+                                     else pair_ks_gemm2_trim<NTR_, 1>(t, s, g, vec, zv, half, T, sy, rank1); }              \
+                         else if (ni == 2) pair_ks_gemm2_impl<NTR_, 2>(t, s, g, vec, zv, half, T, sy, rank1);         \
+                         else pair_ks_gemm2_impl<NTR_, 1>(t, s, g, vec, zv, half, T, sy, rank1); } while (0)
     switch (g.ntr) { case 1: SC_G2(1); break; case 2: SC_G2(2); break; case 3: SC_G2(3); break; default: SC_G2(4); }
 #undef SC_G2
 }

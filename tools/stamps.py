@@ -19,9 +19,11 @@ b.workspace[:S * (24 if PAIRS else 16) * 8].zero_()
 b.fit(int(os.environ.get("STAMP_ITERS", "1")), e_rel=0, check_every=0)
 torch.cuda.synchronize()
 st = b.workspace[:S * 16 * 8].view(torch.int64).view(S, 16).cpu().numpy()
+pw_raw = None
 if PAIRS:
     # per component: the lead's arrival at B5, and {arrival - B4, B4 - B3, last sweep level, NTR, NTC, slot} (fused2.h)
     pw = b.workspace[S * 16 * 8:S * 24 * 8].view(torch.int64).view(S, 4, 2).cpu().numpy()
+    pw_raw = pw[:, :, 1]                                        # (every scene's words, in the stamps' order: STAMP_SYM)
     if int(os.environ.get("STAMP_ITERS", "1")) > 1 and S > 2048: pw = pw[:S - 1024]
     pw = pw[(pw[:, :, 0] > 0).all(axis=1)]                      # scenes with four present components
     arr, w = pw[:, :, 0].astype(np.float64), pw[:, :, 1]
@@ -61,6 +63,20 @@ if os.environ.get("STAMP_PROLOGUE"):
              ("stamp 2 -> first use of an image", st[:, 14] - st[:, 2]), ("first use of an image -> end of the gradient pass (stamp 3)", st[:, 3] - st[:, 14])]
     for name, v in parts:
         print("prologue: %-62s mean %6d  p50 %6d  p90 %6d" % (name, v.mean(), np.median(v), np.percentile(v, 90)))
+elif os.environ.get("STAMP_SYM"):
+    # library built with -DSC_STAMP_SYM (and -DSC_STAMP_PAIRS for the window's tile counts): slots 11 / 14 / 15 / 7 = wave 0
+    # in front of its column sums, behind pair_ks_z, behind GEMM 1, behind GEMM 2 (fused2.h); wave 0 leads slot 0's pair
+    ks = (st[:, 11] > 0) & (st[:, 14] > 0) & (st[:, 15] > 0) & (st[:, 7] > 0)          # k-space symmetry, not flip / centred
+    sets = [("all leads", ks)]
+    if pw_raw is not None:
+        w = pw_raw[:len(st)]
+        first = ((w >> 54) & 3) == 0
+        ntr, ntc = (np.where(first, (w >> 48) & 7, 0)).max(1), (np.where(first, (w >> 51) & 7, 0)).max(1)
+        sets.append(("4 x 4 tiles", ks & (ntr == 4) & (ntc == 4)))
+    parts = [("colsums", 11, 8), ("wait B1", 8, 12), ("z", 12, 14), ("GEMM 1", 14, 15), ("wait B2", 15, 13), ("GEMM 2", 13, 7),
+             ("wait B3", 7, 9)]
+    for name, m in sets:
+        print("sym wave0, %s (n=%d): " % (name, m.sum()) + "  ".join("%s %d" % (n, (st[m, j] - st[m, i]).mean()) for n, i, j in parts))
 elif os.environ.get("STAMP_WORKER"):
     # library built with -DSC_STAMP_WORKER: slots 12 / 13 = start / end of the worker's step-size work (fused2.h), on
     # the worker wave; 9 / 10 = wave 0 after B3 / after B4 (its pair's sweep lies between them)
@@ -82,7 +98,7 @@ elif st[:, 12].any():
     if st[:, 11].any(): print("P2 wave0 own tail:", (st[:, 11] - st[:, 10]).mean().round(0))
 print("phase cycles mean:", dt.mean(axis=0).round(0), " total", (st[:, 6] - st[:, 0]).mean())
 print("phase cycles p90 :", np.percentile(dt, 90, axis=0).round(0))
-if st[:, 7].any() and st[:, 11].any():
+if st[:, 7].any() and st[:, 11].any() and not os.environ.get("STAMP_SYM"):
     cyc, ticks = (st[:, 6] - st[:, 0]).astype(float), (st[:, 11] - st[:, 7]).astype(float)
     ok = ticks > 0
     print("in-kernel clock (shader cycles per 100 MHz tick x 100 MHz): median %.0f MHz, p10 %.0f, p90 %.0f" % (
