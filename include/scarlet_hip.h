@@ -550,9 +550,9 @@ int scarlet_init_extended_frames(scarlet_batch *b, const scarlet_frames *f, cons
  *     scarlet_source_update_frames, and b->group is allowed: the shared centre (and, every fifth iteration, the shift) of
  *     each source is measured on its scene's own frame -- the patch around the previous centre is clipped to h x w, so the
  *     centroid's radius is cut at the scene's own last row and column, as the reference cuts it for the scene alone --
- *     and the update kernels take that centre as given.  With b->group == NULL they ARE those two calls; with
- *     f->frame_hw == NULL they ARE scarlet_fit_constrained / scarlet_source_update_constrained without a prior; both bit
- *     for bit.  Groups never take a one-launch iteration: such a batch runs the general path.
+ *     and the update kernels take that centre as given.  They are scarlet_fit_with / scarlet_source_update_with of the
+ *     same members (scarlet_fit_request, below), so a NULL group or frame_hw gives the bits of the call without it.
+ *     Groups never take a one-launch iteration: such a batch runs the general path.
  *   - scarlet_init_sources_frames_mixed is scarlet_init_sources on each scene's own frame, with spec->kind and b->group
  *     honoured: a point source's centre test and the clipping of the pasted model PSF are the own frame's; the layers of
  *     a multi-component source are cut from the extended start on the own frame, and their least-squares SEDs sum over
@@ -569,9 +569,8 @@ int scarlet_source_update_frames_grouped(scarlet_batch *b, const scarlet_frames 
 
 /* Ragged frames, groups and update options together: a catalogue whose sources carry the stock update functions' options.
  * The contract of the two _grouped calls above with scarlet_update_options beside the constraints:
- *   - b->group is allowed.  f == NULL or o == NULL is SCARLET_E_ARG.
- *   - With f->frame_hw == NULL and b->group == NULL they ARE scarlet_fit_options / scarlet_source_update_options; with every
- *     member of `o` NULL they ARE scarlet_fit_frames_grouped / scarlet_source_update_frames_grouped; both bit for bit.
+ *   - b->group is allowed.  f == NULL or o == NULL is SCARLET_E_ARG.  (scarlet_fit_with of the same members: a NULL
+ *     frame_hw, group or member of `o` gives the bits of the call without it.)
  *   - A point or extended source runs the options pipeline on its scene's own bounds.  A multi-component source's shared
  *     centre (and, every fifth iteration, if it is symmetric, the centroid) is measured on the flux-weighted sum of its
  *     layers before any option acts; each layer then gets the symmetry (no shift: _KSPACE is soft with strength 1), the
@@ -898,6 +897,39 @@ int scarlet_observations_products_frames_lowres(const scarlet_batch *state, cons
                                                 const scarlet_lowres_frames *const *lowres_frames, const int32_t *band0,
                                                 int n_obs, const scarlet_products *state_out, const scarlet_products *out,
                                                 void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ---- A fit in one request.  Every scarlet_fit* and scarlet_source_update* function above is a fixed-shape form of the
+ * two calls below: it fills this struct from its arguments and goes through the same check and the same body.
+ * A request is accepted iff one of those named functions accepts the same members (the table is in DESIGN.md, 5i):
+ *   n_obs = 0 (the batch's own images, at most 8 bands; lowres / lowres_frames must be NULL, SCARLET_E_ARG):
+ *     constraints, b->n_components and b->group go with at most one of prior, options, frames->frame_hw -- except that
+ *     options and frame_hw go together; a prior with frame_hw or with options is SCARLET_E_NOTIMPL;
+ *   n_obs = 1..8 (the `large` kind throughout; up to SCARLET_MAX_CHANNELS model channels):
+ *     a prior goes with constraints, lowres, more than 8 channels and b->group, not with frame_hw (E_NOTIMPL);
+ *     options go with constraints and b->n_components alone: with a prior, frame_hw, lowres, more than 8 channels or
+ *     b->group they are E_NOTIMPL;  frame_hw with b->group is E_NOTIMPL;  frame_hw with a lowres[i] needs its
+ *     lowres_frames[i], and lowres_frames[i] needs frame_hw and lowres[i] (scarlet_fit_observations_frames_lowres).
+ * `options` counts as given when the pointer is not NULL, `frames` when frame_hw is not NULL, `lowres` and
+ * `lowres_frames` when the list is not NULL. */
+typedef struct scarlet_fit_request {
+    const scarlet_constraints *constraints;              /* NULL or all-NULL members: the batch's scalars     */
+    const scarlet_prior *prior;                          /* NULL: none                                        */
+    const scarlet_update_options *options;               /* NULL: the stock pipeline                          */
+    const scarlet_frames *frames;                        /* NULL or frame_hw = NULL: uniform frames           */
+    scarlet_batch *const *obs;                           /* n_obs observation batches, and ...                */
+    const int32_t *band0;                                /* ... the first model channel of each               */
+    const scarlet_lowres *const *lowres;                 /* NULL, or n_obs pointers (NULL = on the model grid) */
+    const scarlet_lowres_frames *const *lowres_frames;   /* NULL, or n_obs pointers (NULL = no own tables)    */
+    int32_t n_obs;                                       /* 0: the batch's own images                         */
+    int32_t max_iter;
+    double e_rel;
+    int32_t approximate_L, check_every;
+} scarlet_fit_request;          /* 88 bytes */
+/* the host-side check of scarlet_fit_with alone: launches nothing, reads no device memory */
+int scarlet_fit_request_check(const scarlet_batch *b, const scarlet_fit_request *r);
+int scarlet_fit_with(scarlet_batch *b, const scarlet_fit_request *r, void *stream);
+/* reads only constraints, prior (its L_comp), options and frames of the request; everything else is ignored */
+int scarlet_source_update_with(scarlet_batch *b, const scarlet_fit_request *r, int in_iteration, void *stream);
 
 /* Single phases, exposed for tests and for Python-overridden update() methods:        */
 /* _backward + _set_lipschitz + gradient step (blend.py:81-96): reads buffer cur, writes

@@ -124,6 +124,16 @@ class ScarletLowresFrames(Structure):
     _fields_ = [("dims", c_void_p), ("uy", c_void_p), ("ux", c_void_p)]
 
 
+class ScarletFitRequest(Structure):
+    """struct scarlet_fit_request of include/scarlet_hip.h (field order must match)."""
+    _fields_ = [("constraints", POINTER(ScarletConstraints)), ("prior", POINTER(ScarletPrior)),
+                ("options", POINTER(ScarletUpdateOptions)), ("frames", POINTER(ScarletFrames)),
+                ("obs", POINTER(POINTER(ScarletBatch))), ("band0", c_void_p),
+                ("lowres", POINTER(POINTER(ScarletLowres))), ("lowres_frames", POINTER(POINTER(ScarletLowresFrames))),
+                ("n_obs", c_int32), ("max_iter", c_int32), ("e_rel", c_double), ("approximate_L", c_int32),
+                ("check_every", c_int32)]
+
+
 class ScarletProducts(Structure):
     """struct scarlet_products of include/scarlet_hip.h (field order must match); `components` is a HOST pointer."""
     _fields_ = [("model", c_void_p), ("rendered", c_void_p), ("residual", c_void_p), ("loss", c_void_p), ("flux", c_void_p),
@@ -254,6 +264,9 @@ _SIGNATURES = {
                                                             POINTER(POINTER(ScarletBatch)), POINTER(POINTER(ScarletLowres)),
                                                             POINTER(POINTER(ScarletLowresFrames)), _P, c_int,
                                                             POINTER(ScarletProducts), POINTER(ScarletProducts), _P, c_int64, _P]),
+    "scarlet_fit_request_check": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFitRequest)]),
+    "scarlet_fit_with": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFitRequest), _P]),
+    "scarlet_source_update_with": (c_int, [POINTER(ScarletBatch), POINTER(ScarletFitRequest), c_int, _P]),
     "scarlet_convergence_sums": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_batch_prepare_psf": (c_int, [POINTER(ScarletBatch), _P]),
     "scarlet_convolve_same": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P]),

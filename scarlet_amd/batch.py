@@ -859,7 +859,7 @@ class BlendBatch(object):
         self.fix_morph = None
         self._init_checked = False    # init_sources ran: scenes may carry STATUS_BAD_INIT
         self._catalog = None          # from_catalog: the tables of catalog_arrays, for init_catalog and source()
-        self._catalog_options = False  # from_catalog with update options: the _frames_options entry points
+        self._catalog_options = False  # from_catalog with update options (they go with frames and group there)
         self.group = None
         if group is not None:
             g = np.asarray(group, dtype=np.int32).reshape(S, K)
@@ -918,42 +918,39 @@ class BlendBatch(object):
         """True when a constraint setting was given per component."""
         return bool(self.constraints)
 
-    # Every call into the library's loops goes through these two and _fit_observations.  The *_constrained entry points
-    # with a NULL member read that setting from the batch's scalars, and with prior = NULL step without one.
+    # Every call into the library's loops goes through one request (scarlet_fit_request): whatever the batch carries --
+    # its constraints (a NULL member reads that setting from the batch's scalars), update options, frames, the
+    # observations with their low-resolution structs and tables -- and the prior's struct `ps`.  The library refuses what
+    # does not go together (DESIGN.md 5i) and copies the pointer arrays into its argument structs before it launches
+    # anything; `keep` holds them until the call has returned.
+    def _request(self, ps, max_iter=0, e_rel=0.0, approximate_L=False, check_every=0):
+        r = _lib.ScarletFitRequest()
+        r.constraints, r.frames = ctypes.pointer(self._cons), ctypes.pointer(self._frames)
+        if self._upd is not None:
+            r.options = ctypes.pointer(self._upd)
+        if ps is not None:
+            r.prior = ctypes.pointer(ps)
+        r.max_iter, r.e_rel, r.approximate_L, r.check_every = int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every)
+        keep = None
+        if self._observations is not None:
+            r.n_obs = n = len(self._observations)
+            r.obs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
+            keep = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
+            r.band0 = keep.ctypes.data
+            if any(x is not None for x in self._lowres):
+                none = ctypes.POINTER(_lib.ScarletLowres)()
+                r.lowres = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
+                if self.frame_shapes is not None:           # (each low-resolution observation with its own tables)
+                    r.lowres_frames = self._lowres_frames()
+        return r, keep
+
     def _lib_fit(self, ps, max_iter, e_rel, approximate_L, check_every):
-        if self._catalog_options:                   # (never with a prior: _refuse_update_prior)
-            return _lib.check(_lib.lib.scarlet_fit_frames_options(
-                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ctypes.byref(self._upd),
-                int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
-        if self._upd is not None:                   # (never with a prior or ragged frames: refused before)
-            return _lib.check(_lib.lib.scarlet_fit_options(
-                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(max_iter), float(e_rel),
-                int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
-        if self.frame_shapes is not None:           # (never with a prior: _refuse_frames_prior)
-            fit_frames = _lib.lib.scarlet_fit_frames_grouped if self._catalog is not None else _lib.lib.scarlet_fit_frames
-            return _lib.check(fit_frames(
-                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(max_iter), float(e_rel),
-                int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
-        return _lib.check(_lib.lib.scarlet_fit_constrained(
-            ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(max_iter),
-            float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr()))
+        r, keep = self._request(ps, max_iter, e_rel, approximate_L, check_every)
+        return _lib.check(_lib.lib.scarlet_fit_with(ctypes.byref(self._c), ctypes.byref(r), _lib.stream_ptr()))
 
     def _lib_update(self, ps, in_iteration):
-        if self._catalog_options:
-            return _lib.check(_lib.lib.scarlet_source_update_frames_options(
-                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ctypes.byref(self._upd),
-                int(in_iteration), _lib.stream_ptr()))
-        if self._upd is not None:
-            return _lib.check(_lib.lib.scarlet_source_update_options(
-                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), int(in_iteration), _lib.stream_ptr()))
-        if self.frame_shapes is not None:
-            update_frames = (_lib.lib.scarlet_source_update_frames_grouped if self._catalog is not None
-                             else _lib.lib.scarlet_source_update_frames)
-            return _lib.check(update_frames(
-                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), int(in_iteration), _lib.stream_ptr()))
-        return _lib.check(_lib.lib.scarlet_source_update_constrained(
-            ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), int(in_iteration),
-            _lib.stream_ptr()))
+        r, keep = self._request(ps)
+        return _lib.check(_lib.lib.scarlet_source_update_with(ctypes.byref(self._c), ctypes.byref(r), int(in_iteration), _lib.stream_ptr()))
 
     def _alloc_workspace(self):
         """The workspace for the batch as its struct describes it now (it grows with a difference kernel); the library
@@ -1507,8 +1504,7 @@ class BlendBatch(object):
     def fit(self, max_iter=200, e_rel=1e-2, approximate_L=False, check_every=10, prior=None):
         """Blend.fit for every scene (reference blend.py:65-102).  Scenes that reach e_rel
         stop iterating individually.  Returns the number of iterations launched.  A batch made by
-        `from_observations` fits all its observations jointly (scarlet_fit_observations_constrained, with a prior
-        scarlet_fit_observations_prior; every other batch runs scarlet_fit_constrained, with or without a prior).
+        `from_observations` fits all its observations jointly.  Every batch goes through scarlet_fit_with.
 
         prior : None, or what scarlet_amd.prior describes -- a QuadraticPrior and / or constant given tensors (one
             call into the library with the prior's struct), a callable evaluated once per iteration on the
@@ -1521,8 +1517,6 @@ class BlendBatch(object):
         self.active.fill_(1)          # a new fit() call iterates again, like the reference
         if self._init_checked:        # ... except the scenes whose init_sources input was bad
             self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
-        if self._observations is not None and prior is None:
-            return self._fit_observations(max_iter, e_rel, approximate_L, check_every)
         if prior is not None:
             return self._fit_prior(prior, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every))
         return self._lib_fit(None, max_iter, e_rel, approximate_L, check_every)
@@ -1530,27 +1524,26 @@ class BlendBatch(object):
     def step(self, e_rel=1e-2, approximate_L=False, prior=None):
         """One iteration in three separately callable phases (used by tests and by the
         Python-level update() override path).  A batch made by `from_observations` runs one iteration
-        of scarlet_fit_observations_constrained (scarlet_fit_observations_prior with one).  `prior`: as in `fit`."""
+        of its joint fit.  `prior`: as in `fit`."""
         self._refuse_frames_prior(prior)
         self._refuse_update_prior(prior)
         self._ensure_mse_capacity(1)
         if self._upd is not None and self._observations is None:
-            # one iteration of scarlet_fit_options -- for a catalogue batch of scarlet_fit_frames_options: the device checks
-            # (counts, frames, options) come before the gradient step
+            # one iteration of the library's loop: the device checks (counts, frames, options) come before the gradient step
             self._lib_fit(None, 1, e_rel, approximate_L, 0)
             return
         if self._observations is not None:
             if self._init_checked:
                 self.active.masked_fill_((self.status & _lib.STATUS_BAD_INIT) != 0, 0)
             if prior is None:
-                self._fit_observations(1, e_rel, approximate_L, 0)
+                self._lib_fit(None, 1, e_rel, approximate_L, 0)
                 return
         if prior is not None:
             quad, given, fns = _prior.split_priors(prior)
             self._prior_iteration(self._prior_struct(quad), given, fns, float(e_rel), int(bool(approximate_L)))
             return
         if self.frame_shapes is not None and self.group is not None:
-            # (from_catalog) one iteration of scarlet_fit_frames_grouped: its device check of the frames comes first
+            # (from_catalog) one iteration of the library's loop: its device check of the frames comes first
             self._lib_fit(None, 1, e_rel, approximate_L, 0)
             return
         s = _lib.stream_ptr()
@@ -1612,7 +1605,7 @@ class BlendBatch(object):
             dicts += [fn(sed, morph) for fn in fns]
         self._set_given(ps, dicts)
         if self._observations is not None:                             # one iteration of the joint fit, no host look
-            self._fit_observations(1, e_rel, approximate_L, 0, ps)
+            self._lib_fit(ps, 1, e_rel, approximate_L, 0)
             return
         s = _lib.stream_ptr()
         _lib.check(_lib.lib.scarlet_backward_step_prior(ctypes.byref(self._c), ctypes.byref(ps), approximate_L, s))
@@ -1625,8 +1618,6 @@ class BlendBatch(object):
         if not fns:
             # nothing changes between iterations: the library's own loop
             self._set_given(ps, given)
-            if self._observations is not None:
-                return self._fit_observations(max_iter, e_rel, approximate_L, check_every, ps)
             return self._lib_fit(ps, max_iter, e_rel, approximate_L, check_every)
         launched = 0
         for i in range(max_iter):
@@ -1835,44 +1826,6 @@ class BlendBatch(object):
         none = ctypes.POINTER(_lib.ScarletLowresFrames)()
         return (ctypes.POINTER(_lib.ScarletLowresFrames) * len(self._lowres))(
             *[none if x is None or "frames" not in x[1] else ctypes.pointer(x[1]["frames"]) for x in self._lowres])
-
-    def _fit_observations(self, max_iter, e_rel, approximate_L, check_every, ps=None):
-        """The joint fit against `_observations` (scarlet_fit_observations_lowres_large when one of them is
-        low-resolution: the LDS-resident kernels where the model frame lets them, the streamed form beyond;
-        scarlet_fit_observations_prior, which takes both kinds, with the prior's struct `ps`;
-        scarlet_fit_observations_frames when the observations carry frame shapes, scarlet_fit_observations_frames_lowres
-        when one of those is low-resolution).  The
-        library copies the pointer arrays into its argument structs before it launches anything."""
-        n = len(self._observations)
-        ptrs = (ctypes.POINTER(_lib.ScarletBatch) * n)(*[ctypes.pointer(ob._c) for _, ob in self._observations])
-        first = np.array([o.band0 for o, _ in self._observations], dtype=np.int32)
-        band0 = first.ctypes.data_as(ctypes.c_void_p)
-        tail = (n, int(max_iter), float(e_rel), int(bool(approximate_L)), int(check_every), _lib.stream_ptr())
-        lows = None
-        if any(x is not None for x in self._lowres):
-            none = ctypes.POINTER(_lib.ScarletLowres)()
-            lows = (ctypes.POINTER(_lib.ScarletLowres) * n)(*[none if x is None else ctypes.pointer(x[0]) for x in self._lowres])
-        if self._upd is not None:                   # (same grid, C <= 8, no prior, uniform frames: refused before)
-            return _lib.check(_lib.lib.scarlet_fit_observations_options(
-                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(self._upd), ptrs, band0, *tail))
-        if self.frame_shapes is not None and lows is not None:      # (each low-resolution observation with its own tables)
-            return _lib.check(_lib.lib.scarlet_fit_observations_frames_lowres(
-                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ptrs, lows, self._lowres_frames(),
-                band0, *tail))
-        if self.frame_shapes is not None:           # (never with a prior; any channel count)
-            return _lib.check(_lib.lib.scarlet_fit_observations_frames(
-                ctypes.byref(self._c), ctypes.byref(self._frames), ctypes.byref(self._cons), ptrs, band0, *tail))
-        if self._wide:
-            return _lib.check(_lib.lib.scarlet_fit_observations_wide(
-                ctypes.byref(self._c), ctypes.byref(self._cons), None if ps is None else ctypes.byref(ps), ptrs, lows, band0, *tail))
-        if ps is not None:
-            return _lib.check(_lib.lib.scarlet_fit_observations_prior(
-                ctypes.byref(self._c), ctypes.byref(self._cons), ctypes.byref(ps), ptrs, lows, band0, *tail))
-        if lows is not None:
-            return _lib.check(_lib.lib.scarlet_fit_observations_lowres_large(
-                ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, lows, band0, *tail))
-        return _lib.check(_lib.lib.scarlet_fit_observations_constrained(
-            ctypes.byref(self._c), ctypes.byref(self._cons), ptrs, band0, *tail))
 
     def init_combined(self, bg_rms, obs_idx=0, obs_psfs=None, model_psf=None, thresh=1.0, init_monotonic=None):
         """CombinedExtendedSource for every component (reference source.py:183-240, 495-536): the SED is the

@@ -1815,8 +1815,7 @@ __global__ void k_zero_int(int *p) { *p = 0; }
 // L_comp: the constants each component stepped with (scarlet_prior::L_comp), or NULL: the scene's
 // cons: the components' own switches, or NULL: the batch's.  skip_status: status bits of the scenes a constructor call leaves alone
 // frame_hw: scarlet_frames::frame_hw of the batch (or of the view: advanced to its first scene), or NULL
-// upd: the batch's update options (never with a box stage; with frame_hw or group only through the _frames_options entry
-// points, check_options_call refuses the pair for every other one), or NULL: the stock pipeline
+// upd: the batch's update options (never with a box stage; check_request says what they go with), or NULL: the stock pipeline
 struct UpdateOpts { const double *L_comp; const scarlet_constraints *cons; int skip_status; const int32_t *frame_hw;
                     const scarlet_update_options *upd; };
 // in_iteration = 0: the constructors' call (UpdateArgs::force_it0)
@@ -2110,7 +2109,7 @@ static int launch_prior_step(const scarlet_batch *b, const scarlet_prior *p, voi
 }
 
 
-// The bodies of the entry points, each behind check_call.  `p` NULL: no prior; `c` NULL or all-NULL: the batch's scalars.
+// The bodies of the entry points, each behind its host check.  `p` NULL: no prior; `c` NULL or all-NULL: the batch's scalars.
 // raw_gradient = 1 with a prior: buffer 1-cur receives the gradients, the prior's step turns them into the stepped factors
 static int backward_call(scarlet_batch *b, const scarlet_prior *p, int approximate_L, int raw_gradient, void *stream)
 {
@@ -2134,57 +2133,96 @@ extern "C" int scarlet_backward_step_prior(scarlet_batch *b, const scarlet_prior
     return rc ? rc : backward_call(b, p, approximate_L, 1, stream);
 }
 
-static int update_call(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int in_iteration, void *stream,
-                       const int32_t *frame_hw = nullptr, const scarlet_update_options *upd = nullptr)
+// ---- one request (scarlet_fit_request) behind every entry point that fits or updates.  A named entry point fills the
+// request from its arguments and differs from the others only in its Rules; check_request (below, with the observations)
+// is the one host-side check, and DESIGN.md 5i the table of what goes together.
+enum {
+    NEED_C = 1, NEED_P = 2, NEED_F = 4, NEED_O = 8, NEED_LOWRES = 16, NEED_LRF = 32,       // members that may not be NULL
+    FRAMES_LATE = 64,        // frames = NULL is found after the batch's own checks (scarlet_fit_frames, _frames_grouped: they
+                             // check the batch first), everywhere else before them
+    GROUP_FRAMES = 128, GROUP_OPTIONS = 256,               // b->group is accepted with frame_hw / with options
+    MULTI = 512,             // fits r.obs (n_obs 1..8); without: the batch's own images
+    LARGE = 1024,            // low-resolution observations beyond LDS take the streamed form
+    NO_COUNTS = 2048,        // scarlet_fit_multi: n_components on the state or an observation is refused first
+};
+struct Rules { unsigned flags; int bmax; };                // bmax: SC_BMAX, or SC_CMAX (the state's channel count then decides)
+static const Rules RULES_ONE = {GROUP_FRAMES | GROUP_OPTIONS, SC_BMAX}, RULES_MANY = {MULTI | LARGE, SC_CMAX};   // scarlet_fit_with
+static int check_request(const scarlet_batch *b, const scarlet_fit_request &r, const Rules &u);
+static scarlet_fit_request loop_request(int max_iter, double e_rel, int approximate_L, int check_every,
+                                        scarlet_batch *const *obs = nullptr, const int32_t *band0 = nullptr, int n_obs = 0)
 {
-    if (!opts_any(upd)) upd = nullptr;
+    scarlet_fit_request r = {};
+    r.obs = obs; r.band0 = band0; r.n_obs = n_obs;
+    r.max_iter = max_iter; r.e_rel = e_rel; r.approximate_L = approximate_L; r.check_every = check_every;
+    return r;
+}
+// what the constraint pipeline reads of a request: an all-NULL struct counts as none
+static UpdateOpts update_opts(const scarlet_fit_request &r)
+{
+    return {r.prior ? r.prior->L_comp : nullptr, cons_any(r.constraints) ? r.constraints : nullptr, 0,
+            r.frames ? r.frames->frame_hw : nullptr, opts_any(r.options) ? r.options : nullptr};
+}
+
+static int update_call(scarlet_batch *b, const scarlet_fit_request &r, int in_iteration, void *stream)
+{
+    UpdateOpts uo = update_opts(r);
     int rc = check_counts(b, stream);
-    if (!rc) rc = check_frames(b, frame_hw, stream);
+    if (!rc) rc = check_frames(b, uo.frame_hw, stream);
     // the constructors' call (in_iteration = 0) ignores `active`: a scene the initialisation refused stays untouched
     // (BAD_COUNT scenes have no present component, scene_ncomp), and so does one whose options are refused here
-    const bool any = cons_any(c);
-    const int skip = ((any || upd) && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
-    if (!rc) rc = check_options(b, upd, in_iteration ? 1 : 0, skip, stream, frame_hw ? SCARLET_STATUS_BAD_FRAME : 0);
+    const int skip = ((uo.cons || uo.upd) && !in_iteration) ? SCARLET_STATUS_BAD_INIT | SCARLET_STATUS_BAD_COUNT : 0;
+    if (!rc) rc = check_options(b, uo.upd, in_iteration ? 1 : 0, skip, stream, uo.frame_hw ? SCARLET_STATUS_BAD_FRAME : 0);
     if (rc) return rc;
-    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, stream,
-                         {p ? p->L_comp : nullptr, any ? c : nullptr, (upd && !in_iteration) ? skip | SCARLET_STATUS_BAD_OPTION : skip,
-                          frame_hw, upd});
+    uo.skip_status = (uo.upd && !in_iteration) ? skip | SCARLET_STATUS_BAD_OPTION : skip;
+    return launch_update(b, ws_layout(b, WS_PEEK), in_iteration ? 1 : 0, stream, uo);
+}
+// (of the request only constraints, prior, options and frames are read)
+static int update_with(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, const scarlet_update_options *o,
+                       const scarlet_frames *f, const Rules &u, int in_iteration, void *stream)
+{
+    scarlet_fit_request r = {};
+    r.constraints = c; r.prior = p; r.options = o; r.frames = f;
+    const int rc = check_request(b, r, u);
+    return rc ? rc : update_call(b, r, in_iteration, stream);
 }
 extern "C" int scarlet_source_update(scarlet_batch *b, int in_iteration, void *stream)
 {
-    const int rc = check_call(b, false, nullptr, false, nullptr);
-    return rc ? rc : update_call(b, nullptr, nullptr, in_iteration, stream);
+    return update_with(b, nullptr, nullptr, nullptr, nullptr, {0, SC_BMAX}, in_iteration, stream);
 }
 extern "C" int scarlet_source_update_prior(scarlet_batch *b, const scarlet_prior *p, int in_iteration, void *stream)
 {
-    const int rc = check_call(b, false, nullptr, true, p);
-    return rc ? rc : update_call(b, nullptr, p, in_iteration, stream);
+    return update_with(b, nullptr, p, nullptr, nullptr, {NEED_P, SC_BMAX}, in_iteration, stream);
 }
 extern "C" int scarlet_source_update_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p,
                                                  int in_iteration, void *stream)
 {
-    const int rc = check_call(b, true, c, false, p);
-    return rc ? rc : update_call(b, c, p, in_iteration, stream);
+    return update_with(b, c, p, nullptr, nullptr, {NEED_C, SC_BMAX}, in_iteration, stream);
+}
+extern "C" int scarlet_source_update_with(scarlet_batch *b, const scarlet_fit_request *r, int in_iteration, void *stream)
+{
+    if (!r) return set_err(SCARLET_E_ARG, "null request");
+    return update_with(b, r->constraints, r->prior, r->options, r->frames, RULES_ONE, in_iteration, stream);
 }
 
 // One observation: the fused launch where it applies (never with a prior), two half-batches on two streams where the
 // layout splits the batch (see split_views; never with a prior), the general step otherwise.
-// frame_hw: the scenes' own frames (scarlet_fit_frames; never with a prior), or NULL
-// upd: update options (scarlet_fit_options, scarlet_fit_frames_options; never with a prior): the general step on one
-// pipeline -- no one-launch iteration, no box stage -- or NULL
-static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const scarlet_prior *p, int max_iter, double e_rel,
-                    int approximate_L, int check_every, void *stream, const int32_t *frame_hw = nullptr,
-                    const scarlet_update_options *upd = nullptr)
+// frame_hw: the scenes' own frames (never with a prior), or NULL
+// upd: update options (never with a prior): the general step on one pipeline -- no one-launch iteration, no box stage
+static int fit_call(scarlet_batch *b, const scarlet_fit_request &r, void *stream)
 {
     int rc;
-    if (!cons_any(cons)) cons = nullptr;
-    if (!opts_any(upd)) upd = nullptr;
+    const UpdateOpts uo = update_opts(r);
+    const scarlet_constraints *cons = uo.cons;
+    const scarlet_prior *p = r.prior;
+    const scarlet_update_options *upd = uo.upd;
+    const int32_t *frame_hw = uo.frame_hw;
+    const int max_iter = r.max_iter, approximate_L = r.approximate_L, check_every = r.check_every;
+    const double e_rel = r.e_rel;
     if ((rc = check_counts(b, stream)) || (rc = check_frames(b, frame_hw, stream)) ||
         (rc = check_options(b, upd, 1, 0, stream, frame_hw ? SCARLET_STATUS_BAD_FRAME : 0)))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     const WsLayout l = ws_layout(b, WS_FIX);
-    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw, upd};
     if (upd)     // gradients, step, the constraint kernels' options instances (on the scenes' own frames with frame_hw), convergence test
         return fit_loop(b, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
             const int r = backward_impl(b, l, approximate_L, 0, stream);
@@ -2236,67 +2274,63 @@ static int fit_call(scarlet_batch *b, const scarlet_constraints *cons, const sca
         return SCARLET_OK;
     });
 }
+// check and body of the entry points that fit the batch's own images
+static int fit_one(scarlet_batch *b, const scarlet_fit_request &r, const Rules &u, void *stream)
+{
+    const int rc = check_request(b, r, u);
+    return rc ? rc : fit_call(b, r, stream);
+}
 extern "C" int scarlet_fit(scarlet_batch *b, int max_iter, double e_rel, int approximate_L,
                            int check_every, void *stream)
 {
-    const int rc = check_call(b, false, nullptr, false, nullptr, max_iter);
-    return rc ? rc : fit_call(b, nullptr, nullptr, max_iter, e_rel, approximate_L, check_every, stream);
+    return fit_one(b, loop_request(max_iter, e_rel, approximate_L, check_every), {0, SC_BMAX}, stream);
 }
 extern "C" int scarlet_fit_prior(scarlet_batch *b, const scarlet_prior *p, int max_iter, double e_rel, int approximate_L,
                                  int check_every, void *stream)
 {
-    const int rc = check_call(b, false, nullptr, true, p, max_iter);
-    return rc ? rc : fit_call(b, nullptr, p, max_iter, e_rel, approximate_L, check_every, stream);
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every);
+    r.prior = p;
+    return fit_one(b, r, {NEED_P, SC_BMAX}, stream);
 }
 extern "C" int scarlet_fit_constrained(scarlet_batch *b, const scarlet_constraints *c, const scarlet_prior *p, int max_iter,
                                        double e_rel, int approximate_L, int check_every, void *stream)
 {
-    const int rc = check_call(b, true, c, false, p, max_iter);
-    return rc ? rc : fit_call(b, c, p, max_iter, e_rel, approximate_L, check_every, stream);
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every);
+    r.constraints = c; r.prior = p;
+    return fit_one(b, r, {NEED_C, SC_BMAX}, stream);
 }
 
-// ---- update options (scarlet_update_options): scarlet_fit_constrained / scarlet_source_update_constrained without a prior
-// and with the options; one with every member NULL IS that call
-static int check_options_call(const scarlet_batch *b, const scarlet_update_options *o)
-{
-    if (!o) return set_err(SCARLET_E_ARG, "options is NULL (pass a scarlet_update_options with NULL members for the defaults)");
-    if (b && b->group) return set_err(SCARLET_E_NOTIMPL, "update options with group: the layers of a multi-component source are tied to soft symmetry");
-    return SCARLET_OK;
-}
+// ---- update options (scarlet_update_options); one with every member NULL is the stock pipeline
 extern "C" int scarlet_fit_options(scarlet_batch *b, const scarlet_constraints *c, const scarlet_update_options *o, int max_iter,
                                    double e_rel, int approximate_L, int check_every, void *stream)
 {
-    int rc = check_options_call(b, o);
-    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
-    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, nullptr, o);
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every);
+    r.constraints = c; r.options = o;
+    return fit_one(b, r, {NEED_O, SC_BMAX}, stream);
 }
 extern "C" int scarlet_source_update_options(scarlet_batch *b, const scarlet_constraints *c, const scarlet_update_options *o,
                                              int in_iteration, void *stream)
 {
-    int rc = check_options_call(b, o);
-    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr);
-    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, nullptr, o);
+    return update_with(b, c, nullptr, o, nullptr, {NEED_O, SC_BMAX}, in_iteration, stream);
 }
 
-// ---- scenes with their own frames (scarlet_frames): scarlet_fit_constrained / scarlet_source_update_constrained without
-// a prior and with frame_hw; the device check of the entries, alone, for callers that step phase by phase
+// ---- scenes with their own frames (scarlet_frames); the device check of the entries, alone, for callers that step
+// phase by phase.  With group (_grouped: the layers of multi-component sources) k_group_centers<RAGGED> measures each
+// source's shared centre on its scene's own frame in front of the RAGGED update kernels; with update options (_options:
+// a catalogue batch whose sources carry the stock update functions' options) the RAGGED x OPTIONS instances of the
+// constraint kernels run.  The device checks run in the order counts, frames, options (fit_call, update_call).
 extern "C" int scarlet_fit_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c, int max_iter,
                                   double e_rel, int approximate_L, int check_every, void *stream)
 {
-    int rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
-    if (!rc) rc = check_frames_call(b, f);
-    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, f->frame_hw);
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every);
+    r.frames = f; r.constraints = c;
+    return fit_one(b, r, {NEED_F | FRAMES_LATE, SC_BMAX}, stream);
 }
 extern "C" int scarlet_source_update_frames(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
                                             int in_iteration, void *stream)
 {
-    int rc = check_call(b, c != nullptr, c, false, nullptr);
-    if (!rc) rc = check_frames_call(b, f);
-    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw);
+    return update_with(b, c, nullptr, nullptr, f, {NEED_F | FRAMES_LATE, SC_BMAX}, in_iteration, stream);
 }
-// ... and with group (the layers of multi-component sources): k_group_centers<RAGGED> measures each source's shared
-// centre on its scene's own frame in front of the RAGGED update kernels.  Without group they are the two calls above,
-// without frame_hw scarlet_fit_constrained / scarlet_source_update_constrained.
 static int check_frames_grouped_call(const scarlet_frames *f)
 {
     return f ? SCARLET_OK : set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
@@ -2304,41 +2338,27 @@ static int check_frames_grouped_call(const scarlet_frames *f)
 extern "C" int scarlet_fit_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c, int max_iter,
                                           double e_rel, int approximate_L, int check_every, void *stream)
 {
-    int rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
-    if (!rc) rc = check_frames_grouped_call(f);
-    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, f->frame_hw);
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every);
+    r.frames = f; r.constraints = c;
+    return fit_one(b, r, {NEED_F | FRAMES_LATE | GROUP_FRAMES, SC_BMAX}, stream);
 }
 extern "C" int scarlet_source_update_frames_grouped(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
                                                     int in_iteration, void *stream)
 {
-    int rc = check_call(b, c != nullptr, c, false, nullptr);
-    if (!rc) rc = check_frames_grouped_call(f);
-    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw);
-}
-// ... and with update options (a catalogue batch whose sources carry the stock update functions' options): the RAGGED x
-// OPTIONS instances of the constraint kernels, `group` allowed.  Without frame_hw and group they are scarlet_fit_options /
-// scarlet_source_update_options, with every member of `o` NULL the two _grouped calls above.  The device checks run in
-// the order counts, frames, options (fit_call, update_call).
-static int check_frames_options_call(const scarlet_frames *f, const scarlet_update_options *o)
-{
-    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
-    if (!o) return set_err(SCARLET_E_ARG, "options is NULL (pass a scarlet_update_options with NULL members for the defaults)");
-    return SCARLET_OK;
+    return update_with(b, c, nullptr, nullptr, f, {NEED_F | FRAMES_LATE | GROUP_FRAMES, SC_BMAX}, in_iteration, stream);
 }
 extern "C" int scarlet_fit_frames_options(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
                                           const scarlet_update_options *o, int max_iter, double e_rel, int approximate_L,
                                           int check_every, void *stream)
 {
-    int rc = check_frames_options_call(f, o);
-    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr, max_iter);
-    return rc ? rc : fit_call(b, c, nullptr, max_iter, e_rel, approximate_L, check_every, stream, f->frame_hw, o);
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every);
+    r.frames = f; r.constraints = c; r.options = o;
+    return fit_one(b, r, {NEED_F | NEED_O | GROUP_FRAMES | GROUP_OPTIONS, SC_BMAX}, stream);
 }
 extern "C" int scarlet_source_update_frames_options(scarlet_batch *b, const scarlet_frames *f, const scarlet_constraints *c,
                                                     const scarlet_update_options *o, int in_iteration, void *stream)
 {
-    int rc = check_frames_options_call(f, o);
-    if (!rc) rc = check_call(b, c != nullptr, c, false, nullptr);
-    return rc ? rc : update_call(b, c, nullptr, in_iteration, stream, f->frame_hw, o);
+    return update_with(b, c, nullptr, o, f, {NEED_F | NEED_O | GROUP_FRAMES | GROUP_OPTIONS, SC_BMAX}, in_iteration, stream);
 }
 extern "C" int scarlet_check_frames(scarlet_batch *b, const scarlet_frames *f, void *stream)
 {
@@ -2653,21 +2673,24 @@ static ObsKernel wide_contract_kernel(const ContractPlan &cp, bool prior)
 // Several observations: one pipeline, every iteration the observation step (the observations' G planes, the contraction
 // over them, L x n_obs, the step) and the tail.  `p` NULL: no prior; given: the passes that write a step are the PRIOR
 // instances (multiobs.h), which read the prior in the pass that already holds the factors and their gradients
-// frame_hw: the scenes' own frames (scarlet_fit_observations_frames, _frames_lowres; no prior), or NULL.
+// frame_hw: the scenes' own frames (no prior), or NULL.
 // lrf: NULL, or n_obs pointers: the per-scene tables of the low-resolution observations of such scenes
-// (scarlet_fit_observations_frames_lowres; the caller has checked them against `lowres` and frame_hw).
+// (check_request has checked them against `lowres` and frame_hw).
 // Only the tail and the low-resolution kernels of such scenes read the frames: the morphologies and the observations' weights are zero outside a scene's frame, so the
 // planes, the contraction and the Lipschitz constants sum nothing there, and what a PSF's adjoint and the step write
 // outside is zeroed by the RAGGED constraint kernels before anything reads it
-static int fit_observations_call(scarlet_batch *state, const scarlet_constraints *cons, scarlet_batch *const *obs,
-                                 const int32_t *band0, int n_obs, int max_iter, double e_rel, int approximate_L,
-                                 int check_every, void *stream, const scarlet_lowres *const *lowres = nullptr,
-                                 bool large = false, const scarlet_prior *p = nullptr, const int32_t *frame_hw = nullptr,
-                                 const scarlet_lowres_frames *const *lrf = nullptr, const scarlet_update_options *upd = nullptr)
+static int fit_observations_call(scarlet_batch *state, const scarlet_fit_request &r, bool large, void *stream)
 {
     int rc;
-    if (!cons_any(cons)) cons = nullptr;
-    if (!opts_any(upd)) upd = nullptr;        // (update options of the state, scarlet_fit_observations_options: the tail reads them)
+    const UpdateOpts uo = update_opts(r);     // (with a prior the sparse_l0 / sparse_l1 cut uses each component's own step, update.py:71-82)
+    const scarlet_update_options *upd = uo.upd;        // (update options of the state: the tail reads them)
+    const scarlet_prior *p = r.prior;
+    const int32_t *frame_hw = uo.frame_hw, *band0 = r.band0;
+    scarlet_batch *const *obs = r.obs;
+    const scarlet_lowres *const *lowres = r.lowres;
+    const scarlet_lowres_frames *const *lrf = r.lowres_frames;
+    const int n_obs = r.n_obs, max_iter = r.max_iter, approximate_L = r.approximate_L, check_every = r.check_every;
+    const double e_rel = r.e_rel;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = check_counts(state, stream)) || (rc = check_frames(state, frame_hw, stream)) || (rc = check_options(state, upd, 1, 0, stream)))
         return rc;
@@ -2752,8 +2775,6 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
         if (wide) hipLaunchKernelGGL(k_wide_lmorph, dim3(m.S), dim3(SC_BLOCK), lmorph_lds, st, ga);
         else hipLaunchKernelGGL(k_bigk_lmorph<SC_KHUGE>, dim3(m.S), dim3(SC_WAVE), 0, st, ga);
     };
-    // with a prior the sparse_l0 / sparse_l1 cut uses each component's own step (update.py:71-82)
-    const UpdateOpts uo = {p ? p->L_comp : nullptr, cons, 0, frame_hw, upd};
     return fit_loop(state, l, max_iter, check_every, st, [&](int, bool, int *) -> int {
         prof_start(0, st);
         for (int o = 0; o < n_obs; ++o) {
@@ -2793,164 +2814,27 @@ static int fit_observations_call(scarlet_batch *state, const scarlet_constraints
     });
 }
 
-// the one check of the observation entry points: the list, the state (check_call), every observation against it
-static int check_observations(const scarlet_batch *state, bool need_c, const scarlet_constraints *c, scarlet_batch *const *obs,
-                              const int32_t *band0, int n_obs, int max_iter, const scarlet_lowres *const *lowres = nullptr,
-                              bool large = false, int bmax = SC_BMAX)
-{
-    if (n_obs < 1 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "1 to 8 observations");
-    if (!obs || !band0) return set_err(SCARLET_E_ARG, "null observation list");
-    int rc = check_call(state, need_c, c, false, nullptr, max_iter, bmax);
-    for (int o = 0; !rc && o < n_obs; ++o) {
-        const scarlet_batch *ob = obs[o];
-        if (!ob) return set_err(SCARLET_E_ARG, "null observation batch");
-        const scarlet_lowres *lr = lowres ? lowres[o] : nullptr;
-        if (lr) {
-            // a low-resolution observation: its batch has the observation's own h x w and no difference kernel
-            if (ob->S != state->S || ob->K != state->K || ob->H != lr->h || ob->W != lr->w || ob->B < 1 || band0[o] < 0 ||
-                band0[o] + ob->B > state->B || ob->mse_capacity < 1)
-                return set_err(SCARLET_E_ARG, "a low-resolution observation does not fit the model frame or its scarlet_lowres");
-            if (ob->diff_kernel)
-                return set_err(SCARLET_E_ARG, "a low-resolution observation takes no diff_kernel: its PSFs are in dhat");
-            if (ob->n_components)
-                return set_err(SCARLET_E_ARG, "an observation batch takes no n_components: the state's counts govern every observation");
-            if ((rc = check_lowres(lr, state->H, state->W, ob->B, true, large)) || (rc = check_batch(ob))) return rc;
-            continue;
-        }
-        if (ob->S != state->S || ob->K != state->K || ob->H != state->H || ob->W != state->W || ob->B < 1 ||
-            band0[o] < 0 || band0[o] + ob->B > state->B || ob->mse_capacity < 1)
-            return set_err(SCARLET_E_ARG, "an observation does not fit the model frame");
-        if (ob->n_components)
-            return set_err(SCARLET_E_ARG, "an observation batch takes no n_components: the state's counts govern every observation");
-        rc = check_batch(ob);
-    }
-    return rc;
-}
-
-extern "C" int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
-                                        int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
-{
-    const int rc = check_observations(state, false, nullptr, obs, band0, n_obs, max_iter);
-    return rc ? rc : fit_observations_call(state, nullptr, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
-}
-
-extern "C" int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
-                                                    const int32_t *band0, int n_obs, int max_iter, double e_rel,
-                                                    int approximate_L, int check_every, void *stream)
-{
-    const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
-}
-
-// scarlet_fit_observations_constrained with update options on the state: same-grid observations, at most 8 model channels
-extern "C" int scarlet_fit_observations_options(scarlet_batch *state, const scarlet_constraints *c, const scarlet_update_options *o,
-                                                scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter,
-                                                double e_rel, int approximate_L, int check_every, void *stream)
-{
-    int rc = check_options_call(state, o);
-    if (!rc && state && state->B > SC_BMAX)
-        rc = set_err(SCARLET_E_NOTIMPL, "update options with a wide state (more than 8 model channels): not implemented");
-    if (!rc) rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
-                                           nullptr, false, nullptr, nullptr, nullptr, o);
-}
-
-extern "C" int scarlet_fit_observations_lowres(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
-                                               const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
-                                               int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
-{
-    if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
-    const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter, lowres);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, lowres);
-}
-
-extern "C" int scarlet_fit_observations_lowres_large(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
-                                                     const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
-                                                     int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
-{
-    if (!lowres) return set_err(SCARLET_E_ARG, "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
-    const int rc = check_observations(state, true, c, obs, band0, n_obs, max_iter, lowres, true);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream, lowres, true);
-}
-
-extern "C" int scarlet_fit_observations_prior(scarlet_batch *state, const scarlet_constraints *c, const scarlet_prior *p,
-                                              scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
-                                              const int32_t *band0, int n_obs, int max_iter, double e_rel,
-                                              int approximate_L, int check_every, void *stream)
-{
-    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, lowres, true);
-    if (!rc) rc = check_prior(p);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
-                                           lowres, true, p);
-}
-
-// scarlet_fit_observations_prior over a model frame of up to SCARLET_MAX_CHANNELS channels; cons, p and lowres may be NULL
-extern "C" int scarlet_fit_observations_wide(scarlet_batch *state, const scarlet_constraints *c, const scarlet_prior *p,
-                                             scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
-                                             const int32_t *band0, int n_obs, int max_iter, double e_rel,
-                                             int approximate_L, int check_every, void *stream)
-{
-    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, lowres, true, SC_CMAX);
-    if (!rc && p) rc = check_prior(p);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
-                                           lowres, true, p);
-}
-
-// scarlet_fit_observations_constrained / _wide (the state's channel count decides, as it does between those two) for
-// scenes with their own frames; `c` may be NULL.  With frame_hw = NULL it is one of those two calls.
-extern "C" int scarlet_fit_observations_frames(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c,
-                                               scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter,
-                                               double e_rel, int approximate_L, int check_every, void *stream)
-{
-    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
-    const int bmax = state && state->B > SC_BMAX ? SC_CMAX : SC_BMAX;
-    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, nullptr, false, bmax);
-    if (!rc) rc = check_frames_call(state, f);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
-                                           nullptr, false, nullptr, f->frame_hw);
-}
-
-// The host checks of the per-scene tables of low-resolution observations (the _frames_lowres entry points), after
-// check_observations / check_lowres_products and check_frames_call; no device call
-static int check_lowres_frames_call(const scarlet_frames *f, const scarlet_lowres *const *lowres,
+// The host checks of the per-scene tables of low-resolution observations, after the observations' and the frames' own;
+// no device call.  Either list may be NULL: no entry
+static int check_lowres_frames_call(const int32_t *frame_hw, const scarlet_lowres *const *lowres,
                                     const scarlet_lowres_frames *const *lrf, int n_obs)
 {
     for (int o = 0; o < n_obs; ++o) {
-        if (lrf[o] && !lowres[o])
-            return set_err(SCARLET_E_ARG, "scarlet_lowres_frames for an observation that has no scarlet_lowres");
-        if (lowres[o] && !lrf[o] && f->frame_hw)
+        const scarlet_lowres *lr = lowres ? lowres[o] : nullptr;
+        const scarlet_lowres_frames *lf = lrf ? lrf[o] : nullptr;
+        if (lf && !lr) return set_err(SCARLET_E_ARG, "scarlet_lowres_frames for an observation that has no scarlet_lowres");
+        if (lr && !lf && frame_hw)
             return set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames) with a low-resolution observation that has no "
                                               "scarlet_lowres_frames: its operator would be that of the padded frame");
-        if (!lrf[o]) continue;
-        if (!f->frame_hw) return set_err(SCARLET_E_ARG, "scarlet_lowres_frames without frame_hw");
-        if (!lrf[o]->dims || !lrf[o]->uy || !lrf[o]->ux) return set_err(SCARLET_E_ARG, "scarlet_lowres_frames: null table");
-        if (!lowres[o]->v_per_scene || !lowres[o]->dhat_per_scene)
+        if (!lf) continue;
+        if (!frame_hw) return set_err(SCARLET_E_ARG, "scarlet_lowres_frames without frame_hw");
+        if (!lf->dims || !lf->uy || !lf->ux) return set_err(SCARLET_E_ARG, "scarlet_lowres_frames: null table");
+        if (!lr->v_per_scene || !lr->dhat_per_scene)
             return set_err(SCARLET_E_ARG, "scarlet_lowres_frames: the scarlet_lowres needs v_per_scene = dhat_per_scene = 1");
     }
     return SCARLET_OK;
 }
-
-// scarlet_fit_observations_lowres_large / _wide (the state's channel count decides) for scenes with their own frames,
-// whose low-resolution observations bring their own operators (scarlet_lowres_frames); `c` may be NULL
-extern "C" int scarlet_fit_observations_frames_lowres(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c,
-                                                      scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
-                                                      const scarlet_lowres_frames *const *lowres_frames, const int32_t *band0,
-                                                      int n_obs, int max_iter, double e_rel, int approximate_L, int check_every,
-                                                      void *stream)
-{
-    if (!f) return set_err(SCARLET_E_ARG, "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)");
-    if (!lowres || !lowres_frames)
-        return set_err(SCARLET_E_ARG, "null low-resolution list (pass arrays of n_obs pointers, NULL = same grid / no tables of its own)");
-    const int bmax = state && state->B > SC_BMAX ? SC_CMAX : SC_BMAX;
-    int rc = check_observations(state, c != nullptr, c, obs, band0, n_obs, max_iter, lowres, true, bmax);
-    if (!rc) rc = check_frames_call(state, f);
-    if (!rc) rc = check_lowres_frames_call(f, lowres, lowres_frames, n_obs);
-    return rc ? rc : fit_observations_call(state, c, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream,
-                                           lowres, true, nullptr, f->frame_hw, lowres_frames);
-}
-
-// scarlet_fit_observations for callers without ragged counts: counts on the state or on an observation are refused
-// right after the shape checks, before any pointer of the batches is looked at
+// scarlet_fit_multi: counts are refused right after the shape checks, before any pointer of the batches is looked at
 static int refuse_counts(const scarlet_batch *b)
 {
     const int rc = check_shape(b);
@@ -2958,14 +2842,163 @@ static int refuse_counts(const scarlet_batch *b)
         return set_err(SCARLET_E_NOTIMPL, "scarlet_fit_multi does not take n_components (ragged batches): pass NULL");
     return rc;
 }
+static int refuse(const char *a, const char *b)
+{
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s with %s: not implemented", a, b);
+    return set_err(SCARLET_E_NOTIMPL, msg);
+}
+// The one host-side check of a request, in this order: the members that must be there and those that do not go
+// together; the observation list; the batch (check_call); every observation against it; then the prior of a joint fit,
+// the frames (FRAMES_LATE: also their presence) and the low-resolution tables.  Nothing is launched.
+static int check_request(const scarlet_batch *b, const scarlet_fit_request &r, const Rules &u)
+{
+    const auto has = [&](unsigned f) { return (u.flags & f) != 0; };
+    const char *no_frames = "frames is NULL (pass a scarlet_frames with frame_hw = NULL for uniform frames)";
+    const int32_t *frame_hw = r.frames ? r.frames->frame_hw : nullptr;
+    const bool multi = has(MULTI);
+    int rc = SCARLET_OK;
+    if (has(NO_COUNTS)) {
+        rc = refuse_counts(b);
+        for (int o = 0; !rc && r.obs && r.n_obs <= SCARLET_MAX_OBSERVATIONS && o < r.n_obs; ++o)
+            if (r.obs[o]) rc = refuse_counts(r.obs[o]);
+        if (rc) return rc;
+    }
+    if (has(NEED_F) && !has(FRAMES_LATE) && !r.frames) return set_err(SCARLET_E_ARG, no_frames);
+    if (has(NEED_O) && !r.options) return set_err(SCARLET_E_ARG, "options is NULL (pass a scarlet_update_options with NULL members for the defaults)");
+    if (r.options && b && b->group && !has(GROUP_OPTIONS))
+        return set_err(SCARLET_E_NOTIMPL, "update options with group: the layers of a multi-component source are tied to soft symmetry");
+    if (r.options && multi && b && b->B > SC_BMAX)
+        return set_err(SCARLET_E_NOTIMPL, "update options with a wide state (more than 8 model channels): not implemented");
+    if (has(NEED_LOWRES) && (!r.lowres || (has(NEED_LRF) && !r.lowres_frames)))
+        return set_err(SCARLET_E_ARG, has(NEED_LRF) ? "null low-resolution list (pass arrays of n_obs pointers, NULL = same grid / no tables of its own)"
+                                                    : "null low-resolution list (pass an array of n_obs pointers, NULL = same grid)");
+    // (what no named entry point's signature can say)
+    if (!multi && (r.lowres || r.lowres_frames)) return set_err(SCARLET_E_ARG, "lowres / lowres_frames without observations (n_obs = 0)");
+    if (r.prior && frame_hw) return refuse("a prior", "frame_hw (ragged frames)");
+    if (r.prior && r.options) return refuse("a prior", "update options");
+    if (multi && r.options && frame_hw) return refuse("update options of a joint fit", "frame_hw (ragged frames)");
+    if (multi && r.options && r.lowres) return refuse("update options of a joint fit", "lowres (a low-resolution observation)");
+    if (multi && (r.n_obs < 1 || r.n_obs > SCARLET_MAX_OBSERVATIONS)) return set_err(SCARLET_E_ARG, "1 to 8 observations");
+    if (multi && (!r.obs || !r.band0)) return set_err(SCARLET_E_ARG, "null observation list");
+    rc = check_call(b, has(NEED_C) || r.constraints, r.constraints, has(NEED_P) && !multi, multi ? nullptr : r.prior, r.max_iter, u.bmax);
+    for (int o = 0; !rc && multi && o < r.n_obs; ++o) {
+        const scarlet_batch *ob = r.obs[o];
+        if (!ob) return set_err(SCARLET_E_ARG, "null observation batch");
+        const scarlet_lowres *lr = r.lowres ? r.lowres[o] : nullptr;
+        // a low-resolution observation: its batch has the observation's own h x w and no difference kernel
+        if (ob->S != b->S || ob->K != b->K || ob->H != (lr ? lr->h : b->H) || ob->W != (lr ? lr->w : b->W) || ob->B < 1 ||
+            r.band0[o] < 0 || r.band0[o] + ob->B > b->B || ob->mse_capacity < 1)
+            return set_err(SCARLET_E_ARG, lr ? "a low-resolution observation does not fit the model frame or its scarlet_lowres"
+                                             : "an observation does not fit the model frame");
+        if (lr && ob->diff_kernel)
+            return set_err(SCARLET_E_ARG, "a low-resolution observation takes no diff_kernel: its PSFs are in dhat");
+        if (ob->n_components)
+            return set_err(SCARLET_E_ARG, "an observation batch takes no n_components: the state's counts govern every observation");
+        if (lr && (rc = check_lowres(lr, b->H, b->W, ob->B, true, has(LARGE)))) return rc;
+        rc = check_batch(ob);
+    }
+    if (!rc && multi && (has(NEED_P) || r.prior)) rc = check_prior(r.prior);
+    if (!rc && has(NEED_F) && !r.frames) rc = set_err(SCARLET_E_ARG, no_frames);
+    if (!rc && frame_hw && b->group && !has(GROUP_FRAMES)) rc = set_err(SCARLET_E_NOTIMPL, "frame_hw (ragged frames) with group: not implemented");
+    if (!rc && multi) rc = check_lowres_frames_call(frame_hw, r.lowres, r.lowres_frames, r.n_obs);
+    return rc;
+}
+extern "C" int scarlet_fit_request_check(const scarlet_batch *b, const scarlet_fit_request *r)
+{
+    if (!r) return set_err(SCARLET_E_ARG, "null request");
+    return check_request(b, *r, r->n_obs == 0 ? RULES_ONE : RULES_MANY);
+}
+
+// check and body of the entry points that fit the request's observations.  The named ones below are fixed shapes of
+// scarlet_fit_with: what each requires and refuses is in its Rules, what the members mean in the header.
+static int fit_many(scarlet_batch *state, const scarlet_fit_request &r, const Rules &u, void *stream)
+{
+    const int rc = check_request(state, r, u);
+    return rc ? rc : fit_observations_call(state, r, (u.flags & LARGE) != 0, stream);
+}
+extern "C" int scarlet_fit_with(scarlet_batch *b, const scarlet_fit_request *r, void *stream)
+{
+    if (!r) return set_err(SCARLET_E_ARG, "null request");
+    return r->n_obs == 0 ? fit_one(b, *r, RULES_ONE, stream) : fit_many(b, *r, RULES_MANY, stream);
+}
+extern "C" int scarlet_fit_observations(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
+                                        int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    return fit_many(state, loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs), {MULTI, SC_BMAX}, stream);
+}
 extern "C" int scarlet_fit_multi(scarlet_batch *state, scarlet_batch *const *obs, const int32_t *band0, int n_obs,
                                  int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
 {
-    int rc = refuse_counts(state);
-    if (obs && n_obs <= SCARLET_MAX_OBSERVATIONS)
-        for (int o = 0; !rc && o < n_obs; ++o)
-            if (obs[o]) rc = refuse_counts(obs[o]);
-    return rc ? rc : scarlet_fit_observations(state, obs, band0, n_obs, max_iter, e_rel, approximate_L, check_every, stream);
+    return fit_many(state, loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs), {MULTI | NO_COUNTS, SC_BMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_constrained(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                                    const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                                    int approximate_L, int check_every, void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.constraints = c;
+    return fit_many(state, r, {MULTI | NEED_C, SC_BMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_options(scarlet_batch *state, const scarlet_constraints *c, const scarlet_update_options *o,
+                                                scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter,
+                                                double e_rel, int approximate_L, int check_every, void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.constraints = c; r.options = o;
+    return fit_many(state, r, {MULTI | NEED_O, SC_BMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_lowres(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                               const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                               int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.constraints = c; r.lowres = lowres;
+    return fit_many(state, r, {MULTI | NEED_C | NEED_LOWRES, SC_BMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_lowres_large(scarlet_batch *state, const scarlet_constraints *c, scarlet_batch *const *obs,
+                                                     const scarlet_lowres *const *lowres, const int32_t *band0, int n_obs,
+                                                     int max_iter, double e_rel, int approximate_L, int check_every, void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.constraints = c; r.lowres = lowres;
+    return fit_many(state, r, {MULTI | NEED_C | NEED_LOWRES | LARGE, SC_BMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_prior(scarlet_batch *state, const scarlet_constraints *c, const scarlet_prior *p,
+                                              scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                              const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                              int approximate_L, int check_every, void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.constraints = c; r.prior = p; r.lowres = lowres;
+    return fit_many(state, r, {MULTI | NEED_P | LARGE, SC_BMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_wide(scarlet_batch *state, const scarlet_constraints *c, const scarlet_prior *p,
+                                             scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                             const int32_t *band0, int n_obs, int max_iter, double e_rel,
+                                             int approximate_L, int check_every, void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.constraints = c; r.prior = p; r.lowres = lowres;
+    return fit_many(state, r, {MULTI | LARGE, SC_CMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_frames(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c,
+                                               scarlet_batch *const *obs, const int32_t *band0, int n_obs, int max_iter,
+                                               double e_rel, int approximate_L, int check_every, void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.frames = f; r.constraints = c;
+    return fit_many(state, r, {MULTI | NEED_F, SC_CMAX}, stream);
+}
+extern "C" int scarlet_fit_observations_frames_lowres(scarlet_batch *state, const scarlet_frames *f, const scarlet_constraints *c,
+                                                      scarlet_batch *const *obs, const scarlet_lowres *const *lowres,
+                                                      const scarlet_lowres_frames *const *lowres_frames, const int32_t *band0,
+                                                      int n_obs, int max_iter, double e_rel, int approximate_L, int check_every,
+                                                      void *stream)
+{
+    scarlet_fit_request r = loop_request(max_iter, e_rel, approximate_L, check_every, obs, band0, n_obs);
+    r.frames = f; r.constraints = c; r.lowres = lowres; r.lowres_frames = lowres_frames;
+    return fit_many(state, r, {MULTI | NEED_F | NEED_LOWRES | NEED_LRF | LARGE, SC_CMAX}, stream);
 }
 
 static int init_combined_sed_call(scarlet_batch *state, const float *images, int B, int band0, const float *obs_psf_peak,
@@ -3675,7 +3708,7 @@ extern "C" int scarlet_observations_products_frames_lowres(const scarlet_batch *
         return set_err(SCARLET_E_ARG, "null low-resolution list (pass arrays of n_obs pointers, NULL = same grid / no tables of its own)");
     if (n_obs < 0 || n_obs > SCARLET_MAX_OBSERVATIONS) return set_err(SCARLET_E_ARG, "products: bad observation list");
     if (int rc = check_frames_call(state, f)) return rc;
-    if (int rc = check_lowres_frames_call(f, lowres, lowres_frames, n_obs)) return rc;
+    if (int rc = check_lowres_frames_call(f->frame_hw, lowres, lowres_frames, n_obs)) return rc;
     return observations_products_call(state, obs, lowres, band0, n_obs, state_out, out, scratch, scratch_bytes, stream,
                                       state->B > SC_BMAX ? SC_CMAX : SC_BMAX, f->frame_hw, lowres_frames);
 }

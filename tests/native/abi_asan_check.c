@@ -36,6 +36,22 @@ int main(void)
     dist[0] = N + 5;                                   /* out-of-range order index */
     EXPECT(scarlet_host_prox_weighted_monotonic_f64(x64, N, w64, offsets, dist, N - 1, 0.) == SCARLET_E_ARG);
     dist[0] = 0;
+    /* a fit in one request: every refusal comes before a launch, and the message buffers hold the composed texts */
+    scarlet_batch sb;
+    scarlet_fit_request rq;
+    scarlet_prior pr;
+    scarlet_frames fr;
+    memset(&sb, 0, sizeof sb); memset(&rq, 0, sizeof rq); memset(&pr, 0, sizeof pr);
+    int frame_hw[2] = {H, W};
+    fr.frame_hw = frame_hw;
+    EXPECT(scarlet_fit_with(&sb, NULL, NULL) == SCARLET_E_ARG && scarlet_source_update_with(&sb, NULL, 1, NULL) == SCARLET_E_ARG);
+    EXPECT(scarlet_fit_with(NULL, &rq, NULL) == SCARLET_E_ARG && scarlet_source_update_with(NULL, &rq, 1, NULL) == SCARLET_E_ARG);
+    EXPECT(scarlet_fit_with(&sb, &rq, NULL) == SCARLET_E_ARG && !strcmp(scarlet_last_error(), "bad batch shape"));
+    rq.prior = &pr; rq.frames = &fr;
+    EXPECT(scarlet_fit_with(&sb, &rq, NULL) == SCARLET_E_NOTIMPL && strstr(scarlet_last_error(), "frame_hw"));
+    EXPECT(scarlet_source_update_with(&sb, &rq, 0, NULL) == SCARLET_E_NOTIMPL && strstr(scarlet_last_error(), "prior"));
+    rq.frames = NULL; rq.n_obs = 9;
+    EXPECT(scarlet_fit_with(&sb, &rq, NULL) == SCARLET_E_ARG && scarlet_fit_request_check(&sb, &rq) == SCARLET_E_ARG);
     /* calls that allocate: SCARLET_OK with a GPU, SCARLET_E_HIP without; either way nothing may leak */
     int rc[6];
     rc[0] = scarlet_host_prox_weighted_monotonic_f32(x32, N, w32, offsets, dist, N - 1, 0.f);

@@ -248,7 +248,7 @@ def test_inactive_scene_stays_untouched():
     b.active.fill_(1)
     b.active[1] = 0
     before = [t.clone() for t in (b.sed[0], b.sed[1], b.morph[0], b.morph[1])]
-    b._fit_observations(ITERS, 0.0, False, 0)
+    b._lib_fit(None, ITERS, 0.0, False, 0)
     torch.cuda.synchronize()
     assert bool((planes[1] == 0x5a).all()) and bool((losses[1] == 0x5a).all())
     assert not bool((planes[0] == 0x5a).all()) and not bool((losses[2] == 0x5a).all())
